@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoising-steps/sec (train + sample) on ML-1M-shaped latents.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1: starts its N ranks itself, sdrm_amd/launch.py)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                                (N > 1: starts its N ranks itself, sdrm_amd/launch.py)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,12 +16,19 @@ train:sample mix cyclically.  Randomness is the engine's Philox mode.  N>1: the 
 users are sharded over ranks (strong scaling: the job is fixed), RCCL all-reduce of 5 loss scalars and
 of the flat gradient per train step, no communication while sampling.
 
-Timing protocol (warm-up, then the median of 5 repeats): an untimed pre-heat of one whole job cycle
-(93 steps: clocks, caches, every kernel variant of the mix loaded) plus the --warmup steps, then the --steps window is
-timed FIVE times back to back, each window bracketed by barrier + device sync on both sides and reduced with MAX over
-ranks; `value` / `ms_per_step` are the MEDIAN window, `window_min_ms` / `window_max_ms` the extremes.  A separate,
-untimed-for-throughput pass records HIP events around every GEMM launch (on the launch stream) for `roofline`; it runs
-at least two job cycles so that the dominant class is averaged over >= 30 launches whatever --steps is.
+Timing protocol: an untimed pre-heat of one whole job cycle (93 steps: clocks, caches, every kernel variant of the mix
+loaded) plus the --warmup steps, then ONE window of exactly --steps steps along the walk, bracketed by barrier + device
+sync on both sides and reduced with MAX over ranks; `value` / `ms_per_step` are that window.  A window shorter than a job
+cycle holds a whole number of train steps: `config.timed_train_steps` says how many the timed steps held.
+
+--dump-outputs DIR: after the timed steps, what the timed path handed its caller, as float32 .npy files (see dump_outputs).
+
+--full adds what the plain run leaves out (warm-up, then the median of 5 repeats): the --steps window
+timed again at least FIVE times back to back (`windows_value` / `windows_ms_per_step`: median window per train-step-count
+class; `window_min_ms` / `window_max_ms` the extremes); an untimed-for-throughput pass that records HIP events around every
+GEMM launch (on the launch stream) for `roofline` - at least two job cycles, so that the dominant class is averaged over
+>= 30 launches whatever --steps is; train-only and sample-only rates; the other BASELINE.json configs and the CPU
+baselines (unless --no-other-configs / --no-cpu-baseline).
 
 Prints ONE JSON line on rank 0."""
 from __future__ import annotations
@@ -73,6 +81,8 @@ class Job:
         self.call_id = 0
         self.handshake_timeouts = 0
         self.left = 0
+        self.last_loss = None      # what the walk's caller receives: the device loss of the last train step,
+        self.last_latents = None   # the x_0 latents of the last sampling call that ended (None: its result was invalid)
 
     def guarded(self, call, retry):
         """The launches that synchronise work-groups through an XCD's L2 (csrc/rows48.h, csrc/sample_persist.h) wait with a bound; a
@@ -87,6 +97,13 @@ class Job:
             self.handshake_timeouts += 1
             print(f"bench.py: {ex} - continuing without that path", file=sys.stderr)
             return call() if retry else None
+
+    def finish_sampling(self):
+        """Walks on until the open sampling call (if any) has ended, train steps included, so that the walk stays in phase with
+        the job cycle; the call's result does not depend on those train steps (the sampler works on its snapshot of the net
+        taken at sample_begin)."""
+        while self.sampling:
+            self.step()
 
     def lr(self):
         ep = (self.train_count // self.wl["batches_per_epoch"]) % self.wl["epochs"]
@@ -110,7 +127,7 @@ class Job:
             m += 1
         self.left = self.e.sample_steps(m)
         if self.left == 0:
-            self.guarded(self.e.sample_end, retry=False)
+            self.last_latents = self.guarded(self.e.sample_end, retry=False)
             self.sampling = False
         self.k += m
         return m, 0
@@ -118,8 +135,8 @@ class Job:
     def step(self):
         wl = self.wl
         if is_train(self.k, self.n_train, self.cycle):
-            self.guarded(lambda: self.tr.train_step(self.x0, self.lr(), row0=self.row0, step=self.train_count, seed=self.seed, nd=wl["nd"]),
-                         retry=True)
+            self.last_loss = self.guarded(lambda: self.tr.train_step(self.x0, self.lr(), row0=self.row0, step=self.train_count,
+                                                                     seed=self.seed, nd=wl["nd"]), retry=True)
             self.train_count += 1
             kind = "train"
         else:
@@ -130,7 +147,7 @@ class Job:
                 self.left = wl["T"]
             self.left = self.e.sample_steps(1)
             if self.left == 0:
-                self.guarded(self.e.sample_end, retry=False)
+                self.last_latents = self.guarded(self.e.sample_end, retry=False)
                 self.sampling = False
             kind = "sample"
         self.k += 1
@@ -395,15 +412,50 @@ def combine_windows(window_ms, window_trains, K):
     return ms * 1e-3, {"train": trains, "sample": K - trains}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, eng, job, write=True):
+    """--dump-outputs: what the timed walk handed its caller, taken right after the timed steps, as float32 .npy files -
+      train_loss.npy      [1]     the loss the last train step returned
+      params.npy          [P]     the flat parameters after the timed steps (sdrm_get_params)
+      sample_latents.npy  [n, L]  the x_0 latents of the sampling call the walk's last sampling step belonged to (a call still
+                                  open is walked to its end first, untimed: Job.finish_sampling; N > 1: this rank's rows)
+    The same arguments give the same inputs (seeded latents and parameters, Philox randoms keyed by seed, step and call), so
+    two builds can be compared file by file.  Every rank walks the same steps; only `write` ranks write."""
+    def host(v):
+        return None if v is None else np.atleast_1d(v.detach().to(torch.float32).cpu().numpy())
+
+    arrays = {"train_loss": host(job.last_loss), "params": host(eng.get_params())} if write else {}
+    job.finish_sampling()
+    if not write:
+        return
+    arrays["sample_latents"] = host(job.last_latents)
+    for k in [k for k, a in arrays.items() if a is None]:
+        print(f"bench.py: --dump-outputs: no valid {k} to write", file=sys.stderr)
+        del arrays[k]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=186)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (last train loss, parameters, sampling latents) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: repeated windows, the per-kernel event passes and "
+                         "roofline, train-only / sample-only rates, the other BASELINE.json configs and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the extra legs on the other BASELINE.json configs (steps/s, launches per step, roofline time)")
-    ap.add_argument("--windows", type=int, default=5, help="least number of timed repeats of the --steps window")
+                    help="--full: skip the extra legs on the other BASELINE.json configs (steps/s, launches per step, roofline time)")
+    ap.add_argument("--windows", type=int, default=5, help="--full: least number of timed repeats of the --steps window")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
     ap.add_argument("--exchange", default="rccl-abi", choices=["rccl-abi", "torch"],
                     help="N > 1: collectives issued inside libsdrm_hip.so over RCCL (default) or by torch.distributed between the phases")
@@ -525,90 +577,101 @@ def main():
     n_cycle = wl["epochs"] * wl["batches_per_epoch"] + T
     for _ in range(n_cycle + args.warmup):
         job.step()
-    # ---- the --steps window, timed several times back to back along the job's cyclic walk; each window: barrier + sync,
-    # EXACTLY K steps, barrier + sync, MAX over ranks.  A window shorter than a job cycle holds a whole number of train
-    # steps (20 steps: 3 or 4, i.e. 15 % or 20 % against the job's 16.1 %), so windows are only comparable within their
-    # train-step count: the figure reported is the MEDIAN window of each composition class, the classes weighted by how
-    # often the walk produces them, over a number of windows that covers whole job cycles - robust like a median,
-    # unbiased in the train:sample mix whatever --steps is.
-    n_windows = pick_windows(args.steps, n_cycle, args.windows)
-    window_ms, window_trains, enqueue_ms = [], [], []
-    for w in range(n_windows):
+
+    def window(K):
+        """EXACTLY K steps along the job's cyclic walk (a run of sampling steps never crosses the window's end), bracketed by
+        barrier + sync on both sides: (wall ms, MAX over ranks; train steps in it; this rank's host enqueue ms)."""
         barrier()
         t0 = time.perf_counter()
-        n_tr = 0
-        done = 0
-        while done < args.steps:                      # EXACTLY K steps: a run of sampling steps never crosses the window's end
-            m, tr = job.advance(args.steps - done)
+        n_tr = done = 0
+        while done < K:
+            m, tr = job.advance(K - done)
             done += m
             n_tr += tr
-        enqueue_ms.append((time.perf_counter() - t0) * 1e3)   # the host's share: the loop without the synchronisation behind it
+        enq_ms = (time.perf_counter() - t0) * 1e3   # the host's share: the loop without the synchronisation behind it
         barrier()
-        dt_w = time.perf_counter() - t0
-        tmax = torch.tensor([dt_w], dtype=torch.float64, device=dev)
+        tmax = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
         if world > 1:
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        window_ms.append(float(tmax.cpu()) * 1e3)
-        window_trains.append(n_tr)
-    dt, kinds = combine_windows(window_ms, window_trains, args.steps)
+        return float(tmax.cpu()) * 1e3, n_tr, enq_ms
 
+    # ---- the timed steps: ONE window of exactly --steps steps along the walk; `value` / `ms_per_step` are this window
+    head_ms, head_trains, head_enqueue_ms = window(args.steps)
+    dt, kinds = head_ms * 1e-3, {"train": head_trains, "sample": args.steps - head_trains}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, job, write=rank == 0)
     sampler_chains = int(getattr(eng, "sampler_chains", 1))   # (concurrent row chains of the sampling call, by size)
-    # The event passes time the sampler on ONE chain: intervals of launches that share the chip overlap (and the library would run the
-    # chains one after the other under an event profile: half-size launches that cannot fill the chip alone) - either way not a
-    # per-kernel figure.  One chain is the same kernels on full-size launches; the timed windows above ran `sampler_chains`.
-    if sampler_chains > 1 and hasattr(eng, "debug_set"):
-        while job.k % job.cycle != 0:      # to the start of a job cycle: no sampling call open
-            job.step()
-        eng.debug_set(chains=1)
-    # ---- second, untimed-for-throughput pass with HIP events around every GEMM launch: at least two job cycles, so the
-    # dominant class (one batched weight-gradient launch per train step) is averaged over >= 30 launches
-    prof_steps = max(args.steps, 2 * n_cycle)
-    eng.profile_begin(capacity=prof_steps * 16)
-    l0 = eng.launch_count()
-    prof_kinds = {"train": 0, "sample": 0}
-    for _ in range(prof_steps):
-        prof_kinds[job.step()] += 1
-    launches_total = eng.launch_count() - l0
-    prof = eng.profile_end()
-    # ---- third pass: the dominant class alone.  Every bracketed launch puts two marker packets on the stream and the markers of
-    # neighbouring launches inflate each other's intervals (3-10 us per launch: a class of 312 short launches gains a millisecond);
-    # with only one class bracketed its interval is the kernel plus one dispatch gap - the figure rocprofv3 --kernel-trace agrees
-    # with.  The three largest classes of the pass above are each timed alone; the dominant class is the largest of THOSE totals.
-    prof_dom, dom_name = None, None
-    if prof:
-        alone = {}
-        for cand, _ in sorted(prof.items(), key=lambda kv: -kv[1][0])[:3]:
-            eng.profile_begin(capacity=prof_steps * 4, only=cand)
-            for _ in range(prof_steps):
+
+    if args.full:
+        # ---- the --steps window, timed again several times back to back along the job's cyclic walk.  A window shorter than
+        # a job cycle holds a whole number of train steps (20 steps: 3 or 4, i.e. 15 % or 20 % against the job's 16.1 %), so
+        # windows are only comparable within their train-step count: `windows_value` is the MEDIAN window of each composition
+        # class, the classes weighted by how often the walk produces them, over a number of windows that covers whole job
+        # cycles - robust like a median, unbiased in the train:sample mix whatever --steps is.
+        n_windows = pick_windows(args.steps, n_cycle, args.windows)
+        window_ms, window_trains = [], []
+        for _ in range(n_windows):
+            ms, n_tr, _ = window(args.steps)
+            window_ms.append(ms)
+            window_trains.append(n_tr)
+        windows_dt, _ = combine_windows(window_ms, window_trains, args.steps)
+
+        # The event passes time the sampler on ONE chain: intervals of launches that share the chip overlap (and the library would run the
+        # chains one after the other under an event profile: half-size launches that cannot fill the chip alone) - either way not a
+        # per-kernel figure.  One chain is the same kernels on full-size launches; the timed windows ran `sampler_chains`.
+        if sampler_chains > 1 and hasattr(eng, "debug_set"):
+            while job.k % job.cycle != 0:      # to the start of a job cycle: no sampling call open
                 job.step()
-            got = eng.profile_end().get(cand)
-            if got:
-                alone[cand] = got
-        if alone:
-            dom_name = max(alone.items(), key=lambda kv: kv[1][0])[0]
-            prof_dom = alone[dom_name]
-        eng.profile_begin(capacity=1)          # (all classes again for any later caller)
-        eng.profile_end()
-    if sampler_chains > 1 and hasattr(eng, "debug_set"):
-        eng.debug_set(chains=-1)
+            eng.debug_set(chains=1)
+        # ---- second, untimed-for-throughput pass with HIP events around every GEMM launch: at least two job cycles, so the
+        # dominant class (one batched weight-gradient launch per train step) is averaged over >= 30 launches
+        prof_steps = max(args.steps, 2 * n_cycle)
+        eng.profile_begin(capacity=prof_steps * 16)
+        l0 = eng.launch_count()
+        prof_kinds = {"train": 0, "sample": 0}
+        for _ in range(prof_steps):
+            prof_kinds[job.step()] += 1
+        launches_total = eng.launch_count() - l0
+        prof = eng.profile_end()
+        # ---- third pass: the dominant class alone.  Every bracketed launch puts two marker packets on the stream and the markers of
+        # neighbouring launches inflate each other's intervals (3-10 us per launch: a class of 312 short launches gains a millisecond);
+        # with only one class bracketed its interval is the kernel plus one dispatch gap - the figure rocprofv3 --kernel-trace agrees
+        # with.  The three largest classes of the pass above are each timed alone; the dominant class is the largest of THOSE totals.
+        prof_dom, dom_name = None, None
+        if prof:
+            alone = {}
+            for cand, _ in sorted(prof.items(), key=lambda kv: -kv[1][0])[:3]:
+                eng.profile_begin(capacity=prof_steps * 4, only=cand)
+                for _ in range(prof_steps):
+                    job.step()
+                got = eng.profile_end().get(cand)
+                if got:
+                    alone[cand] = got
+            if alone:
+                dom_name = max(alone.items(), key=lambda kv: kv[1][0])[0]
+                prof_dom = alone[dom_name]
+            eng.profile_begin(capacity=1)          # (all classes again for any later caller)
+            eng.profile_end()
+        if sampler_chains > 1 and hasattr(eng, "debug_set"):
+            eng.debug_set(chains=-1)
 
-    # ---- separate train-only / sample-only rates (extra information, not `value`)
-    def rate(fn, reps):
-        barrier()
-        t = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        barrier()
-        return reps / (time.perf_counter() - t)
+        # ---- separate train-only / sample-only rates (extra information, not `value`)
+        def rate(fn, reps):
+            barrier()
+            t = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            barrier()
+            return reps / (time.perf_counter() - t)
 
-    if job.sampling:                      # drain a sampling call left open by the cyclic walk
-        while eng.sample_steps(1) != 0:
-            pass
-        eng.sample_end()
-        job.sampling = False
-    train_rate = rate(lambda: trainer.train_step(x0, wl["lr"], row0=row0, step=7, seed=99, nd=wl["nd"]), 20)
-    eng.sample_begin(n_local, nd=wl["nd"], seed=5, call_id=777, row0=srow0)
-    sample_rate = rate(lambda: eng.sample_steps(1), 60)
+        if job.sampling:                      # drain a sampling call left open by the cyclic walk
+            while eng.sample_steps(1) != 0:
+                pass
+            eng.sample_end()
+            job.sampling = False
+        train_rate = rate(lambda: trainer.train_step(x0, wl["lr"], row0=row0, step=7, seed=99, nd=wl["nd"]), 20)
+        eng.sample_begin(n_local, nd=wl["nd"], seed=5, call_id=777, row0=srow0)
+        sample_rate = rate(lambda: eng.sample_steps(1), 60)
 
     # what every rank ran on: its device, its rows, the communicator it sees (a SCALE record then shows that RCCL saw N ranks)
     comm_n, comm_r = eng.comm_info()
@@ -628,7 +691,7 @@ def main():
                 print(f"bench.py: the RCCL communicator does not span the job ({world} ranks): {bad}", file=sys.stderr)
             sys.exit(4)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         dom = (dom_name, prof[dom_name]) if (prof and dom_name in prof) else (max(prof.items(), key=lambda kv: kv[1][0]) if prof else None)
         roof = None
         if dom:
@@ -655,16 +718,14 @@ def main():
                     "algorithmic_flops_per_launch": flops / launches,
                     "all_kernels": {k: {"ms": round(v[0], 3), "launches": v[1],
                                         "tflops": round(v[2] / (v[0] * 1e-3) / 1e12, 2)} for k, v in prof.items()}}
+    if rank == 0:
         n_train = wl["epochs"] * wl["batches_per_epoch"]
         job_flops = (kinds["train"] * train_flops(B, L, T, H) + kinds["sample"] * sample_flops(n, L, T, H))
         out = {
             "metric": "denoising-steps/sec (train+sample) on ML-1M latents", "value": round(args.steps / dt, 2),
             "unit": "denoising-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong",
-            "windows": len(window_ms), "window_ms": [round(v, 3) for v in window_ms], "window_train_steps": window_trains,
-            "window_min_ms": round(min(window_ms), 3), "window_max_ms": round(max(window_ms), 3),
-            "host_enqueue_frac": round(sum(enqueue_ms) / sum(window_ms), 3),   # rank 0: time spent queueing the windows' steps / their wall time
-            "window_rule": "median per train-step-count class, classes weighted by frequency; windows span whole job cycles",
+            "host_enqueue_frac": round(head_enqueue_ms / head_ms, 3),   # rank 0: time spent queueing the timed steps / their wall time
             "preheat_steps": n_cycle,
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": wl["name"], "latent": L, "width": W, "timesteps": T, "hidden_layers": H,
@@ -677,16 +738,23 @@ def main():
                                        if (world > 1 or args.rehearse_exchange) else "none")},
             "exchange_used": exchange_used, "ranks": rank_info, "handshake_timeouts": job.handshake_timeouts,
             "whole_job_tflops": round(job_flops / dt / 1e12, 2),
-            "train_steps_per_s": round(train_rate, 2), "sample_steps_per_s": round(sample_rate, 2),
-            "launches_per_step": round(launches_total / prof_steps, 2),
             "library_source_hash": eng.lib.sdrm_source_hash().decode()[:16],
-            "roofline": roof,
         }
-        if world == 1 and not args.no_other_configs:
-            out["other_configs"] = other_configs(with_cpu=not args.no_cpu_baseline)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(wl)
-            out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
+        if args.full:
+            out.update({
+                "windows_value": round(args.steps / windows_dt, 2), "windows_ms_per_step": round(windows_dt / args.steps * 1e3, 4),
+                "windows": len(window_ms), "window_ms": [round(v, 3) for v in window_ms], "window_train_steps": window_trains,
+                "window_min_ms": round(min(window_ms), 3), "window_max_ms": round(max(window_ms), 3),
+                "window_rule": "median per train-step-count class, classes weighted by frequency; windows span whole job cycles",
+                "train_steps_per_s": round(train_rate, 2), "sample_steps_per_s": round(sample_rate, 2),
+                "launches_per_step": round(launches_total / prof_steps, 2),
+                "roofline": roof,
+            })
+            if world == 1 and not args.no_other_configs:
+                out["other_configs"] = other_configs(with_cpu=not args.no_cpu_baseline)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(wl)
+                out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
         sys.stdout.flush()
         os.write(REAL_STDOUT, (json.dumps(out) + "\n").encode())   # the ONE line of this command's stdout
     if world > 1:

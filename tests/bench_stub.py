@@ -18,6 +18,9 @@ class StubEngine:
     def set_params(self, flat):
         pass
 
+    def get_params(self):
+        return torch.zeros(self.P)
+
     def _work(self):
         self._launches += 1
         time.sleep(2e-4)

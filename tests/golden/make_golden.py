@@ -21,6 +21,7 @@ the latents themselves.  Randomness is injected by temporarily replacing
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 import sys
 import types
@@ -223,12 +224,34 @@ def fixture_schedule(ref):
     np.savez_compressed(os.path.join(HERE, "schedule.npz"), **out)
 
 
-def fixture_timestep_embedding(ref):
+# MKL's float32 exp / cos / sin kernels differ by instruction set, and so does the reference's table (up to 2e-6 at T = 198):
+# besides this host's tables, the fixture holds the reference's tables under the kernels a host without AVX-512 runs
+# (MKL_ENABLE_INSTRUCTIONS caps the set MKL picks its kernels from when it loads: one child process per set), each with the
+# frequencies the reference's expression computes under those kernels, so that a test can tell which set its own host uses.
+TEMB_MKL_SETS = ("AVX2", "SSE4_2")
+
+
+def _temb_tables(ref):
     out = {}
     for T in (3, 7, 8, 78, 83, 93, 198):
         net = ref.SDRM(4, T, 4, 0)
         t = torch.arange(0, T + 1, dtype=torch.long)
         out[f"temb_{T}"] = net.timestep_embedding(t, T).numpy().copy()
+        half = T // 2   # train_SDRM.py:107, the reference's own expression
+        out[f"freqs_{T}"] = torch.exp(-math.log(10_000) * torch.arange(start=0, end=half, dtype=torch.float32) / half).numpy().copy()
+    return out
+
+
+def fixture_timestep_embedding(ref):
+    import subprocess
+    import tempfile
+    out = _temb_tables(ref)
+    for isa in TEMB_MKL_SETS:
+        with tempfile.TemporaryDirectory() as d:
+            path = os.path.join(d, "temb.npz")
+            subprocess.run([sys.executable, os.path.abspath(__file__), "temb_child", path], check=True,
+                           env=dict(os.environ, MKL_ENABLE_INSTRUCTIONS=isa))
+            out.update({f"{k}@{isa}": v for k, v in np.load(path).items()})
     np.savez_compressed(os.path.join(HERE, "timestep_embedding.npz"), **out)
 
 
@@ -649,6 +672,9 @@ def fixture_vae_decode(ref):
 def main():
     torch.set_num_threads(8)
     ref = load_reference()
+    if sys.argv[1:2] == ["temb_child"]:      # (fixture_timestep_embedding: this process's MKL kernels)
+        np.savez(sys.argv[2], **_temb_tables(ref))
+        return
     which = sys.argv[1:] or ["schedule", "temb", "forward", "train", "train_wide", "elementwise", "sampling", "fullsize", "host", "equal_sparsity", "rank_metrics", "vae_decode"]
     if which == ["equal_sparsity"]:     # numpy only: no need to import the reference
         fixture_equal_sparsity()

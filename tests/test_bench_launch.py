@@ -64,3 +64,44 @@ def test_rank_5_of_8_failing_ends_the_command_nonzero_in_time(hook):
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert "rank 5 asked to fail" in r.stderr
     assert time.time() - t0 < 150
+
+
+def test_plain_run_times_exactly_the_steps_and_nothing_else():
+    r = run_bench("--steps", "25", "--warmup", "3", "--stub-engine")
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json_line(r.stdout)
+    assert d["steps"] == 25 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["config"]["timed_train_steps"] + d["config"]["timed_sample_steps"] == 25
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert key in d
+    for extra in ("window_ms", "roofline", "train_steps_per_s", "sample_steps_per_s", "launches_per_step", "other_configs", "cpu_baseline"):
+        assert extra not in d, extra
+
+
+def test_full_run_adds_the_extra_legs():
+    r = run_bench("--steps", "12", "--warmup", "2", "--windows", "2", "--full", "--stub-engine")
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json_line(r.stdout)
+    assert d["steps"] == 12 and d["value"] > 0
+    assert d["windows"] >= 2 and len(d["window_ms"]) == d["windows"] and d["windows_value"] > 0
+    for extra in ("roofline", "train_steps_per_s", "sample_steps_per_s", "launches_per_step"):
+        assert extra in d, extra
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_dump_outputs(tmp_path, gpus):
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for out in dirs:
+        r = run_bench("--gpus", str(gpus), "--steps", "12", "--warmup", "2", "--stub-engine", "--dump-outputs", str(out))
+        assert r.returncode == 0, r.stderr[-2000:]
+        json_line(r.stdout)
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == ["params.npy", "sample_latents.npy", "train_loss.npy"]
+    total = 0
+    for name in names:
+        a, b = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0
+        np.testing.assert_array_equal(a, b)
+        total += a.nbytes
+    assert total <= 64 << 20

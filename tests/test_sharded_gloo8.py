@@ -26,6 +26,41 @@ WORLD = 8
 N_SAMPLE = 5429
 
 
+BLOCK = 64
+
+
+def sample_in_blocks(o, xT, z, keep, row0):
+    """The oracle's sampling call over rows row0 .. row0 + n, on one thread, in blocks of BLOCK rows aligned to the GLOBAL row
+    index and zero-padded to BLOCK rows: every row then goes through GEMMs of one shape, at one position in the block, whichever
+    rank holds it.  A CPU BLAS may round a row differently for another row count or thread count (MKL's AVX2 kernels do); what
+    is under test is the sharding - randoms keyed by the global row, rows independent - not the host's BLAS."""
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        xT, z, keep = (torch.as_tensor(a) for a in (xT, z, keep))
+        n = xT.shape[0]
+        out = np.empty((n, xT.shape[1]), dtype=np.float32)
+        lo = 0
+        while lo < n:
+            g0 = (row0 + lo) // BLOCK * BLOCK                 # the global block holding row row0 + lo
+            hi = min(n, g0 + BLOCK - row0)
+            at = row0 + lo - g0                               # that row's position in the block
+
+            def block(a, dim):
+                shape = list(a.shape)
+                shape[dim] = BLOCK
+                b = torch.zeros(shape, dtype=a.dtype)
+                b.narrow(dim, at, hi - lo).copy_(a.narrow(dim, lo, hi - lo))
+                return b
+
+            got = o.sample(block(xT, 0), block(z, 1), block(keep, 1))
+            out[lo:hi] = got[at:at + hi - lo].numpy()
+            lo = hi
+        return out
+    finally:
+        torch.set_num_threads(threads)
+
+
 def _worker(rank, port, init, x0, q, overlap, n_sample):
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     dist.init_process_group("gloo", rank=rank, world_size=WORLD)
@@ -43,7 +78,7 @@ def _worker(rank, port, init, x0, q, overlap, n_sample):
         # this rank's users of the sampling call, no collective: randoms keyed by (seed, call id, GLOBAL row)
         s0, n_local = shard_rows(n_sample, rank, WORLD)
         xT, z, keep, _ = pr.sample_randoms(SEED, 3, s0, n_local, L, T, ND, False)
-        lat = (s0, eng.o.sample(xT, z, keep).numpy())
+        lat = (s0, sample_in_blocks(eng.o, xT, z, keep, s0))
     q.put((rank, eng.o.flat(eng.names), losses, (r0, rows), lat))
     dist.barrier()
     dist.destroy_process_group()
@@ -102,5 +137,5 @@ def test_eight_rank_sampling_is_the_single_process_sample():
         k = int(np.prod(shapes[n]))
         o.o.p[n] = torch.from_numpy(results[0][1][off:off + k].reshape(shapes[n]).copy())
         off += k
-    want = o.o.sample(xT, z, keep).numpy()
+    want = sample_in_blocks(o.o, xT, z, keep, 0)
     assert np.array_equal(got, want)                               # rows are independent: sharding changes no bit
