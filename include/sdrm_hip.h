@@ -214,7 +214,11 @@ int sdrm_perturb_input(sdrm_engine* e, const float* x, const int64_t* t, const f
 
 /* Pre-activations of eps-net layer `layer` (0..H) from the last sdrm_train_forward, as [3,B,W]
  * (pass order P,S,Q).  Parity tests use their signs to evaluate the oracle with the same PReLU
- * derivative choice at pre-activations that are zero within fp32 rounding (DESIGN.md "kink flips"). */
+ * derivative choice at pre-activations that are zero within fp32 rounding (DESIGN.md "kink flips").
+ * Valid from that forward until the parameters change: some paths keep activations only and rebuild the
+ * pre-activations from the PReLU slopes of the forward, so after sdrm_adam_step, a whole sdrm_train_step /
+ * sdrm_train_step_sharded (their tail applies Adam) or sdrm_set_params the call returns SDRM_ERR_STATE
+ * and writes nothing - on every path, whether that forward stored them or not. */
 int sdrm_get_preacts(const sdrm_engine* e, int layer, float* out, void* stream);
 
 /* ---- introspection for bench.py / profiling ---------------------------------------------------- */

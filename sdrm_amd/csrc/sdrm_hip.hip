@@ -151,6 +151,7 @@ struct sdrm_engine {
   int cur_B = 0, cur_MP = 0;
   const float* cur_x0 = nullptr;
   bool fwd_done = false;
+  bool fwd_params_live = false;     // no parameter has changed since that forward (sdrm_get_preacts rebuilds from the live PReLU slopes)
   int last_S = 1, last_dgrad_blocks = 0;
   bool bwd_begun = false;
   bool fold_sums = false;            // sdrm_train_step: the seed kernel folds the loss partials itself (no k_loss_sums launch)
@@ -555,6 +556,7 @@ int launch_adam(sdrm_engine* e, const float* grad, float lr, int update, hipStre
   SDRM_LAUNCH(e, k_adam, grid, dim3(256), 0, st, tab, a);
   HIP_TRY(e, hipGetLastError());
   e->tables_fresh = false;
+  e->fwd_params_live = false;
   return SDRM_OK;
 }
 
@@ -1624,6 +1626,7 @@ int sdrm_train_forward(sdrm_engine* e, const float* x0, int B, int64_t row0, int
   const int MP = round_up(3 * B, BM), n = e->T + 1;
   const int cfg = choose_cfg(e->tune, MP, e->tune.nt32_max_rows_train);   // one tile for every NT launch of the step
   e->fwd_done = false;
+  e->fwd_params_live = true;
 
   e->cur_grouped = false; e->cur_act = false; e->cur_sk = false; e->cur_g16 = false; e->cur_rows = MP; e->cur_parts = 1; e->cur_skip_pre = false;
   if (int xs = split_status(e)) return xs;
@@ -2005,7 +2008,7 @@ int backward_tail(sdrm_engine* e, float* gout, int which, bool update, float lr,
   if (per_lane <= 8) SDRM_LAUNCH(e, k_tail<8>, dim3((unsigned)blocks), dim3(TAIL_THREADS), 0, st, a);
   else SDRM_LAUNCH(e, k_tail<16>, dim3((unsigned)blocks), dim3(TAIL_THREADS), 0, st, a);
   HIP_TRY(e, hipGetLastError());
-  if (update) e->tables_fresh = false;
+  if (update) { e->tables_fresh = false; e->fwd_params_live = false; }
   if (which & BUCKET_FIRST) {
     const int eb = tail_emb_blocks_a(W, T) + tail_emb_blocks_b(T) + tail_emb_blocks_c(T);
     SDRM_LAUNCH(e, k_tail_emb, dim3((unsigned)eb), dim3(256), tail_emb_lds_floats(T, e->TP) * sizeof(float), st, a);
@@ -2650,6 +2653,12 @@ int sdrm_get_preacts(const sdrm_engine* e, int layer, float* out, void* stream) 
   sdrm_engine* me = const_cast<sdrm_engine*>(e);
   if (!e->fwd_done) return fail(me, SDRM_ERR_STATE, "sdrm_get_preacts: no train forward yet");
   if (layer < 0 || layer > e->H) return fail(me, SDRM_ERR_ARG, "sdrm_get_preacts: layer outside [0,H]");
+  // A forward that skipped the stores (skip_pre) left activations only: k_unpad_pre rebuilds v = h / slope and picks `act` or `pre` by the
+  // slope AS IT IS NOW.  Once Adam (sdrm_adam_step, the fused tail of sdrm_train_step) or sdrm_set_params has moved the slopes that is
+  // another number, or a buffer the forward never wrote: the forward's pre-activations are gone.
+  if (!e->fwd_params_live)
+    return fail(me, SDRM_ERR_STATE, "sdrm_get_preacts: the parameters have changed since the train forward (Adam step or sdrm_set_params): "
+                                    "its pre-activations are gone");
   const float* actl = (e->cur_act && e->cur_skip_pre && e->act) ? e->act + (size_t)layer * e->MPmax * e->WP : nullptr;
   SDRM_LAUNCH(e, k_unpad_pre, dim3(256), dim3(256), 0, (hipStream_t)stream, (const float*)pre_buf(me, layer), actl,
                      (const float*)slope_ptr(me, layer), e->cur_B, e->W, e->WP, (e->cur_sk || e->cur_g16) ? 2 : (e->cur_grouped ? 1 : 0), out);
