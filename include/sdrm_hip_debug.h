@@ -5,7 +5,9 @@
  * checks, whatever the size thresholds currently are) and by tools/ (tile sweeps).
  *
  * Every setter acts on ONE handle: tile / path selection lives in the engine (sdrm_hip.h "Conventions"), so
- * forcing a variant on one engine never changes what another engine in the same process launches.
+ * forcing a variant on one engine never changes what another engine in the same process launches.  The kernel path of a
+ * train step is decided once, by its sdrm_train_forward: a setter called between a forward and its backward takes effect at the
+ * next sdrm_train_forward; some of them drop the pending forward, as said below.
  */
 #ifndef SDRM_HIP_DEBUG_H
 #define SDRM_HIP_DEBUG_H
@@ -80,7 +82,7 @@ int sdrm_debug_set_sample_persist(sdrm_engine* e, int mode);
 int sdrm_debug_split_skew(sdrm_engine* e, unsigned skew);
 /* Strip-owned weight gradients (csrc/wgrad2.h: every weight gradient of a step in one balanced round of one work-group per CU,
  * bias gradients from the ones column of the layer inputs) behind the row-owned forward: 1 (default) on, 0 the batched 64x64-tile
- * split-K launch; also env SDRM_WGRAD_STRIPS.  Takes effect with the next backward. */
+ * split-K launch; also env SDRM_WGRAD_STRIPS.  Takes effect with the next train forward. */
 int sdrm_debug_set_wgrad_strips(sdrm_engine* e, int on);
 /* Row-owned input gradients (csrc/dgrad_rows.h: one work-group per CU owns 96 stacked rows and every column of a layer's input
  * gradient, operands straight from global memory, PReLU' and the slope partial sums on 16-byte quads) behind the row-owned

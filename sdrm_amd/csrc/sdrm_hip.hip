@@ -10,6 +10,8 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/sdrm_hip.h"
@@ -82,6 +84,28 @@ struct Tuning {
                                  // 0 never, 1 when the batch fills whole rounds of one 96-row work-group per CU, 2 whenever the net allows
 };
 
+// The kernel path of ONE train step: decided once, by plan_step() in sdrm_train_forward, and frozen there.  The backward,
+// sdrm_get_train_outputs and sdrm_get_preacts read it; none of them looks at the tuning values again, so what the forward left
+// in the buffers and what the backward expects there cannot disagree (a sdrm_debug_set_* call takes effect at the next forward).
+struct StepPlan {
+  enum Path { PER_LAYER, SKINNY, ROW96, ROW48 };   // one launch per layer (64x64 / 32x32 tiles); the narrow nets' step (csrc/skinny_step.h);
+                                                   // row-owned on 96-row (csrc/rowchain.h) / 48-row (csrc/rows48.h) work-groups
+  enum Dgrad { TILES, ROWS_PER_LAYER, CHAIN, SKINNY_OWN };   // k_loss_seed + a tile GEMM per layer; k_loss_seed + a row-owned launch per layer
+                                                   // (csrc/dgrad_rows.h); seeds + every layer in ONE row-owned launch; inside k_skinny_bwd
+  Path path = PER_LAYER;
+  Dgrad dgrad = TILES;
+  int B = 0;                         // users of the step
+  int parts = 1;                     // work-groups per row group (ROW48: 1, or 2 / 4 column-split)
+  int groups = 0, users_per_group = 1;   // user groups of the stacked rows (PER_LAYER: every user its own)
+  int rows = 0, MP = 0;              // stacked rows the forward really writes (whole groups), and the same rounded up to the tile
+  int order = 0;                     // stacked row order (elementwise.h: stacked_row): 0 plain, 1 grouped by 32 users, 2 by 16
+  int loss_parts = 0;                // loss partials the forward leaves (the narrow nets': G or 4 G, known once its forward is launched)
+  bool acts_stored = false;          // the forward stores the activations prelu(pre[k]) in `act` beside pre[k] ...
+  bool strips_ok = false;            // ... and a one-call backward may take the strip-owned weight gradients (csrc/wgrad2.h)
+  // the row-owned dgrads read the activations: the forward need not store pre-activations (rowchain.h: skip_pre)
+  bool skip_pre() const { return acts_stored && (dgrad == ROWS_PER_LAYER || dgrad == CHAIN); }
+};
+
 struct sdrm_engine {
   int L, W, T, H, max_rows, device;
   Tuning tune;
@@ -96,12 +120,7 @@ struct sdrm_engine {
   float *WhfT = nullptr, *WofT = nullptr;                 // the same of the transposes ([k = out][n = in]) for the row-owned dgrads
   float *W0f = nullptr, *Whf = nullptr, *Wof = nullptr;   // fragment-packed copies [WP/16][WP/16][64][4] for the row-owned forward
                                                           // (layer 0: the latent columns only); null when the net does not qualify
-  bool cur_grouped = false;          // stacked row order of the last train_forward (elementwise.h: stacked_row)
-  bool cur_sk = false;               // ... grouped by 16 users (the narrow nets' step, csrc/skinny_step.h)
-  bool cur_g16 = false;              // ... grouped by 16 users by the 48-row row-owned forward (csrc/rows48.h)
-  int cur_rows = 0;                  // stacked rows the last train_forward really wrote (whole groups; cur_MP rounds them up to the tile)
-  bool cur_skip_pre = false;         // that forward was told not to store the pre-activations (the row-owned dgrads read the activations)
-  int cur_parts = 1;                 // work-groups per row group of that forward (csrc/rows48.h: 1, or 2 / 4 column-split)
+  StepPlan plan;                     // what the last train_forward ran on (plan_step)
   // column-split row groups: hand-shake counters of the forward / of the dgrad chain [256 groups][32], never reset while the
   // launch geometry stays the same (xgeo); the abort word lives in host-visible memory (xabort_host / its device alias)
   unsigned *xcntF = nullptr, *xcntC = nullptr;
@@ -112,11 +131,9 @@ struct sdrm_engine {
   unsigned* xcntS = nullptr;         // the persistent sampler's row-tile counters [256][32] and what they stand at (phases x column tiles)
   uint32_t xphaseS = 0;
   unsigned xskew = 0;                // test hook (sdrm_debug_split_skew): added once to the next split launch's counter base
-  int cur_sk_np = 0;                 // ... and the loss partials its forward left (G, or 4 G: csrc/skinny_fwd4.h)
   bool tables_fresh = false;         // B0tab / the C0^T columns of W0c belong to the current parameters
   float* act = nullptr;              // activations prelu(pre[k]) [H+1][MPmax][WP], written by the row-owned forward beside pre[k]:
                                      // the weight gradients of that step read their operand without PReLU on load
-  bool cur_act = false;              // the last train_forward stored them
   int ones_col = -1;                 // pad column round_up(W, 4) < WP of the layer inputs that carries 1.0 (the padded biases put it there,
                                      // the row-owned forward's staging into U): column ones_col of a weight-gradient slab is then the
                                      // bias gradient (csrc/wgrad2.h); -1: none
@@ -148,13 +165,11 @@ struct sdrm_engine {
   std::vector<float> h_beta, h_alpha, h_alphabar;
   int64_t adam_t = 0;
   // state of the last train_forward
-  int cur_B = 0, cur_MP = 0;
-  const float* cur_x0 = nullptr;
+  const float* fwd_x0 = nullptr;    // its batch (the backward's loss seeds read it again)
   bool fwd_done = false;
   bool fwd_params_live = false;     // no parameter has changed since that forward (sdrm_get_preacts rebuilds from the live PReLU slopes)
   int last_S = 1, last_dgrad_blocks = 0;
   bool bwd_begun = false;
-  bool fold_sums = false;            // sdrm_train_step: the seed kernel folds the loss partials itself (no k_loss_sums launch)
   int bwd_S0 = 1, bwd_SH = 1, bwd_SO = 1, bwd_kc0 = 0, bwd_kcH = 0, bwd_kcO = 0, bwd_dgrad_blocks = 0;
   int bwd_hidden_apps = 0;           // slab sets of the shared hidden layer's weight gradient per K-slice: H (one per application), or 1 (already summed)
   int bwd_cfg_w = 0;                 // tile of the split-K launches, fixed by backward_chain for the whole backward
@@ -273,6 +288,49 @@ const float* slope_ptr(sdrm_engine* e, int layer) { return e->p + (layer == 0 ? 
 // ---- GEMM launch helpers ----------------------------------------------------------------------
 struct Prof { sdrm_engine* e; int cls; double flops; };
 
+// ONE launch between the two events of an event profile (sdrm_profile_begin): recorded only while the profile is on, has room,
+// and takes this class (sdrm_profile_only); a null engine (the sdrm_debug_gemm* entry points) records nothing.  `launch` issues
+// the kernel and returns its status.
+template <class Launch>
+hipError_t profiled(sdrm_engine* e, int cls, double flops, hipStream_t st, Launch&& launch) {
+  const bool rec = e && e->prof_on && (int)e->prof_cls.size() < e->prof_cap && (e->prof_only < 0 || e->prof_only == cls);
+  size_t slot = 0;
+  if (rec) {
+    slot = e->prof_cls.size();
+    e->prof_cls.push_back(cls);
+    e->prof_flops.push_back(flops);
+    const hipError_t st0 = hipEventRecord(e->prof_ev[2 * slot], st);
+    if (st0 != hipSuccess) return st0;
+  }
+  hipError_t rc = launch();
+  if (rec && rc == hipSuccess) rc = hipEventRecord(e->prof_ev[2 * slot + 1], st);
+  return rc;
+}
+// ... for the launch helpers that return SDRM_* codes: the status of profiled(), with the kernel's name in the message
+int hip_rc(sdrm_engine* e, const char* kernel, hipError_t st) {
+  return st == hipSuccess ? SDRM_OK : fail(e, SDRM_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(st));
+}
+
+// Runtime value -> template argument: f is a generic callable that takes the value as a std::integral_constant (VAL reads it back
+// as a constant expression).  with_int_in tries LO + I for every I of the sequence; a value outside calls nothing and returns false.
+#define VAL(c) (decltype(c)::value)
+template <int LO, int... I, class F>
+bool with_int_in(int v, std::integer_sequence<int, I...>, int& rc, F&& f) {
+  return ((v == LO + I && ((rc = f(std::integral_constant<int, LO + I>{})), true)) || ...);
+}
+template <class F>
+int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// The column tiles CT = WP / 32 of the row-owned kernels and the strip widths of k_wgrad_strips: 4 .. 11, the widths the
+// fragment-packed weight copies exist for (sdrm_create).  tests/test_isa_lint.py holds the instantiations made here to its lists.
+constexpr int CT_MIN = 4, CT_MAX = 11;
+template <class F>
+int with_col_tiles(sdrm_engine* e, F&& f) {
+  int rc = SDRM_OK;
+  if (with_int_in<CT_MIN>(e->WP / 32, std::make_integer_sequence<int, CT_MAX - CT_MIN + 1>{}, rc, f)) return rc;
+  return fail(e, SDRM_ERR_SHAPE, "row-owned kernels: padded width outside 128..352");
+}
+
 #ifdef SDRM_STAMPS
 unsigned long long* g_wgrad_stamps = nullptr;   // diagnostic build: 8 stamp slots per work-group of the batched wgrad launch
 int g_wgrad_stamps_cap = 0, g_wgrad_stamps_n = 0;
@@ -338,26 +396,16 @@ hipError_t launch_gemm_cfg(GemmArgs& a, int M, int N, int splits, hipStream_t st
     if (spanA * 4 >= (1ull << 32) || spanB * 4 >= (1ull << 32)) return hipErrorInvalidValue;
   }
   dim3 grid(EPI == EPI_SLAB ? (unsigned)(a.nblocks * splits) : (unsigned)a.nblocks, 1, 1);
-  sdrm_engine* e = pr.e;
-  const bool rec = e && e->prof_on && (int)e->prof_cls.size() < e->prof_cap && (e->prof_only < 0 || e->prof_only == pr.cls);
-  size_t slot = 0;
-  if (rec) {
-    slot = e->prof_cls.size();
-    e->prof_cls.push_back(pr.cls);
-    e->prof_flops.push_back(pr.flops);
-    hipError_t st0 = hipEventRecord(e->prof_ev[2 * slot], st);
-    if (st0 != hipSuccess) return st0;
-  }
+  return profiled(pr.e, pr.cls, pr.flops, st, [&] {
 #ifdef SDRM_STAMPS
-  if (g_wgrad_stamps && g_stamp_class >= 0 && pr.e && pr.cls == g_stamp_class && (int)grid.x <= g_wgrad_stamps_cap) {
-    a.stamps = g_wgrad_stamps;
-    g_wgrad_stamps_n = (int)grid.x;
-  }
+    if (g_wgrad_stamps && g_stamp_class >= 0 && pr.e && pr.cls == g_stamp_class && (int)grid.x <= g_wgrad_stamps_cap) {
+      a.stamps = g_wgrad_stamps;
+      g_wgrad_stamps_n = (int)grid.x;
+    }
 #endif
-  SDRM_LAUNCH(pr.e, (gemm_kernel<Cfg, LA, LB, XA, XB, EPI>), grid, dim3(NTHREADS), 0, st, a);
-  hipError_t rc = hipGetLastError();
-  if (rec && rc == hipSuccess) rc = hipEventRecord(e->prof_ev[2 * slot + 1], st);
-  return rc;
+    SDRM_LAUNCH(pr.e, (gemm_kernel<Cfg, LA, LB, XA, XB, EPI>), grid, dim3(NTHREADS), 0, st, a);
+    return hipGetLastError();
+  });
 }
 
 template <int LA, int LB, int XA, int XB, int EPI>
@@ -444,25 +492,16 @@ hipError_t launch_wgrad_batch(sdrm_engine* e, const WgradSpec* w, int n, int Mro
   if (grid > g_wgrad_stamps_cap) for (int k = 0; k < n; ++k) b.p[k].stamps = nullptr;
   else if (g_stamp_class < 0) g_wgrad_stamps_n = grid;
 #endif
-  const bool rec = e->prof_on && (int)e->prof_cls.size() < e->prof_cap && (e->prof_only < 0 || e->prof_only == pr.cls);
-  size_t slot = 0;
-  if (rec) {
-    slot = e->prof_cls.size();
-    e->prof_cls.push_back(pr.cls);
-    e->prof_flops.push_back(pr.flops);
-    hipError_t st0 = hipEventRecord(e->prof_ev[2 * slot], st);
-    if (st0 != hipSuccess) return st0;
-  }
-  // plain_b: every B operand is stored as the kernel needs it (activations written by the row-owned forward): no PReLU on load
-  if (plain_b)
-    SDRM_LAUNCH(e, (gemm_batch_kernel<Cfg0, LD_MCONTIG, LD_MCONTIG, XF_NONE, XF_NONE, EPI_SLAB>), dim3((unsigned)grid),
-                       dim3(NTHREADS), 0, st, b);
-  else
-    SDRM_LAUNCH(e, (gemm_batch_kernel<Cfg0, LD_MCONTIG, LD_MCONTIG, XF_NONE, XF_PRELU, EPI_SLAB>), dim3((unsigned)grid),
-                       dim3(NTHREADS), 0, st, b);
-  hipError_t rc = hipGetLastError();
-  if (rec && rc == hipSuccess) rc = hipEventRecord(e->prof_ev[2 * slot + 1], st);
-  return rc;
+  return profiled(e, pr.cls, pr.flops, st, [&] {
+    // plain_b: every B operand is stored as the kernel needs it (activations written by the row-owned forward): no PReLU on load
+    if (plain_b)
+      SDRM_LAUNCH(e, (gemm_batch_kernel<Cfg0, LD_MCONTIG, LD_MCONTIG, XF_NONE, XF_NONE, EPI_SLAB>), dim3((unsigned)grid),
+                         dim3(NTHREADS), 0, st, b);
+    else
+      SDRM_LAUNCH(e, (gemm_batch_kernel<Cfg0, LD_MCONTIG, LD_MCONTIG, XF_NONE, XF_PRELU, EPI_SLAB>), dim3((unsigned)grid),
+                         dim3(NTHREADS), 0, st, b);
+    return hipGetLastError();
+  });
 }
 
 // Split-K plan of a backward's weight gradients: ONE slice count for all of them (so the one-call and the two-call backward
@@ -561,29 +600,9 @@ int launch_adam(sdrm_engine* e, const float* grad, float lr, int update, hipStre
 }
 
 // Strip-owned weight gradients (csrc/wgrad2.h): every weight gradient of the step in one balanced round of one work-group per CU.
-// Taken by the one-call backward when the forward was the row-owned one (the operands are stored as the kernel reads them:
-// activations, a ones column for the bias gradients) and the slices stay within the slab count.
-bool use_strips(const sdrm_engine* e) {
-  return (e->cur_grouped || e->cur_g16) && e->cur_act && e->ones_col >= 0 && e->tune.strips > 0 && e->H + 2 <= WG2_MAX_PROBLEMS && e->WP >= 128 && e->WP <= 352;
-}
-
-template <int NT>
-int launch_wgrad_strips_nt(sdrm_engine* e, const Wg2Args& a, double flops, hipStream_t st) {
-  const bool rec = e->prof_on && (int)e->prof_cls.size() < e->prof_cap && (e->prof_only < 0 || e->prof_only == PC_WGRAD_STRIPS);
-  size_t slot = 0;
-  if (rec) {
-    slot = e->prof_cls.size();
-    e->prof_cls.push_back(PC_WGRAD_STRIPS);
-    e->prof_flops.push_back(flops);
-    HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot], st));
-  }
-  SDRM_LAUNCH(e, (k_wgrad_strips<NT>), dim3((unsigned)(a.units * a.slices)), dim3(NTHREADS), 0, st, a);
-  HIP_TRY(e, hipGetLastError());
-  if (rec) HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot + 1], st));
-  return SDRM_OK;
-}
-
-int launch_wgrad_strips(sdrm_engine* e, int MP, double flops, hipStream_t st) {
+// Taken by the one-call backward when the forward was a row-owned one (StepPlan::strips_ok: the operands are stored as the kernel
+// reads them - activations, a ones column for the bias gradients) and the slices stay within the slab count.
+int launch_wgrad_strips(sdrm_engine* e, double flops, hipStream_t st) {
   const int H = e->H;
   Wg2Args a{};
   int ktiles[WG2_MAX_PROBLEMS], n = 0;
@@ -599,7 +618,7 @@ int launch_wgrad_strips(sdrm_engine* e, int MP, double flops, hipStream_t st) {
   int S = 256 / units;
   if (S < 1) S = 1;
   if (S > S_MAX) S = S_MAX;
-  MP = e->cur_rows;   // the rows the forward wrote (whole groups, a multiple of 16): the padding behind them is not summed over
+  const int MP = e->plan.rows;   // the rows the forward wrote (whole groups, a multiple of 16): the padding behind them is not summed over
   const int kchunk = round_up((MP + S - 1) / S, WG2_BK);
   const int slices = (MP + kchunk - 1) / kchunk;
   for (int k = H; k >= 1; --k)   // the shared hidden layer: one problem per application, slabs [application][slice]
@@ -608,16 +627,12 @@ int launch_wgrad_strips(sdrm_engine* e, int MP, double flops, hipStream_t st) {
   a.slices = slices; a.rows = MP; a.kchunk = kchunk;
   e->bwd_S0 = e->bwd_SH = e->bwd_SO = slices;
   e->bwd_strips = true;
-  switch (e->WP / 32) {
-    case 4: return launch_wgrad_strips_nt<4>(e, a, flops, st);
-    case 5: return launch_wgrad_strips_nt<5>(e, a, flops, st);
-    case 6: return launch_wgrad_strips_nt<6>(e, a, flops, st);
-    case 7: return launch_wgrad_strips_nt<7>(e, a, flops, st);
-    case 8: return launch_wgrad_strips_nt<8>(e, a, flops, st);
-    case 9: return launch_wgrad_strips_nt<9>(e, a, flops, st);
-    case 10: return launch_wgrad_strips_nt<10>(e, a, flops, st);
-    default: return launch_wgrad_strips_nt<11>(e, a, flops, st);
-  }
+  return with_col_tiles(e, [&](auto nt) {
+    return hip_rc(e, "k_wgrad_strips", profiled(e, PC_WGRAD_STRIPS, flops, st, [&] {
+      SDRM_LAUNCH(e, (k_wgrad_strips<VAL(nt)>), dim3((unsigned)(a.units * a.slices)), dim3(NTHREADS), 0, st, a);
+      return hipGetLastError();
+    }));
+  });
 }
 
 EmbTabArgs emb_args(sdrm_engine* e) {
@@ -654,33 +669,14 @@ bool skinny_net(const sdrm_engine* e) { return e->tune.skinny && e->LP <= 64 && 
 // partial sums when the batch fills whole rounds of the chip's 256 CUs (measured at B = 8192, L = 340: 169 us against
 // 182 + 18.7 + 11.7 us); a last round that leaves more than a sixth of the CUs idle loses to the per-layer path.
 // row-owned dgrads (dgrad_rows.h): the stacked rows are whole 96-row work-groups (the grouped order of the row-owned forward),
-// reduction axis == output axis == the padded width (LP == WP: L == W)
-// will the backward of a row-owned forward of `rows` stacked rows (padded to MP) be the row-owned dgrads (dr_layer: chain or one
-// launch per layer)?  Asked by the forward too: they read activations, so it need not store pre-activations (rowchain.h: skip_pre)
-bool row_dgrads_follow(const sdrm_engine* e, bool g16, int MP) {
-  if (!e->WhfT || e->tune.dgrad_rows <= 0 || e->LP != e->WP || e->WP < 128 || e->WP > 352) return false;
-  return g16 ? e->H + 1 <= DR_MAX_LAYERS : MP % RC_ROWS == 0;
-}
-bool use_dgrad_rows(const sdrm_engine* e, int MP) {
-  return e->cur_grouped && e->WhfT && e->tune.dgrad_rows > 0 && e->LP == e->WP && MP % RC_ROWS == 0 && e->WP >= 128 && e->WP <= 352;
-}
+// reduction axis == output axis == the padded width (LP == WP: L == W).  Whether they follow a forward is decided with the
+// forward, in plan_step (StepPlan::dgrad): they read activations, so that forward need not store pre-activations (rowchain.h: skip_pre).
 
-template <int CT>
-int launch_dgrad_rows_ct(sdrm_engine* e, const DgradRowsArgs& a, int G, double flops, hipStream_t st) {
-  const bool rec = e->prof_on && (int)e->prof_cls.size() < e->prof_cap && (e->prof_only < 0 || e->prof_only == PC_DGRAD_ROWS);
-  size_t slot = 0;
-  if (rec) {
-    slot = e->prof_cls.size();
-    e->prof_cls.push_back(PC_DGRAD_ROWS);
-    e->prof_flops.push_back(flops);
-    HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot], st));
-  }
-  // (the weight copies' compact last K-step, elementwise.h: L == W on this path)
-  if (rc_light_klast(e->W, e->WP) >= 0) SDRM_LAUNCH(e, (k_dgrad_rows<CT, true>), dim3((unsigned)G), dim3(NTHREADS), 0, st, a);
-  else SDRM_LAUNCH(e, (k_dgrad_rows<CT, false>), dim3((unsigned)G), dim3(NTHREADS), 0, st, a);
-  HIP_TRY(e, hipGetLastError());
-  if (rec) HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot + 1], st));
-  return SDRM_OK;
+// The forms <CT, LIGHT> of the row-owned kernels: CT column tiles, LIGHT the weight copies' compact last K-step (elementwise.h;
+// L == W on these paths: one answer for every layer).
+template <class F>
+int with_row_form(sdrm_engine* e, F&& f) {
+  return with_col_tiles(e, [&](auto ct) { return with_bool(rc_light_klast(e->W, e->WP) >= 0, [&](auto light) { return f(ct, light); }); });
 }
 
 // out[MP][WP] = (G[MP][WP] * W) * prelu'(pre), W given as the fragment-packed [k = out][n = in] copy
@@ -689,56 +685,39 @@ DgradRowsArgs dgrad_rows_args(const sdrm_engine* e, const float* G, const float*
   DgradRowsArgs a{};
   a.G = G; a.ldg = e->WP; a.WfT = WfT; a.pre = pre; a.ldp = e->WP; a.slope = slope; a.out = out; a.ldo = e->WP; a.slope_part = partial;
   // the layer's activations sit at the same place of the `act` buffer as its pre-activations in `pre`
-  a.act = e->act ? e->act + (pre - e->pre) : nullptr; a.from_act = (e->cur_act && e->cur_skip_pre && a.act) ? 1 : 0;
+  a.act = e->act ? e->act + (pre - e->pre) : nullptr; a.from_act = (e->plan.skip_pre() && a.act) ? 1 : 0;
   return a;
 }
 
 int launch_dgrad_rows(sdrm_engine* e, const float* G, const float* WfT, const float* pre, const float* slope, float* out, float* partial,
-                      int MP, double flops, hipStream_t st) {
+                      int groups, double flops, hipStream_t st) {
   const DgradRowsArgs a = dgrad_rows_args(e, G, WfT, pre, slope, out, partial);
-  const int Gn = MP / RC_ROWS;
-  switch (e->WP / 32) {
-    case 4: return launch_dgrad_rows_ct<4>(e, a, Gn, flops, st);
-    case 5: return launch_dgrad_rows_ct<5>(e, a, Gn, flops, st);
-    case 6: return launch_dgrad_rows_ct<6>(e, a, Gn, flops, st);
-    case 7: return launch_dgrad_rows_ct<7>(e, a, Gn, flops, st);
-    case 8: return launch_dgrad_rows_ct<8>(e, a, Gn, flops, st);
-    case 9: return launch_dgrad_rows_ct<9>(e, a, Gn, flops, st);
-    case 10: return launch_dgrad_rows_ct<10>(e, a, Gn, flops, st);
-    default: return launch_dgrad_rows_ct<11>(e, a, Gn, flops, st);
-  }
+  return with_row_form(e, [&](auto ct, auto light) {
+    return hip_rc(e, "k_dgrad_rows", profiled(e, PC_DGRAD_ROWS, flops, st, [&] {
+      SDRM_LAUNCH(e, (k_dgrad_rows<VAL(ct), VAL(light)>), dim3((unsigned)groups), dim3(NTHREADS), 0, st, a);
+      return hipGetLastError();
+    }));
+  });
+}
+
+// the layers of the row-owned chain, output layer first (the 96-row and the 48-row chain alike)
+void dgrad_chain_args(sdrm_engine* e, const SeedArgs& seed, DgradChainArgs& ca) {
+  const int H = e->H;
+  ca.seed = seed; ca.nlayers = H + 1;
+  ca.layer[0] = dgrad_rows_args(e, e->dY, e->WofT, pre_buf(e, H), slope_ptr(e, H), dpre_buf(e, H), e->alpha_part + (size_t)H * e->alpha_part_stride);
+  for (int k = H; k >= 1; --k)
+    ca.layer[H + 1 - k] = dgrad_rows_args(e, dpre_buf(e, k), e->WhfT, pre_buf(e, k - 1), slope_ptr(e, k - 1), dpre_buf(e, k - 1),
+                                          e->alpha_part + (size_t)(k - 1) * e->alpha_part_stride);
 }
 
 // loss value + gradient seeds + every layer's dgrad in one launch (k_dgrad_chain)
-template <int CT>
-int launch_dgrad_chain_ct(sdrm_engine* e, const DgradChainArgs& a, int G, double flops, hipStream_t st) {
-  const bool rec = e->prof_on && (int)e->prof_cls.size() < e->prof_cap && (e->prof_only < 0 || e->prof_only == PC_DGRAD_ROWS);
-  size_t slot = 0;
-  if (rec) {
-    slot = e->prof_cls.size();
-    e->prof_cls.push_back(PC_DGRAD_ROWS);
-    e->prof_flops.push_back(flops);
-    HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot], st));
-  }
-  if (rc_light_klast(e->W, e->WP) >= 0) SDRM_LAUNCH(e, (k_dgrad_chain<CT, true>), dim3((unsigned)G), dim3(NTHREADS), 0, st, a);
-  else SDRM_LAUNCH(e, (k_dgrad_chain<CT, false>), dim3((unsigned)G), dim3(NTHREADS), 0, st, a);
-  HIP_TRY(e, hipGetLastError());
-  if (rec) HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot + 1], st));
-  return SDRM_OK;
-}
-
-int launch_dgrad_chain(sdrm_engine* e, const DgradChainArgs& a, int MP, double flops, hipStream_t st) {
-  const int Gn = MP / RC_ROWS;
-  switch (e->WP / 32) {
-    case 4: return launch_dgrad_chain_ct<4>(e, a, Gn, flops, st);
-    case 5: return launch_dgrad_chain_ct<5>(e, a, Gn, flops, st);
-    case 6: return launch_dgrad_chain_ct<6>(e, a, Gn, flops, st);
-    case 7: return launch_dgrad_chain_ct<7>(e, a, Gn, flops, st);
-    case 8: return launch_dgrad_chain_ct<8>(e, a, Gn, flops, st);
-    case 9: return launch_dgrad_chain_ct<9>(e, a, Gn, flops, st);
-    case 10: return launch_dgrad_chain_ct<10>(e, a, Gn, flops, st);
-    default: return launch_dgrad_chain_ct<11>(e, a, Gn, flops, st);
-  }
+int launch_dgrad_chain(sdrm_engine* e, const DgradChainArgs& a, int groups, double flops, hipStream_t st) {
+  return with_row_form(e, [&](auto ct, auto light) {
+    return hip_rc(e, "k_dgrad_chain", profiled(e, PC_DGRAD_ROWS, flops, st, [&] {
+      SDRM_LAUNCH(e, (k_dgrad_chain<VAL(ct), VAL(light)>), dim3((unsigned)groups), dim3(NTHREADS), 0, st, a);
+      return hipGetLastError();
+    }));
+  });
 }
 
 bool use_rowchain(const sdrm_engine* e, int B) {
@@ -783,6 +762,47 @@ int rows48_parts(const sdrm_engine* e, int B) {
   return (G >= 160 && G <= 256) ? 1 : 0;   // (2545 .. 4096 users; measured: 2560 users 231 against 235 us, 2688 231 / 241, 2432 228 / 224)
 }
 
+// The plan of a train step of B users: which kernels run it (the size rules above, asked here and nowhere else), what its forward
+// leaves in the buffers, and what its backward does with that.
+StepPlan plan_step(const sdrm_engine* e, int B) {
+  StepPlan p;
+  p.B = B;
+  auto grouped = [&](StepPlan::Path path, int order, int users, int rows_per_group) {
+    p.path = path; p.order = order; p.users_per_group = users;
+    p.groups = (B + users - 1) / users;
+    p.rows = p.groups * rows_per_group;
+    p.loss_parts = p.groups;
+  };
+  if (skinny_net(e)) {
+    grouped(StepPlan::SKINNY, 2, SK_USERS, SK_ROWS);
+    p.dgrad = StepPlan::SKINNY_OWN;
+  } else if (use_rowchain(e, B)) {
+    grouped(StepPlan::ROW96, 1, RC_USERS, RC_ROWS);
+  } else if (const int parts = rows48_parts(e, B)) {
+    grouped(StepPlan::ROW48, 2, R48_USERS, R48_ROWS);
+    p.parts = parts;
+    p.loss_parts = p.groups * parts;
+  } else {
+    p.groups = B;
+    p.rows = round_up(3 * B, BM);
+    p.loss_parts = LOSS_BLOCKS;
+  }
+  p.MP = round_up(p.rows, BM);
+  if (p.path == StepPlan::ROW96 || p.path == StepPlan::ROW48) {
+    p.acts_stored = true;
+    p.strips_ok = e->ones_col >= 0 && e->tune.strips > 0 && e->H + 2 <= WG2_MAX_PROBLEMS && e->WP >= 128 && e->WP <= 352;
+    // the envelope of the row-owned dgrads: the transposed fragment-packed copies, one padded width for every axis; the chains keep
+    // every layer's arguments in one struct; the 96-row kernels want the padded rows to be whole work-groups (the 48-row chain
+    // clears the padding rows behind its last group itself, and has no launch-per-layer form: tune.dgrad_rows == 2 runs its chain too)
+    const bool rows_ok = e->WhfT && e->tune.dgrad_rows > 0 && e->LP == e->WP && e->WP >= 128 && e->WP <= 352;
+    const bool chain_fits = e->H + 1 <= DR_MAX_LAYERS;
+    if (rows_ok && p.path == StepPlan::ROW48 && chain_fits) p.dgrad = StepPlan::CHAIN;
+    if (rows_ok && p.path == StepPlan::ROW96 && p.MP % RC_ROWS == 0)
+      p.dgrad = (e->tune.dgrad_rows == 1 && chain_fits) ? StepPlan::CHAIN : StepPlan::ROWS_PER_LAYER;
+  }
+  return p;
+}
+
 // the hand-shake counters of a column-split launch: they count on from launch to launch while the geometry stays the same
 int split_sync(sdrm_engine* e, bool chain, int groups, int parts, int phases, hipStream_t st, unsigned** cnt, unsigned* base) {
   unsigned*& c = chain ? e->xcntC : e->xcntF;
@@ -811,121 +831,43 @@ int split_status(sdrm_engine* e) {
                                "that train step are invalid; the path is switched off for this handle");
 }
 
-template <int CT, int PARTS>
-int launch_rows48_forward_ctp(sdrm_engine* e, const RowChainArgs& a, int grid, hipStream_t st) {
-  if constexpr (PARTS == 1 && CT % 2 == 1) {   // 2 CT = 4 q + 2 column tiles: the shared-tile form
-    if (e->tune.rows48_share & 1) {
-      if (a.light) SDRM_LAUNCH(e, (k_rows48_fwd<CT, true, 1, true>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, a);
-      else SDRM_LAUNCH(e, (k_rows48_fwd<CT, false, 1, true>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, a);
-      return SDRM_OK;
-    }
-  }
-  if (a.light) SDRM_LAUNCH(e, (k_rows48_fwd<CT, true, PARTS>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, a);
-  else SDRM_LAUNCH(e, (k_rows48_fwd<CT, false, PARTS>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, a);
-  return SDRM_OK;
+// The forms <CT, LIGHT, PARTS, SHARE> of the 48-row kernels (csrc/rows48.h): 1 / 2 / 4 work-groups per row group, and the shared-tile
+// form - for one work-group per group and 2 CT = 4 q + 2 column tiles (odd CT) only, where `share` asks for it.  Not the full
+// product: a form nobody launches is a kernel nobody lints (tests/test_isa_lint.py).
+template <class F>
+int with_rows48_form(sdrm_engine* e, int parts, bool share, F&& f) {
+  return with_row_form(e, [&](auto ct, auto light) {
+    if constexpr (VAL(ct) % 2 == 1)
+      if (parts == 1 && share) return f(ct, light, std::integral_constant<int, 1>{}, std::true_type{});
+    if (parts == 4) return f(ct, light, std::integral_constant<int, 4>{}, std::false_type{});
+    if (parts == 2) return f(ct, light, std::integral_constant<int, 2>{}, std::false_type{});
+    return f(ct, light, std::integral_constant<int, 1>{}, std::false_type{});
+  });
 }
 
-template <int CT>
-int launch_rows48_forward_ct(sdrm_engine* e, RowChainArgs& a, int G, int parts, hipStream_t st) {
-  const double flops = 2.0 * 3 * a.B * ((double)e->W * e->L + (double)e->H * e->W * e->W + (double)e->L * e->W);
-  const bool rec = e->prof_on && (int)e->prof_cls.size() < e->prof_cap && (e->prof_only < 0 || e->prof_only == PC_ROW_FWD);
-  size_t slot = 0;
-  if (parts > 1) {
-    if (int rc = split_sync(e, false, G, parts, e->H + 1, st, &a.xcnt, &a.xbase)) return rc;
-    a.xabort = e->xabort_dev; a.ngroups = G;
-  }
-  if (rec) {
-    slot = e->prof_cls.size();
-    e->prof_cls.push_back(PC_ROW_FWD);
-    e->prof_flops.push_back(flops);
-    HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot], st));
-  }
-  const int grid = rows48_grid(G, parts);
-  if (parts == 4) launch_rows48_forward_ctp<CT, 4>(e, a, grid, st);
-  else if (parts == 2) launch_rows48_forward_ctp<CT, 2>(e, a, grid, st);
-  else launch_rows48_forward_ctp<CT, 1>(e, a, grid, st);
-  HIP_TRY(e, hipGetLastError());
-  if (rec) HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot + 1], st));
-  return SDRM_OK;
-}
-
-template <int CT, int PARTS>
-int launch_rows48_chain_ctp(sdrm_engine* e, const DgradChain48Args& a, int grid, hipStream_t st) {
-  if constexpr (PARTS == 1 && CT % 2 == 1) {   // 2 CT = 4 q + 2 column tiles: the shared-tile form
-    if (e->tune.rows48_share & 2) {
-      if (rc_light_klast(e->W, e->WP) >= 0) SDRM_LAUNCH(e, (k_rows48_dgrad_chain<CT, true, 1, true>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, a);
-      else SDRM_LAUNCH(e, (k_rows48_dgrad_chain<CT, false, 1, true>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, a);
-      return SDRM_OK;
-    }
-  }
-  if (rc_light_klast(e->W, e->WP) >= 0) SDRM_LAUNCH(e, (k_rows48_dgrad_chain<CT, true, PARTS>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, a);
-  else SDRM_LAUNCH(e, (k_rows48_dgrad_chain<CT, false, PARTS>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, a);
-  return SDRM_OK;
-}
-
-template <int CT>
-int launch_rows48_chain_ct(sdrm_engine* e, DgradChain48Args& a, int G, int parts, double flops, hipStream_t st) {
-  const bool rec = e->prof_on && (int)e->prof_cls.size() < e->prof_cap && (e->prof_only < 0 || e->prof_only == PC_DGRAD_ROWS);
-  size_t slot = 0;
+int launch_rows48_chain(sdrm_engine* e, DgradChain48Args& a, int G, int parts, double flops, hipStream_t st) {
   if (parts > 1) {
     if (int rc = split_sync(e, true, G, parts, std::max(1, a.c.nlayers - 1), st, &a.xcnt, &a.xbase)) return rc;
     a.xabort = e->xabort_dev; a.ngroups = G;
   }
-  if (rec) {
-    slot = e->prof_cls.size();
-    e->prof_cls.push_back(PC_DGRAD_ROWS);
-    e->prof_flops.push_back(flops);
-    HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot], st));
-  }
   const int grid = rows48_grid(G, parts);
-  if (parts == 4) launch_rows48_chain_ctp<CT, 4>(e, a, grid, st);
-  else if (parts == 2) launch_rows48_chain_ctp<CT, 2>(e, a, grid, st);
-  else launch_rows48_chain_ctp<CT, 1>(e, a, grid, st);
-  HIP_TRY(e, hipGetLastError());
-  if (rec) HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot + 1], st));
-  return SDRM_OK;
+  return with_rows48_form(e, parts, (e->tune.rows48_share & 2) != 0, [&](auto ct, auto light, auto np, auto share) {
+    return hip_rc(e, "k_rows48_dgrad_chain", profiled(e, PC_DGRAD_ROWS, flops, st, [&] {
+      SDRM_LAUNCH(e, (k_rows48_dgrad_chain<VAL(ct), VAL(light), VAL(np), VAL(share)>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, a);
+      return hipGetLastError();
+    }));
+  });
 }
 
-int launch_rows48_chain(sdrm_engine* e, DgradChain48Args& a, int G, int parts, double flops, hipStream_t st) {
-  switch (e->WP / 32) {
-    case 4: return launch_rows48_chain_ct<4>(e, a, G, parts, flops, st);
-    case 5: return launch_rows48_chain_ct<5>(e, a, G, parts, flops, st);
-    case 6: return launch_rows48_chain_ct<6>(e, a, G, parts, flops, st);
-    case 7: return launch_rows48_chain_ct<7>(e, a, G, parts, flops, st);
-    case 8: return launch_rows48_chain_ct<8>(e, a, G, parts, flops, st);
-    case 9: return launch_rows48_chain_ct<9>(e, a, G, parts, flops, st);
-    case 10: return launch_rows48_chain_ct<10>(e, a, G, parts, flops, st);
-    default: return launch_rows48_chain_ct<11>(e, a, G, parts, flops, st);
-  }
-}
-
-template <int CT>
-int launch_row_forward_ct(sdrm_engine* e, const RowChainArgs& a, int G, hipStream_t st) {
-  // profile class: the algorithmic flops of the H + 2 layers of the three passes (staging, loss sums and the streamed copies ride along)
-  const double flops = 2.0 * 3 * a.B * ((double)e->W * e->L + (double)e->H * e->W * e->W + (double)e->L * e->W);
-  const bool rec = e->prof_on && (int)e->prof_cls.size() < e->prof_cap && (e->prof_only < 0 || e->prof_only == PC_ROW_FWD);
-  size_t slot = 0;
-  if (rec) {
-    slot = e->prof_cls.size();
-    e->prof_cls.push_back(PC_ROW_FWD);
-    e->prof_flops.push_back(flops);
-    HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot], st));
-  }
-  if (a.light) SDRM_LAUNCH(e, (k_row_fwd<CT, true>), dim3((unsigned)G), dim3(NTHREADS), 0, st, a);
-  else SDRM_LAUNCH(e, (k_row_fwd<CT, false>), dim3((unsigned)G), dim3(NTHREADS), 0, st, a);
-  HIP_TRY(e, hipGetLastError());
-  if (rec) HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot + 1], st));
-  return SDRM_OK;
-}
-
-int launch_row_forward(sdrm_engine* e, const float* x0, int B, int64_t row0, int mode, const sdrm_train_randoms* rnd, uint64_t seed,
-                       uint64_t step, float nd, int G, hipStream_t st, int rows48_parts_ = 0) {
-  const int n = e->T + 1;
+// the row-owned forward of the step `p` plans: staging, every layer and the loss partial sums of p.groups user groups in one launch
+int launch_row_forward(sdrm_engine* e, const StepPlan& p, const float* x0, int64_t row0, int mode, const sdrm_train_randoms* rnd,
+                       uint64_t seed, uint64_t step, float nd, hipStream_t st) {
+  const int n = e->T + 1, G = p.groups;
   RowChainArgs a{};
   a.x0 = x0;
   if (mode == SDRM_RNG_EXPLICIT) { a.noise = rnd->noise; a.t = rnd->t; a.keep = rnd->keep; }
   a.sqrt_ab = e->sched + 3 * n; a.one_minus_ab = e->sched + 4 * n; a.tembP = e->tembP;
-  a.B = B; a.L = e->L; a.T = e->T; a.H = e->H;
+  a.B = p.B; a.L = e->L; a.T = e->T; a.H = e->H;
   a.mode = mode; a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.step = (uint32_t)step; a.row0 = row0; a.nd = nd;
   a.W0f = e->W0f; a.Whf = e->Whf; a.Wof = e->Wof; a.bh = e->bhc; a.bo = e->boc; a.B0tab = e->B0tab; a.ldtab = e->WP;
   a.slope0 = slope_ptr(e, 0); a.slopeh = e->H > 0 ? slope_ptr(e, 1) : slope_ptr(e, 0);
@@ -935,35 +877,28 @@ int launch_row_forward(sdrm_engine* e, const float* x0, int B, int64_t row0, int
   a.act = e->act;
   a.loss_part = e->loss_part;
   a.sweep = (e->tune.rows48_share & 4) ? 1 : 0;
-  {
-    const int MPg = rows48_parts_ > 0 ? round_up(G * R48_ROWS, BM) : round_up(G * RC_ROWS, BM);
-    a.skip_pre = row_dgrads_follow(e, rows48_parts_ > 0, MPg) ? 1 : 0;
-    e->cur_skip_pre = a.skip_pre != 0;
-  }
-  if (rows48_parts_ > 0) {
-    switch (e->WP / 32) {
-      case 4: return launch_rows48_forward_ct<4>(e, a, G, rows48_parts_, st);
-      case 5: return launch_rows48_forward_ct<5>(e, a, G, rows48_parts_, st);
-      case 6: return launch_rows48_forward_ct<6>(e, a, G, rows48_parts_, st);
-      case 7: return launch_rows48_forward_ct<7>(e, a, G, rows48_parts_, st);
-      case 8: return launch_rows48_forward_ct<8>(e, a, G, rows48_parts_, st);
-      case 9: return launch_rows48_forward_ct<9>(e, a, G, rows48_parts_, st);
-      case 10: return launch_rows48_forward_ct<10>(e, a, G, rows48_parts_, st);
-      case 11: return launch_rows48_forward_ct<11>(e, a, G, rows48_parts_, st);
-      default: return fail(e, SDRM_ERR_SHAPE, "row-owned forward: padded width outside 128..352");
+  a.skip_pre = p.skip_pre() ? 1 : 0;
+  // profile class: the algorithmic flops of the H + 2 layers of the three passes (staging, loss sums and the streamed copies ride along)
+  const double flops = 2.0 * 3 * a.B * ((double)e->W * e->L + (double)e->H * e->W * e->W + (double)e->L * e->W);
+  if (p.path == StepPlan::ROW48) {
+    if (p.parts > 1) {
+      if (int rc = split_sync(e, false, G, p.parts, e->H + 1, st, &a.xcnt, &a.xbase)) return rc;
+      a.xabort = e->xabort_dev; a.ngroups = G;
     }
+    const int grid = rows48_grid(G, p.parts);
+    return with_rows48_form(e, p.parts, (e->tune.rows48_share & 1) != 0, [&](auto ct, auto light, auto np, auto share) {
+      return hip_rc(e, "k_rows48_fwd", profiled(e, PC_ROW_FWD, flops, st, [&] {
+        SDRM_LAUNCH(e, (k_rows48_fwd<VAL(ct), VAL(light), VAL(np), VAL(share)>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, a);
+        return hipGetLastError();
+      }));
+    });
   }
-  switch (e->WP / 32) {
-    case 4: return launch_row_forward_ct<4>(e, a, G, st);
-    case 5: return launch_row_forward_ct<5>(e, a, G, st);
-    case 6: return launch_row_forward_ct<6>(e, a, G, st);
-    case 7: return launch_row_forward_ct<7>(e, a, G, st);
-    case 8: return launch_row_forward_ct<8>(e, a, G, st);
-    case 9: return launch_row_forward_ct<9>(e, a, G, st);
-    case 10: return launch_row_forward_ct<10>(e, a, G, st);
-    case 11: return launch_row_forward_ct<11>(e, a, G, st);
-    default: return fail(e, SDRM_ERR_SHAPE, "row-owned forward: padded width outside 128..352");
-  }
+  return with_row_form(e, [&](auto ct, auto light) {
+    return hip_rc(e, "k_row_fwd", profiled(e, PC_ROW_FWD, flops, st, [&] {
+      SDRM_LAUNCH(e, (k_row_fwd<VAL(ct), VAL(light)>), dim3((unsigned)G), dim3(NTHREADS), 0, st, a);
+      return hipGetLastError();
+    }));
+  });
 }
 
 // the narrow nets' train step (csrc/skinny_step.h): forward (which = 0) / backward (which = 1) over G = ceil(B / 16) user groups
@@ -1600,8 +1535,9 @@ int sdrm_adam_reset(sdrm_engine* e, void* stream) {
 namespace {
 bool sample_persist_fits(const sdrm_engine* e, const SampleState& s);   // (below, beside the sampler)
 }
-int sdrm_train_forward(sdrm_engine* e, const float* x0, int B, int64_t row0, int mode, const sdrm_train_randoms* rnd,
-                       uint64_t seed, uint64_t step, float nd, double* sums, void* stream) {
+// fold_sums (sdrm_train_step): the backward folds the loss partials itself - no k_loss_sums launch here
+static int train_forward_impl(sdrm_engine* e, const float* x0, int B, int64_t row0, int mode, const sdrm_train_randoms* rnd,
+                              uint64_t seed, uint64_t step, float nd, double* sums, void* stream, bool fold_sums) {
   if (!e || !x0) return fail(e, SDRM_ERR_ARG, "sdrm_train_forward: null pointer");
   if (B < 1 || B > e->max_rows) return fail(e, SDRM_ERR_SHAPE, "sdrm_train_forward: B outside [1, max_rows]");
   if (mode == SDRM_RNG_EXPLICIT && (!rnd || !rnd->noise || !rnd->t || !rnd->keep))
@@ -1623,14 +1559,12 @@ int sdrm_train_forward(sdrm_engine* e, const float* x0, int B, int64_t row0, int
     HIP_TRY(e, hipEventRecord(e->ev_fork, st));
     e->detach_armed = true;
   }
-  const int MP = round_up(3 * B, BM), n = e->T + 1;
-  const int cfg = choose_cfg(e->tune, MP, e->tune.nt32_max_rows_train);   // one tile for every NT launch of the step
   e->fwd_done = false;
   e->fwd_params_live = true;
-
-  e->cur_grouped = false; e->cur_act = false; e->cur_sk = false; e->cur_g16 = false; e->cur_rows = MP; e->cur_parts = 1; e->cur_skip_pre = false;
   if (int xs = split_status(e)) return xs;
-  if (skinny_net(e)) {
+  e->plan = plan_step(e, B);
+  StepPlan& p = e->plan;
+  if (p.path == StepPlan::SKINNY) {
     // narrow net (csrc/skinny_step.h): staging, all layers and the loss partial sums of 16 users' P, S, Q rows per work-group in
     // ONE launch; the tables B0tab = b0 + C0[t] come from the last step's tail (or are made now, after a parameter upload)
     int rc = e->WeP ? SDRM_OK : ensure_tables(e, st);   // (T <= 128: the forward makes its users' rows of the table itself)
@@ -1651,101 +1585,73 @@ int sdrm_train_forward(sdrm_engine* e, const float* x0, int B, int64_t row0, int
       rc = launch_sk_step(e, ka, 0, ka.G, st);
       if (rc) return rc;
     }
-    e->cur_sk_np = ka.NP;
-    if (!e->fold_sums) {
-      SDRM_LAUNCH(e, k_loss_sums, dim3(1), dim3(256), 0, st, (const double*)e->loss_part, ka.NP, (double)B * (double)e->L,
-                         sums ? sums : e->sums);
-      HIP_TRY(e, hipGetLastError());
-    }
-    e->cur_B = B; e->cur_MP = round_up(SK_ROWS * ka.G, BM); e->cur_rows = SK_ROWS * ka.G; e->cur_x0 = x0; e->cur_sk = true; e->fwd_done = true;
-    return SDRM_OK;
-  }
-
-  if (use_rowchain(e, B)) {
-    // row-owned forward (rowchain.h): the step's tables (the launch also pulls the batch into L2), then staging + every layer +
-    // the loss partial sums in ONE launch
+    p.loss_parts = ka.NP;
+  } else if (p.path == StepPlan::ROW96 || p.path == StepPlan::ROW48) {
+    // row-owned forward (rowchain.h; rows48.h: the same on 48-row work-groups, p.parts of them per row group): the step's tables
+    // (the launch also pulls the batch into L2), then staging + every layer + the loss partial sums in ONE launch
     int rc = emb_tables(e, st, x0, (size_t)B * e->L);
     if (rc) return rc;
-    const int G = (B + RC_USERS - 1) / RC_USERS, MPg = round_up(G * RC_ROWS, BM);
-    rc = launch_row_forward(e, x0, B, row0, mode, rnd, seed, step, nd, G, st);
+    rc = launch_row_forward(e, p, x0, row0, mode, rnd, seed, step, nd, st);
     if (rc) return rc;
-    if (!e->fold_sums) {
-      SDRM_LAUNCH(e, k_loss_sums, dim3(1), dim3(256), 0, st, (const double*)e->loss_part, G, (double)B * (double)e->L,
-                         sums ? sums : e->sums);
+    e->hold_needed = true;
+  } else {
+    const int MP = p.MP, n = e->T + 1;
+    const int cfg = choose_cfg(e->tune, MP, e->tune.nt32_max_rows_train);   // one tile for every NT launch of the step
+    PrepTrainArgs pa{};
+    pa.x0 = x0;
+    if (mode == SDRM_RNG_EXPLICIT) { pa.noise = rnd->noise; pa.t = rnd->t; pa.keep = rnd->keep; }
+    pa.sqrt_ab = e->sched + 3 * n; pa.one_minus_ab = e->sched + 4 * n; pa.tembP = e->tembP;
+    pa.U = e->U; pa.tdev = e->tdev;
+    pa.B = B; pa.L = e->L; pa.LP = e->LP; pa.K0 = e->K0; pa.T = e->T; pa.MP = MP;
+    pa.mode = mode; pa.seed_lo = (uint32_t)seed; pa.seed_hi = (uint32_t)(seed >> 32); pa.step = (uint32_t)step;
+    pa.row0 = row0; pa.nd = nd;
+    {
+      // the step's tables ride on the staging launch: C0^T in the trailing columns of W0c (what the plain sdrm_forward multiplies its
+      // one-hot(t) columns with) and B0tab = b0 + C0[t], which layer 0 below adds per row
+      pa.emb = emb_args(e);
+      e->tables_fresh = true;
+      pa.emb_row0 = B + (MP - 3 * B);
+      pa.emb_chunks = (e->WP + 63) / 64;
+      pa.emb_blocks = (e->T + 1) * pa.emb_chunks;
+      const int main_blocks = (int)(((int64_t)pa.emb_row0 * (e->K0 / 4) + 255) / 256);
+      SDRM_LAUNCH(e, k_prep_train, dim3(pa.emb_blocks + main_blocks), dim3(256), 2 * e->T * sizeof(float), st, pa);
       HIP_TRY(e, hipGetLastError());
     }
-    e->cur_B = B; e->cur_MP = MPg; e->cur_rows = G * RC_ROWS; e->cur_x0 = x0; e->cur_grouped = true; e->cur_act = true; e->fwd_done = true;
-    e->hold_needed = true;
-    return SDRM_OK;
-  }
-
-  if (const int parts = rows48_parts(e, B)) {
-    // the same on 48-row work-groups (rows48.h; `parts` of them per row group): tables, then ONE launch
-    int rc = emb_tables(e, st, x0, (size_t)B * e->L);
-    if (rc) return rc;
-    const int G = (B + R48_USERS - 1) / R48_USERS, MPg = round_up(G * R48_ROWS, BM);
-    rc = launch_row_forward(e, x0, B, row0, mode, rnd, seed, step, nd, G, st, parts);
-    if (rc) return rc;
-    if (!e->fold_sums) {
-      SDRM_LAUNCH(e, k_loss_sums, dim3(1), dim3(256), 0, st, (const double*)e->loss_part, G * parts, (double)B * (double)e->L,
-                         sums ? sums : e->sums);
-      HIP_TRY(e, hipGetLastError());
+    {
+      // Layer 0 contracts over the latent columns only (K = LP instead of LP + TP: a fifth less work at ML-1M): every row's
+      // time-embedding term is a row of B0tab, added in the epilogue.  The trailing columns of U carry temb[t_row] (round 4; before: a
+      // one-hot(t)): the layer-0 weight gradient multiplies them to deliver M = dpre0^T * temb (csrc/tail.h).
+      GemmArgs a{};
+      a.C = pre_buf(e, 0); a.ldc = e->WP; a.bias = e->B0tab; a.ldtab = e->WP; a.trow = e->tdev; a.trow_B = B;
+      HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_ROWTAB>(a, e->U, e->K0, e->W0c, e->K0, MP, e->WP, e->LP, st,
+                                                         Prof{e, PC_FWD_L0, 2.0 * 3 * B * (double)e->W * e->L}, cfg)));   // K = the latents: the time-embedding term is a table row
     }
-    e->cur_B = B; e->cur_MP = MPg; e->cur_rows = G * R48_ROWS; e->cur_x0 = x0; e->cur_g16 = true; e->cur_parts = parts; e->cur_act = true;
-    e->hold_needed = true;
-    e->fwd_done = true;
-    return SDRM_OK;
-  }
-
-  PrepTrainArgs pa{};
-  pa.x0 = x0;
-  if (mode == SDRM_RNG_EXPLICIT) { pa.noise = rnd->noise; pa.t = rnd->t; pa.keep = rnd->keep; }
-  pa.sqrt_ab = e->sched + 3 * n; pa.one_minus_ab = e->sched + 4 * n; pa.tembP = e->tembP;
-  pa.U = e->U; pa.tdev = e->tdev;
-  pa.B = B; pa.L = e->L; pa.LP = e->LP; pa.K0 = e->K0; pa.T = e->T; pa.MP = MP;
-  pa.mode = mode; pa.seed_lo = (uint32_t)seed; pa.seed_hi = (uint32_t)(seed >> 32); pa.step = (uint32_t)step;
-  pa.row0 = row0; pa.nd = nd;
-  {
-    // the step's tables ride on the staging launch: C0^T in the trailing columns of W0c (what the plain sdrm_forward multiplies its
-    // one-hot(t) columns with) and B0tab = b0 + C0[t], which layer 0 below adds per row
-    pa.emb = emb_args(e);
-    e->tables_fresh = true;
-    pa.emb_row0 = B + (MP - 3 * B);
-    pa.emb_chunks = (e->WP + 63) / 64;
-    pa.emb_blocks = (e->T + 1) * pa.emb_chunks;
-    const int main_blocks = (int)(((int64_t)pa.emb_row0 * (e->K0 / 4) + 255) / 256);
-    SDRM_LAUNCH(e, k_prep_train, dim3(pa.emb_blocks + main_blocks), dim3(256), 2 * e->T * sizeof(float), st, pa);
+    int rc = hidden_forward(e, MP, 3 * B, st, cfg);
+    if (rc) return rc;
+    {
+      GemmArgs a{};
+      a.C = e->Y; a.ldc = e->LP; a.bias = e->boc; a.slopeA = slope_ptr(e, e->H);
+      a.rows_valid = MP; a.cols_valid = e->LP;
+      HIP_TRY(e, (gemm_forward<XF_PRELU, EPI_BIAS_TANH>(a, pre_buf(e, e->H), e->WP, e->Woc, e->WP, MP, e->LP, e->WP, st,
+                                                        Prof{e, PC_FWD_OUT, 2.0 * 3 * B * (double)e->L * e->W}, cfg)));
+    }
+    LossArgs la{};
+    la.Y = e->Y; la.x0 = x0; la.B = B; la.L = e->L; la.LP = e->LP; la.part = e->loss_part;
+    SDRM_LAUNCH(e, k_loss_partials, dim3(LOSS_BLOCKS), dim3(1024), 0, st, la);
     HIP_TRY(e, hipGetLastError());
   }
-  {
-    // Layer 0 contracts over the latent columns only (K = LP instead of LP + TP: a fifth less work at ML-1M): every row's
-    // time-embedding term is a row of B0tab, added in the epilogue.  The trailing columns of U carry temb[t_row] (round 4; before: a
-    // one-hot(t)): the layer-0 weight gradient multiplies them to deliver M = dpre0^T * temb (csrc/tail.h).
-    GemmArgs a{};
-    a.C = pre_buf(e, 0); a.ldc = e->WP; a.bias = e->B0tab; a.ldtab = e->WP; a.trow = e->tdev; a.trow_B = B;
-    HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_ROWTAB>(a, e->U, e->K0, e->W0c, e->K0, MP, e->WP, e->LP, st,
-                                                       Prof{e, PC_FWD_L0, 2.0 * 3 * B * (double)e->W * e->L}, cfg)));   // K = the latents: the time-embedding term is a table row
-  }
-  int rc = hidden_forward(e, MP, 3 * B, st, cfg);
-  if (rc) return rc;
-  {
-    GemmArgs a{};
-    a.C = e->Y; a.ldc = e->LP; a.bias = e->boc; a.slopeA = slope_ptr(e, e->H);
-    a.rows_valid = MP; a.cols_valid = e->LP;
-    HIP_TRY(e, (gemm_forward<XF_PRELU, EPI_BIAS_TANH>(a, pre_buf(e, e->H), e->WP, e->Woc, e->WP, MP, e->LP, e->WP, st,
-                                                      Prof{e, PC_FWD_OUT, 2.0 * 3 * B * (double)e->L * e->W}, cfg)));
-  }
-  LossArgs la{};
-  la.Y = e->Y; la.x0 = x0; la.B = B; la.L = e->L; la.LP = e->LP; la.part = e->loss_part;
-  SDRM_LAUNCH(e, k_loss_partials, dim3(LOSS_BLOCKS), dim3(1024), 0, st, la);
-  HIP_TRY(e, hipGetLastError());
-  if (!e->fold_sums) {
-    SDRM_LAUNCH(e, k_loss_sums, dim3(1), dim3(256), 0, st, (const double*)e->loss_part, LOSS_BLOCKS,
-                       (double)B * (double)e->L, sums ? sums : e->sums);
+  if (!fold_sums) {
+    SDRM_LAUNCH(e, k_loss_sums, dim3(1), dim3(256), 0, st, (const double*)e->loss_part, p.loss_parts, (double)B * (double)e->L,
+                       sums ? sums : e->sums);
     HIP_TRY(e, hipGetLastError());
   }
-  e->cur_B = B; e->cur_MP = MP; e->cur_x0 = x0; e->fwd_done = true;
+  e->fwd_x0 = x0; e->fwd_done = true;
   return SDRM_OK;
+}
+
+int sdrm_train_forward(sdrm_engine* e, const float* x0, int B, int64_t row0, int mode, const sdrm_train_randoms* rnd,
+                       uint64_t seed, uint64_t step, float nd, double* sums, void* stream) {
+  return train_forward_impl(e, x0, B, row0, mode, rnd, seed, step, nd, sums, stream, false);
 }
 
 // Backward in two calls, so that a data-parallel caller can all-reduce one gradient bucket while the other is
@@ -1759,112 +1665,90 @@ int sdrm_train_forward(sdrm_engine* e, const float* x0, int B, int64_t row0, int
 namespace {
 
 // loss seeds, the dgrad chain down to layer 0, and the layer-0 weight gradient (whose time-embedding columns deliver M, csrc/tail.h)
-int backward_chain(sdrm_engine* e, const double* sums, float* loss, hipStream_t st, bool with_wgrad0) {
-  const int B = e->cur_B, MP = e->cur_MP, H = e->H;
+int backward_chain(sdrm_engine* e, const double* sums, float* loss, hipStream_t st, bool with_wgrad0, bool fold_sums) {
+  const StepPlan& p = e->plan;
+  const int B = p.B, MP = p.MP, H = e->H;
   e->bwd_strips = false;
   SeedArgs sa{};
-  sa.sums = e->fold_sums ? nullptr : (sums ? sums : e->sums); sa.Y = e->Y; sa.x0 = e->cur_x0; sa.dY = e->dY; sa.loss = loss;
-  sa.B = B; sa.L = e->L; sa.LP = e->LP; sa.MP = MP; sa.grouped = (e->cur_sk || e->cur_g16) ? 2 : (e->cur_grouped ? 1 : 0);
+  sa.sums = fold_sums ? nullptr : (sums ? sums : e->sums); sa.Y = e->Y; sa.x0 = e->fwd_x0; sa.dY = e->dY; sa.loss = loss;
+  sa.B = B; sa.L = e->L; sa.LP = e->LP; sa.MP = MP; sa.grouped = p.order;
   sa.part = e->loss_part;
-  sa.nblk = e->cur_grouped ? (B + RC_USERS - 1) / RC_USERS : (e->cur_g16 ? e->cur_parts * ((B + R48_USERS - 1) / R48_USERS) : LOSS_BLOCKS);
+  sa.nblk = p.loss_parts;
   sa.count = (double)B * (double)e->L;
-  // the row-owned chain (dgrad_rows.h) computes the seeds itself; every other path launches k_loss_seed
-  const bool chain48 = e->cur_g16 && e->WhfT && e->tune.dgrad_rows > 0 && e->LP == e->WP && H + 1 <= DR_MAX_LAYERS;
-  const bool chain = chain48 || (use_dgrad_rows(e, MP) && e->tune.dgrad_rows == 1 && H + 1 <= DR_MAX_LAYERS);
-  if (!chain && !e->cur_sk) {
-    const int nslots = e->cur_grouped ? RC_USERS * ((B + RC_USERS - 1) / RC_USERS) : (e->cur_g16 ? R48_USERS * ((B + R48_USERS - 1) / R48_USERS) : B);
+  // the row-owned chain (dgrad_rows.h) and the narrow nets' backward compute the seeds themselves; every other form launches k_loss_seed
+  if (p.dgrad == StepPlan::TILES || p.dgrad == StepPlan::ROWS_PER_LAYER) {
+    const int nslots = p.groups * p.users_per_group;
     const unsigned need = (unsigned)(((size_t)(nslots + (MP - 3 * nslots)) * (e->LP / 4) + 255) / 256);
     dim3 grid(std::min(need, 2048u));   // grid-stride beyond: see k_loss_seed
     SDRM_LAUNCH(e, k_loss_seed, grid, dim3(256), 0, st, sa);
     HIP_TRY(e, hipGetLastError());
   }
-  int S0, SH, SO, kc0, kcH, kcO;
+  int S0, kc0;
   pick_splits(e->tune, MP, wgrad_tiles(e->tune, e->WP, e->K0) + H * wgrad_tiles(e->tune, e->WP, e->WP) + wgrad_tiles(e->tune, e->LP, e->WP),
               S0, kc0);
-  SH = SO = S0; kcH = kcO = kc0;
-  // every dgrad writes [MP,WP]: one tile shape for all of them, so the slope partial counts agree
-  const int cfg_d = choose_cfg(e->tune, MP, e->tune.nt32_max_rows_train);
   const int cfg_w = pick_cfg(e->tune);   // tile of every split-K launch of this backward (backward_wgrads reuses it)
   e->bwd_cfg_w = cfg_w;
-  const int dgrad_blocks = ((MP + kCfgBM[cfg_d] - 1) / kCfgBM[cfg_d]) * ((e->WP + kCfgBN[cfg_d] - 1) / kCfgBN[cfg_d]);
   const double flO = 2.0 * 3 * B * (double)e->L * e->W, flH = 2.0 * 3 * B * (double)e->W * e->W;
   const double fl0 = 2.0 * 3 * B * (double)e->W * (e->L + e->T);
   e->bwd_hidden_apps = H;
-  if (e->cur_sk) {
-    // narrow net (csrc/skinny_step.h): the sums' fold, the loss value, the seeds, the whole dgrad chain AND every weight / bias /
-    // slope gradient of a work-group's users in one launch; one slab set per work-group (the hidden layer's applications already
-    // summed), at most S_MAX of them - a work-group then walks several groups of users
-    SkStepArgs ka = sk_step_args(e, B);
-    ka.NP = e->cur_sk_np;
-    ka.x0 = e->cur_x0; ka.sums = sa.sums; ka.count = sa.count; ka.loss = loss;
-    const int S = std::min(ka.G, S_MAX);
-    int rc = launch_sk_step(e, ka, 1, S, st);
-    if (rc) return rc;
-    e->bwd_S0 = e->bwd_SH = e->bwd_SO = S; e->bwd_hidden_apps = 1; e->bwd_dgrad_blocks = S;
-    e->bwd_kc0 = e->bwd_kcH = e->bwd_kcO = 0;
-    return SDRM_OK;
-  }
-  if (chain48) {
-    // one work-group per 48 stacked rows runs the whole chain (csrc/rows48.h): one slope partial per work-group and layer
-    DgradChain48Args c8{};
-    DgradChainArgs& ca = c8.c;
-    ca.seed = sa; ca.nlayers = H + 1;
-    ca.layer[0] = dgrad_rows_args(e, e->dY, e->WofT, pre_buf(e, H), slope_ptr(e, H), dpre_buf(e, H), e->alpha_part + (size_t)H * e->alpha_part_stride);
-    for (int k = H; k >= 1; --k)
-      ca.layer[H + 1 - k] = dgrad_rows_args(e, dpre_buf(e, k), e->WhfT, pre_buf(e, k - 1), slope_ptr(e, k - 1), dpre_buf(e, k - 1),
-                                            e->alpha_part + (size_t)(k - 1) * e->alpha_part_stride);
-    const int Gn = e->cur_rows / R48_ROWS;
-    c8.pad_rows = MP - e->cur_rows;
-    int rc = launch_rows48_chain(e, c8, Gn, e->cur_parts, flO + H * flH, st);
-    if (rc) return rc;
-    if (with_wgrad0)
-      HIP_TRY(e, (gemm_wgrad<XF_NONE>(dpre_buf(e, 0), e->WP, e->WP, e->U, e->K0, e->K0, nullptr, MP, S0, kc0, e->slab0, e->db0s, st,
-                                      Prof{e, PC_WGRAD_L0, fl0}, cfg_w)));
-    e->bwd_kc0 = kc0;
-    e->bwd_S0 = S0; e->bwd_SH = SH; e->bwd_SO = SO; e->bwd_dgrad_blocks = Gn * e->cur_parts;
-    e->bwd_kcH = kcH; e->bwd_kcO = kcO;
-    return SDRM_OK;
-  }
-  if (use_dgrad_rows(e, MP)) {
-    // one work-group per 96 stacked rows (and layer): one slope partial per work-group
-    int rc = SDRM_OK;
-    if (chain) {
-      DgradChainArgs ca{};
-      ca.seed = sa; ca.nlayers = H + 1;
-      ca.layer[0] = dgrad_rows_args(e, e->dY, e->WofT, pre_buf(e, H), slope_ptr(e, H), dpre_buf(e, H), e->alpha_part + (size_t)H * e->alpha_part_stride);
-      for (int k = H; k >= 1; --k)
-        ca.layer[H + 1 - k] = dgrad_rows_args(e, dpre_buf(e, k), e->WhfT, pre_buf(e, k - 1), slope_ptr(e, k - 1), dpre_buf(e, k - 1),
-                                              e->alpha_part + (size_t)(k - 1) * e->alpha_part_stride);
-      rc = launch_dgrad_chain(e, ca, MP, flO + H * flH, st);
-    } else {
-      rc = launch_dgrad_rows(e, e->dY, e->WofT, pre_buf(e, H), slope_ptr(e, H), dpre_buf(e, H),
-                             e->alpha_part + (size_t)H * e->alpha_part_stride, MP, flO, st);
+  int dgrad_blocks = 0;   // work-groups of a dgrad launch: each leaves one slope partial per layer
+  switch (p.dgrad) {
+    case StepPlan::SKINNY_OWN: {
+      // narrow net (csrc/skinny_step.h): the sums' fold, the loss value, the seeds, the whole dgrad chain AND every weight / bias /
+      // slope gradient of a work-group's users in one launch; one slab set per work-group (the hidden layer's applications already
+      // summed), at most S_MAX of them - a work-group then walks several groups of users
+      SkStepArgs ka = sk_step_args(e, B);
+      ka.NP = p.loss_parts;
+      ka.x0 = e->fwd_x0; ka.sums = sa.sums; ka.count = sa.count; ka.loss = loss;
+      const int S = std::min(ka.G, S_MAX);
+      int rc = launch_sk_step(e, ka, 1, S, st);
+      if (rc) return rc;
+      e->bwd_S0 = e->bwd_SH = e->bwd_SO = S; e->bwd_hidden_apps = 1; e->bwd_dgrad_blocks = S;
+      e->bwd_kc0 = e->bwd_kcH = e->bwd_kcO = 0;
+      return SDRM_OK;
+    }
+    case StepPlan::CHAIN: {
+      // one work-group per 96 stacked rows - or `parts` per 48 (csrc/rows48.h) - runs the whole chain: one slope partial per work-group and layer
+      DgradChain48Args c8{};
+      dgrad_chain_args(e, sa, c8.c);
+      c8.pad_rows = MP - p.rows;
+      dgrad_blocks = p.groups * p.parts;
+      int rc = p.path == StepPlan::ROW48 ? launch_rows48_chain(e, c8, p.groups, p.parts, flO + H * flH, st)
+                                         : launch_dgrad_chain(e, c8.c, p.groups, flO + H * flH, st);
+      if (rc) return rc;
+      break;
+    }
+    case StepPlan::ROWS_PER_LAYER: {
+      // one work-group per 96 stacked rows (and layer): one slope partial per work-group
+      dgrad_blocks = p.groups;
+      int rc = launch_dgrad_rows(e, e->dY, e->WofT, pre_buf(e, H), slope_ptr(e, H), dpre_buf(e, H),
+                                 e->alpha_part + (size_t)H * e->alpha_part_stride, p.groups, flO, st);
       for (int k = H; k >= 1 && !rc; --k)
         rc = launch_dgrad_rows(e, dpre_buf(e, k), e->WhfT, pre_buf(e, k - 1), slope_ptr(e, k - 1), dpre_buf(e, k - 1),
-                               e->alpha_part + (size_t)(k - 1) * e->alpha_part_stride, MP, flH, st);
+                               e->alpha_part + (size_t)(k - 1) * e->alpha_part_stride, p.groups, flH, st);
+      if (rc) return rc;
+      break;
     }
-    if (rc) return rc;
-    if (with_wgrad0)
-      HIP_TRY(e, (gemm_wgrad<XF_NONE>(dpre_buf(e, 0), e->WP, e->WP, e->U, e->K0, e->K0, nullptr, MP, S0, kc0, e->slab0, e->db0s, st,
-                                      Prof{e, PC_WGRAD_L0, fl0}, cfg_w)));
-    e->bwd_kc0 = kc0;
-    e->bwd_S0 = S0; e->bwd_SH = SH; e->bwd_SO = SO; e->bwd_dgrad_blocks = MP / RC_ROWS;
-    e->bwd_kcH = kcH; e->bwd_kcO = kcO;
-    return SDRM_OK;
+    case StepPlan::TILES: {
+      // every dgrad writes [MP,WP]: one tile shape for all of them, so the slope partial counts agree
+      const int cfg_d = choose_cfg(e->tune, MP, e->tune.nt32_max_rows_train);
+      dgrad_blocks = ((MP + kCfgBM[cfg_d] - 1) / kCfgBM[cfg_d]) * ((e->WP + kCfgBN[cfg_d] - 1) / kCfgBN[cfg_d]);
+      // dpre[k] = gradient w.r.t. pre-activation k (kept for the weight gradients that run later)
+      HIP_TRY(e, gemm_dgrad(e, e->dY, e->LP, e->WocT, e->LP, MP, e->LP, e->WP, dpre_buf(e, H), pre_buf(e, H), slope_ptr(e, H),
+                            e->alpha_part + (size_t)H * e->alpha_part_stride, st, flO, cfg_d));
+      for (int k = H; k >= 1; --k)
+        HIP_TRY(e, gemm_dgrad(e, dpre_buf(e, k), e->WP, e->WhcT, e->WP, MP, e->WP, e->WP, dpre_buf(e, k - 1), pre_buf(e, k - 1),
+                              slope_ptr(e, k - 1), e->alpha_part + (size_t)(k - 1) * e->alpha_part_stride, st, flH, cfg_d));
+      break;
+    }
   }
-  // dpre[k] = gradient w.r.t. pre-activation k (kept for the weight gradients that run later)
-  HIP_TRY(e, gemm_dgrad(e, e->dY, e->LP, e->WocT, e->LP, MP, e->LP, e->WP, dpre_buf(e, H), pre_buf(e, H), slope_ptr(e, H),
-                        e->alpha_part + (size_t)H * e->alpha_part_stride, st, flO, cfg_d));
-  for (int k = H; k >= 1; --k)
-    HIP_TRY(e, gemm_dgrad(e, dpre_buf(e, k), e->WP, e->WhcT, e->WP, MP, e->WP, e->WP, dpre_buf(e, k - 1), pre_buf(e, k - 1),
-                          slope_ptr(e, k - 1), e->alpha_part + (size_t)(k - 1) * e->alpha_part_stride, st, flH, cfg_d));
   // layer 0 (no latent dgrad: XT.grad is never read, Q7)
   if (with_wgrad0)
     HIP_TRY(e, (gemm_wgrad<XF_NONE>(dpre_buf(e, 0), e->WP, e->WP, e->U, e->K0, e->K0, nullptr, MP, S0, kc0, e->slab0, e->db0s, st,
                                     Prof{e, PC_WGRAD_L0, fl0}, cfg_w)));
-  e->bwd_kc0 = kc0;
-  e->bwd_S0 = S0; e->bwd_SH = SH; e->bwd_SO = SO; e->bwd_dgrad_blocks = dgrad_blocks;
-  e->bwd_kcH = kcH; e->bwd_kcO = kcO;
+  // ONE slice count for every weight gradient of this backward (pick_splits)
+  e->bwd_S0 = e->bwd_SH = e->bwd_SO = S0; e->bwd_kc0 = e->bwd_kcH = e->bwd_kcO = kc0;
+  e->bwd_dgrad_blocks = dgrad_blocks;
   return SDRM_OK;
 }
 
@@ -1873,8 +1757,9 @@ int backward_chain(sdrm_engine* e, const double* sums, float* loss, hipStream_t 
 // dgrad chain is done.  More problems than a batch holds (H > 6) go in several batches; a forced tile shape
 // (SDRM_TILE) falls back to one launch per layer.
 int backward_wgrads(sdrm_engine* e, hipStream_t st, bool with_wgrad0) {
-  if (e->cur_sk) return SDRM_OK;   // the narrow nets' backward launch has left every weight gradient in its slabs
-  const int B = e->cur_B, MP = e->cur_MP, H = e->H, SH = e->bwd_SH, SO = e->bwd_SO;
+  const StepPlan& p = e->plan;
+  if (p.path == StepPlan::SKINNY) return SDRM_OK;   // the narrow nets' backward launch has left every weight gradient in its slabs
+  const int B = p.B, MP = p.MP, H = e->H, SH = e->bwd_SH, SO = e->bwd_SO;
   const double flO = 2.0 * 3 * B * (double)e->L * e->W, flH = 2.0 * 3 * B * (double)e->W * e->W;
   const double fl0 = 2.0 * 3 * B * (double)e->W * (e->L + e->T);
   if (e->bwd_cfg_w > 0) {   // a forced tile other than the default: the batched kernel is built for the default only
@@ -1890,7 +1775,7 @@ int backward_wgrads(sdrm_engine* e, hipStream_t st, bool with_wgrad0) {
                                        e->dbHs + (size_t)(k - 1) * SH * e->WP, st, Prof{e, PC_WGRAD, flH}, cfg_w)));
     return SDRM_OK;
   }
-  if (with_wgrad0 && use_strips(e)) return launch_wgrad_strips(e, MP, fl0 + flO + H * flH, st);
+  if (with_wgrad0 && p.strips_ok) return launch_wgrad_strips(e, fl0 + flO + H * flH, st);
   std::vector<WgradSpec> w;
   std::vector<double> fl;
   if (with_wgrad0) {
@@ -1898,7 +1783,7 @@ int backward_wgrads(sdrm_engine* e, hipStream_t st, bool with_wgrad0) {
     fl.push_back(fl0);
   }
   // operand of the upper layers' weight gradients: the stored pre-activation (PReLU on load), or the activation itself
-  const bool plain = e->cur_act;
+  const bool plain = p.acts_stored;
   auto opnd = [&](int k) { return plain ? e->act + (size_t)k * e->MPmax * e->WP : pre_buf(e, k); };
   w.push_back(WgradSpec{e->dY, e->LP, e->LP, opnd(H), e->WP, e->WP, slope_ptr(e, H), SO, e->bwd_kcO, e->slabO, e->dbOs});
   fl.push_back(flO);
@@ -2026,7 +1911,7 @@ int sdrm_train_backward_begin(sdrm_engine* e, const double* sums, float* grad, f
   e->bwd_begun = false;
   float* gout = grad ? grad : e->g;
   e->grad_src = gout;
-  int rc = backward_chain(e, sums, loss, st, true);
+  int rc = backward_chain(e, sums, loss, st, true, false);
   if (!rc) rc = backward_tail(e, gout, BUCKET_FIRST, false, 0.f, st);
   if (rc) return rc;
   e->bwd_begun = true;
@@ -2051,11 +1936,12 @@ int sdrm_train_backward_finish(sdrm_engine* e, float* grad, void* stream) {
 // (Round 5 measured the single-GPU tail as two concurrent halves - the hidden / output layers' jobs on an auxiliary stream beside layer 0's
 // jobs + k_tail_emb, optionally + the next step's k_emb_tables: the fork and the join cost more than the overlap gains on this runtime,
 // train step 450.7 -> 467.3 / 457.4 us at B = 8192, 72.8 -> 98.9 at B = 160, ADM 47.2 -> 66.4: profiles/r05_tail_split.txt.)
-static int train_backward_impl(sdrm_engine* e, const double* sums, float* grad, float* loss, hipStream_t st, const float* fused_lr) {
+static int train_backward_impl(sdrm_engine* e, const double* sums, float* grad, float* loss, hipStream_t st, const float* fused_lr,
+                               bool fold_sums) {
   e->bwd_begun = false;
   float* gout = grad ? grad : e->g;
   e->grad_src = gout;
-  int rc = backward_chain(e, sums, loss, st, false);
+  int rc = backward_chain(e, sums, loss, st, false, fold_sums);
   if (!rc) rc = backward_wgrads(e, st, true);
   if (!rc) rc = hold_point(e, st);
   if (!rc) rc = backward_tail(e, gout, BUCKET_BOTH, fused_lr != nullptr, fused_lr ? *fused_lr : 0.f, st);
@@ -2065,7 +1951,7 @@ static int train_backward_impl(sdrm_engine* e, const double* sums, float* grad, 
 int sdrm_train_backward(sdrm_engine* e, const double* sums, float* grad, float* loss, void* stream) {
   if (!e) return SDRM_ERR_ARG;
   if (!e->fwd_done) return fail(e, SDRM_ERR_STATE, "sdrm_train_backward: no forward to back-propagate");
-  return train_backward_impl(e, sums, grad, loss, (hipStream_t)stream, nullptr);
+  return train_backward_impl(e, sums, grad, loss, (hipStream_t)stream, nullptr, false);
 }
 
 int sdrm_grad_buckets(const sdrm_engine* e, int64_t* first_off, int64_t* first_len, int64_t* second_off, int64_t* second_len) {
@@ -2085,14 +1971,12 @@ int sdrm_adam_step(sdrm_engine* e, const float* grad, float lr, void* stream) {
 int sdrm_train_step(sdrm_engine* e, const float* x0, int B, float lr, int mode, const sdrm_train_randoms* rnd,
                     uint64_t seed, uint64_t step, float nd, float* loss, void* stream) {
   if (!e) return SDRM_ERR_ARG;
-  e->fold_sums = true;    // one process, one GPU: nobody needs the five sums between the forward and the backward ...
-  int rc = sdrm_train_forward(e, x0, B, 0, mode, rnd, seed, step, nd, nullptr, stream);
-  e->fold_sums = false;
+  // one process, one GPU: nobody needs the five sums between the forward and the backward (fold_sums: the seed kernel folds the
+  // loss partials itself) ...
+  int rc = train_forward_impl(e, x0, B, 0, mode, rnd, seed, step, nd, nullptr, stream, true);
   if (rc) return rc;
-  e->fold_sums = true;
   e->adam_t += 1;         // ... nor the flat gradient between the backward and Adam: the tail applies it (csrc/tail.h)
-  rc = train_backward_impl(e, nullptr, nullptr, loss, (hipStream_t)stream, &lr);
-  e->fold_sums = false;
+  rc = train_backward_impl(e, nullptr, nullptr, loss, (hipStream_t)stream, &lr, true);
   if (rc) e->adam_t -= 1;
   return rc;
 }
@@ -2235,8 +2119,8 @@ int sdrm_get_train_outputs(const sdrm_engine* e, float* psq, void* stream) {
   if (!e || !psq) return SDRM_ERR_ARG;
   sdrm_engine* me = const_cast<sdrm_engine*>(e);
   if (!e->fwd_done) return fail(me, SDRM_ERR_STATE, "sdrm_get_train_outputs: no forward yet");
-  SDRM_LAUNCH(e, k_unpad_psq, dim3(256), dim3(256), 0, (hipStream_t)stream, (const float*)e->Y, e->cur_B, e->L,
-                     e->LP, (e->cur_sk || e->cur_g16) ? 2 : (e->cur_grouped ? 1 : 0), psq);
+  SDRM_LAUNCH(e, k_unpad_psq, dim3(256), dim3(256), 0, (hipStream_t)stream, (const float*)e->Y, e->plan.B, e->L,
+                     e->LP, e->plan.order, psq);
   HIP_TRY(me, hipGetLastError());
   return SDRM_OK;
 }
@@ -2492,17 +2376,11 @@ int launch_sample_persist(sdrm_engine* e, SampleState& s, int count, hipStream_t
   e->xphaseS += (uint32_t)(steps * (e->H + 2));
   const int grid = 8 * tiles_n * ((tiles_m + 7) / 8);
   const double flops = 2.0 * s.n * ((double)e->W * e->L + (double)e->H * e->W * e->W + (double)e->L * e->W) * steps;
-  const bool rec = e->prof_on && (int)e->prof_cls.size() < e->prof_cap && (e->prof_only < 0 || e->prof_only == PC_SMP_PERSIST);
-  size_t slot = 0;
-  if (rec) {
-    slot = e->prof_cls.size();
-    e->prof_cls.push_back(PC_SMP_PERSIST);
-    e->prof_flops.push_back(flops);
-    HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot], st));
-  }
-  SDRM_LAUNCH(e, (k_sample_persist<Cfg4>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, P);
-  HIP_TRY(e, hipGetLastError());
-  if (rec) HIP_TRY(e, hipEventRecord(e->prof_ev[2 * slot + 1], st));
+  const int rc = hip_rc(e, "k_sample_persist", profiled(e, PC_SMP_PERSIST, flops, st, [&] {
+    SDRM_LAUNCH(e, (k_sample_persist<Cfg4>), dim3((unsigned)grid), dim3(NTHREADS), 0, st, P);
+    return hipGetLastError();
+  }));
+  if (rc) return rc;
   s.i_next -= steps;
   return SDRM_OK;
 }
@@ -2659,9 +2537,9 @@ int sdrm_get_preacts(const sdrm_engine* e, int layer, float* out, void* stream) 
   if (!e->fwd_params_live)
     return fail(me, SDRM_ERR_STATE, "sdrm_get_preacts: the parameters have changed since the train forward (Adam step or sdrm_set_params): "
                                     "its pre-activations are gone");
-  const float* actl = (e->cur_act && e->cur_skip_pre && e->act) ? e->act + (size_t)layer * e->MPmax * e->WP : nullptr;
+  const float* actl = (e->plan.skip_pre() && e->act) ? e->act + (size_t)layer * e->MPmax * e->WP : nullptr;
   SDRM_LAUNCH(e, k_unpad_pre, dim3(256), dim3(256), 0, (hipStream_t)stream, (const float*)pre_buf(me, layer), actl,
-                     (const float*)slope_ptr(me, layer), e->cur_B, e->W, e->WP, (e->cur_sk || e->cur_g16) ? 2 : (e->cur_grouped ? 1 : 0), out);
+                     (const float*)slope_ptr(me, layer), e->plan.B, e->W, e->WP, e->plan.order, out);
   HIP_TRY(me, hipGetLastError());
   return SDRM_OK;
 }

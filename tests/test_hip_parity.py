@@ -421,7 +421,7 @@ def row_group_steps_are_reproducible(engine_cls, dims, path, lr=1e-3):
 # to four real k in its last padded K-step of 16 takes the compact form (rc_light_klast, csrc/elementwise.h), any other the plain one.
 # H in {0, 1, 2} spread over the list.  B = 370: 24 groups of 16 users (the last one holds 2) on the 48-row kernels; 12 groups of 32 users
 # (the last one holds 18) on the 96-row ones - an even count, so their stacked rows are whole 96-row groups and the row-owned dgrads
-# (k_dgrad_chain) follow the forward (csrc/sdrm_hip.hip: row_dgrads_follow), which B = 333 with its 11 groups would not reach.
+# (k_dgrad_chain) follow the forward (csrc/sdrm_hip.hip: plan_step), which B = 333 with its 11 groups would not reach.
 CT_BATCH = 370
 # The learning rate of the four-step comparison with the per-layer path.  Its measure - the parameters after four Adam steps - is not
 # a smooth function of the gradients: Adam's update lr g / (|g| + eps) has the slope lr / eps = 1e5 lr at g = 0, so ONE element whose
@@ -884,7 +884,7 @@ def test_preactivations_after_a_whole_step(engine_cls, slopes, path):
     lr = 1e-2, slope 0.25), or, once a slope had crossed 1e-6, a buffer that forward never wrote.  The library now refuses such a read
     (SDRM_ERR_STATE); a read that is answered - any read, on any path - must be the forward's own values, bit for bit: engine `a`
     runs the three phases, engine `b` the one-call step from the same inputs (the same forward kernel; what it stores is decided
-    from path and shape alone, csrc/sdrm_hip.hip: row_dgrads_follow)."""
+    from path and shape alone, csrc/sdrm_hip.hip: plan_step)."""
     from sdrm_amd.engine import SdrmError
     L, W, T, H, B = 136, 136, 12, 2, 150
     lr = 1e-2

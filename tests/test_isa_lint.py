@@ -11,7 +11,8 @@ generated code for any other:
   * no VALU instruction inside the K loops of the dgrad kernels at all (operands by raw buffer loads with scalar offsets).
 
 Every instantiation the host can launch is compiled (16 row-owned cases, 8 strip widths: about five minutes on one core), and
-test_every_launched_instantiation_is_linted keeps the lists below in step with the dispatch switches of csrc/sdrm_hip.hip.
+test_every_launched_instantiation_is_linted holds the lists below to the kernels csrc/sdrm_hip.hip really instantiates: it
+cross-compiles that translation unit for the device and compares the symbols.
 """
 import os
 import re
@@ -32,16 +33,22 @@ def _hipcc():
     pytest.skip("hipcc not available")
 
 
+def _device_asm(src: str, *defines: str) -> str:
+    """gfx950 assembly of the device side of the HIP source file `src`."""
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "k.s")
+        res = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", *defines, "-o", out, src],
+                             capture_output=True, text=True)
+        assert res.returncode == 0, res.stderr
+        return open(out).read()
+
+
 def _compile(instantiations: str, header: str = "rows48.h") -> str:
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "k.hip")
         with open(src, "w") as f:
             f.write(f'#include "{CSRC}/{header}"\n' + instantiations)
-        out = os.path.join(d, "k.s")
-        res = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, src],
-                             capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr
-        return open(out).read()
+        return _device_asm(src)
 
 
 def _kernels(asm: str):
@@ -91,27 +98,46 @@ LINT_LIGHT = [False, True]
 LINT_PARTS = [1, 2, 4]
 LINT_NT = [4, 5, 6, 7, 8, 9, 10, 11]
 
+# the asm-MFMA kernel templates and the argument struct each takes
+ROW_OWNED = {"k_dgrad_chain": "DgradChainArgs", "k_dgrad_rows": "DgradRowsArgs", "k_row_fwd": "RowChainArgs",
+             "k_rows48_fwd": "RowChainArgs", "k_rows48_dgrad_chain": "DgradChain48Args"}
 
-@pytest.mark.parametrize("lightb", LINT_LIGHT)
+
+def _row_owned_instantiations(ct, lightb):
+    """(kernel, template arguments) of everything test_row_owned_kernels_isa compiles for one (CT, LIGHT): the 96-row kernels; the same
+    step on 48-row work-groups (csrc/rows48.h: the same asm MFMAs through the same K-step templates) with one work-group per row group,
+    with two (column-split, the form the size rule takes for 1281 .. 2048 users) and with four (batches of at most 1024 users,
+    sdrm_debug_set_rows48_split(e, 4)); and, for 4 q + 2 column tiles, their shared-tile form (the waves of a pair split one tile's K-steps),
+    which exists for one work-group per group only."""
+    inst = [(k, (ct, lightb)) for k in ("k_dgrad_chain", "k_dgrad_rows", "k_row_fwd")]
+    for k in ("k_rows48_fwd", "k_rows48_dgrad_chain"):
+        inst += [(k, (ct, lightb, parts, False)) for parts in LINT_PARTS]
+        if ct % 2:
+            inst.append((k, (ct, lightb, 1, True)))
+    return inst
+
+
+def _instantiation(symbol):
+    """(kernel, template arguments) of the mangled name of a kernel in namespace sdrm whose template arguments are ints and bools (default
+    arguments are part of the name); (kernel, None) for any other."""
+    m = re.match(r"_ZN4sdrm(\d+)", symbol)
+    if not m:
+        return symbol, None
+    end = m.end() + int(m.group(1))
+    targs = re.match(r"I((?:L[ib]\d+E)+)E", symbol[end:])
+    if not targs:
+        return symbol[m.end():end], None
+    return symbol[m.end():end], tuple(bool(int(v)) if t == "b" else int(v) for t, v in re.findall(r"L([ib])(\d+)E", targs.group(1)))
+
+
+@pytest.mark.parametrize("lightb", LINT_LIGHT)   # the compact last K-step (340 = 21 * 16 + 4: the headline width), or the plain one
 @pytest.mark.parametrize("ct", LINT_CT)
 def test_row_owned_kernels_isa(ct, lightb):
-    light = "true" if lightb else "false"   # the compact last K-step (340 = 21 * 16 + 4: the headline width), or the plain one
-    asm = _compile(f"template __global__ void sdrm::k_dgrad_chain<{ct}, {light}>(const sdrm::DgradChainArgs);\n"
-                   f"template __global__ void sdrm::k_dgrad_rows<{ct}, {light}>(const sdrm::DgradRowsArgs);\n"
-                   f"template __global__ void sdrm::k_row_fwd<{ct}, {light}>(const sdrm::RowChainArgs);\n"
-                   # the same step on 48-row work-groups (csrc/rows48.h): the same asm MFMAs through the same K-step templates
-                   f"template __global__ void sdrm::k_rows48_fwd<{ct}, {light}>(const sdrm::RowChainArgs);\n"
-                   f"template __global__ void sdrm::k_rows48_dgrad_chain<{ct}, {light}>(const sdrm::DgradChain48Args);\n"
-                   # ... and with two work-groups per row group (column-split, the form the size rule takes for 1281 .. 2048 users)
-                   f"template __global__ void sdrm::k_rows48_fwd<{ct}, {light}, 2>(const sdrm::RowChainArgs);\n"
-                   f"template __global__ void sdrm::k_rows48_dgrad_chain<{ct}, {light}, 2>(const sdrm::DgradChain48Args);\n"
-                   # ... and with four (batches of at most 1024 users, sdrm_debug_set_rows48_split(e, 4))
-                   f"template __global__ void sdrm::k_rows48_fwd<{ct}, {light}, 4>(const sdrm::RowChainArgs);\n"
-                   f"template __global__ void sdrm::k_rows48_dgrad_chain<{ct}, {light}, 4>(const sdrm::DgradChain48Args);\n"
-                   # ... and the shared-tile form (4 q + 2 column tiles: the waves of a pair split one tile's K-steps)
-                   + (f"template __global__ void sdrm::k_rows48_fwd<{ct}, {light}, 1, true>(const sdrm::RowChainArgs);\n"
-                      f"template __global__ void sdrm::k_rows48_dgrad_chain<{ct}, {light}, 1, true>(const sdrm::DgradChain48Args);\n" if ct % 2 else ""))
+    inst = _row_owned_instantiations(ct, lightb)
+    asm = _compile("".join("template __global__ void sdrm::%s<%s>(const sdrm::%s);\n" % (k, ", ".join(str(a).lower() for a in targs), ROW_OWNED[k])
+                           for k, targs in inst))
     ks = _kernels(asm)
+    assert sorted(i for i in map(_instantiation, ks) if i[0] in ROW_OWNED) == sorted(inst)   # (what test_every_launched_instantiation_is_linted reads the library's symbols with)
     names = {"chain": [n for n in ks if "k_dgrad_chain" in n and "rows48" not in n], "rows": [n for n in ks if "k_dgrad_rows" in n],
              "fwd": [n for n in ks if "k_row_fwd" in n], "fwd48": [n for n in ks if "k_rows48_fwd" in n and "ELi2E" not in n and "ELi4E" not in n and "ELi1ELb1E" not in n],
              "chain48": [n for n in ks if "k_rows48_dgrad_chain" in n and "ELi2E" not in n and "ELi4E" not in n and "ELi1ELb1E" not in n],
@@ -262,32 +288,24 @@ def test_strips_kernel_loop_is_clean(nt):
             assert len(valu) * 8 <= nm, (len(valu), nm, valu[:6])
 
 
-def _launched(text, launcher):
-    """The template arguments `launcher<N>(` is called with in the host code (the `case N:` and `default:` arms of its dispatch)."""
-    return sorted({int(n) for n in re.findall(r"\b%s<(\d+)>\(" % launcher, text)})
-
-
 def test_every_launched_instantiation_is_linted():
-    """The lint is what the correctness of the asm-MFMA kernels rests on, so an instantiation the host can launch must be one it
-    compiles: the dispatch switches of csrc/sdrm_hip.hip, read as text, against the parameter lists above."""
-    text = open(os.path.join(CSRC, "sdrm_hip.hip")).read()
-    for launcher in ("launch_row_forward_ct", "launch_rows48_forward_ct", "launch_dgrad_rows_ct", "launch_dgrad_chain_ct", "launch_rows48_chain_ct"):
-        cts = _launched(text, launcher)
-        assert cts, launcher + ": no dispatch found (renamed? then this test must follow it)"
-        assert set(cts) <= set(LINT_CT), (launcher, "launches column-tile counts the ISA lint does not compile", sorted(set(cts) - set(LINT_CT)))
-    nts = _launched(text, "launch_wgrad_strips_nt")
-    assert nts and set(nts) <= set(LINT_NT), ("launch_wgrad_strips_nt", sorted(set(nts) - set(LINT_NT)))
-    for launcher in ("launch_rows48_forward_ctp", "launch_rows48_chain_ctp"):
-        parts = sorted({int(n) for n in re.findall(r"\b%s<CT, (\d+)>\(" % launcher, text)})
-        assert parts and set(parts) <= set(LINT_PARTS), (launcher, parts)
-    # every kernel launch of these templates goes through the launchers above, with LIGHT a literal and the shared-tile form only at PARTS == 1
-    kernels = ("k_row_fwd", "k_rows48_fwd", "k_dgrad_rows", "k_dgrad_chain", "k_rows48_dgrad_chain", "k_wgrad_strips")
-    forms = {k: set(re.findall(r"\(%s<([^>]*)>\)" % k, text)) for k in kernels}
-    assert forms["k_row_fwd"] == {"CT, true", "CT, false"} and forms["k_dgrad_rows"] == forms["k_dgrad_chain"] == forms["k_row_fwd"], forms
-    want48 = {"CT, true, PARTS", "CT, false, PARTS", "CT, true, 1, true", "CT, false, 1, true"}
-    assert forms["k_rows48_fwd"] == want48 and forms["k_rows48_dgrad_chain"] == want48, forms
-    assert forms["k_wgrad_strips"] == {"NT"}, forms
-    assert {"true" if b else "false" for b in LINT_LIGHT} == {"true", "false"}
+    """The lint is what the correctness of the asm-MFMA kernels rests on, so the instantiations the library holds must be the ones it
+    compiles, no more and no fewer: csrc/sdrm_hip.hip itself, cross-compiled for the device (about four minutes on one core), and the
+    kernels found in it against what the parameter lists above make the lint tests compile.  Equality: a kernel the host can launch and the
+    lint never saw fails here, and so does a lint case for a kernel that is gone."""
+    library = {}
+    for symbol in _kernels(_device_asm(os.path.join(CSRC, "sdrm_hip.hip"), '-DSDRM_SOURCE_HASH="isa-lint"')):
+        kernel, targs = _instantiation(symbol)
+        library.setdefault(kernel, set()).add(targs)
+    linted = {k: set() for k in ROW_OWNED}
+    for ct in LINT_CT:
+        for lightb in LINT_LIGHT:
+            for k, targs in _row_owned_instantiations(ct, lightb):
+                linted[k].add(targs)
+    linted["k_wgrad_strips"] = {(nt,) for nt in LINT_NT}
+    for k, want in linted.items():
+        have = library.get(k, set())
+        assert have == want, (k, "in the library, not linted:", sorted(have - want), "linted, not in the library:", sorted(want - have))
 
 
 def _tile_cfg4():
