@@ -313,6 +313,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
   // empty asm makes the values live at this point.
   asm volatile("" ::"s"(p.A), "s"(p.B), "s"(p.lda), "s"(p.ldb), "s"(p.K), "s"(p.kchunk), "s"(p.tiles_n), "s"(p.nblocks),
                "s"(p.magic_tiles_n), "s"(p.limA), "s"(p.limB));
+  if constexpr (EPI == EPI_TANH_REV) asm volatile("" ::"s"(p.revX), "s"(p.revU), "s"(p.rev_ldx), "s"(p.rev_s0), "s"(p.rev_n), "s"(p.bias));
+  if constexpr (EPI == EPI_BIAS_PRELU) asm volatile("" ::"s"(p.bias), "s"(p.slopeE));
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -432,6 +434,47 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
         }
       }
   };
+  // What the epilogue of the sampler's launches reads from global memory is known before the first MFMA, so it is requested
+  // there, behind the first operand loads, and waits in registers: a load issued in the epilogue is a round trip with nothing
+  // left to hide it, at the end of every work-group (and the compiler chained the state loads of EPI_TANH_REV - load, wait,
+  // update, store, once per accumulator row: four round trips in a row on the 16-wide tile).
+  //   bias (EPI_TANH_REV, EPI_BIAS_PRELU): one value per accumulator tile; the column is clamped instead of predicated (a tile
+  //   beyond limB is skipped by the epilogue, its value is never used).  EPI_BIAS_PRELU: the activation's slope with it.
+  //   sampler state X (EPI_TANH_REV): the lane's own elements, the epilogue's addresses and its row predicate - the loads are
+  //   raw buffer loads on a resource that starts at the work-group's first state row and ends with the last row below rev_n, so
+  //   a row the epilogue skips is not read (a load beyond the resource returns zero without touching memory).  COHA as for the
+  //   A operand: inside k_sample_persist the state was written by the previous step of the same launch.
+  // Only on the 16-wide MFMA tile, which is what the sampler's launches of up to 4096 rows and k_sample_persist run on: the state
+  // is 4 registers per accumulator tile there.  On the 32-wide MFMA it would be 16 (the 64x64 tile's EPI_TANH_REV kernel stands at
+  // 100 VGPRs, the wider tiles' at 128), and the one bias register takes the 64x64 EPI_BIAS_PRELU kernel from 72 to 74 VGPRs,
+  // seven waves per SIMD to six: those instantiations keep their loads in the epilogue.
+  constexpr bool PF_BIAS = (EPI == EPI_TANH_REV || EPI == EPI_BIAS_PRELU) && (MF == 16);
+  constexpr bool PF_STATE = (EPI == EPI_TANH_REV) && (MF == 16);
+  float pf_bias[TM][TN], pf_slope = 0.f;
+  float pf_x[TM][TN][PF_STATE ? NR : 1];
+  auto epi_prefetch = [&]() {
+    if constexpr (PF_BIAS) {
+      if constexpr (EPI == EPI_BIAS_PRELU) pf_slope = *p.slopeE;   // (a vector load too: the compiler does not know the slope constant)
+#pragma unroll
+      for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b) pf_bias[a][b] = p.bias[min(n0 + wn * (BN / Cfg::WN) + b * MF + l31, p.limB - 1)];
+    }
+    if constexpr (PF_STATE) {
+      const int rows_left = min(max(p.rev_n - p.rev_s0 - m0, 0), BM);   // state rows of this work-group's tile
+      const brsrc resX = make_brsrc(p.revX + (size_t)(p.rev_s0 + m0) * p.rev_ldx, (uint32_t)rows_left * (uint32_t)p.rev_ldx * 4u);
+#pragma unroll
+      for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b) {
+          const int col = n0 + wn * (BN / Cfg::WN) + b * MF + l31;
+          const int r0 = wm * (BM / Cfg::WM) + a * MF + 4 * lhi;   // rbase - m0
+#pragma unroll
+          for (int r = 0; r < NR; ++r)
+            pf_x[a][b][r] = bload1a<COHA>(resX, (uint32_t)((r0 + ((MF == 32) ? (r & 3) + 8 * (r >> 2) : r)) * p.rev_ldx + col) * 4u, 0u);
+        }
+    }
+  };
   const int aoffk = (wm * (BM / Cfg::WM) + l31) * LDK + ((MF == 32) ? (BK / 2) : 4) * lhi;
   const int boffk = (wn * (BN / Cfg::WN) + l31) * LDK + ((MF == 32) ? (BK / 2) : 4) * lhi;
 
@@ -518,6 +561,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
         t_ld = __builtin_amdgcn_s_memtime();     // setup done, first loads issued
         __builtin_amdgcn_sched_barrier(0);
 #endif
+        epi_prefetch();
         if constexpr (EPI == EPI_TANH_REV) rev_draw();   // VALU work under the first loads' round trip
         st(ra0, rb0, 0);
 #if defined(SDRM_STAMPS) && SDRM_STAMPS == 2
@@ -529,6 +573,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
         ld(ra1, rb1, 3);
       } else {
         ld(ra0, rb0, 0);
+        epi_prefetch();
         if constexpr (EPI == EPI_TANH_REV) rev_draw();
         st(ra0, rb0, 0);
         ld(ra0, rb0, 1);
@@ -610,6 +655,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
     if (nt > 0) {
       ld(ra0, rb0, 0);
       ld(ra1, rb1, 1);
+      epi_prefetch();
       st(ra0, rb0, 0);
       ld(ra0, rb0, 2);
       st(ra1, rb1, 1);
@@ -654,7 +700,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
   auto rowoff = [](int r) { return (MF == 32) ? (r & 3) + 8 * (r >> 2) : r; };
   float slope_sum = 0.f;
   const float slopeE = (EPI == EPI_DPRELU) ? *p.slopeE : 0.f;
-  const float slopeP = (EPI == EPI_BIAS_PRELU) ? *p.slopeE : 0.f;
+  const float slopeP = (EPI == EPI_BIAS_PRELU) ? (PF_BIAS ? pf_slope : *p.slopeE) : 0.f;
   float* __restrict__ Cp = p.C;
 #pragma unroll
   for (int a = 0; a < TM; ++a) {
@@ -668,7 +714,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
       float bias = 0.f;
       if (EPI == EPI_BIAS || EPI == EPI_BIAS_TANH || EPI == EPI_BIAS_TANH_G || EPI == EPI_TANH_REV || EPI == EPI_BIAS_G ||
           EPI == EPI_BIAS_PRELU)
-        bias = p.bias[col];
+        bias = PF_BIAS ? pf_bias[a][b] : p.bias[col];
       if (EPI == EPI_BIAS || EPI == EPI_PLAIN) {
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
@@ -700,7 +746,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
           if (row + p.rev_s0 < p.rev_n) {
             const size_t xi = (size_t)(p.rev_s0 + row) * p.rev_ldx + col;
             const float e = tanh_fast(acc[a][b][r] + bias);
-            const float xn = (col < p.rev_L) ? (p.revX[xi] - e * p.rev_c1) / p.rev_sqrt_alpha + p.rev_sqrt_beta * z : 0.f;
+            const float xn = (col < p.rev_L) ? ((PF_STATE ? pf_x[a][b][r] : p.revX[xi]) - e * p.rev_c1) / p.rev_sqrt_alpha + p.rev_sqrt_beta * z : 0.f;
             p.revX[xi] = xn;
             if (noise) p.revU[xi] = kp ? 2.f * xn : 0.f;
           }
