@@ -280,6 +280,34 @@ typedef struct sdrm_vae_decoder {
   int latent, hidden, n_items;
 } sdrm_vae_decoder;
 int sdrm_vae_decode(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z, int n, float* out, void* stream);
+/* The VAE encode hook on the device, FROZEN and in EVAL MODE only (reference: train_SDRM.py:210-212 `encoder = Linear(N_ITEMS,
+ * hidden) -> Tanh -> Linear(hidden, 2*latent)`, :241-250 `VAE.encode` with is_training == 0 and dropout off, called per batch at :323):
+ *   z  = mu = W2[:L] tanh(W1 x / max(|x|_2, 1e-12) + b1) + b2[:L]
+ *   kl = -0.5 * mean over rows of sum(1 + logvar - mu^2 - exp(logvar)),   logvar = rows L..2L of the second Linear.
+ * Dropout, the reparameterisation draw (the reference multiplies it by is_training == 0) and anything backward are out of scope: a
+ * VAE in train mode is not this function.
+ * sdrm_vae_encoder_load stages the encoder once into library-owned buffers (W1 transposed [n_items, hidden padded to 4] for the CSR
+ * form, zero-padded tiled copies of W1 and W2 for the GEMM, the biases); the struct holds DEVICE pointers to the four nn.Linear tensors
+ * as PyTorch stores them, free again once the call is ordered on `stream`.  A second load replaces the first.  Envelope: 1 <= latent <=
+ * 4096, 1 <= hidden <= 16384, 1 <= n_items <= 2^20.  Both encode calls return SDRM_ERR_STATE while no encoder is loaded.
+ * sdrm_vae_encode: x [n, n_items] float32 dense (n_items is the loaded encoder's) -> z [n, latent]; one staging launch (L2
+ * normalisation) and two launches of the fp32 MFMA GEMM.
+ * sdrm_vae_encode_csr: the same z for the CSR rows rows[0..b) (or row0 .. row0+b-1 when rows is null) of a device-resident matrix
+ * [n_rows, n_items], under the contract of sdrm_csr_rows_to_dense (int64 indptr, int32 indices, float32 data or null for all ones;
+ * canonical CSR: no column twice in a row; stored zeros are legal).  The first Linear is a gather of the rows of W1 transposed that
+ * the row's entries name, summed in CSR order: no dense batch exists, and a row's z does not depend on where it sits in the batch, bit
+ * for bit.  Row ids, indptr pairs and column indices are range-checked on the device into the same status word: an offending entry
+ * contributes nothing, an offending row is encoded as an empty row, and sdrm_feed_status reports it.
+ * kl (device float) may be null: then only the mu half of the second Linear is computed.  Scratch is library-owned and grow-only. */
+typedef struct sdrm_vae_encoder {
+  const float* w1; const float* b1;   /* encoder[0]: [hidden, n_items], [hidden] */
+  const float* w2; const float* b2;   /* encoder[2]: [2*latent, hidden], [2*latent] */
+  int n_items, hidden, latent;
+} sdrm_vae_encoder;
+int sdrm_vae_encoder_load(sdrm_engine* e, const sdrm_vae_encoder* enc, void* stream);
+int sdrm_vae_encode(sdrm_engine* e, const float* x, int n, float* z, float* kl, void* stream);
+int sdrm_vae_encode_csr(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows,
+                        const int64_t* rows, int64_t row0, int b, float* z, float* kl, void* stream);
 /* Recall@k and NDCG@k of a score matrix against held-out interactions (reference: utilities.py:116-171,
  * mask_training_examples + recall_at_k_batch + NDCG_binary_at_k_batch, as svd_benchmark.py:58-66 chains them).
  * scores [U, I] float32 row-major; held_* / train_* are CSR index arrays over the same U rows (int64 indptr [U+1],

@@ -23,6 +23,11 @@ class VaeDecoder(C.Structure):
                 ("n_items", c_int)]
 
 
+class VaeEncoder(C.Structure):
+    _fields_ = [("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("n_items", c_int), ("hidden", c_int),
+                ("latent", c_int)]
+
+
 # name -> (restype, argtypes); mirrors include/sdrm_hip.h one to one
 SIGNATURES = {
     "sdrm_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_void_p)]),
@@ -80,6 +85,9 @@ SIGNATURES = {
     "sdrm_csr_rows_to_dense": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "sdrm_feed_status": (c_int, [c_void_p, c_void_p]),
     "sdrm_vae_decode": (c_int, [c_void_p, C.POINTER(VaeDecoder), c_void_p, c_int, c_void_p, c_void_p]),
+    "sdrm_vae_encoder_load": (c_int, [c_void_p, C.POINTER(VaeEncoder), c_void_p]),
+    "sdrm_vae_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "sdrm_vae_encode_csr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "sdrm_equal_sparsity": (c_int, [c_void_p, c_void_p, c_int64, C.c_double, c_void_p, c_void_p, c_void_p]),
     "sdrm_rank_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -18,6 +18,7 @@
 #include "../../include/sdrm_hip_debug.h"
 #include "decode.h"
 #include "elementwise.h"
+#include "encode.h"
 #include "exchange.h"
 #include "feed.h"
 #include "gemm.h"
@@ -176,6 +177,13 @@ struct sdrm_engine {
   // grow-only scratch of sdrm_vae_decode (padded latents / weights / hidden activations)
   float* dec_buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t dec_cap[6] = {0, 0, 0, 0, 0, 0};
+  // the frozen VAE encoder staged by sdrm_vae_encoder_load (csrc/encode.h) and the grow-only scratch of the encode calls
+  enum { ENC_W1T = 0, ENC_W1, ENC_B1, ENC_W2, ENC_B2, ENC_XN, ENC_HID, ENC_OUT2, ENC_DENSE, ENC_BUFS };
+  float* enc_buf[ENC_BUFS] = {};     // W1^T [items][Hq] | tiled W1, b1, W2, b2 | normalised rows, hidden activations, [n][2 latent], densified rows
+  size_t enc_cap[ENC_BUFS] = {};
+  double* enc_part = nullptr;        // partial sums of the kl (k_encode_kl_rows)
+  bool enc_loaded = false;
+  int enc_items = 0, enc_hidden = 0, enc_latent = 0;
   Exchange xch;                      // RCCL communicator of the user-sharded step (sdrm_comm_init_rank / sdrm_allreduce_init)
   mutable int64_t n_launches = 0;    // kernel launches issued through this handle since sdrm_create
   // The sampler's own copy of everything it reads of the net (padded weights, biases, the folded bias table b0 + C0[i], the two
@@ -1456,6 +1464,9 @@ int sdrm_destroy(sdrm_engine* e) {
   (void)sdrm_comm_destroy(e);
   for (float* b : e->dec_buf)
     if (b) (void)hipFree(b);
+  for (float* b : e->enc_buf)
+    if (b) (void)hipFree(b);
+  if (e->enc_part) (void)hipFree(e->enc_part);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_hold) (void)hipEventDestroy(e->ev_hold);
   for (int c = 0; c < 3; ++c) {
@@ -2680,6 +2691,161 @@ int sdrm_vae_decode(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z,
   if (!out) return fail(e, SDRM_ERR_ARG, "sdrm_vae_decode: null output");
   if (int jr = join_chains(e, (hipStream_t)stream)) return jr;
   return decode_launches(e, dec, z, n, out, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// VAE encode hook, frozen and in eval mode (train_SDRM.py:241-250, called at :323), csrc/encode.h.
+namespace {
+
+constexpr int ENC_KL_PARTS = 512;    // work-groups of k_encode_kl_rows
+constexpr int ENC_GATHER_MAX_Q = 1024;   // float4 slices of the hidden vector k_encode_csr holds in registers (256 threads x 4): hidden <= 4096
+
+int enc_grow(sdrm_engine* e, int slot, size_t n) {
+  if (n <= e->enc_cap[slot]) return SDRM_OK;
+  if (e->enc_buf[slot]) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(e->enc_buf[slot])); e->enc_buf[slot] = nullptr; e->enc_cap[slot] = 0; }
+  HIP_TRY(e, dalloc(&e->enc_buf[slot], n));
+  e->enc_cap[slot] = n;
+  return SDRM_OK;
+}
+
+struct EncDims { int Ip, Hq, Hp, Hr, L2p, L2r; };
+EncDims enc_dims(int n_items, int hidden, int latent) {
+  EncDims d;
+  d.Ip = round_up(n_items, 32); d.Hq = round_up(hidden, 4); d.Hp = round_up(hidden, 32); d.Hr = round_up(d.Hp, 128);
+  d.L2p = round_up(2 * latent, 32); d.L2r = round_up(d.L2p, 128);
+  return d;
+}
+
+// The second Linear on the hidden activations enc_buf[ENC_HID] [rows64][Hp], and the kl.  kl null: only the mu rows of W2, straight into z.
+int encode_tail(sdrm_engine* e, int n, float* z, float* kl, hipStream_t st) {
+  const EncDims d = enc_dims(e->enc_items, e->enc_hidden, e->enc_latent);
+  const int L = e->enc_latent;
+  const int rows64 = round_up(n, BM);
+  const int cfg = choose_cfg(e->tune, rows64, e->tune.nt32_max_rows);
+  GemmArgs a{};
+  a.bias = e->enc_buf[sdrm_engine::ENC_B2];
+  a.rows_valid = n;
+  if (!kl) {
+    a.C = z; a.ldc = L; a.cols_valid = L;
+    HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, e->enc_buf[sdrm_engine::ENC_HID], d.Hp, e->enc_buf[sdrm_engine::ENC_W2], d.Hp, rows64,
+                                                   round_up(L, 32), d.Hp, st, Prof{nullptr, 0, 0.0}, cfg)));
+    return SDRM_OK;
+  }
+  if (int rc = enc_grow(e, sdrm_engine::ENC_OUT2, (size_t)n * 2 * L)) return rc;
+  a.C = e->enc_buf[sdrm_engine::ENC_OUT2]; a.ldc = 2 * L; a.cols_valid = 2 * L;
+  HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, e->enc_buf[sdrm_engine::ENC_HID], d.Hp, e->enc_buf[sdrm_engine::ENC_W2], d.Hp, rows64, d.L2p,
+                                                 d.Hp, st, Prof{nullptr, 0, 0.0}, cfg)));
+  const int parts = std::min(n, ENC_KL_PARTS);
+  SDRM_LAUNCH(e, k_encode_kl_rows, dim3(parts), dim3(256), 0, st, (const float*)e->enc_buf[sdrm_engine::ENC_OUT2], n, L, z, e->enc_part);
+  HIP_TRY(e, hipGetLastError());
+  SDRM_LAUNCH(e, k_encode_kl_sum, dim3(1), dim3(256), 0, st, (const double*)e->enc_part, parts, n, kl);
+  HIP_TRY(e, hipGetLastError());
+  return SDRM_OK;
+}
+
+// x [n, n_items] dense -> z (, kl): normalise + pad, Linear + tanh, tail
+int encode_dense_launches(sdrm_engine* e, const float* x, int n, float* z, float* kl, hipStream_t st) {
+  const EncDims d = enc_dims(e->enc_items, e->enc_hidden, e->enc_latent);
+  const int MP = round_up(n, 128), rows64 = round_up(n, BM);
+  int rc;
+  if ((rc = enc_grow(e, sdrm_engine::ENC_XN, (size_t)MP * d.Ip)) || (rc = enc_grow(e, sdrm_engine::ENC_HID, (size_t)MP * d.Hp))) return rc;
+  SDRM_LAUNCH(e, k_encode_norm_rows, dim3(n), dim3(256), 0, st, x, e->enc_items, e->enc_buf[sdrm_engine::ENC_XN], d.Ip);
+  HIP_TRY(e, hipGetLastError());
+  GemmArgs a{};
+  a.C = e->enc_buf[sdrm_engine::ENC_HID]; a.ldc = d.Hp; a.bias = e->enc_buf[sdrm_engine::ENC_B1];
+  HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_TANH>(a, e->enc_buf[sdrm_engine::ENC_XN], d.Ip, e->enc_buf[sdrm_engine::ENC_W1], d.Ip, rows64, d.Hp,
+                                                   d.Ip, st, Prof{nullptr, 0, 0.0}, choose_cfg(e->tune, rows64, e->tune.nt32_max_rows))));
+  return encode_tail(e, n, z, kl, st);
+}
+
+int launch_encode_csr(sdrm_engine* e, void (*kernel)(const EncodeCsrArgs), int tpr, const EncodeCsrArgs& a, hipStream_t st) {
+  const int rpw = 256 / tpr;
+  SDRM_LAUNCH(e, kernel, dim3((unsigned)((a.b + rpw - 1) / rpw)), dim3(256), 0, st, a);
+  HIP_TRY(e, hipGetLastError());
+  return SDRM_OK;
+}
+
+int check_encoder(sdrm_engine* e, const sdrm_vae_encoder* d, const char* who) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!d || !d->w1 || !d->b1 || !d->w2 || !d->b2) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (d->latent < 1 || d->latent > 4096 || d->hidden < 1 || d->hidden > 16384 || d->n_items < 1 || d->n_items > (1 << 20))
+    return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": latent, hidden or n_items outside the supported envelope");
+  return SDRM_OK;
+}
+
+}  // namespace
+
+int sdrm_vae_encoder_load(sdrm_engine* e, const sdrm_vae_encoder* enc, void* stream) {
+  if (int rc = check_encoder(e, enc, "sdrm_vae_encoder_load")) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (int jr = join_chains(e, st)) return jr;
+  const EncDims d = enc_dims(enc->n_items, enc->hidden, enc->latent);
+  e->enc_loaded = false;
+  int rc;
+  if ((rc = enc_grow(e, sdrm_engine::ENC_W1T, (size_t)enc->n_items * d.Hq)) || (rc = enc_grow(e, sdrm_engine::ENC_W1, (size_t)d.Hr * d.Ip)) ||
+      (rc = enc_grow(e, sdrm_engine::ENC_B1, d.Hr)) || (rc = enc_grow(e, sdrm_engine::ENC_W2, (size_t)d.L2r * d.Hp)) ||
+      (rc = enc_grow(e, sdrm_engine::ENC_B2, d.L2r)))
+    return rc;
+  if (!e->enc_part) HIP_TRY(e, dalloc(&e->enc_part, ENC_KL_PARTS));
+  PadSegs sg{};
+  int64_t most = 0;
+  int k = 0;
+  auto pad = [&](const float* src, int rows, int cols, float* dst, int rowsP, int colsP) {
+    sg.src[k] = src; sg.dst[k] = dst; sg.rows[k] = rows; sg.cols[k] = cols; sg.rowsP[k] = rowsP; sg.colsP[k] = colsP;
+    most = std::max<int64_t>(most, (int64_t)rowsP * (colsP / 4));
+    ++k;
+  };
+  pad(enc->w1, enc->hidden, enc->n_items, e->enc_buf[sdrm_engine::ENC_W1], d.Hr, d.Ip);
+  pad(enc->b1, 1, enc->hidden, e->enc_buf[sdrm_engine::ENC_B1], 1, d.Hr);
+  pad(enc->w2, 2 * enc->latent, enc->hidden, e->enc_buf[sdrm_engine::ENC_W2], d.L2r, d.Hp);
+  pad(enc->b2, 1, 2 * enc->latent, e->enc_buf[sdrm_engine::ENC_B2], 1, d.L2r);
+  SDRM_LAUNCH(e, k_pad2d, dim3((unsigned)std::min<int64_t>(2048, (most + 255) / 256), 4), dim3(256), 0, st, sg);
+  HIP_TRY(e, hipGetLastError());
+  SDRM_LAUNCH(e, k_encode_w1t, dim3((unsigned)((enc->n_items + 31) / 32), (unsigned)((d.Hq + 31) / 32)), dim3(256), 0, st, enc->w1, enc->hidden,
+              enc->n_items, e->enc_buf[sdrm_engine::ENC_W1T], d.Hq);
+  HIP_TRY(e, hipGetLastError());
+  e->enc_items = enc->n_items; e->enc_hidden = enc->hidden; e->enc_latent = enc->latent;
+  e->enc_loaded = true;
+  return SDRM_OK;
+}
+
+int sdrm_vae_encode(sdrm_engine* e, const float* x, int n, float* z, float* kl, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!x || !z) return fail(e, SDRM_ERR_ARG, "sdrm_vae_encode: null pointer");
+  if (!e->enc_loaded) return fail(e, SDRM_ERR_STATE, "sdrm_vae_encode: no encoder loaded (sdrm_vae_encoder_load)");
+  if (n < 1 || n > (1 << 22)) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode: n outside 1 .. 2^22");
+  if (int jr = join_chains(e, (hipStream_t)stream)) return jr;
+  return encode_dense_launches(e, x, n, z, kl, (hipStream_t)stream);
+}
+
+int sdrm_vae_encode_csr(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows,
+                        const int64_t* rows, int64_t row0, int b, float* z, float* kl, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!indptr || !indices || !z) return fail(e, SDRM_ERR_ARG, "sdrm_vae_encode_csr: null pointer");
+  if (!e->enc_loaded) return fail(e, SDRM_ERR_STATE, "sdrm_vae_encode_csr: no encoder loaded (sdrm_vae_encoder_load)");
+  if (b < 1 || b > (1 << 22) || row0 < 0 || n_rows < 1) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode_csr: b outside 1 .. 2^22, n_rows < 1 or row0 < 0");
+  if (!rows && row0 + b > n_rows) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode_csr: rows row0 .. row0 + b - 1 end behind the matrix");
+  hipStream_t st = (hipStream_t)stream;
+  if (int jr = join_chains(e, st)) return jr;
+  const EncDims d = enc_dims(e->enc_items, e->enc_hidden, e->enc_latent);
+  const int q = d.Hq / 4;
+  if (q > ENC_GATHER_MAX_Q) {   // a hidden vector wider than the gather kernel's registers: densify into scratch, then the dense form
+    if (int rc = enc_grow(e, sdrm_engine::ENC_DENSE, (size_t)b * e->enc_items)) return rc;
+    if (int rc = sdrm_csr_rows_to_dense(e, indptr, indices, data, n_rows, rows, row0, b, e->enc_items, e->enc_buf[sdrm_engine::ENC_DENSE], stream)) return rc;
+    return encode_dense_launches(e, e->enc_buf[sdrm_engine::ENC_DENSE], b, z, kl, st);
+  }
+  if (int rc = enc_grow(e, sdrm_engine::ENC_HID, (size_t)round_up(b, 128) * d.Hp)) return rc;
+  EncodeCsrArgs a{};
+  a.indptr = indptr; a.indices = indices; a.data = data; a.rows = rows; a.row0 = row0; a.n_rows = n_rows; a.b = b; a.n_items = e->enc_items;
+  a.flag = e->feed_flag; a.w1t = e->enc_buf[sdrm_engine::ENC_W1T]; a.b1 = e->enc_buf[sdrm_engine::ENC_B1]; a.Hq = d.Hq; a.Hp = d.Hp;
+  a.hid = e->enc_buf[sdrm_engine::ENC_HID];
+  int rc;
+  if (q <= 64) rc = launch_encode_csr(e, k_encode_csr<64, 1, 8>, 64, a, st);          // one wave per row, four rows per work-group (ADM: hidden 200)
+  else if (q <= 256) rc = launch_encode_csr(e, k_encode_csr<256, 1, 8>, 256, a, st);   // one work-group per row (ML-1M 600, ML-100k 930)
+  else if (q <= 512) rc = launch_encode_csr(e, k_encode_csr<256, 2, 4>, 256, a, st);
+  else rc = launch_encode_csr(e, k_encode_csr<256, 4, 2>, 256, a, st);
+  if (rc) return rc;
+  return encode_tail(e, b, z, kl, st);
 }
 
 int sdrm_equal_sparsity(sdrm_engine* e, const float* x, int64_t n, double q, uint8_t* out, float* threshold, void* stream) {

@@ -464,6 +464,63 @@ class Engine:
         self._check(self.lib.sdrm_vae_decode(self._h, C.byref(dec), _ptr(z), z.shape[0], _ptr(out), _stream()), "sdrm_vae_decode")
         return out
 
+    # ------------------------------------------------------------------ VAE encode on the engine (frozen, eval mode)
+    def vae_encoder_load(self, w1, b1, w2, b2):
+        """Stages the frozen encoder `Linear(n_items, hidden) -> Tanh -> Linear(hidden, 2 latent)` (train_SDRM.py:210-212) given as
+        its four tensors; the engine keeps its own copies.  A second load replaces the first."""
+        w1, b1, w2, b2 = (self._dev(t.detach() if isinstance(t, torch.Tensor) else t, torch.float32) for t in (w1, b1, w2, b2))
+        if w1.dim() != 2 or w2.dim() != 2 or w2.shape[0] % 2:
+            raise SdrmError("vae_encoder_load: expected encoder[0].weight [hidden, items] and encoder[2].weight [2 latent, hidden]")
+        hidden, n_items = w1.shape
+        latent = w2.shape[0] // 2
+        if tuple(b1.shape) != (hidden,) or tuple(w2.shape) != (2 * latent, hidden) or tuple(b2.shape) != (2 * latent,):
+            raise SdrmError("vae_encoder_load: expected encoder[0].weight [hidden, items], .bias [hidden], encoder[2].weight [2 latent, hidden], .bias [2 latent]")
+        enc = _lib.VaeEncoder(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), n_items, hidden, latent)
+        self._check(self.lib.sdrm_vae_encoder_load(self._h, C.byref(enc), _stream()), "sdrm_vae_encoder_load")
+        self._keepalive = (w1, b1, w2, b2)
+        self._encoder = (int(n_items), int(hidden), int(latent))
+
+    def _encoder_dims(self, who):
+        enc = getattr(self, "_encoder", None)
+        if enc is None:
+            raise SdrmError(f"{who}: SDRM_ERR_STATE: no encoder loaded (vae_encoder_load)")
+        return enc
+
+    def _kl_out(self, return_kl):
+        return torch.empty((), dtype=torch.float32, device=self.device) if return_kl else None
+
+    def vae_encode(self, x, return_kl=False):
+        """`VAE.encode(x)` in eval mode (train_SDRM.py:241-250) for a dense x [n, n_items]: z = mu [n, latent] (and the kl as a 0-d
+        device tensor when asked).  A width other than the loaded encoder's raises SdrmError (SDRM_ERR_SHAPE): the C call takes none."""
+        n_items, _, latent = self._encoder_dims("sdrm_vae_encode")
+        x = self._dev(x, torch.float32)
+        if x.dim() != 2 or x.shape[1] != n_items:
+            raise SdrmError(f"sdrm_vae_encode: SDRM_ERR_SHAPE: x must be [n,{n_items}], got {tuple(x.shape)}")
+        z = torch.empty(x.shape[0], latent, dtype=torch.float32, device=self.device)
+        kl = self._kl_out(return_kl)
+        self._check(self.lib.sdrm_vae_encode(self._h, _ptr(x), x.shape[0], _ptr(z), _ptr(kl), _stream()), "sdrm_vae_encode")
+        return (z, kl) if return_kl else z
+
+    def vae_encode_csr(self, csr_dev, rows=None, row0=0, b=None, return_kl=False, check=True):
+        """The same z straight from the rows `rows` (or row0 .. row0+b-1) of a `csr_to_device` matrix: the first Linear is a gather
+        of W1's columns, no dense batch exists.  Range checks and `check` as in `csr_rows_to_dense`."""
+        n_items, _, latent = self._encoder_dims("sdrm_vae_encode_csr")
+        indptr, indices, data, (n_rows, width) = csr_dev
+        if width != n_items:
+            raise SdrmError(f"sdrm_vae_encode_csr: SDRM_ERR_SHAPE: the matrix has {width} columns, the encoder {n_items}")
+        if rows is not None:
+            rows = self._dev(rows, torch.int64)
+            b = rows.numel()
+        elif b is None:
+            raise SdrmError("vae_encode_csr: give `rows` or `row0` and `b`")
+        z = torch.empty(b, latent, dtype=torch.float32, device=self.device)
+        kl = self._kl_out(return_kl)
+        self._check(self.lib.sdrm_vae_encode_csr(self._h, _ptr(indptr), _ptr(indices), _ptr(data), int(n_rows), _ptr(rows), int(row0), int(b),
+                                                 _ptr(z), _ptr(kl), _stream()), "sdrm_vae_encode_csr")
+        if check:
+            self.feed_status()
+        return (z, kl) if return_kl else z
+
     def csr_to_device(self, m):
         """(indptr i64, indices i32, data f32 | None for an all-ones matrix, shape) of a scipy sparse matrix, on the device."""
         m = m.tocsr().copy()

@@ -75,6 +75,25 @@ class DeviceFeed:
             yield x, x
         self.engine.feed_status()   # the device-side range checks of the epoch's batches, read once (one sync per epoch)
 
+    def latents(self, engine=None):
+        """One epoch of the SAME feed as latents: the permutation draw `iter()` would make, each batch encoded by the frozen
+        eval-mode VAE encoder loaded into `engine` (default: the feed's own; `Engine.vae_encoder_load`) straight from the CSR
+        rows - `sdrm_vae_encode_csr`, no dense batch - or, where the gather does not pay (`train_SDRM.encode_csr_pays`), densified
+        and encoded by `sdrm_vae_encode`.  Yields z [b, latent]."""
+        from .train_SDRM import encode_csr_pays
+        eng = engine if engine is not None else self.engine
+        n_rows, n_items = self.csr[3]
+        density = float(self.csr[1].numel()) / (float(n_rows) * float(n_items))
+        gather = encode_csr_pays(density, n_items, eng._encoder_dims("DeviceFeed.latents")[1])
+        perm = torch.randperm(self.n_rows, generator=self.gen).to(eng.device)
+        for lo in range(0, self.n_rows, self.batch_size):
+            rows = perm[lo:lo + self.batch_size]
+            if gather:
+                yield eng.vae_encode_csr(self.csr, rows=rows, check=False)
+            else:
+                yield eng.vae_encode(eng.csr_rows_to_dense(self.csr, rows=rows, check=False))
+        eng.feed_status()
+
 
 def equal_sparsity(raw, sparsity: float, engine) -> np.ndarray:
     """main.py:177-180, `(raw >= np.quantile(raw.flatten(), SPARSITY)).astype(int)`, on the device
@@ -117,7 +136,7 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
                              VAE_LR=hp["vae_lr"], DIFF_LATENT=hp["latent"], N_HIDDEN_MLP_LAYERS=hp["H"], DIFF_LR=hp["lr"],
                              DIFF_TRAINING_EPOCHS=hp["epochs"], TIMESTEPS=hp["T"], noise_divider=hp["nd"], VAE_DIR_PATH=vae_dir,
                              TRAIN_PARTIAL_VALID_DATA=train_partial, VALID_DATA=valid, OPTIMIZATION_OBJECTIVE="Recall@10",
-                             verbose=verbose, cache_latents=hp.get("cache_latents", False))
+                             verbose=verbose, cache_latents=hp.get("cache_latents", False), engine_encode=hp.get("engine_encode", False))
     out = {}
     M = ts.sample_ddpm(n_users, net, vae, hp["latent"], hp["nd"], timesteps="random", n_timesteps=hp["T"]).detach()
     F = ts.sample_ddpm(n_users, net, vae, hp["latent"], hp["nd"], n_timesteps=hp["T"]).detach()

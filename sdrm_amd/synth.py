@@ -149,6 +149,31 @@ def synth_vae_decoder(latent: int, hidden: int, n_items: int, seed: int = 0):
     return w1, b1, w2, b2
 
 
+def synth_vae_encoder(n_items: int, hidden: int, latent: int, seed: int):
+    """Tensors of a `Linear(n_items, hidden) -> Tanh -> Linear(hidden, 2 latent)` encoder (train_SDRM.py:210-212), drawn like
+    `synth_vae_decoder`: (w1 [hidden, n_items], b1 [hidden], w2 [2 latent, hidden], b2 [2 latent]), float32.  The biases are
+    N(0, 0.1) rather than the initialiser's N(0, 0.001) so that a test sees them."""
+    rs = np.random.RandomState(seed)
+    a1, a2 = np.sqrt(6.0 / (n_items + hidden)), np.sqrt(6.0 / (hidden + 2 * latent))
+    w1 = rs.uniform(-a1, a1, size=(hidden, n_items)).astype(np.float32)
+    b1 = (rs.standard_normal(hidden) * 0.1).astype(np.float32)
+    w2 = rs.uniform(-a2, a2, size=(2 * latent, hidden)).astype(np.float32)
+    b2 = (rs.standard_normal(2 * latent) * 0.1).astype(np.float32)
+    return w1, b1, w2, b2
+
+
+def synth_feed_csr(n_rows: int, n_items: int, density: float, seed: int, ratings: bool = True):
+    """A canonical scipy CSR matrix [n_rows, n_items] float32 with about `density` of its entries stored (at least one per
+    row), values 1..5 (`ratings`) or all ones: what a feed of the published datasets looks like."""
+    from scipy.sparse import csr_matrix
+    rs = np.random.RandomState(seed)
+    counts = np.maximum(1, rs.binomial(n_items, density, size=n_rows))
+    indptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    indices = np.concatenate([np.sort(rs.choice(n_items, size=c, replace=False)) for c in counts]).astype(np.int32)
+    data = rs.randint(1, 6, size=indices.size).astype(np.float32) if ratings else np.ones(indices.size, np.float32)
+    return csr_matrix((data, indices, indptr), shape=(n_rows, n_items))
+
+
 def synth_train_randoms(B: int, L: int, T: int, nd: float, seed: int):
     """One train step's explicit randoms: eps=nd*N(0,1) [B,L], t~U{1..T} [B] i64,
     three Bernoulli(0.5) keep-masks [3,B,L] u8 (pass order P,S,Q)."""

@@ -10,8 +10,9 @@ hyperparameter_search.py:147,386,691 can be pointed here:
     train_variational_autoencoder (:115-188)  checkpoint (:75)  resume (:66)  DEVICE (:18)
 
 What runs where: the eps-net forward/backward/Adam and the whole reverse-sampling loop run in the HIP
-engine (no torch ops); the VAE's pre-training and its encode hook stay in PyTorch on the same device, as
-the north-star asks; the decode hook at the end of `sample_ddpm` runs on the engine's GEMM when the
+engine (no torch ops); the VAE's pre-training stays in PyTorch on the same device, as the north-star asks, and so does its encode
+hook unless `train_SDRM(..., engine_encode=True)` hands the frozen eval-mode encoder to the engine (`sdrm_vae_encode` /
+`sdrm_vae_encode_csr`); the decode hook at the end of `sample_ddpm` runs on the engine's GEMM when the
 decoder is the reference's two-layer MLP and as the PyTorch module otherwise.  The engine draws its randomness with on-device Philox keyed
 by `torch.initial_seed()`-derived seeds; explicit randoms can be injected for parity runs.
 
@@ -264,12 +265,15 @@ def _set_schedule_globals(eng):
 
 def train_SDRM(dl, N_ITEMS, VAE_HIDDEN, VAE_LATENT, VAE_BATCH_SIZE, VAE_LR, DIFF_LATENT, N_HIDDEN_MLP_LAYERS, DIFF_LR,
                DIFF_TRAINING_EPOCHS, TIMESTEPS, noise_divider, VAE_DIR_PATH, TRAIN_PARTIAL_VALID_DATA, VALID_DATA,
-               OPTIMIZATION_OBJECTIVE, verbose=False, variational_ae=None, cache_latents=False):
+               OPTIMIZATION_OBJECTIVE, verbose=False, variational_ae=None, cache_latents=False, engine_encode=False):
     """(:271-340) Train the VAE (PyTorch), freeze it, then train the eps-net on its latents in the HIP
     engine.  `dl` yields `(x, _)` with x a sparse/dense [b, N_ITEMS] tensor.  Extras (keyword-only in
     spirit): `variational_ae` = an already trained VAE to reuse; `cache_latents` = encode the feed once
     per call instead of once per batch per epoch (identical latents since the frozen eval-mode encoder
-    is deterministic, Q13; only the order of torch RNG consumption changes)."""
+    is deterministic, Q13; only the order of torch RNG consumption changes); `engine_encode` = run the frozen eval-mode encode
+    hook on the engine (`sdrm_vae_encode` for a dense batch, `sdrm_vae_encode_csr` straight from the CSR rows of a
+    `pipeline.DeviceFeed`) when the VAE qualifies (`encoder_tensors`) and the shape pays (`engine_encode_pays`); any other VAE is
+    called as the module it is.  Off by default: nothing existing changes by a bit."""
     if not torch.cuda.is_available():
         raise SdrmError("train_SDRM needs a ROCm device (no CPU fallback)")
     if variational_ae is None:
@@ -287,21 +291,49 @@ def train_SDRM(dl, N_ITEMS, VAE_HIDDEN, VAE_LATENT, VAE_BATCH_SIZE, VAE_LR, DIFF
     eng = DIFF.engine(1)
     _set_schedule_globals(eng)
 
+    enc = encoder_tensors(variational_ae) if engine_encode else None
+    if enc is not None and not engine_encode_pays(getattr(dl, "batch_size", None) or 1, enc[0].shape[1], enc[0].shape[0], enc[2].shape[0] // 2):
+        enc = None
+    if enc is not None:
+        eng = DIFF.engine(max(1, int(getattr(dl, "batch_size", None) or 1)))   # sized once: a rebuild mid-epoch would drop the encoder
+        eng.vae_encoder_load(*enc)
+    enc_latent = enc[2].shape[0] // 2 if enc is not None else 0
+
+    def rng_in_step(b):
+        # the reference's encode draws one randn_like([b, latent]) even in eval (the shim's VAE keeps it, Q12): drawn and
+        # discarded here, so that torch's device generator is where the module would have left it
+        torch.randn(b, enc_latent, device=DEVICE)
+
     def latents(x):
         with torch.no_grad():
             x = x.to_dense() if x.layout != torch.strided else x
+            if enc is not None:
+                z = DIFF.engine(1).vae_encode(x.to(DEVICE))
+                rng_in_step(z.shape[0])
+                return z
             z, _ = variational_ae.encode(x.to(DEVICE))
         return z.float().contiguous()
 
-    cached = [latents(x) for x, _ in iter(dl)] if cache_latents else None
+    def epoch_latents():
+        if enc is not None and hasattr(dl, "latents"):   # pipeline.DeviceFeed: straight from the CSR rows, no dense batch
+            for z in dl.latents(DIFF.engine(1)):
+                rng_in_step(z.shape[0])
+                yield z
+        else:
+            for x, _ in iter(dl):
+                yield latents(x)
+
+    cached = list(epoch_latents()) if cache_latents else None
     start, step = time.time(), 0
     for ep in range(DIFF_TRAINING_EPOCHS):
         if verbose:
             print(f"SDRM Epoch: {ep + 1}/{DIFF_TRAINING_EPOCHS}", end="\r")
         lr = DIFF_LR * (1 - ep / DIFF_TRAINING_EPOCHS)                     # linear decay (:316)
-        feed = cached if cached is not None else (latents(x) for x, _ in iter(dl))
+        feed = cached if cached is not None else epoch_latents()
         for z in feed:
             eng = DIFF.engine(z.shape[0])
+            if enc is not None and getattr(eng, "_encoder", None) is None:   # the engine was rebuilt for a larger batch
+                eng.vae_encoder_load(*enc)
             DIFF.last_loss = eng.train_step(z, lr, seed=DIFF._seed, step=step, nd=noise_divider)   # (:326-337)
             step += 1
     if verbose:
@@ -323,6 +355,22 @@ def decoder_tensors(vae_net):
     return ts
 
 
+def encoder_tensors(vae_net):
+    """The four tensors of a `Linear -> Tanh -> Linear` encoder (the reference's, :210-212) if `vae_net` has one on a ROCm device
+    in float32, is in eval mode and has `is_training == 0` - the frozen hook `sdrm_vae_encode` computes (z = mu, no dropout, no
+    reparameterisation draw) - else None (any other encode hook is called as the module it is)."""
+    enc = getattr(vae_net, "encoder", None)
+    if not (isinstance(enc, nn.Sequential) and len(enc) == 3 and isinstance(enc[0], nn.Linear) and isinstance(enc[1], nn.Tanh)
+            and isinstance(enc[2], nn.Linear) and enc[0].bias is not None and enc[2].bias is not None):
+        return None
+    if getattr(vae_net, "training", True) or getattr(vae_net, "is_training", 1) != 0:
+        return None
+    ts = (enc[0].weight, enc[0].bias, enc[2].weight, enc[2].bias)
+    if any(t.dtype != torch.float32 or not t.is_cuda for t in ts) or enc[2].weight.shape[0] % 2:
+        return None
+    return ts
+
+
 def _decode(eng, vae_net, latents):
     """vae_net.decode(latents) (:49 / :61).  The reference's own decoder (this module's `VAE`, or any module that sets
     `sdrm_engine_decode = True` and keeps the `Linear -> Tanh -> Linear` decoder) runs on the engine's MFMA GEMM
@@ -338,6 +386,24 @@ def engine_decode_pays(n_users: int, hidden: int, n_items: int) -> bool:
     every BASELINE shape - ML-100k (843 x 1008) 50 us against 62, ML-1M (5429 x 3125) 224 against 294, ADM (9558 x 8582) 361
     against 381 (profiles/r04_next_rows_bench.txt) - so the hook is always routed to the engine; kept as the one place to change
     that."""
+    return True
+
+
+def encode_csr_pays(density: float, n_items: int, hidden: int) -> bool:
+    """CSR input: True = the gather (`sdrm_vae_encode_csr`), False = densify + `sdrm_vae_encode`.  Both forms do work proportional
+    to n_items x hidden per row - the gather moves density x n_items rows of W1^T, the GEMM multiplies all n_items - so the one
+    knob is the density.  Measured (profiles/vae_encode_bench.txt, us per batch, dense / gather): ML-1M at 5 % 339 / 230 (B = 8192)
+    and 47.5 / 21.5 (B = 160), ADM at 1.2 % 110 / 16; ML-100k's real rows at 10 % 37.2 / 38.5, outside the 0.8 us spread of that
+    file: the GEMM.  The crossing lies between 5 % and 10 % and is not measured closer; 8 % is the line.  A hidden layer wider than
+    the gather kernel's registers (4096) is densified by the library anyway."""
+    return density < 0.08 and hidden <= 4096
+
+
+def engine_encode_pays(batch: int, n_items: int, hidden: int, latent: int) -> bool:
+    """Where the engine's encode beats the PyTorch module it replaces (feed densified + `VAE.encode`): at every measured shape, in
+    both forms (profiles/vae_encode_bench.txt, us per batch, module / engine dense / engine CSR: ML-100k B = 550 162 / 37 / 39,
+    ML-1M B = 160 169 / 48 / 22, B = 8192 546 / 339 / 230, ADM B = 850 176 / 110 / 16), so an opted-in hook is always routed to the
+    engine; kept as the one place to change that."""
     return True
 
 
