@@ -7,7 +7,8 @@
  * Every setter acts on ONE handle: tile / path selection lives in the engine (sdrm_hip.h "Conventions"), so
  * forcing a variant on one engine never changes what another engine in the same process launches.  The kernel path of a
  * train step is decided once, by its sdrm_train_forward: a setter called between a forward and its backward takes effect at the
- * next sdrm_train_forward; some of them drop the pending forward, as said below.
+ * next sdrm_train_forward; some of them drop the pending forward, as said below.  The path of a sampling call - the narrow nets' one
+ * launch, the persistent kernel, or a launch per layer - is decided once as well, by its sdrm_sample_begin.
  */
 #ifndef SDRM_HIP_DEBUG_H
 #define SDRM_HIP_DEBUG_H
@@ -97,7 +98,8 @@ int sdrm_debug_rowchain_available(const sdrm_engine* e);
  * every other case uses the stand-alone k_reverse_update): 0 never, 1 (default) for launches of at most 4096 rows - the
  * shards of a multi-GPU run, which run on the 32x32 tile where one launch less per reverse step is worth more than the
  * epilogue's Philox work - 2 always; also env SDRM_FUSE_REV.  Results are identical up to the rounding of the update
- * arithmetic. */
+ * arithmetic.  Not refused inside a sampling call: the per-layer launches of that call follow the new mode from their next step on;
+ * whether the call may take the persistent kernel (mode 0 rules it out) was decided by its sdrm_sample_begin and stays. */
 int sdrm_debug_set_fused_reverse(sdrm_engine* e, int mode);
 /* Row chains of a sampling call (csrc/sdrm_hip.hip: independent row ranges run on separate HIP streams so that one
  * chain's launch gaps are filled by another's kernels): -1 = by size (default: sdrm_debug_chains), 1..4 forced; also env SDRM_CHAINS.
@@ -106,7 +108,7 @@ int sdrm_debug_set_fused_reverse(sdrm_engine* e, int mode);
 int sdrm_debug_set_chains(sdrm_engine* e, int chains);
 /* The number of row chains of the sampling call in progress (or of the last one); by size: two once the call has 2560 x 352 elements
  * per layer (ML-1M: n >= 2560 rows).  While an event profile is recorded (sdrm_profile_begin) the chains run one after the other.
- * How chains and train steps queued between sampling steps share the chip (csrc/sdrm_hip.hip: chains_for, hold_chains, hold_point) has two
+ * How chains and train steps queued between sampling steps share the chip (csrc/sdrm_hip.hip: ChainSched) has two
  * environment switches for A/B runs, read at sdrm_create: SDRM_DETACH=0 keeps the one chain of a small call on the caller's stream
  * (default: on an auxiliary stream, beside train steps of the per-layer path), SDRM_HOLD_EARLY=0 makes the chains wait for the end of a
  * row-owned train step (default: for its weight gradients; the tail runs beside them). */

@@ -53,9 +53,9 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 struct Tuning {
   int force_cfg = -1;            // SDRM_TILE: -1 = automatic, 0..4 forced tile shape
   int chains = -1;               // SDRM_CHAINS: sampler row chains, -1 = by size, 1..4 forced
-  int detach = 1;                // SDRM_DETACH: the one chain of a small sampling call runs on an auxiliary stream (chains_for)
-  int hold_early = 1;            // SDRM_HOLD_EARLY: the chains of a sampling call wait for the weight gradients of a train step queued
-                                 // between two of its steps (1) or for the whole step (0): hold_point
+  int detach = 1;                // SDRM_DETACH: the one chain of a small sampling call runs on an auxiliary stream (ChainSched)
+  int hold_early = 1;            // SDRM_HOLD_EARLY: the chains of a sampling call wait for the weight gradients of a row-owned train step
+                                 // queued between two of its steps (1) or for the whole step (0): chains_wgrads_queued
   int fuse_rev = 1;              // SDRM_FUSE_REV: reverse update fused into the out-layer GEMM epilogue (full-resolution PHILOX
                                  // sampling): 0 never, 1 for launches of at most FUSE_REV_MAX_ROWS rows, 2 always
   int skinny = 1;                // (2: with the 16-user train forward instead of the 4-user one) LDS-resident kernels for nets with padded widths <= 64 (persistent sampler, fused train
@@ -107,6 +107,39 @@ struct StepPlan {
   bool skip_pre() const { return acts_stored && (dgrad == ROWS_PER_LAYER || dgrad == CHAIN); }
 };
 
+// ONE sampling call: what sdrm_sample_begin was given and what it decided from everything that is fixed for the call, written there
+// in one place and read by every later entry point of the call.  sdrm_sample_steps counts i_next down; nothing else changes until the
+// next sdrm_sample_begin (sdrm_debug_chains reports `chains` of the last call after it has ended).
+struct SampleCall {
+  enum Path { SKINNY, PERSIST, PER_LAYER };   // the narrow nets' one launch for the whole loop (csrc/skinny.h), issued by sdrm_sample_begin;
+                                              // reverse steps without kernel boundaries (csrc/sample_persist.h: sample_persist_fits), taken
+                                              // while the abort word is clear (persist_now), else as PER_LAYER; one launch per layer
+  bool active = false;
+  int n = 0, multires = 0, mode = 0; float nd = 1.f; const float *xT = nullptr, *z = nullptr; const uint8_t* keep = nullptr;   // the
+  uint64_t seed = 0, call_id = 0; int64_t row0 = 0;                                                            // arguments of the call
+  int MP = 0, i_next = 0;                     // n rounded up to the row granule; the next reverse step, 0: none left
+  Path path = PER_LAYER;
+  int chains = 1, chunk = 0;                  // row chains (chains_for) and the rows of each but the last
+  // multi-resolution: active prefix per step (every row when full resolution), slot -> row, Tj by slot and by row
+  std::vector<int> nact, perm;
+  std::vector<int64_t> tj_sorted, tj_orig;
+  uint32_t persist_phase = 0;                 // what the persistent kernel's row-tile counters (xcntS) stand at, in phases
+};
+
+// Where the row chains of the sampling call run and what their next launches wait for: touched by the chains_* functions and
+// chains_join only (the rules, and what was measured, stand above them).
+struct ChainSched {
+  enum State { ON_CALLER,      // every chain on the caller's stream, nothing pending
+               DETACH_ARMED,   // a train step was queued beside a small call: ev_fork marks the point behind the call's last step
+               FORKED };       // chains on auxiliary streams, pending: joined by the next entry point that needs the result
+  State state = ON_CALLER;
+  bool detached = false;       // the ONE chain of a small call runs on aux[0], till the call ends (else: chain 0 on the caller's stream, c on aux[c - 1])
+  // the train steps queued since the last sampling step
+  bool train_queued = false;   // there was one: the chains' next launches come behind it
+  bool train_row_owned = false;   // one of them was row-owned (one work-group per CU): the chains wait for such a step
+  bool hold_marked = false;    // ev_hold is recorded behind its weight gradients
+};
+
 struct sdrm_engine {
   int L, W, T, H, max_rows, device;
   Tuning tune;
@@ -129,8 +162,7 @@ struct sdrm_engine {
   uint32_t xepochF = 0, xepochC = 0;
   int xgeoF = 0, xgeoC = 0;           // (parts << 16 | groups) of the launches the counters have counted
   bool xcd_ok = false;               // the probe launch of sdrm_create found work-group b on XCD b & 7
-  unsigned* xcntS = nullptr;         // the persistent sampler's row-tile counters [256][32] and what they stand at (phases x column tiles)
-  uint32_t xphaseS = 0;
+  unsigned* xcntS = nullptr;         // the persistent sampler's row-tile counters [256][32] (SampleCall::persist_phase: what they stand at)
   unsigned xskew = 0;                // test hook (sdrm_debug_split_skew): added once to the next split launch's counter base
   bool tables_fresh = false;         // B0tab / the C0^T columns of W0c belong to the current parameters
   float* act = nullptr;              // activations prelu(pre[k]) [H+1][MPmax][WP], written by the row-owned forward beside pre[k]:
@@ -161,8 +193,6 @@ struct sdrm_engine {
   SelectState* sel = nullptr;        // radix-select workspace of sdrm_equal_sparsity
   float* one_dev = nullptr;          // 1.0f (identity PReLU slope for layer 0 inside the batched weight-gradient launch)
   unsigned* feed_flag = nullptr;     // status word of the sparse batch feed (csrc/feed.h: out-of-range row ids / column indices)
-  std::vector<int> smp_nact, smp_perm;
-  std::vector<int64_t> smp_tj_sorted, smp_tj_orig;
   std::vector<float> h_beta, h_alpha, h_alphabar;
   int64_t adam_t = 0;
   // state of the last train_forward
@@ -192,25 +222,12 @@ struct sdrm_engine {
   // for the whole loop, is issued by sdrm_sample_begin itself and so reads the parameters of that moment).
   float* smp_w = nullptr;
   size_t smp_off[7] = {0, 0, 0, 0, 0, 0, 0};   // W0c, Whc, Woc, bhc, boc, B0tab, slopes
-  struct SampleStateT {
-    bool active; int n, MP, multires, mode, i_next; float nd; const float* z; const uint8_t* keep;
-    uint64_t seed, call_id; int64_t row0;
-    const float* xT; bool skinny; bool skinny_launched; int i_start;
-  } smp = {false, 0, 0, 0, 0, 0, 1.f, nullptr, nullptr, 0, 0, 0, nullptr, false, false, 0};
-  // sampler row chains: independent row ranges of one sampling call run on their own streams so that one
-  // chain's launch gaps / prologues / tails are filled by another chain's kernels (chain 0 = caller's stream)
+  SampleCall call;
+  // sampler row chains: row ranges of one sampling call on streams of their own (ChainSched)
   hipStream_t aux[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev_hold = nullptr;      // behind the weight gradients of a train step that runs between two sampling steps (hold_point)
-  int n_chains = 1, chain_chunk = 0;
-  int n_aux = 0;                     // chains on auxiliary streams: n_chains - 1 (the first chain on the caller's stream), or the one chain
-                                     // of a small call, detached (chains_for)
-  bool detach_armed = false;         // a train step was queued beside a small call on the caller's stream: ev_fork marks the point behind the
-                                     // call's last step, the next sdrm_sample_steps moves the chain to aux[0] (sdrm_train_forward)
-  bool hold_needed = false;          // the last train forward was a row-owned one (one work-group per CU): chains wait for such a step (hold_chains)
-  bool chains_pending = false;
-  bool hold_recorded = false;        // ... and its ev_hold was recorded behind that step's weight gradients (hold_point)
-  bool train_since_sample = false;   // a train step was queued since the last sampling step: the chains' next launches wait for it (hold_chains)
+  hipEvent_t ev_hold = nullptr;      // behind the weight gradients of a train step that runs between two sampling steps (chains_wgrads_queued)
+  ChainSched chain_sched;
   // event profiling (bench only)
   bool prof_on = false;
   int prof_cap = 0;
@@ -223,8 +240,6 @@ struct sdrm_engine {
   int64_t prof_n[16] = {0};
   std::string err;
 };
-
-typedef sdrm_engine::SampleStateT SampleState;
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
                  PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_COUNT };
@@ -672,6 +687,17 @@ int emb_tables(sdrm_engine* e, hipStream_t st, const float* warm = nullptr, size
 int ensure_tables(sdrm_engine* e, hipStream_t st) { return e->tables_fresh ? SDRM_OK : emb_tables(e, st); }
 
 bool skinny_net(const sdrm_engine* e) { return e->tune.skinny && e->LP <= 64 && e->WP <= 64; }
+// The forms <NL, NW> of the narrow nets' kernels (csrc/skinny.h, skinny_step.h, skinny_fwd4.h): the 16-column tiles with real columns
+// of the latent and of the hidden width, 1..4 each (more: the form of 4)
+template <class F>
+int with_skinny_form(sdrm_engine* e, F&& f) {
+  const auto tiles = std::make_integer_sequence<int, 4>{};
+  int rc = SDRM_OK;
+  with_int_in<1>(std::min((e->L + 15) / 16, 4), tiles, rc, [&](auto nl) {
+    return with_int_in<1>(std::min((e->W + 15) / 16, 4), tiles, rc, [&](auto nw) { return f(nl, nw); }), rc;
+  });
+  return rc;
+}
 
 // Row-owned train forward (rowchain.h): one 96-row work-group per CU.  It replaces staging + H + 2 GEMM launches + the loss
 // partial sums when the batch fills whole rounds of the chip's 256 CUs (measured at B = 8192, L = 340: 169 us against
@@ -739,15 +765,133 @@ bool use_rowchain(const sdrm_engine* e, int B) {
   return rounds == 1 ? G >= 154 : G * 6 >= rounds * 256 * 5;
 }
 
+// ---- the row chains of a sampling call ----------------------------------------------------------
+// Rows are independent through the whole reverse loop, so a row range can run as a chain of launches on a stream of its own; the
+// ramp and drain of one chain's launch are then filled by the other's.  Measured in round 5 (tools/ab/chain_ab.py,
+// profiles/r05_sampler_chains.txt; us per reverse step of the ML-1M net, whole calls): two chains win from ~2700 rows on - 2715 rows
+// 30.4 -> 27.3, 4096 rows 40.3 -> 36.1, 5429 rows 48.8 -> 44.4, 8192 rows 67.3 -> 59.5 - and lose below (1358 rows 20.1 -> 22.9: a
+// launch of half the rows no longer fills the chip).  Three chains: 42.6 at 5429 rows, worse elsewhere, and worse inside a job that
+// trains between sampling steps; more than two are not what the host's launch rate bounds (tools/ab/chain_threads.py: one host
+// thread per chain gives the same 43.4; a captured graph with forked streams replays at 65).
+// The rule: two chains once the call has 2560 x 352 elements per layer, i.e. each chain's launch still has ~130 work-groups.
+int chains_for(const Tuning& t, int n, int WP) {
+  if (t.chains >= 1) return t.chains > 4 ? 4 : t.chains;
+  return (size_t)n * (size_t)WP >= (size_t)2560 * 352 ? 2 : 1;
+}
+
+// the abort word of the XCD-local launches lives in host-mapped memory the GPU writes: read it as volatile
+inline unsigned xabort_read(const sdrm_engine* e) { return e->xabort_host ? *(volatile const unsigned*)e->xabort_host : 0u; }
+// The call's path is PERSIST and the abort word - the one input of that path that stays live - is clear.
+bool persist_now(const sdrm_engine* e) { return e->call.path == SampleCall::PERSIST && xabort_read(e) == 0u; }
+
+// ChainSched, one function per event.  ON_CALLER -> FORKED at the first steps of a call of several chains, ON_CALLER -> DETACH_ARMED ->
+// FORKED for the one chain of a small call, FORKED -> ON_CALLER at every join:
+//  * Chain 0 of several runs on the caller's stream, the others on auxiliary streams; they are joined lazily (chains_join).
+//  * A small call is one chain on the caller's stream - on a stream of its own a plain call is ~3 us per step SLOWER
+//    (tools/ab/detach_ab.py: 679 rows 17.0 -> 19.7, ML-100k 58.1 -> 62.4) - until a train step is queued beside it: from then on the
+//    chain is detached, it runs on aux[0] and the caller's stream carries the train steps.  A train step of the per-layer path - eleven
+//    dependent launches of 5-13 us on a mostly idle chip - and the four launches of a small sampling step are both latency chains, and
+//    two latency chains on two streams fill each other's gaps.
+//  * A train step between two sampling steps (bench.py's walk) does not join the chains: the call reads its own snapshot of the net
+//    and runs in buffers of its own - Us, X, smp_pre, smp_Y - so what the chains have queued may finish beside the start of the step.
+//    Behind a per-layer step their next launches wait for nothing; behind a ROW-OWNED one for its last MFMA kernel, the weight
+//    gradients (SDRM_HOLD_EARLY=0: for all that is queued when they are launched) - one cross-stream dependency per train step instead
+//    of a join and a fork.  With none, a launch of one work-group per CU finds some CUs busy with the other stream's work-groups and ends
+//    a whole work-group time later: 8850 -> 8565 steps/s.  What follows the weight gradients - the tail's two launches - is latency- and
+//    HBM-bound on a fraction of the chip; the chains' next GEMMs run beside it (the tail writes the live parameters).
+//  * While an event profile is recorded (sdrm_profile_begin) the chains run one after the other on the caller's stream: intervals of
+//    launches that share the chip would overlap and say nothing about either kernel.
+int chains_on_aux(const sdrm_engine* e) { return e->chain_sched.detached ? 1 : e->call.chains - 1; }
+
+// Chains still running on the auxiliary streams are folded back into `st` before anything else touches the engine's buffers or parameters.
+int chains_join(sdrm_engine* e, hipStream_t st) {
+  e->bwd_begun = false;   // a backward that was begun but never finished is abandoned
+  if (e->chain_sched.state != ChainSched::FORKED) return SDRM_OK;
+  for (int c = 0; c < chains_on_aux(e); ++c) {
+    HIP_TRY(e, hipEventRecord(e->ev_join[c], e->aux[c]));
+    HIP_TRY(e, hipStreamWaitEvent(st, e->ev_join[c], 0));
+  }
+  e->chain_sched.state = ChainSched::ON_CALLER;
+  return SDRM_OK;
+}
+
+// sdrm_sample_begin: the chains of the call before are joined (by that call's count), the new call starts on the caller's stream
+int chains_begin(sdrm_engine* e, hipStream_t st) {
+  if (int jr = chains_join(e, st)) return jr;
+  e->chain_sched.state = ChainSched::ON_CALLER;
+  e->chain_sched.detached = false;
+  return SDRM_OK;
+}
+
+// A train forward is about to be queued on `st`, in front of its launches (no join: see above).  Beside a small call that is still on
+// the caller's stream the detach is armed: the mark behind the call's last step is taken now.
+int chains_train_forward(sdrm_engine* e, hipStream_t st) {
+  ChainSched& s = e->chain_sched;
+  const SampleCall& c = e->call;
+  if (!s.train_queued) s.train_row_owned = false;   // (kept over several train steps in a row)
+  s.train_queued = true; s.hold_marked = false;
+  if (e->tune.detach > 0 && c.active && c.path != SampleCall::SKINNY && c.i_next >= 1 && c.chains == 1 && !s.detached &&
+      s.state == ChainSched::ON_CALLER && !e->prof_on && !persist_now(e)) {
+    HIP_TRY(e, hipEventRecord(e->ev_fork, st));
+    s.state = ChainSched::DETACH_ARMED;
+  }
+  return SDRM_OK;
+}
+void chains_train_row_owned(sdrm_engine* e) { e->chain_sched.train_row_owned = true; }   // ... and it was a row-owned one, launched
+
+// The weight gradients of that step - its last MFMA kernel - are queued on `st`: the point pending chains wait for
+int chains_wgrads_queued(sdrm_engine* e, hipStream_t st) {
+  if (e->chain_sched.state != ChainSched::FORKED || !e->tune.hold_early || !e->chain_sched.train_row_owned) return SDRM_OK;
+  HIP_TRY(e, hipEventRecord(e->ev_hold, st));
+  e->chain_sched.hold_marked = true;
+  return SDRM_OK;
+}
+
+// Is a small call running beside this train step, on its detached chain or about to be (rows48_parts)?
+bool chains_small_call_beside(const sdrm_engine* e) {
+  return e->call.active && (e->chain_sched.state == ChainSched::DETACH_ARMED || (e->chain_sched.state == ChainSched::FORKED && e->chain_sched.detached));
+}
+
+// In front of the launches of one sdrm_sample_steps: on[c] = the stream of chain c
+int chains_streams(sdrm_engine* e, hipStream_t st, hipStream_t (&on)[4]) {
+  ChainSched& s = e->chain_sched;
+  auto aux_wait = [&](hipEvent_t ev) -> int {
+    for (int c = 0; c < chains_on_aux(e); ++c) HIP_TRY(e, hipStreamWaitEvent(e->aux[c], ev, 0));
+    return SDRM_OK;
+  };
+  // pending chains behind a row-owned train step: its own mark if it left one, else everything queued on `st` so far
+  auto hold = [&]() -> int {
+    if (!s.train_queued || !s.train_row_owned) return SDRM_OK;
+    if (s.hold_marked) { s.hold_marked = false; return aux_wait(e->ev_hold); }
+    HIP_TRY(e, hipEventRecord(e->ev_fork, st));
+    return aux_wait(e->ev_fork);
+  };
+  if (e->prof_on) {
+    if (s.state == ChainSched::DETACH_ARMED) s.state = ChainSched::ON_CALLER;
+    if (int jr = chains_join(e, st)) return jr;
+  } else if (s.state == ChainSched::DETACH_ARMED) {   // the first steps behind a train step that was queued beside this small call
+    s.detached = true;
+    if (int rc = aux_wait(e->ev_fork)) return rc;
+    s.state = ChainSched::FORKED;
+    if (int rc = hold()) return rc;
+  } else if (s.state == ChainSched::FORKED) {
+    if (int rc = hold()) return rc;
+  } else if (chains_on_aux(e) > 0) {   // fork: the chains on auxiliary streams start after everything queued on `st` so far
+    HIP_TRY(e, hipEventRecord(e->ev_fork, st));
+    if (int rc = aux_wait(e->ev_fork)) return rc;
+    s.state = ChainSched::FORKED;
+  }
+  s.train_queued = false;
+  for (int c = 0; c < 4; ++c) on[c] = e->prof_on ? st : s.detached ? e->aux[0] : c == 0 ? st : e->aux[c - 1];
+  return SDRM_OK;
+}
+
 // The same step on 48-row work-groups (csrc/rows48.h), for batches the 96-row kernels would leave CUs idle with.  Returns the
 // work-groups per 16-user row group, 0: not this path.
 //   1: the groups of the batch fill most of ONE round of the chip (160..256 groups: 2545..4096 users; two work-groups fit a CU, but
 //      a second round's worth then shares the matrix pipes: no faster than the per-layer path);
 //   2 / 4 (column-split groups, exchanged through one XCD's L2): batches of at most 2048 / 1024 users, whose groups x parts fit the
 //      chip's 256 CUs - every work-group of such a launch must be resident at once; by size only 2, for 1281 .. 2048 users.
-// the abort word of the XCD-local launches lives in host-mapped memory the GPU writes: read it as volatile
-inline unsigned xabort_read(const sdrm_engine* e) { return e->xabort_host ? *(volatile const unsigned*)e->xabort_host : 0u; }
-
 int rows48_grid(int groups, int parts) { return parts == 1 ? groups : 8 * parts * ((groups + 7) / 8); }
 int rows48_parts(const sdrm_engine* e, int B) {
   if (!e->W0f || e->tune.rows48 <= 0 || e->tune.force_cfg >= 0 || e->tune.rowchain >= 2) return 0;
@@ -762,11 +906,10 @@ int rows48_parts(const sdrm_engine* e, int B) {
   // (measured, tools/rows48_probe.py, profiles/r05_rows48_probe.txt: two work-groups per group beat the per-layer path from ~1300
   // users on - B = 2048: 174 against 201 us, B = 1536: 164 against 170 - four per group do not: B = 1024: 140 against 131, the
   // redundant staging and the two hand-shakes per kernel cost what the five launches saved)
-  // ... unless a small sampling call is in progress on its detached chain (chains_for): beside it the eleven launches of the per-layer
+  // ... unless a small sampling call is in progress on its detached chain (ChainSched): beside it the eleven launches of the per-layer
   // path, which it may run along with, beat the column-split kernels, which hold it (tools/ab/walk_host.py, one rank of four - 2048 users,
   // 1358 sampled rows - in bench.py's walk: 25.2 k -> 27.1 k steps/s).  The two paths differ in the last bits of a step.
-  const bool beside_sampler = e->smp.active && (e->detach_armed || (e->chains_pending && e->n_aux == e->n_chains));
-  if (can_split && e->tune.split == 1 && G > 80 && rows48_grid(G, 2) <= 256) return beside_sampler ? 0 : 2;       // 1281 .. 2048 users
+  if (can_split && e->tune.split == 1 && G > 80 && rows48_grid(G, 2) <= 256) return chains_small_call_beside(e) ? 0 : 2;   // 1281 .. 2048 users
   return (G >= 160 && G <= 256) ? 1 : 0;   // (2545 .. 4096 users; measured: 2560 users 231 against 235 us, 2688 231 / 241, 2432 228 / 224)
 }
 
@@ -953,39 +1096,11 @@ int launch_sk_fwd4_nlnw(sdrm_engine* e, const SkStepArgs& ka, hipStream_t st, bo
 }
 
 int launch_sk_fwd4(sdrm_engine* e, const SkStepArgs& ka, hipStream_t st, bool* done) {
-  const int NL = (e->L + 15) / 16, NW = (e->W + 15) / 16;
-#define SK4_ROW(nl)                                                           \
-  switch (NW) {                                                               \
-    case 1: return launch_sk_fwd4_nlnw<nl, 1>(e, ka, st, done);               \
-    case 2: return launch_sk_fwd4_nlnw<nl, 2>(e, ka, st, done);               \
-    case 3: return launch_sk_fwd4_nlnw<nl, 3>(e, ka, st, done);               \
-    default: return launch_sk_fwd4_nlnw<nl, 4>(e, ka, st, done);              \
-  }
-  switch (NL) {
-    case 1: SK4_ROW(1)
-    case 2: SK4_ROW(2)
-    case 3: SK4_ROW(3)
-    default: SK4_ROW(4)
-  }
-#undef SK4_ROW
+  return with_skinny_form(e, [&](auto nl, auto nw) { return launch_sk_fwd4_nlnw<VAL(nl), VAL(nw)>(e, ka, st, done); });
 }
 
 int launch_sk_step(sdrm_engine* e, const SkStepArgs& ka, int which, int grid, hipStream_t st) {
-  const int NL = (e->L + 15) / 16, NW = (e->W + 15) / 16;   // tiles with real columns (1..4 each)
-#define SK_ROW(nl)                                                                  \
-  switch (NW) {                                                                     \
-    case 1: return launch_sk_step_nlnw<nl, 1>(e, ka, which, grid, st);              \
-    case 2: return launch_sk_step_nlnw<nl, 2>(e, ka, which, grid, st);              \
-    case 3: return launch_sk_step_nlnw<nl, 3>(e, ka, which, grid, st);              \
-    default: return launch_sk_step_nlnw<nl, 4>(e, ka, which, grid, st);             \
-  }
-  switch (NL) {
-    case 1: SK_ROW(1)
-    case 2: SK_ROW(2)
-    case 3: SK_ROW(3)
-    default: SK_ROW(4)
-  }
-#undef SK_ROW
+  return with_skinny_form(e, [&](auto nl, auto nw) { return launch_sk_step_nlnw<VAL(nl), VAL(nw)>(e, ka, which, grid, st); });
 }
 
 // eps-net layers 1..H and the output pre-activation inputs; layer 0 is launched by the caller
@@ -1019,67 +1134,6 @@ int hidden_forward(sdrm_engine* e, int MP, int rows, hipStream_t st, int cfg, in
                                                  Prof{e, cls, fl}, cfg)));
   }
   return SDRM_OK;
-}
-
-// Chains still running on the auxiliary streams are folded back into `st` before anything else touches
-// the engine's buffers or parameters.
-int join_chains(sdrm_engine* e, hipStream_t st) {
-  e->bwd_begun = false;   // a backward that was begun but never finished is abandoned
-  if (!e->chains_pending) return SDRM_OK;
-  for (int c = 0; c < e->n_aux; ++c) {
-    HIP_TRY(e, hipEventRecord(e->ev_join[c], e->aux[c]));
-    HIP_TRY(e, hipStreamWaitEvent(st, e->ev_join[c], 0));
-  }
-  e->chains_pending = false;
-  return SDRM_OK;
-}
-
-// The row chains of a sampling call in progress wait for everything queued on `st` so far (the end of a train step that ran between
-// two of its steps): their launches would otherwise share the chip with the step's one-work-group-per-CU kernels, which then end a
-// whole work-group time later (measured: 8850 -> 8565 steps/s with no dependency at all).
-int hold_chains(sdrm_engine* e, hipStream_t st) {
-  if (!e->chains_pending) return SDRM_OK;
-  if (e->hold_recorded) {   // the train step left its own mark: behind its weight gradients (hold_point)
-    for (int c = 0; c < e->n_aux; ++c) HIP_TRY(e, hipStreamWaitEvent(e->aux[c], e->ev_hold, 0));
-    e->hold_recorded = false;
-    return SDRM_OK;
-  }
-  HIP_TRY(e, hipEventRecord(e->ev_fork, st));
-  for (int c = 0; c < e->n_aux; ++c) HIP_TRY(e, hipStreamWaitEvent(e->aux[c], e->ev_fork, 0));
-  return SDRM_OK;
-}
-// ... and the point they wait for: behind the step's last MFMA kernel, the weight gradients.  What follows - the tail's two launches -
-// is latency- and HBM-bound on a fraction of the chip; the chains' next GEMMs run beside it (they read the call's snapshot of the net,
-// the tail writes the live parameters).
-int hold_point(sdrm_engine* e, hipStream_t st) {
-  if (!e->chains_pending || !e->tune.hold_early || !e->hold_needed) return SDRM_OK;
-  HIP_TRY(e, hipEventRecord(e->ev_hold, st));
-  e->hold_recorded = true;
-  return SDRM_OK;
-}
-
-// Row chains for a sampling call of n rows (rows are independent through the whole reverse loop, so a row range can run as a chain
-// of launches on a stream of its own; the ramp and drain of one chain's launch are then filled by the other's).  Measured in round 5
-// (tools/ab/chain_ab.py, profiles/r05_sampler_chains.txt; us per reverse step of the ML-1M net, whole calls): two chains win from
-// ~2700 rows on - 2715 rows 30.4 -> 27.3, 4096 rows 40.3 -> 36.1, 5429 rows 48.8 -> 44.4, 8192 rows 67.3 -> 59.5 - and lose below
-// (1358 rows 20.1 -> 22.9: a launch of half the rows no longer fills the chip).  Three chains: 42.6 at 5429 rows, worse elsewhere, and
-// worse inside a job that trains between sampling steps; more than two are not what the host's launch rate bounds
-// (tools/ab/chain_threads.py: one host thread per chain gives the same 43.4; a captured graph with forked streams replays at 65).
-// The rule: two chains once the call has 2560 x 352 elements per layer, i.e. each chain's launch still has ~130 work-groups.
-// A smaller call is one chain on the caller's stream - until a train step is queued beside it: from then on the chain runs on an
-// auxiliary stream (n_aux = 1, "detached", sdrm_train_forward; the caller's stream then carries the train steps): a train step of the per-layer path - eleven dependent launches of 5-13 us on a mostly idle chip -
-// and the four launches of a small sampling step are both latency chains, and two latency chains on two streams fill each other's
-// gaps.  Such a train step does not hold the chains (hold_chains is for row-owned steps, whose one-work-group-per-CU kernels lose a
-// whole work-group time to a busy CU).
-// A train step between two sampling steps (bench.py's walk) does not join the chains: the sampler runs in layer buffers of its own, what
-// the chains have queued may finish beside the start of the step, and their next launches wait for its end (hold_chains).  With no
-// dependency at all - chains running on beside the whole train step - a launch of one work-group per CU finds some CUs busy with the
-// other stream's work-groups and ends a whole work-group time later: 8850 -> 8565 steps/s.
-// While an event profile is recorded (sdrm_profile_begin) the chains run one after the other on the caller's stream: intervals of
-// launches that share the chip would overlap and say nothing about either kernel.
-int chains_for(const Tuning& t, int n, int WP) {
-  if (t.chains >= 1) return t.chains > 4 ? 4 : t.chains;
-  return (size_t)n * (size_t)WP >= (size_t)2560 * 352 ? 2 : 1;
 }
 
 int upload_schedule(sdrm_engine* e, float beta1, float beta2) {
@@ -1180,7 +1234,7 @@ int sdrm_debug_set_rows48_share(sdrm_engine* e, int on) {
 
 int sdrm_debug_set_sample_persist(sdrm_engine* e, int mode) {
   if (!e) return SDRM_ERR_ARG;
-  if (e->smp.active) return fail(e, SDRM_ERR_STATE, "sdrm_debug_set_sample_persist: inside a sampling call");
+  if (e->call.active) return fail(e, SDRM_ERR_STATE, "sdrm_debug_set_sample_persist: inside a sampling call");
   e->tune.smp_persist = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
   return SDRM_OK;
 }
@@ -1246,11 +1300,11 @@ int sdrm_debug_set_chains(sdrm_engine* e, int chains) {
   return SDRM_OK;
 }
 
-int sdrm_debug_chains(const sdrm_engine* e) { return e ? e->n_chains : 0; }
+int sdrm_debug_chains(const sdrm_engine* e) { return e ? e->call.chains : 0; }
 
 int sdrm_debug_set_tile(sdrm_engine* e, int cfg) {
   if (!e) return SDRM_ERR_ARG;
-  if (e->bwd_begun || e->smp.active)
+  if (e->bwd_begun || e->call.active)
     return fail(e, SDRM_ERR_STATE, "sdrm_debug_set_tile: a two-call backward or a sampling call is in progress");
   e->fwd_done = false;   // the slope-partial layout of a backward is fixed by its forward's tile: a pending forward is dropped
   e->tune.force_cfg = cfg;
@@ -1496,7 +1550,7 @@ int sdrm_get_schedule(const sdrm_engine* e, float* b, float* a, float* ab) {
 int sdrm_set_params(sdrm_engine* e, const float* flat, void* stream) {
   if (!e || !flat) return fail(e, SDRM_ERR_ARG, "sdrm_set_params: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if (int jr = join_chains(e, st)) return jr;
+  if (int jr = chains_join(e, st)) return jr;
   HIP_TRY(e, hipMemcpyAsync(e->p, flat, e->P * 4, hipMemcpyDeviceToDevice, st));
   return launch_adam(e, nullptr, 0.f, 0, st);  // re-pack only
 }
@@ -1543,9 +1597,6 @@ int sdrm_adam_reset(sdrm_engine* e, void* stream) {
 }
 
 // ---------------------------------------------------------------------------------------------
-namespace {
-bool sample_persist_fits(const sdrm_engine* e, const SampleState& s);   // (below, beside the sampler)
-}
 // fold_sums (sdrm_train_step): the backward folds the loss partials itself - no k_loss_sums launch here
 static int train_forward_impl(sdrm_engine* e, const float* x0, int B, int64_t row0, int mode, const sdrm_train_randoms* rnd,
                               uint64_t seed, uint64_t step, float nd, double* sums, void* stream, bool fold_sums) {
@@ -1555,21 +1606,8 @@ static int train_forward_impl(sdrm_engine* e, const float* x0, int B, int64_t ro
     return fail(e, SDRM_ERR_ARG, "sdrm_train_forward: EXPLICIT mode needs noise, t and keep");
   if (mode != SDRM_RNG_EXPLICIT && mode != SDRM_RNG_PHILOX) return fail(e, SDRM_ERR_ARG, "bad rng mode");
   hipStream_t st = (hipStream_t)stream;
-  // (No join_chains here: a sampling call in progress reads its own snapshot of the net and runs in its own buffers - Us, X, smp_pre,
-  // smp_Y - so what its row chains have queued on the auxiliary streams may finish beside the start of this step; the chains' NEXT
-  // launches wait for the step's end: hold_chains, from the next sdrm_sample_steps - one cross-stream dependency per train step instead of
-  // a join and a fork.)
   e->bwd_begun = false;   // a backward that was begun but never finished is abandoned
-  if (!e->train_since_sample) e->hold_needed = false;   // (set below by a row-owned forward; kept over several train steps in a row)
-  e->train_since_sample = true; e->hold_recorded = false;
-  // A small sampling call (one chain) runs on the caller's stream until a train step is queued beside it - on a stream of its own a
-  // plain call is ~3 us per step SLOWER (tools/ab/detach_ab.py: 679 rows 17.0 -> 19.7, ML-100k 58.1 -> 62.4).  From here on its chain
-  // is detached (chains_for): the mark behind its last step is taken now, in front of this step's launches.
-  if (e->tune.detach > 0 && e->smp.active && !e->smp.skinny && e->smp.i_next >= 1 && e->n_chains == 1 && e->n_aux == 0 && !e->detach_armed &&
-      !e->prof_on && !sample_persist_fits(e, e->smp)) {
-    HIP_TRY(e, hipEventRecord(e->ev_fork, st));
-    e->detach_armed = true;
-  }
+  if (int cr = chains_train_forward(e, st)) return cr;   // (no chains_join: a sampling call in progress shares nothing with this step)
   e->fwd_done = false;
   e->fwd_params_live = true;
   if (int xs = split_status(e)) return xs;
@@ -1604,7 +1642,7 @@ static int train_forward_impl(sdrm_engine* e, const float* x0, int B, int64_t ro
     if (rc) return rc;
     rc = launch_row_forward(e, p, x0, row0, mode, rnd, seed, step, nd, st);
     if (rc) return rc;
-    e->hold_needed = true;
+    chains_train_row_owned(e);
   } else {
     const int MP = p.MP, n = e->T + 1;
     const int cfg = choose_cfg(e->tune, MP, e->tune.nt32_max_rows_train);   // one tile for every NT launch of the step
@@ -1936,7 +1974,7 @@ int sdrm_train_backward_finish(sdrm_engine* e, float* grad, void* stream) {
   float* gout = grad ? grad : e->g;
   if (gout != e->grad_src) return fail(e, SDRM_ERR_ARG, "sdrm_train_backward_finish: different gradient buffer than begin");
   int rc = backward_wgrads(e, st, false);
-  if (!rc) rc = hold_point(e, st);
+  if (!rc) rc = chains_wgrads_queued(e, st);
   if (!rc) rc = backward_tail(e, gout, BUCKET_SECOND, false, 0.f, st);
   e->bwd_begun = false;
   return rc;
@@ -1954,7 +1992,7 @@ static int train_backward_impl(sdrm_engine* e, const double* sums, float* grad, 
   e->grad_src = gout;
   int rc = backward_chain(e, sums, loss, st, false, fold_sums);
   if (!rc) rc = backward_wgrads(e, st, true);
-  if (!rc) rc = hold_point(e, st);
+  if (!rc) rc = chains_wgrads_queued(e, st);
   if (!rc) rc = backward_tail(e, gout, BUCKET_BOTH, fused_lr != nullptr, fused_lr ? *fused_lr : 0.f, st);
   return rc;
 }
@@ -1974,7 +2012,7 @@ int sdrm_grad_buckets(const sdrm_engine* e, int64_t* first_off, int64_t* first_l
 
 int sdrm_adam_step(sdrm_engine* e, const float* grad, float lr, void* stream) {
   if (!e) return SDRM_ERR_ARG;
-  if (int jr = join_chains(e, (hipStream_t)stream)) return jr;
+  if (int jr = chains_join(e, (hipStream_t)stream)) return jr;
   e->adam_t += 1;
   return launch_adam(e, grad, lr, 1, (hipStream_t)stream);
 }
@@ -2140,7 +2178,7 @@ int sdrm_get_train_outputs(const sdrm_engine* e, float* psq, void* stream) {
 static int forward_rows(sdrm_engine* e, const float* x, const int64_t* t, int t_uniform, int n, int mode,
                         const uint8_t* keep, uint64_t seed, uint64_t step, int64_t row0, float* out, int ldout,
                         int cols_valid, hipStream_t st) {
-  if (int jr = join_chains(e, st)) return jr;
+  if (int jr = chains_join(e, st)) return jr;
   const int MP = round_up(n, BM);
   const int cfg = choose_cfg(e->tune, MP, e->tune.nt32_max_rows);
   PrepFwdArgs pa{};
@@ -2204,67 +2242,98 @@ int sdrm_perturb_input(sdrm_engine* e, const float* x, const int64_t* t, const f
   return SDRM_OK;
 }
 
+namespace {
 // The narrow-net sampler: ONE persistent launch runs the whole reverse loop (rows are independent across all timesteps).  It is
 // issued by sdrm_sample_begin, on that call's stream, so the call reads the parameters as they are at its begin - the same
 // contract as the snapshot of the per-layer path; sdrm_sample_steps is then only book-keeping for the resumable API.
-static int launch_skinny_sampler(sdrm_engine* e, hipStream_t st) {
-  SampleState& s = e->smp;
-  const int n = s.n, L = e->L;
+int launch_skinny_sampler(sdrm_engine* e, const SampleCall& s, hipStream_t st) {
   SkinnyArgs ka{};
   ka.W0c = e->W0c; ka.K0 = e->K0; ka.Whc = e->Whc; ka.Woc = e->Woc; ka.bh = e->bhc; ka.bo = e->boc;
   ka.B0tab = e->B0tab; ka.slope0 = slope_ptr(e, 0); ka.slopeh = e->H > 0 ? slope_ptr(e, 1) : slope_ptr(e, 0);
   ka.rev = e->rev_dev; ka.xT = s.xT; ka.Z = s.z; ka.keep = s.keep;
   ka.Tj = s.multires ? e->Tj_dev : nullptr; ka.rowid = s.multires ? e->rowid_dev : nullptr;
-  ka.out = e->X; ka.n = n; ka.L = L; ka.W = e->W; ka.T = e->T; ka.H = e->H;
+  ka.out = e->X; ka.n = s.n; ka.L = e->L; ka.W = e->W; ka.T = e->T; ka.H = e->H;
   ka.mode = s.mode; ka.seed_lo = (uint32_t)s.seed; ka.seed_hi = (uint32_t)(s.seed >> 32);
   ka.call_id = (uint32_t)s.call_id; ka.row0 = s.row0; ka.nd = s.nd;
   ka.LPs = e->LP; ka.WPs = e->WP;
-  const int NL = (L + 15) / 16, NW = (e->W + 15) / 16;           // tiles with real columns (1..4 each)
-  dim3 grid((n + 15) / 16), block(64 * (NL > NW ? NL : NW));   // 16 rows per work-group, one wave per column tile
-#define SKINNY_LAUNCH(nl, nw) SDRM_LAUNCH(e, (k_skinny_sample<nl, nw>), grid, block, 0, st, ka)
-#define SKINNY_ROW(nl)                                 \
-switch (NW) {                                        \
-  case 1: SKINNY_LAUNCH(nl, 1); break;               \
-  case 2: SKINNY_LAUNCH(nl, 2); break;               \
-  case 3: SKINNY_LAUNCH(nl, 3); break;               \
-  default: SKINNY_LAUNCH(nl, 4); break;              \
+  return with_skinny_form(e, [&](auto nl, auto nw) {   // 16 rows per work-group, one wave per column tile
+    SDRM_LAUNCH(e, (k_skinny_sample<VAL(nl), VAL(nw)>), dim3((s.n + 15) / 16), dim3(64 * std::max(VAL(nl), VAL(nw))), 0, st, ka);
+    HIP_TRY(e, hipGetLastError());
+    return SDRM_OK;
+  });
 }
-  switch (NL) {
-    case 1: SKINNY_ROW(1); break;
-    case 2: SKINNY_ROW(2); break;
-    case 3: SKINNY_ROW(3); break;
-    default: SKINNY_ROW(4); break;
-  }
-#undef SKINNY_ROW
-#undef SKINNY_LAUNCH
+
+// The other paths: the call's snapshot of the net (see sdrm_engine::smp_w: one launch for all of its pieces), the sampler state X and the first
+// step's layer-0 input Us; the persistent sampler's counters start every call at zero (row tiles differ from call to call)
+int launch_sample_init(sdrm_engine* e, const SampleCall& s, hipStream_t st) {
+  float* b = e->smp_w;
+  CopySegs cs{};
+  auto seg = [&](int i, int k, const float* src, size_t n_, size_t extra = 0) {
+    cs.src[i] = src; cs.dst[i] = b + e->smp_off[k] + extra; cs.n[i] = src ? (unsigned)n_ : 0u;
+  };
+  seg(0, 0, e->W0c, (size_t)e->WP * e->K0);
+  seg(1, 1, e->H >= 1 ? e->Whc : nullptr, (size_t)e->WP * e->WP);
+  seg(2, 2, e->Woc, (size_t)e->LP * e->WP);
+  seg(3, 3, e->H >= 1 ? e->bhc : nullptr, (size_t)e->WP);
+  seg(4, 4, e->boc, (size_t)e->LP);
+  seg(5, 5, e->B0tab, (size_t)(e->T + 1) * e->WP);
+  seg(6, 6, slope_ptr(e, 0), 1);
+  seg(7, 6, e->H >= 1 ? slope_ptr(e, 1) : nullptr, 1, 1);
+  SDRM_LAUNCH(e, k_copy_segments, dim3(64, 8), dim3(256), 0, st, cs);
   HIP_TRY(e, hipGetLastError());
-  s.skinny_launched = true;
+  SampleInitArgs ia{};
+  ia.xT = s.xT; ia.keep = s.keep; ia.Tj = s.multires ? e->Tj_dev : nullptr; ia.rowid = s.multires ? e->rowid_dev : nullptr;
+  ia.X = e->X; ia.U = e->Us; ia.n = s.n; ia.L = e->L; ia.LP = e->LP; ia.K0 = e->LP; ia.MP = s.MP; ia.T = e->T;
+  ia.mode = s.mode; ia.seed_lo = (uint32_t)s.seed; ia.seed_hi = (uint32_t)(s.seed >> 32);
+  ia.call_id = (uint32_t)s.call_id; ia.row0 = s.row0;
+  ia.bpr = (e->LP / 4 + 255) / 256;
+  dim3 grid((unsigned)((size_t)ia.bpr * s.MP));
+  SDRM_LAUNCH(e, k_sample_init, grid, dim3(256), 0, st, ia);
+  HIP_TRY(e, hipGetLastError());
+  if (e->xcntS) HIP_TRY(e, hipMemsetAsync(e->xcntS, 0, (size_t)256 * 32 * sizeof(unsigned), st));
   return SDRM_OK;
 }
+
+// Reverse steps in one launch (csrc/sample_persist.h): full resolution, PHILOX (the reverse update rides in the out layer's
+// epilogue), a net whose layers share one tiling (L == W), one row chain, a forced tile only if it is the 32x32 one, the chip's
+// block -> XCD mapping, and every work-group resident at once: 32x32 tiles, at most two per CU on the fullest XCD.
+// by size: up to 11 row tiles of 32 (at most two row tiles = 22 work-groups per XCD: one per CU).  Measured (tools/sample_persist_probe.py,
+// profiles/r05_sample_persist_probe.txt): n = 339: 12.1 us per step for a whole call in one launch against 16.5 for the three
+// launches per step (15.7 driven one step per call); n = 679 - the 8-GPU shard: 22 row tiles put 33 work-groups on six XCDs' 32
+// CUs, the doubled CU sets every phase - 16.0 against 16.4 (19.9 one step per call), n = 1024: 18.8 against 17.7: not taken there
+// Asked once per call, by sdrm_sample_begin (the tile's and smp_persist's setters refuse inside one; fuse_rev as it is then): the abort word is persist_now's.
+constexpr int SMP_PERSIST_MAX_ROWS = 352;
+bool sample_persist_fits(const sdrm_engine* e, int n, int MP, int multires, int mode, int chains) {
+  if (e->tune.smp_persist <= 0 || !e->xcd_ok || !e->xcntS || !e->xabort_host) return false;
+  if (multires || mode != SDRM_RNG_PHILOX || e->LP != e->WP || chains != 1) return false;
+  if (e->tune.force_cfg >= 0 && e->tune.force_cfg != 4) return false;
+  if (e->tune.fuse_rev == 0) return false;   // (a caller who asked for the stand-alone reverse update gets the per-layer path)
+  const int tiles_m = MP / 32, tiles_n = e->WP / 32;
+  const int per_xcd = ((tiles_m + 7) / 8) * tiles_n;
+  if (per_xcd > 64 || tiles_m > 256) return false;
+  return e->tune.smp_persist >= 2 || n <= SMP_PERSIST_MAX_ROWS;
+}
+}  // namespace
 
 int sdrm_sample_begin(sdrm_engine* e, int n, float nd, int multires, int mode, const float* xT, const float* z,
                       const uint8_t* keep, const int64_t* Tj, uint64_t seed, uint64_t call_id, int64_t row0,
                       int64_t* Tj_out, void* stream) {
   if (!e) return SDRM_ERR_ARG;
-  e->smp.active = false;
+  SampleCall& c = e->call;
+  c.active = false;
   if (n < 1 || n > 3 * e->max_rows) return fail(e, SDRM_ERR_SHAPE, "sdrm_sample: n outside [1, 3*max_rows]");
   if (mode == SDRM_RNG_EXPLICIT && (!xT || !z || !keep || (multires && !Tj)))
     return fail(e, SDRM_ERR_ARG, "sdrm_sample: EXPLICIT mode needs xT, z, keep (and Tj for multi-resolution)");
   if (mode != SDRM_RNG_EXPLICIT && mode != SDRM_RNG_PHILOX) return fail(e, SDRM_ERR_ARG, "bad rng mode");
   if (multires && n > e->max_rows) return fail(e, SDRM_ERR_SHAPE, "sdrm_sample: multi-resolution n > max_rows");
   hipStream_t st = (hipStream_t)stream;
-  if (int jr = join_chains(e, st)) return jr;
-  const int T = e->T, L = e->L, MP = round_up(n, BM);
+  if (int jr = chains_begin(e, st)) return jr;
+  const int T = e->T;
   e->fwd_done = false;
-  e->n_chains = chains_for(e->tune, n, e->WP);
-  e->chain_chunk = round_up((n + e->n_chains - 1) / e->n_chains, BM);
-  e->n_chains = (n + e->chain_chunk - 1) / e->chain_chunk;
-  e->n_aux = e->n_chains > 1 ? e->n_chains - 1 : 0;   // (the one chain of a small call: detached by the first train step queued beside it)
-  e->detach_armed = false;
   int rc = ensure_tables(e, st);
   if (rc) return rc;
-  int i_start = T;
-  e->smp_nact.assign(T + 2, n);                       // n_act[i] = rows with Tj >= i (all rows when full resolution)
+  int i_first = T;
+  c.nact.assign(T + 2, n);                            // nact[i] = rows with Tj >= i (all rows when full resolution)
   if (multires) {
     // Start steps on the host: drawn with the same Philox call the device would make (PHILOX), or copied
     // back (EXPLICIT; one sync per sampling call).  Slots are then ordered by descending Tj.
@@ -2280,87 +2349,44 @@ int sdrm_sample_begin(sdrm_engine* e, int n, float nd, int multires, int mode, c
       HIP_TRY(e, hipStreamSynchronize(st));
       for (int r = 0; r < n; ++r) tj[r] = tj[r] < 0 ? 0 : (tj[r] > T ? T : tj[r]);
     }
-    std::vector<int> perm(n);
-    for (int r = 0; r < n; ++r) perm[r] = r;
-    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return tj[a] > tj[b]; });
-    e->smp_tj_sorted.resize(n);
-    for (int s = 0; s < n; ++s) e->smp_tj_sorted[s] = tj[perm[s]];
-    e->smp_perm = perm;
+    c.perm.resize(n);
+    for (int r = 0; r < n; ++r) c.perm[r] = r;
+    std::stable_sort(c.perm.begin(), c.perm.end(), [&](int a, int b) { return tj[a] > tj[b]; });
+    c.tj_sorted.resize(n);
+    for (int s = 0; s < n; ++s) c.tj_sorted[s] = tj[c.perm[s]];
     std::vector<int> hist(T + 2, 0);
     for (int r = 0; r < n; ++r) hist[(int)tj[r]]++;
     int acc = 0;
-    for (int i = T; i >= 0; --i) { acc += hist[i]; e->smp_nact[i] = acc; }
-    i_start = (int)e->smp_tj_sorted[0];
-    HIP_TRY(e, hipMemcpyAsync(e->rowid_dev, e->smp_perm.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(e, hipMemcpyAsync(e->Tj_dev, e->smp_tj_sorted.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    for (int i = T; i >= 0; --i) { acc += hist[i]; c.nact[i] = acc; }
+    i_first = (int)c.tj_sorted[0];
+    HIP_TRY(e, hipMemcpyAsync(e->rowid_dev, c.perm.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(e, hipMemcpyAsync(e->Tj_dev, c.tj_sorted.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
     if (Tj_out) {
-      e->smp_tj_orig = tj;
-      HIP_TRY(e, hipMemcpyAsync(Tj_out, e->smp_tj_orig.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+      c.tj_orig = tj;
+      HIP_TRY(e, hipMemcpyAsync(Tj_out, c.tj_orig.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
     }
   }
-  const bool skinny = skinny_net(e);
-  if (skinny) {
-    e->smp = SampleState{true, n, MP, multires, mode, i_start, nd, z, keep, seed, call_id, row0, xT, true, false, i_start};
-    const int rc = launch_skinny_sampler(e, st);
-    if (rc != SDRM_OK) e->smp.active = false;
-    return rc;
-  }
-  {
-    // the call's snapshot of the net (see sdrm_engine::smp_w): one launch for all of its pieces
-    float* b = e->smp_w;
-    CopySegs cs{};
-    auto seg = [&](int i, int k, const float* src, size_t n_, size_t extra = 0) {
-      cs.src[i] = src; cs.dst[i] = b + e->smp_off[k] + extra; cs.n[i] = src ? (unsigned)n_ : 0u;
-    };
-    seg(0, 0, e->W0c, (size_t)e->WP * e->K0);
-    seg(1, 1, e->H >= 1 ? e->Whc : nullptr, (size_t)e->WP * e->WP);
-    seg(2, 2, e->Woc, (size_t)e->LP * e->WP);
-    seg(3, 3, e->H >= 1 ? e->bhc : nullptr, (size_t)e->WP);
-    seg(4, 4, e->boc, (size_t)e->LP);
-    seg(5, 5, e->B0tab, (size_t)(T + 1) * e->WP);
-    seg(6, 6, slope_ptr(e, 0), 1);
-    seg(7, 6, e->H >= 1 ? slope_ptr(e, 1) : nullptr, 1, 1);
-    SDRM_LAUNCH(e, k_copy_segments, dim3(64, 8), dim3(256), 0, st, cs);
-    HIP_TRY(e, hipGetLastError());
-  }
-  SampleInitArgs ia{};
-  ia.xT = xT; ia.keep = keep; ia.Tj = multires ? e->Tj_dev : nullptr; ia.rowid = multires ? e->rowid_dev : nullptr;
-  ia.X = e->X; ia.U = e->Us; ia.n = n; ia.L = L; ia.LP = e->LP; ia.K0 = e->LP; ia.MP = MP; ia.T = T;
-  ia.mode = mode; ia.seed_lo = (uint32_t)seed; ia.seed_hi = (uint32_t)(seed >> 32);
-  ia.call_id = (uint32_t)call_id; ia.row0 = row0;
-  ia.bpr = (e->LP / 4 + 255) / 256;
-  dim3 grid((unsigned)((size_t)ia.bpr * MP));
-  SDRM_LAUNCH(e, k_sample_init, grid, dim3(256), 0, st, ia);
-  HIP_TRY(e, hipGetLastError());
-  e->smp = SampleState{true, n, MP, multires, mode, i_start, nd, z, keep, seed, call_id, row0, xT, false, false, i_start};
-  if (e->xcntS) {   // the persistent sampler's counters start every call at zero (row tiles differ from call to call)
-    HIP_TRY(e, hipMemsetAsync(e->xcntS, 0, (size_t)256 * 32 * sizeof(unsigned), st));
-    e->xphaseS = 0;
-  }
-  return SDRM_OK;
+  // the record of the call
+  c.n = n; c.multires = multires; c.mode = mode; c.nd = nd;
+  c.xT = xT; c.z = z; c.keep = keep;
+  c.seed = seed; c.call_id = call_id; c.row0 = row0;
+  c.MP = round_up(n, BM);
+  const int chains = chains_for(e->tune, n, e->WP);
+  c.chunk = round_up((n + chains - 1) / chains, BM);
+  c.chains = (n + c.chunk - 1) / c.chunk;
+  c.path = skinny_net(e) ? SampleCall::SKINNY
+           : sample_persist_fits(e, n, c.MP, multires, mode, c.chains) ? SampleCall::PERSIST : SampleCall::PER_LAYER;
+  c.i_next = i_first;
+  c.persist_phase = 0;
+  c.active = true;
+  rc = c.path == SampleCall::SKINNY ? launch_skinny_sampler(e, c, st) : launch_sample_init(e, c, st);
+  if (rc) c.active = false;
+  return rc;
 }
 
 namespace {
-// Reverse steps in one launch (csrc/sample_persist.h): full resolution, PHILOX (the reverse update rides in the out layer's
-// epilogue), a net whose layers share one tiling (L == W), one row chain, a forced tile only if it is the 32x32 one, the chip's
-// block -> XCD mapping, and every work-group resident at once: 32x32 tiles, at most two per CU on the fullest XCD.
-// by size: up to 11 row tiles of 32 (at most two row tiles = 22 work-groups per XCD: one per CU).  Measured (tools/sample_persist_probe.py,
-// profiles/r05_sample_persist_probe.txt): n = 339: 12.1 us per step for a whole call in one launch against 16.5 for the three
-// launches per step (15.7 driven one step per call); n = 679 - the 8-GPU shard: 22 row tiles put 33 work-groups on six XCDs' 32
-// CUs, the doubled CU sets every phase - 16.0 against 16.4 (19.9 one step per call), n = 1024: 18.8 against 17.7: not taken there
-constexpr int SMP_PERSIST_MAX_ROWS = 352;
-bool sample_persist_fits(const sdrm_engine* e, const SampleState& s) {
-  if (e->tune.smp_persist <= 0 || !e->xcd_ok || !e->xcntS || !e->xabort_host || xabort_read(e) != 0u) return false;
-  if (s.multires || s.mode != SDRM_RNG_PHILOX || e->LP != e->WP || e->n_chains != 1) return false;
-  if (e->tune.force_cfg >= 0 && e->tune.force_cfg != 4) return false;
-  if (e->tune.fuse_rev == 0) return false;   // (a caller who asked for the stand-alone reverse update gets the per-layer path)
-  const int tiles_m = s.MP / 32, tiles_n = e->WP / 32;
-  const int per_xcd = ((tiles_m + 7) / 8) * tiles_n;
-  if (per_xcd > 64 || tiles_m > 256) return false;
-  return e->tune.smp_persist >= 2 || s.n <= SMP_PERSIST_MAX_ROWS;
-}
-
-int launch_sample_persist(sdrm_engine* e, SampleState& s, int count, hipStream_t st) {
+// count reverse steps from i_next on, in one launch
+int launch_sample_persist(sdrm_engine* e, SampleCall& s, int count, hipStream_t st) {
   const NetView nv = snapshot_view(e);
   const int MP = s.MP, tiles_m = MP / 32, tiles_n = e->WP / 32;
   SamplePersistArgs P{};
@@ -2382,9 +2408,9 @@ int launch_sample_persist(sdrm_engine* e, SampleState& s, int count, hipStream_t
   P.B0tab = nv.B0tab; P.ldtab = e->WP; P.rev = e->rev_dev;
   P.T = e->T; P.H = e->H; P.i_first = s.i_next; P.count = count;
   P.row_tiles = tiles_m; P.tiles_n = tiles_n;
-  P.cnt = e->xcntS; P.base = e->xphaseS * (uint32_t)tiles_n; P.abort_ = e->xabort_dev;
+  P.cnt = e->xcntS; P.base = s.persist_phase * (uint32_t)tiles_n; P.abort_ = e->xabort_dev;
   const int steps = std::min(count, s.i_next);
-  e->xphaseS += (uint32_t)(steps * (e->H + 2));
+  s.persist_phase += (uint32_t)(steps * (e->H + 2));
   const int grid = 8 * tiles_n * ((tiles_m + 7) / 8);
   const double flops = 2.0 * s.n * ((double)e->W * e->L + (double)e->H * e->W * e->W + (double)e->L * e->W) * steps;
   const int rc = hip_rc(e, "k_sample_persist", profiled(e, PC_SMP_PERSIST, flops, st, [&] {
@@ -2395,134 +2421,112 @@ int launch_sample_persist(sdrm_engine* e, SampleState& s, int count, hipStream_t
   s.i_next -= steps;
   return SDRM_OK;
 }
+
+// Reverse step i of the rows [s0, s1) of one chain, on the chain's stream: layer 0, the hidden layers, the out layer, and the
+// reverse update where it does not ride in the out layer's epilogue
+int sample_chain_step(sdrm_engine* e, const SampleCall& s, const NetView& nv, int i, int s0, int s1, hipStream_t sc) {
+  const int L = e->L, rows = s1 - s0, MP = round_up(rows, BM);
+  const size_t nL = (size_t)s.n * L;
+  const int cfg = choose_cfg(e->tune, MP, e->tune.nt32_max_rows);
+  // the sampler keeps ACTIVATIONS in the layer buffers (EPI_BIAS_PRELU): no backward will ask for the pre-activations
+  GemmArgs a0{};
+  a0.C = smp_buf(e, 0) + (size_t)s0 * e->WP; a0.ldc = e->WP; a0.bias = nv.B0tab + (size_t)i * e->WP; a0.slopeE = nv.slope0;
+  HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_PRELU>(a0, e->Us + (size_t)s0 * e->LP, e->LP, nv.W0c, e->K0, MP, e->WP, e->LP, sc,
+                                                    Prof{e, PC_SMP_L0, 2.0 * rows * (double)e->W * e->L}, cfg)));
+  int rc = hidden_forward(e, MP, rows, sc, cfg, s0, PC_SMP_HIDDEN, true, &nv);
+  if (rc) return rc;
+  float c1, sqrt_alpha, sqrt_beta;
+  reverse_coeffs(e, i, c1, sqrt_alpha, sqrt_beta);
+  // (round 5: multi-resolution steps too - their active prefix is a launch like any other, the epilogue keys Philox by the slot's
+  // original row; EXPLICIT randoms keep the stand-alone kernel)
+  const bool fused = s.mode == SDRM_RNG_PHILOX && (e->tune.fuse_rev == 2 || (e->tune.fuse_rev == 1 && rows <= FUSE_REV_MAX_ROWS));
+  GemmArgs a{};
+  a.C = e->smp_Y + (size_t)s0 * e->LP; a.ldc = e->LP; a.bias = nv.boc;
+  a.rows_valid = MP; a.cols_valid = e->LP;
+  const Prof pr{e, PC_SMP_OUT, 2.0 * rows * (double)e->L * e->W};
+  if (fused) {
+    // eps_hat never reaches memory: the epilogue applies denoise_add_noise to the sampler state and writes the
+    // next step's dropped-out input (one launch less per reverse step)
+    a.revX = e->X; a.revU = e->Us; a.rev_ldx = e->LP; a.rev_s0 = s0; a.rev_n = s1; a.rev_L = L; a.rev_step = i;
+    a.rev_c1 = c1; a.rev_sqrt_alpha = sqrt_alpha; a.rev_sqrt_beta = sqrt_beta; a.rev_nd = s.nd;
+    a.rev_seed_lo = (uint32_t)s.seed; a.rev_seed_hi = (uint32_t)(s.seed >> 32); a.rev_call_id = (uint32_t)s.call_id;
+    a.rev_row0 = s.row0; a.rev_rowid = s.multires ? e->rowid_dev : nullptr;
+    HIP_TRY(e, (gemm_forward<XF_NONE, EPI_TANH_REV>(a, smp_buf(e, e->H) + (size_t)s0 * e->WP, e->WP, nv.Woc, e->WP, MP, e->LP, e->WP, sc, pr, cfg)));
+    return SDRM_OK;
+  }
+  HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_TANH>(a, smp_buf(e, e->H) + (size_t)s0 * e->WP, e->WP, nv.Woc, e->WP, MP, e->LP, e->WP, sc, pr, cfg)));
+  ReverseArgs ra{};
+  ra.X = e->X; ra.Y = e->smp_Y; ra.U = e->Us;
+  ra.Z = (s.mode == SDRM_RNG_EXPLICIT && i > 1) ? s.z + (size_t)i * nL : nullptr;
+  ra.keep_next = (s.mode == SDRM_RNG_EXPLICIT && i > 1) ? s.keep + (size_t)(i - 1) * nL : nullptr;
+  ra.Tj = s.multires ? e->Tj_dev : nullptr;
+  ra.rowid = s.multires ? e->rowid_dev : nullptr;
+  ra.s0 = s0; ra.n = s1; ra.L = L; ra.LP = e->LP; ra.K0 = e->LP; ra.step_i = i; ra.nd = s.nd;
+  ra.c1 = c1; ra.sqrt_alpha = sqrt_alpha; ra.sqrt_beta = sqrt_beta;
+  ra.mode = s.mode; ra.seed_lo = (uint32_t)s.seed; ra.seed_hi = (uint32_t)(s.seed >> 32);
+  ra.call_id = (uint32_t)s.call_id; ra.row0 = s.row0;
+  ra.bpr = ((L + 3) / 4 + 255) / 256;
+  ra.rpb = std::max(1, 256 / ((L + 3) / 4));
+  const unsigned rev_grid = ra.rpb > 1 ? (unsigned)((rows + ra.rpb - 1) / ra.rpb) : (unsigned)((size_t)ra.bpr * rows);
+  SDRM_LAUNCH(e, k_reverse_update, dim3(rev_grid), dim3(256), 0, sc, ra);
+  HIP_TRY(e, hipGetLastError());
+  return SDRM_OK;
+}
 }  // namespace
 
 int sdrm_sample_steps(sdrm_engine* e, int count, void* stream) {
   if (!e) return SDRM_ERR_ARG;
-  if (!e->smp.active) return fail(e, SDRM_ERR_STATE, "sdrm_sample_steps: no sampling call in progress");
+  SampleCall& s = e->call;
+  if (!s.active) return fail(e, SDRM_ERR_STATE, "sdrm_sample_steps: no sampling call in progress");
   hipStream_t st = (hipStream_t)stream;
-  SampleState& s = e->smp;
-  const int n = s.n, L = e->L;
-  const size_t nL = (size_t)n * L;
-  if (s.skinny) {
-    // One persistent launch runs the whole reverse loop (rows are independent across all timesteps); the
-    // step counter is then only book-keeping for the resumable API.
-    if (!s.skinny_launched) return fail(e, SDRM_ERR_STATE, "sdrm_sample_steps: the sampler was not launched");
+  if (s.path == SampleCall::SKINNY) {
+    // (launch_skinny_sampler ran the whole loop: the step counter is only book-keeping for the resumable API)
     s.i_next = s.i_next > count ? s.i_next - count : 0;
     return SDRM_OK;
   }
-  // A train forward that was waiting for its backward is dropped (the documented rule of the two-call train API; the sampler has had
-  // layer buffers of its own since round 5 - smp_pre, smp_Y - so whole train steps between sampling steps share nothing with the call).
+  // A train forward that was waiting for its backward is dropped (the documented rule of the two-call train API).  Whole train steps may
+  // run between sdrm_sample_steps calls (bench.py interleaves them): the call reads its own snapshot of the net and has layer buffers of
+  // its own - smp_pre, smp_Y - so they change nothing of it.
   e->fwd_done = false;
   e->bwd_begun = false;
-  // Train steps may run between sdrm_sample_steps calls (bench.py interleaves them): the sampler reads its own snapshot of
-  // the net (sdrm_sample_begin), so they change nothing of this call.
-  if (count > 0 && s.i_next >= 1 && sample_persist_fits(e, s)) return launch_sample_persist(e, s, count, st);
+  if (count > 0 && s.i_next >= 1 && persist_now(e)) return launch_sample_persist(e, s, count, st);
+  hipStream_t on[4];
+  if (int cr = chains_streams(e, st, on)) return cr;
   const NetView nv = snapshot_view(e);
-  const bool serial = e->prof_on;                    // (chains_for: an event profile wants launches that do not share the chip)
-  if (serial) {
-    e->detach_armed = false;
-    if (int jr = join_chains(e, st)) return jr;
-  } else if (e->detach_armed) {                         // the first steps behind a train step that was queued beside this small call
-    e->n_aux = 1;
-    HIP_TRY(e, hipStreamWaitEvent(e->aux[0], e->ev_fork, 0));
-    e->chains_pending = true;
-    e->detach_armed = false;
-    if (e->hold_needed)                                 // (a row-owned step: not beside its MFMA kernels)
-      if (int hr = hold_chains(e, st)) return hr;
-  } else if (e->n_aux > 0 && e->chains_pending && e->train_since_sample) {
-    if (e->hold_needed)
-      if (int hr = hold_chains(e, st)) return hr;
-  } else if (e->n_aux > 0 && !e->chains_pending) {   // fork: the chains on auxiliary streams start after everything queued on st so far
-    HIP_TRY(e, hipEventRecord(e->ev_fork, st));
-    for (int c = 0; c < e->n_aux; ++c) HIP_TRY(e, hipStreamWaitEvent(e->aux[c], e->ev_fork, 0));
-    e->chains_pending = true;                        // joined lazily by the next entry point that needs the result
-  }
-  e->train_since_sample = false;
   for (int done = 0; done < count && s.i_next >= 1; ++done, --s.i_next) {
     const int i = s.i_next;
-    const int na = e->smp_nact[i];                 // active prefix at this step
-    for (int c = 0; c < e->n_chains; ++c) {
-      const int s0 = c * e->chain_chunk, s1 = std::min(na, s0 + e->chain_chunk);
+    const int na = s.nact[i];                      // active prefix at this step
+    for (int c = 0; c < s.chains; ++c) {
+      const int s0 = c * s.chunk, s1 = std::min(na, s0 + s.chunk);
       if (s1 <= s0) break;
-      hipStream_t sc = serial ? st : (e->n_aux == e->n_chains ? e->aux[c] : (c == 0 ? st : e->aux[c - 1]));
-      const int rows = s1 - s0, MP = round_up(rows, BM);
-      const int cfg = choose_cfg(e->tune, MP, e->tune.nt32_max_rows);
-      {
-        // the sampler keeps ACTIVATIONS in the layer buffers (EPI_BIAS_PRELU): no backward will ask for the pre-activations
-        GemmArgs a{};
-        a.C = smp_buf(e, 0) + (size_t)s0 * e->WP; a.ldc = e->WP; a.bias = nv.B0tab + (size_t)i * e->WP; a.slopeE = nv.slope0;
-        HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_PRELU>(a, e->Us + (size_t)s0 * e->LP, e->LP, nv.W0c, e->K0, MP, e->WP, e->LP, sc,
-                                                          Prof{e, PC_SMP_L0, 2.0 * rows * (double)e->W * e->L}, cfg)));
-      }
-      int rc = hidden_forward(e, MP, rows, sc, cfg, s0, PC_SMP_HIDDEN, true, &nv);
-      if (rc) return rc;
-      float c1, sqrt_alpha, sqrt_beta;
-      reverse_coeffs(e, i, c1, sqrt_alpha, sqrt_beta);
-      // (round 5: multi-resolution steps too - their active prefix is a launch like any other, the epilogue keys Philox by the slot's
-      // original row; EXPLICIT randoms keep the stand-alone kernel)
-      const bool fused = s.mode == SDRM_RNG_PHILOX && (e->tune.fuse_rev == 2 || (e->tune.fuse_rev == 1 && rows <= FUSE_REV_MAX_ROWS));
-      {
-        GemmArgs a{};
-        a.C = e->smp_Y + (size_t)s0 * e->LP; a.ldc = e->LP; a.bias = nv.boc;
-        a.rows_valid = MP; a.cols_valid = e->LP;
-        const Prof pr{e, PC_SMP_OUT, 2.0 * rows * (double)e->L * e->W};
-        if (fused) {
-          // eps_hat never reaches memory: the epilogue applies denoise_add_noise to the sampler state and writes the
-          // next step's dropped-out input (one launch less per reverse step)
-          a.revX = e->X; a.revU = e->Us; a.rev_ldx = e->LP; a.rev_s0 = s0; a.rev_n = s1; a.rev_L = L; a.rev_step = i;
-          a.rev_c1 = c1; a.rev_sqrt_alpha = sqrt_alpha; a.rev_sqrt_beta = sqrt_beta; a.rev_nd = s.nd;
-          a.rev_seed_lo = (uint32_t)s.seed; a.rev_seed_hi = (uint32_t)(s.seed >> 32); a.rev_call_id = (uint32_t)s.call_id;
-          a.rev_row0 = s.row0; a.rev_rowid = s.multires ? e->rowid_dev : nullptr;
-          HIP_TRY(e, (gemm_forward<XF_NONE, EPI_TANH_REV>(a, smp_buf(e, e->H) + (size_t)s0 * e->WP, e->WP, nv.Woc, e->WP, MP,
-                                                          e->LP, e->WP, sc, pr, cfg)));
-          continue;
-        }
-        HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_TANH>(a, smp_buf(e, e->H) + (size_t)s0 * e->WP, e->WP, nv.Woc, e->WP, MP,
-                                                         e->LP, e->WP, sc, pr, cfg)));
-      }
-      ReverseArgs ra{};
-      ra.X = e->X; ra.Y = e->smp_Y; ra.U = e->Us;
-      ra.Z = (s.mode == SDRM_RNG_EXPLICIT && i > 1) ? s.z + (size_t)i * nL : nullptr;
-      ra.keep_next = (s.mode == SDRM_RNG_EXPLICIT && i > 1) ? s.keep + (size_t)(i - 1) * nL : nullptr;
-      ra.Tj = s.multires ? e->Tj_dev : nullptr;
-      ra.rowid = s.multires ? e->rowid_dev : nullptr;
-      ra.s0 = s0; ra.n = s1; ra.L = L; ra.LP = e->LP; ra.K0 = e->LP; ra.step_i = i; ra.nd = s.nd;
-      ra.c1 = c1; ra.sqrt_alpha = sqrt_alpha; ra.sqrt_beta = sqrt_beta;
-      ra.mode = s.mode; ra.seed_lo = (uint32_t)s.seed; ra.seed_hi = (uint32_t)(s.seed >> 32);
-      ra.call_id = (uint32_t)s.call_id; ra.row0 = s.row0;
-      ra.bpr = ((L + 3) / 4 + 255) / 256;
-      ra.rpb = std::max(1, 256 / ((L + 3) / 4));
-      const unsigned rev_grid = ra.rpb > 1 ? (unsigned)((rows + ra.rpb - 1) / ra.rpb) : (unsigned)((size_t)ra.bpr * rows);
-      SDRM_LAUNCH(e, k_reverse_update, dim3(rev_grid), dim3(256), 0, sc, ra);
-      HIP_TRY(e, hipGetLastError());
+      if (int rc = sample_chain_step(e, s, nv, i, s0, s1, on[c])) return rc;
     }
   }
   return SDRM_OK;
 }
 
-int sdrm_sample_remaining(const sdrm_engine* e) { return (e && e->smp.active) ? e->smp.i_next : 0; }
+int sdrm_sample_remaining(const sdrm_engine* e) { return (e && e->call.active) ? e->call.i_next : 0; }
 
 int sdrm_sample_end(sdrm_engine* e, float* out, void* stream) {
   if (!e || !out) return SDRM_ERR_ARG;
-  if (!e->smp.active) return fail(e, SDRM_ERR_STATE, "sdrm_sample_end: no sampling call in progress");
-  if (e->smp.i_next >= 1) return fail(e, SDRM_ERR_STATE, "sdrm_sample_end: reverse steps still pending");
-  if (int jr = join_chains(e, (hipStream_t)stream)) return jr;
+  if (!e->call.active) return fail(e, SDRM_ERR_STATE, "sdrm_sample_end: no sampling call in progress");
+  if (e->call.i_next >= 1) return fail(e, SDRM_ERR_STATE, "sdrm_sample_end: reverse steps still pending");
+  if (int jr = chains_join(e, (hipStream_t)stream)) return jr;
   if (xabort_read(e) != 0u) {   // a hand-shake of the persistent sampler (or of a split train step) timed out
     *(volatile unsigned*)e->xabort_host = 0u;
     e->tune.smp_persist = 0; e->tune.split = 0; e->xgeoF = e->xgeoC = 0;
-    e->smp.active = false;
+    e->call.active = false;
     return fail(e, SDRM_ERR_HIP, "a launch that synchronises work-groups through an XCD's L2 (csrc/sample_persist.h, csrc/rows48.h) timed out: "
                                  "the sampling call's result is invalid; those paths are switched off for this handle");
   }
-  if (e->smp.skinny)   // the persistent kernel wrote dense [n,L] rows in original order
-    HIP_TRY(e, hipMemcpyAsync(out, e->X, (size_t)e->smp.n * e->L * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (e->call.path == SampleCall::SKINNY)   // the persistent kernel wrote dense [n,L] rows in original order
+    HIP_TRY(e, hipMemcpyAsync(out, e->X, (size_t)e->call.n * e->L * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   else
-    SDRM_LAUNCH(e, k_unpad_rows, dim3((unsigned)std::min<size_t>(4096, ((size_t)e->smp.n * e->L + 255) / 256)), dim3(256), 0,
-                (hipStream_t)stream, (const float*)e->X, e->LP, out, e->smp.n, e->L,
-                (const int*)(e->smp.multires ? e->rowid_dev : nullptr));
+    SDRM_LAUNCH(e, k_unpad_rows, dim3((unsigned)std::min<size_t>(4096, ((size_t)e->call.n * e->L + 255) / 256)), dim3(256), 0,
+                (hipStream_t)stream, (const float*)e->X, e->LP, out, e->call.n, e->L,
+                (const int*)(e->call.multires ? e->rowid_dev : nullptr));
   HIP_TRY(e, hipGetLastError());
-  e->smp.active = false;
+  e->call.active = false;
   return SDRM_OK;
 }
 
@@ -2627,13 +2631,32 @@ int select_and_binarize(sdrm_engine* e, const float* x, int64_t n, float gamma, 
   return SDRM_OK;
 }
 
-int dec_grow(sdrm_engine* e, int slot, size_t n) {
-  if (n <= e->dec_cap[slot]) return SDRM_OK;
-  if (e->dec_buf[slot]) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(e->dec_buf[slot])); e->dec_buf[slot] = nullptr; e->dec_cap[slot] = 0; }
-  HIP_TRY(e, dalloc(&e->dec_buf[slot], n));
-  e->dec_cap[slot] = n;
+int grow_scratch(sdrm_engine* e, float** buf, size_t* cap, int slot, size_t n) {
+  if (n <= cap[slot]) return SDRM_OK;
+  if (buf[slot]) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(buf[slot])); buf[slot] = nullptr; cap[slot] = 0; }
+  HIP_TRY(e, dalloc(&buf[slot], n));
+  cap[slot] = n;
   return SDRM_OK;
 }
+int dec_grow(sdrm_engine* e, int slot, size_t n) { return grow_scratch(e, e->dec_buf, e->dec_cap, slot, n); }
+int enc_grow(sdrm_engine* e, int slot, size_t n) { return grow_scratch(e, e->enc_buf, e->enc_cap, slot, n); }
+
+// The segments of ONE k_pad2d launch: src [rows, cols] -> dst [rowsP, colsP], zero-padded
+struct PadList {
+  PadSegs sg{};
+  int64_t most = 0;
+  int k = 0;
+  void add(const float* src, int rows, int cols, float* dst, int rowsP, int colsP) {
+    sg.src[k] = src; sg.dst[k] = dst; sg.rows[k] = rows; sg.cols[k] = cols; sg.rowsP[k] = rowsP; sg.colsP[k] = colsP;
+    most = std::max<int64_t>(most, (int64_t)rowsP * (colsP / 4));
+    ++k;
+  }
+  int launch(sdrm_engine* e, hipStream_t st) const {
+    SDRM_LAUNCH(e, k_pad2d, dim3((unsigned)std::min<int64_t>(2048, (most + 255) / 256), (unsigned)k), dim3(256), 0, st, sg);
+    HIP_TRY(e, hipGetLastError());
+    return SDRM_OK;
+  }
+};
 
 // decoder(z) = Linear(hidden, items)(tanh(Linear(latent, hidden)(z)))   (train_SDRM.py:212-214, :252-254): one staging launch, two GEMMs
 int decode_launches(sdrm_engine* e, const sdrm_vae_decoder* d, const float* z, int n, float* out, hipStream_t st) {
@@ -2644,23 +2667,13 @@ int decode_launches(sdrm_engine* e, const sdrm_vae_decoder* d, const float* z, i
   if ((rc = dec_grow(e, Z, (size_t)MP * Lp)) || (rc = dec_grow(e, W1, (size_t)Hr * Lp)) || (rc = dec_grow(e, B1, Hr)) ||
       (rc = dec_grow(e, HID, (size_t)MP * Hp)) || (rc = dec_grow(e, W2, (size_t)Ir * Hp)) || (rc = dec_grow(e, B2, Ir)))
     return rc;
-  {
-    PadSegs sg{};
-    int64_t most = 0;
-    int k = 0;
-    auto pad = [&](const float* src, int rows, int cols, float* dst, int rowsP, int colsP) {
-      sg.src[k] = src; sg.dst[k] = dst; sg.rows[k] = rows; sg.cols[k] = cols; sg.rowsP[k] = rowsP; sg.colsP[k] = colsP;
-      most = std::max<int64_t>(most, (int64_t)rowsP * (colsP / 4));
-      ++k;
-    };
-    pad(z, n, d->latent, e->dec_buf[Z], MP, Lp);
-    pad(d->w1, d->hidden, d->latent, e->dec_buf[W1], Hr, Lp);
-    pad(d->b1, 1, d->hidden, e->dec_buf[B1], 1, Hr);
-    pad(d->w2, d->n_items, d->hidden, e->dec_buf[W2], Ir, Hp);
-    pad(d->b2, 1, d->n_items, e->dec_buf[B2], 1, Ir);
-    SDRM_LAUNCH(e, k_pad2d, dim3((unsigned)std::min<int64_t>(2048, (most + 255) / 256), 5), dim3(256), 0, st, sg);
-    HIP_TRY(e, hipGetLastError());
-  }
+  PadList pad;
+  pad.add(z, n, d->latent, e->dec_buf[Z], MP, Lp);
+  pad.add(d->w1, d->hidden, d->latent, e->dec_buf[W1], Hr, Lp);
+  pad.add(d->b1, 1, d->hidden, e->dec_buf[B1], 1, Hr);
+  pad.add(d->w2, d->n_items, d->hidden, e->dec_buf[W2], Ir, Hp);
+  pad.add(d->b2, 1, d->n_items, e->dec_buf[B2], 1, Ir);
+  if ((rc = pad.launch(e, st))) return rc;
   const int rows64 = round_up(n, BM);
   const int cfg = choose_cfg(e->tune, rows64, e->tune.nt32_max_rows);
   {
@@ -2689,7 +2702,7 @@ int check_decoder(sdrm_engine* e, const sdrm_vae_decoder* d, const float* z, int
 int sdrm_vae_decode(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z, int n, float* out, void* stream) {
   if (int rc = check_decoder(e, dec, z, n, "sdrm_vae_decode")) return rc;
   if (!out) return fail(e, SDRM_ERR_ARG, "sdrm_vae_decode: null output");
-  if (int jr = join_chains(e, (hipStream_t)stream)) return jr;
+  if (int jr = chains_join(e, (hipStream_t)stream)) return jr;
   return decode_launches(e, dec, z, n, out, (hipStream_t)stream);
 }
 
@@ -2700,13 +2713,6 @@ namespace {
 constexpr int ENC_KL_PARTS = 512;    // work-groups of k_encode_kl_rows
 constexpr int ENC_GATHER_MAX_Q = 1024;   // float4 slices of the hidden vector k_encode_csr holds in registers (256 threads x 4): hidden <= 4096
 
-int enc_grow(sdrm_engine* e, int slot, size_t n) {
-  if (n <= e->enc_cap[slot]) return SDRM_OK;
-  if (e->enc_buf[slot]) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(e->enc_buf[slot])); e->enc_buf[slot] = nullptr; e->enc_cap[slot] = 0; }
-  HIP_TRY(e, dalloc(&e->enc_buf[slot], n));
-  e->enc_cap[slot] = n;
-  return SDRM_OK;
-}
 
 struct EncDims { int Ip, Hq, Hp, Hr, L2p, L2r; };
 EncDims enc_dims(int n_items, int hidden, int latent) {
@@ -2778,7 +2784,7 @@ int check_encoder(sdrm_engine* e, const sdrm_vae_encoder* d, const char* who) {
 int sdrm_vae_encoder_load(sdrm_engine* e, const sdrm_vae_encoder* enc, void* stream) {
   if (int rc = check_encoder(e, enc, "sdrm_vae_encoder_load")) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (int jr = join_chains(e, st)) return jr;
+  if (int jr = chains_join(e, st)) return jr;
   const EncDims d = enc_dims(enc->n_items, enc->hidden, enc->latent);
   e->enc_loaded = false;
   int rc;
@@ -2787,20 +2793,12 @@ int sdrm_vae_encoder_load(sdrm_engine* e, const sdrm_vae_encoder* enc, void* str
       (rc = enc_grow(e, sdrm_engine::ENC_B2, d.L2r)))
     return rc;
   if (!e->enc_part) HIP_TRY(e, dalloc(&e->enc_part, ENC_KL_PARTS));
-  PadSegs sg{};
-  int64_t most = 0;
-  int k = 0;
-  auto pad = [&](const float* src, int rows, int cols, float* dst, int rowsP, int colsP) {
-    sg.src[k] = src; sg.dst[k] = dst; sg.rows[k] = rows; sg.cols[k] = cols; sg.rowsP[k] = rowsP; sg.colsP[k] = colsP;
-    most = std::max<int64_t>(most, (int64_t)rowsP * (colsP / 4));
-    ++k;
-  };
-  pad(enc->w1, enc->hidden, enc->n_items, e->enc_buf[sdrm_engine::ENC_W1], d.Hr, d.Ip);
-  pad(enc->b1, 1, enc->hidden, e->enc_buf[sdrm_engine::ENC_B1], 1, d.Hr);
-  pad(enc->w2, 2 * enc->latent, enc->hidden, e->enc_buf[sdrm_engine::ENC_W2], d.L2r, d.Hp);
-  pad(enc->b2, 1, 2 * enc->latent, e->enc_buf[sdrm_engine::ENC_B2], 1, d.L2r);
-  SDRM_LAUNCH(e, k_pad2d, dim3((unsigned)std::min<int64_t>(2048, (most + 255) / 256), 4), dim3(256), 0, st, sg);
-  HIP_TRY(e, hipGetLastError());
+  PadList pad;
+  pad.add(enc->w1, enc->hidden, enc->n_items, e->enc_buf[sdrm_engine::ENC_W1], d.Hr, d.Ip);
+  pad.add(enc->b1, 1, enc->hidden, e->enc_buf[sdrm_engine::ENC_B1], 1, d.Hr);
+  pad.add(enc->w2, 2 * enc->latent, enc->hidden, e->enc_buf[sdrm_engine::ENC_W2], d.L2r, d.Hp);
+  pad.add(enc->b2, 1, 2 * enc->latent, e->enc_buf[sdrm_engine::ENC_B2], 1, d.L2r);
+  if ((rc = pad.launch(e, st))) return rc;
   SDRM_LAUNCH(e, k_encode_w1t, dim3((unsigned)((enc->n_items + 31) / 32), (unsigned)((d.Hq + 31) / 32)), dim3(256), 0, st, enc->w1, enc->hidden,
               enc->n_items, e->enc_buf[sdrm_engine::ENC_W1T], d.Hq);
   HIP_TRY(e, hipGetLastError());
@@ -2814,7 +2812,7 @@ int sdrm_vae_encode(sdrm_engine* e, const float* x, int n, float* z, float* kl, 
   if (!x || !z) return fail(e, SDRM_ERR_ARG, "sdrm_vae_encode: null pointer");
   if (!e->enc_loaded) return fail(e, SDRM_ERR_STATE, "sdrm_vae_encode: no encoder loaded (sdrm_vae_encoder_load)");
   if (n < 1 || n > (1 << 22)) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode: n outside 1 .. 2^22");
-  if (int jr = join_chains(e, (hipStream_t)stream)) return jr;
+  if (int jr = chains_join(e, (hipStream_t)stream)) return jr;
   return encode_dense_launches(e, x, n, z, kl, (hipStream_t)stream);
 }
 
@@ -2826,7 +2824,7 @@ int sdrm_vae_encode_csr(sdrm_engine* e, const int64_t* indptr, const int32_t* in
   if (b < 1 || b > (1 << 22) || row0 < 0 || n_rows < 1) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode_csr: b outside 1 .. 2^22, n_rows < 1 or row0 < 0");
   if (!rows && row0 + b > n_rows) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode_csr: rows row0 .. row0 + b - 1 end behind the matrix");
   hipStream_t st = (hipStream_t)stream;
-  if (int jr = join_chains(e, st)) return jr;
+  if (int jr = chains_join(e, st)) return jr;
   const EncDims d = enc_dims(e->enc_items, e->enc_hidden, e->enc_latent);
   const int q = d.Hq / 4;
   if (q > ENC_GATHER_MAX_Q) {   // a hidden vector wider than the gather kernel's registers: densify into scratch, then the dense form
@@ -2924,7 +2922,7 @@ int sdrm_profile_only(sdrm_engine* e, int cls) {
 int sdrm_profile_end(sdrm_engine* e, void* stream) {
   if (!e) return SDRM_ERR_ARG;
   e->prof_on = false;
-  if (int jr = join_chains(e, (hipStream_t)stream)) return jr;
+  if (int jr = chains_join(e, (hipStream_t)stream)) return jr;
   HIP_TRY(e, hipStreamSynchronize((hipStream_t)stream));
   for (size_t i = 0; i < e->prof_cls.size(); ++i) {
     float ms = 0.f;

@@ -250,7 +250,7 @@ def test_sampler_row_chains_change_no_bit(engine_cls, sample_case, multires):
 @pytest.mark.parametrize("multires", [False, True])
 def test_small_sampling_call_runs_beside_per_layer_train_steps(engine_cls, multires):
     """A sampling call below the two-chain size (679 rows: one rank of eight) is ONE chain on an auxiliary stream, and train steps of the
-    per-layer path queued between its steps do not hold it (csrc/sdrm_hip.hip: chains_for, hold_chains): the call reads its own snapshot
+    per-layer path queued between its steps do not hold it (csrc/sdrm_hip.hip: chains_for, ChainSched): the call reads its own snapshot
     of the net and runs in its own buffers, so the interleaved call - parameters moving under it with every Adam step, its launches
     sharing the chip with the train steps' - reproduces the uninterrupted one bit for bit, and so do the parameters."""
     n, B = 679, 512
