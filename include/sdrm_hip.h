@@ -267,6 +267,23 @@ int sdrm_feed_status(sdrm_engine* e, void* stream);
  * between the two neighbouring order statistics) returns for a float32 array; out (device uint8[n], 4-byte
  * aligned, may be null) receives x >= threshold.  Inputs must not contain NaN. */
 int sdrm_equal_sparsity(sdrm_engine* e, const float* x, int64_t n, double q, uint8_t* out, float* threshold, void* stream);
+/* The same result as a canonical CSR matrix made on the device, either side (reference: main.py:177-180 and the NeuMF branch's
+ * other tail, :259-270, `(F <= np.quantile(F.flatten(), 1 - SPARSITY))`, both turned into csr_matrix / (row, col) form downstream):
+ * x [n_rows, n_cols] float32 row-major (16-byte aligned at its base; rows need not be), q in [0,1], side 0: x >= threshold,
+ * side 1: x <= threshold, threshold exactly sdrm_equal_sparsity's.  No dense matrix exists: one sweep over x writes a bit mask
+ * (ceil(n_cols / 64) 64-bit words per row, engine workspace, grow-only) and integer row counts, a scan makes indptr, and the
+ * column indices are written from the mask alone.  No data array: the matrix is all ones (the convention of the CSR inputs above).
+ * The call is split because nnz is not bounded by the rank (ties at the threshold add any number of elements):
+ * sdrm_equal_sparsity_csr_begin computes the threshold (device float*, may be null), the mask and indptr (device int64
+ *   [n_rows + 1]), synchronises `stream` ONCE and returns nnz = indptr[n_rows] in *nnz_host (host) - 8 bytes read back
+ *   instead of n_rows x n_cols.  A second begin replaces a pending one.  SDRM_ERR_SHAPE: n_rows < 1, n_cols outside [1, 2^31),
+ *   or more than 2^31 mask words; SDRM_ERR_ARG: a null pointer, q outside [0,1], side outside {0, 1}, x not 16-byte aligned.
+ * sdrm_equal_sparsity_csr_end fills indices[0 .. nnz) (device int32; ascending columns within a row, rows in order) from the
+ *   pending mask and ends the call; no store lands outside [0, nnz).  SDRM_ERR_STATE without a pending begin; SDRM_ERR_ARG if
+ *   capacity < nnz (nothing is written and the begin stays pending).  Inputs must not contain NaN. */
+int sdrm_equal_sparsity_csr_begin(sdrm_engine* e, const float* x, int64_t n_rows, int64_t n_cols, double q, int side,
+                                  int64_t* indptr, float* threshold, int64_t* nnz_host, void* stream);
+int sdrm_equal_sparsity_csr_end(sdrm_engine* e, int32_t* indices, int64_t capacity, void* stream);
 
 /* The VAE decode hook on the device (reference: train_SDRM.py:212-214 `decoder = Linear(latent, hidden) -> Tanh ->
  * Linear(hidden, N_ITEMS)`, :252-254 `VAE.decode`, called by sample_ddpm at :49 / :61 on the sampled latents): two launches of

@@ -89,6 +89,9 @@ SIGNATURES = {
     "sdrm_vae_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "sdrm_vae_encode_csr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "sdrm_equal_sparsity": (c_int, [c_void_p, c_void_p, c_int64, C.c_double, c_void_p, c_void_p, c_void_p]),
+    "sdrm_equal_sparsity_csr_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int64, C.c_double, c_int, c_void_p, c_void_p,
+                                              C.POINTER(c_int64), c_void_p]),
+    "sdrm_equal_sparsity_csr_end": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "sdrm_rank_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_source_hash": (C.c_char_p, []),

@@ -16,6 +16,7 @@
 
 #include "../../include/sdrm_hip.h"
 #include "../../include/sdrm_hip_debug.h"
+#include "compact.h"
 #include "decode.h"
 #include "elementwise.h"
 #include "encode.h"
@@ -191,6 +192,12 @@ struct sdrm_engine {
   const float* grad_src = nullptr;   // where the last backward wrote the flat gradient (internal g or the caller's buffer)
   float *rev_dev = nullptr;          // [3][T+1] reverse-step coefficients c1, sqrt(alpha), sqrt(beta)
   SelectState* sel = nullptr;        // radix-select workspace of sdrm_equal_sparsity
+  // sdrm_equal_sparsity_csr_begin / _end (csrc/compact.h): grow-only workspace [mask words | row offsets int64 | row counts uint32]
+  // and the call pending between the two
+  uint64_t* csr_ws = nullptr;
+  size_t csr_ws_cap = 0;             // in 8-byte words
+  int64_t *csr_nnz_host = nullptr, *csr_nnz_dev = nullptr;   // nnz of the scan, in host memory the device writes (and its device alias)
+  struct CsrPending { bool active = false; int64_t n_rows = 0, nnz = 0; int wpr = 0; size_t off_ptr = 0; } csr;
   float* one_dev = nullptr;          // 1.0f (identity PReLU slope for layer 0 inside the batched weight-gradient launch)
   unsigned* feed_flag = nullptr;     // status word of the sparse batch feed (csrc/feed.h: out-of-range row ids / column indices)
   std::vector<float> h_beta, h_alpha, h_alphabar;
@@ -1521,6 +1528,8 @@ int sdrm_destroy(sdrm_engine* e) {
   for (float* b : e->enc_buf)
     if (b) (void)hipFree(b);
   if (e->enc_part) (void)hipFree(e->enc_part);
+  if (e->csr_ws) (void)hipFree(e->csr_ws);
+  if (e->csr_nnz_host) (void)hipHostFree(e->csr_nnz_host);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_hold) (void)hipEventDestroy(e->ev_hold);
   for (int c = 0; c < 3; ++c) {
@@ -2859,6 +2868,83 @@ int sdrm_equal_sparsity(sdrm_engine* e, const float* x, int64_t n, double q, uin
   SDRM_LAUNCH(e, k_select_init, dim3(8), dim3(256), 0, st, e->sel, r0, r1);
   HIP_TRY(e, hipGetLastError());
   return select_and_binarize(e, x, n, gamma, out, threshold, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same result as a canonical CSR matrix made on the device, either side (main.py:177-180, :259-270), csrc/compact.h.
+int sdrm_equal_sparsity_csr_begin(sdrm_engine* e, const float* x, int64_t n_rows, int64_t n_cols, double q, int side,
+                                  int64_t* indptr, float* threshold, int64_t* nnz_host, void* stream) {
+  // (the handle is looked at last: every refusal below can be had without a device)
+  if (!x || !indptr || !nnz_host) return fail(e, SDRM_ERR_ARG, "sdrm_equal_sparsity_csr_begin: null pointer");
+  if (n_rows < 1 || n_cols < 1 || n_cols >= ((int64_t)1 << 31))
+    return fail(e, SDRM_ERR_SHAPE, "sdrm_equal_sparsity_csr_begin: n_rows < 1 or n_cols outside [1, 2^31)");
+  if (!(q >= 0.0 && q <= 1.0)) return fail(e, SDRM_ERR_ARG, "sdrm_equal_sparsity_csr_begin: q outside [0,1]");
+  if (side != 0 && side != 1) return fail(e, SDRM_ERR_ARG, "sdrm_equal_sparsity_csr_begin: side is 0 (>=) or 1 (<=)");
+  if ((uintptr_t)x & 15u) return fail(e, SDRM_ERR_ARG, "sdrm_equal_sparsity_csr_begin: x must be 16-byte aligned");
+  const int64_t wpr = (n_cols + 63) / 64;
+  if (n_rows > (((int64_t)1 << 31) - 256) / wpr)   // the mask is indexed with 32 bits (2^31 words: a matrix of 512 GB and more)
+    return fail(e, SDRM_ERR_SHAPE, "sdrm_equal_sparsity_csr_begin: more than 2^31 mask words");
+  if (!e) return SDRM_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  e->csr.active = false;   // a second begin replaces a pending one
+  const size_t words = (size_t)(n_rows * wpr), off_ptr = words, off_cnt = off_ptr + (size_t)n_rows + 1;
+  const size_t need = off_cnt + ((size_t)n_rows + 1) / 2;
+  if (need > e->csr_ws_cap) {
+    if (e->csr_ws) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(e->csr_ws)); e->csr_ws = nullptr; e->csr_ws_cap = 0; }
+    HIP_TRY(e, dalloc(&e->csr_ws, need));
+    e->csr_ws_cap = need;
+  }
+  if (!e->csr_nnz_host) {
+    HIP_TRY(e, hipHostMalloc((void**)&e->csr_nnz_host, sizeof(int64_t), hipHostMallocMapped));
+    HIP_TRY(e, hipHostGetDevicePointer((void**)&e->csr_nnz_dev, e->csr_nnz_host, 0));
+  }
+  const int64_t n = n_rows * n_cols;
+  int64_t r0, r1;
+  float gamma;
+  quantile_ranks(n, q, r0, r1, gamma);
+  SDRM_LAUNCH(e, k_select_init, dim3(8), dim3(256), 0, st, e->sel, r0, r1);
+  HIP_TRY(e, hipGetLastError());
+  if (int rc = select_and_binarize(e, x, n, gamma, nullptr, threshold, st)) return rc;
+  uint32_t* counts = reinterpret_cast<uint32_t*>(e->csr_ws + off_cnt);
+  int64_t* own = reinterpret_cast<int64_t*>(e->csr_ws + off_ptr);
+  HIP_TRY(e, hipMemsetAsync(counts, 0, (size_t)n_rows * sizeof(uint32_t), st));
+  const dim3 grid((unsigned)((words + 4 * CSR_MASK_WORDS - 1) / (4 * CSR_MASK_WORDS)));   // four waves per work-group
+  if (side == 0) SDRM_LAUNCH(e, (k_csr_mask<0>), grid, dim3(256), 0, st, x, (int)n_cols, (int)wpr, (uint32_t)words, (const float*)&e->sel->threshold, e->csr_ws, counts);
+  else SDRM_LAUNCH(e, (k_csr_mask<1>), grid, dim3(256), 0, st, x, (int)n_cols, (int)wpr, (uint32_t)words, (const float*)&e->sel->threshold, e->csr_ws, counts);
+  HIP_TRY(e, hipGetLastError());
+  *e->csr_nnz_host = -1;
+  SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)counts, n_rows, own, indptr, e->csr_nnz_dev);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipStreamSynchronize(st));
+  const int64_t nnz = *(volatile int64_t*)e->csr_nnz_host;
+  if (nnz < 0 || nnz > n) return fail(e, SDRM_ERR_STATE, "sdrm_equal_sparsity_csr_begin: the row counts do not add up");
+  *nnz_host = nnz;
+  e->csr.active = true; e->csr.n_rows = n_rows; e->csr.nnz = nnz; e->csr.wpr = (int)wpr; e->csr.off_ptr = off_ptr;
+  return SDRM_OK;
+}
+
+int sdrm_equal_sparsity_csr_end(sdrm_engine* e, int32_t* indices, int64_t capacity, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!e->csr.active) return fail(e, SDRM_ERR_STATE, "sdrm_equal_sparsity_csr_end: no sdrm_equal_sparsity_csr_begin is pending");
+  // (a refused call leaves the begin pending: the caller may come back with a buffer that fits)
+  if (capacity < e->csr.nnz) return fail(e, SDRM_ERR_ARG, "sdrm_equal_sparsity_csr_end: capacity < nnz");
+  if (!indices && e->csr.nnz > 0) return fail(e, SDRM_ERR_ARG, "sdrm_equal_sparsity_csr_end: null pointer");
+  const auto& c = e->csr;
+  if (c.nnz > 0) {
+    const int64_t* own = reinterpret_cast<const int64_t*>(e->csr_ws + c.off_ptr);
+    // rows per work-group: 4 (a wave per row) for the wide matrices (3125 columns: 49 words, 8582: 135), 16 for rows of at most 32 words
+    // (843 x 1008: 16 words), where a wave per row would leave three lanes in four without a word
+    if (c.wpr > 32) {
+      const unsigned blocks = (unsigned)std::min<int64_t>((c.n_rows + 3) / 4, 65536);
+      SDRM_LAUNCH(e, (k_csr_fill<64>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint64_t*)e->csr_ws, own, c.n_rows, c.wpr, indices, c.nnz);
+    } else {
+      const unsigned blocks = (unsigned)std::min<int64_t>((c.n_rows + 15) / 16, 65536);
+      SDRM_LAUNCH(e, (k_csr_fill<16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint64_t*)e->csr_ws, own, c.n_rows, c.wpr, indices, c.nnz);
+    }
+    HIP_TRY(e, hipGetLastError());
+  }
+  e->csr.active = false;
+  return SDRM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -444,6 +444,42 @@ class Engine:
                                                  _stream()), "sdrm_equal_sparsity")
         return (out, thr) if return_threshold else out
 
+    _CSR_SIDES = {">=": 0, "<=": 1}
+
+    def equal_sparsity_csr_begin(self, raw, sparsity, side=">="):
+        """First half of `equal_sparsity_csr` (`sdrm_equal_sparsity_csr_begin`): threshold, bit mask and indptr on the device, one
+        stream synchronise, nnz on the host.  Returns (indptr int64 [n_rows + 1], nnz, threshold 0-d float32)."""
+        if side not in self._CSR_SIDES:
+            raise SdrmError(f"equal_sparsity_csr: side must be '>=' or '<=', got {side!r}")
+        raw = self._dev(raw, torch.float32)
+        if raw.dim() != 2:
+            raise SdrmError(f"equal_sparsity_csr: SDRM_ERR_SHAPE: raw must be 2-D, got {tuple(raw.shape)}")
+        indptr = torch.empty(raw.shape[0] + 1, dtype=torch.int64, device=self.device)
+        thr = torch.empty((), dtype=torch.float32, device=self.device)
+        nnz = C.c_int64(-1)
+        self._check(self.lib.sdrm_equal_sparsity_csr_begin(self._h, _ptr(raw), raw.shape[0], raw.shape[1], float(sparsity),
+                                                           self._CSR_SIDES[side], _ptr(indptr), _ptr(thr), C.byref(nnz), _stream()),
+                    "sdrm_equal_sparsity_csr_begin")
+        return indptr, int(nnz.value), thr
+
+    def equal_sparsity_csr_end(self, indices):
+        """Second half: fills `indices` (int32 device tensor of at least nnz elements) from the pending mask."""
+        if indices.dtype != torch.int32 or not indices.is_contiguous() or indices.device != self.device:
+            raise SdrmError("equal_sparsity_csr_end: indices must be a contiguous int32 tensor on the engine's device")
+        self._check(self.lib.sdrm_equal_sparsity_csr_end(self._h, _ptr(indices), indices.numel(), _stream()), "sdrm_equal_sparsity_csr_end")
+        return indices
+
+    def equal_sparsity_csr(self, raw, sparsity, side=">=", return_threshold=False):
+        """main.py:177-180 (`side=">="`) or the NeuMF branch's other tail, main.py:260 (`side="<="`), as a canonical CSR matrix made on
+        the device: (indptr int64 [n_rows + 1], indices int32 [nnz], shape) as device tensors - columns ascend within a row, no data
+        array (all ones, as `csr_to_device` returns for such a matrix) - and the float32 threshold when asked.  `raw` is 2-D, on the
+        device or the host.  No dense 0/1 matrix exists; the one readback is nnz (8 bytes)."""
+        shape = tuple(int(v) for v in raw.shape)
+        indptr, nnz, thr = self.equal_sparsity_csr_begin(raw, sparsity, side)
+        indices = self.equal_sparsity_csr_end(torch.empty(nnz, dtype=torch.int32, device=self.device))
+        out = (indptr, indices, shape)
+        return (out, thr) if return_threshold else out
+
     # ------------------------------------------------------------------ VAE decode on the engine (SURVEY 8f-2)
     def _decoder(self, w1, b1, w2, b2):
         w1, b1, w2, b2 = (self._dev(t.detach() if isinstance(t, torch.Tensor) else t, torch.float32) for t in (w1, b1, w2, b2))

@@ -5,6 +5,7 @@ the GPU box, where the reference itself cannot travel.  SURVEY.md §8f ("next" r
     load_split / partial_valid      dataloaders.py:82-116  (train_test + the 80 % part of a seeded per-user split of valid)
     batch_feed                      main.py:126-137        (BatchSampler(RandomSampler) index batches -> sparse COO tensors)
     equal_sparsity                  main.py:177-185        (threshold at the data's sparsity quantile)
+    equal_sparsity_csr              main.py:177-180, :259-270  (the same as a csr_matrix made on the device, either side)
     compute_mf_results              svd_benchmark.py:17-70 (TruncatedSVD(20, n_iter=100) reconstruction, masked, Recall/NDCG@k)
     run_experiment                  main.py:143-200        (train -> multi-res + full-res sampling -> evaluate)
 """
@@ -12,7 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 import torch
-from scipy.sparse import csr_matrix, vstack
+from scipy.sparse import csr_matrix, issparse, vstack
 
 from . import metrics
 
@@ -103,11 +104,27 @@ def equal_sparsity(raw, sparsity: float, engine) -> np.ndarray:
     return engine.equal_sparsity(raw, float(sparsity)).cpu().numpy().astype(int)
 
 
+def equal_sparsity_csr(raw, sparsity: float, engine, side=">=") -> csr_matrix:
+    """The same binarisation as a `scipy.sparse.csr_matrix` of ints (sorted indices, shape `raw.shape`) built on the device
+    (`sdrm_equal_sparsity_csr_begin` / `_end`; csrc/compact.h): what the consumers of `equal_sparsity` make of its dense result
+    (`csr_matrix(...)`, `.tocoo()`, main.py:263-270).  Only indptr and indices cross to the host, no dense matrix exists on either
+    side.  `side="<="` with `1 - SPARSITY` is the NeuMF branch's other tail, `(F <= np.quantile(F.flatten(), 1 - SPARSITY))`
+    (main.py:260)."""
+    indptr, indices, shape = engine.equal_sparsity_csr(raw, float(sparsity), side=side)
+    indices = indices.cpu().numpy()
+    m = csr_matrix((np.ones(indices.shape[0], dtype=int), indices, indptr.cpu().numpy()), shape=shape)
+    m.has_sorted_indices = True
+    return m
+
+
 def compute_mf_results(training_dataset, testing_dataset, synthetic_data, only_synthetic=True):
     """Recall@k and NDCG@k (k = 1,3,5,10,20,50) of a rank-20 truncated SVD fitted on
-    [synthetic | 80 % of each test user's items] and scored on the held-out 20 %."""
+    [synthetic | 80 % of each test user's items] and scored on the held-out 20 %.  `synthetic_data` may be a scipy sparse
+    matrix (`equal_sparsity_csr`): it is densified here, the fit itself is the dense one either way."""
     from sklearn.decomposition import TruncatedSVD
     test_data, valid_data = metrics.split_train_test_proportion_from_csr_matrix(testing_dataset, batch_size=1000, random_seed=123)
+    if issparse(synthetic_data):
+        synthetic_data = synthetic_data.toarray()
     synthetic = np.asarray(synthetic_data)
     head = synthetic if only_synthetic else training_dataset.toarray()
     training = np.concatenate([head, test_data.toarray()], axis=0)
@@ -141,6 +158,7 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
     M = ts.sample_ddpm(n_users, net, vae, hp["latent"], hp["nd"], timesteps="random", n_timesteps=hp["T"]).detach()
     F = ts.sample_ddpm(n_users, net, vae, hp["latent"], hp["nd"], n_timesteps=hp["T"]).detach()
     V = vae.sample(n_users)
+    binarise = equal_sparsity_csr if hp.get("sparse_synthetic", False) else equal_sparsity   # opt-in: CSR made on the device
     for tag, raw in (("M", M), ("F", F), ("V", V)):
-        out[tag] = compute_mf_results(train, valid, equal_sparsity(raw, sparsity, net.engine()), only_synthetic=True)
+        out[tag] = compute_mf_results(train, valid, binarise(raw, sparsity, net.engine()), only_synthetic=True)
     return out
