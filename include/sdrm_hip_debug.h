@@ -114,6 +114,26 @@ int sdrm_debug_set_chains(sdrm_engine* e, int chains);
  * row-owned train step (default: for its weight gradients; the tail runs beside them). */
 int sdrm_debug_chains(const sdrm_engine* e);
 
+/* What ran last on this handle, read back from the engine's own records (host code only: no device work, nothing changes).
+ * train_path / parts / dgrad: the plan of the last sdrm_train_forward, alone or inside a sdrm_train_step - the kernel path, the work-groups
+ * per 48-row group (1, or 2 / 4 column-split; 1 on every other path) and the form of its input gradients.  sample_path: what the last
+ * sdrm_sample_begin decided (SDRM_SAMPLE_PATH_PERSIST: the persistent kernel while no hand-shake has timed out, else a launch per
+ * layer).  Before the first train forward / sampling call the values are those of a per-layer step.  Any out pointer may be NULL.
+ * Lets a test of the size rules assert which path a batch really took, so that a retuned threshold fails the test instead of
+ * quietly moving what it covers. */
+enum { SDRM_PLAN_PER_LAYER = 0,    /* one launch per layer (64x64 / 32x32 tiles) */
+       SDRM_PLAN_SKINNY = 1,       /* the narrow nets' step (csrc/skinny_step.h) */
+       SDRM_PLAN_ROW96 = 2,        /* row-owned, 96-row work-groups (csrc/rowchain.h) */
+       SDRM_PLAN_ROW48 = 3 };      /* row-owned, 48-row work-groups (csrc/rows48.h); parts > 1: column-split */
+enum { SDRM_PLAN_DGRAD_TILES = 0,            /* k_loss_seed + a tile GEMM per layer */
+       SDRM_PLAN_DGRAD_ROWS_PER_LAYER = 1,   /* k_loss_seed + a row-owned launch per layer (csrc/dgrad_rows.h) */
+       SDRM_PLAN_DGRAD_CHAIN = 2,            /* the seeds and every layer in one row-owned launch */
+       SDRM_PLAN_DGRAD_SKINNY_OWN = 3 };     /* inside the narrow nets' backward kernel */
+enum { SDRM_SAMPLE_PATH_SKINNY = 0,      /* the narrow nets' one launch for the whole loop (csrc/skinny.h) */
+       SDRM_SAMPLE_PATH_PERSIST = 1,     /* reverse steps without kernel boundaries (csrc/sample_persist.h) */
+       SDRM_SAMPLE_PATH_PER_LAYER = 2 }; /* one launch per layer */
+int sdrm_debug_last_plan(const sdrm_engine* e, int* train_path, int* parts, int* dgrad, int* sample_path);
+
 /* Gradient all-reduces of sdrm_train_step_sharded: 1 (default) = one all-reduce of the whole flat gradient after the one-call
  * backward; 2 = the two buckets of sdrm_grad_buckets, the first overlapped with the upper layers' weight gradients on the
  * auxiliary stream (pays when the first bucket's all-reduce takes longer than the ~40 us the hand-offs cost); also env

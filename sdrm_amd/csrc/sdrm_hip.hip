@@ -1309,6 +1309,23 @@ int sdrm_debug_set_chains(sdrm_engine* e, int chains) {
 
 int sdrm_debug_chains(const sdrm_engine* e) { return e ? e->call.chains : 0; }
 
+// the names of include/sdrm_hip_debug.h are the enumerators of StepPlan / SampleCall
+static_assert(SDRM_PLAN_PER_LAYER == (int)StepPlan::PER_LAYER && SDRM_PLAN_SKINNY == (int)StepPlan::SKINNY &&
+              SDRM_PLAN_ROW96 == (int)StepPlan::ROW96 && SDRM_PLAN_ROW48 == (int)StepPlan::ROW48, "sdrm_hip_debug.h: train paths");
+static_assert(SDRM_PLAN_DGRAD_TILES == (int)StepPlan::TILES && SDRM_PLAN_DGRAD_ROWS_PER_LAYER == (int)StepPlan::ROWS_PER_LAYER &&
+              SDRM_PLAN_DGRAD_CHAIN == (int)StepPlan::CHAIN && SDRM_PLAN_DGRAD_SKINNY_OWN == (int)StepPlan::SKINNY_OWN, "sdrm_hip_debug.h: dgrads");
+static_assert(SDRM_SAMPLE_PATH_SKINNY == (int)SampleCall::SKINNY && SDRM_SAMPLE_PATH_PERSIST == (int)SampleCall::PERSIST &&
+              SDRM_SAMPLE_PATH_PER_LAYER == (int)SampleCall::PER_LAYER, "sdrm_hip_debug.h: sampling paths");
+
+int sdrm_debug_last_plan(const sdrm_engine* e, int* train_path, int* parts, int* dgrad, int* sample_path) {
+  if (!e) return SDRM_ERR_ARG;
+  if (train_path) *train_path = (int)e->plan.path;
+  if (parts) *parts = e->plan.parts;
+  if (dgrad) *dgrad = (int)e->plan.dgrad;
+  if (sample_path) *sample_path = (int)e->call.path;
+  return SDRM_OK;
+}
+
 int sdrm_debug_set_tile(sdrm_engine* e, int cfg) {
   if (!e) return SDRM_ERR_ARG;
   if (e->bwd_begun || e->call.active)

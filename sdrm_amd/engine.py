@@ -4,6 +4,7 @@ torch is used only for device memory and streams (plumbing); every numeric step 
 libsdrm_hip.so.  Reference lines are into /root/reference/train_SDRM.py."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import weakref
@@ -24,6 +25,13 @@ def _ptr(t):
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# Engine.last_plan(): the enumerators of include/sdrm_hip_debug.h (sdrm_debug_last_plan) by name
+TRAIN_PATHS = ("per_layer", "skinny", "row96", "row48")
+DGRAD_FORMS = ("tiles", "rows_per_layer", "chain", "skinny_own")
+SAMPLE_PATHS = ("skinny", "persist", "per_layer")
+LastPlan = collections.namedtuple("LastPlan", "train_path parts dgrad sample_path")
 
 
 class _ParamSpan:
@@ -143,6 +151,14 @@ class Engine:
     def sampler_chains(self):
         """Row chains of the sampling call in progress / of the last one (csrc/sdrm_hip.hip: chains_for)."""
         return int(self.lib.sdrm_debug_chains(self._h))
+
+    def last_plan(self):
+        """What ran last on this engine (sdrm_debug_last_plan; host-side, nothing is launched): LastPlan(train_path, parts, dgrad,
+        sample_path) - the kernel path of the last train forward (one of TRAIN_PATHS), its work-groups per 48-row group (2 / 4:
+        column-split), the form of its input gradients (DGRAD_FORMS) and the path of the last sampling call (SAMPLE_PATHS)."""
+        v = [C.c_int() for _ in range(4)]
+        self._check(self.lib.sdrm_debug_last_plan(self._h, *[C.byref(x) for x in v]), "sdrm_debug_last_plan")
+        return LastPlan(TRAIN_PATHS[v[0].value], int(v[1].value), DGRAD_FORMS[v[2].value], SAMPLE_PATHS[v[3].value])
 
     @property
     def rows48_split_available(self):
