@@ -332,14 +332,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_dgrad_chain(const DgradChainArg
       __syncthreads();
       s0 = tot[0]; s1 = tot[1]; s2 = tot[2]; s3 = tot[3]; N = a.count;
     }
-    const double A = s0 / N, C = s1 / N, Rbar = s2 / N;
-    const double V = (N > 1.0) ? (s3 - N * Rbar * Rbar) / (N - 1.0) : __builtin_nan("");
-    const double den = 1e-8 + V;
-    const double k = 0.5 / den;
-    const float cD = (float)(2.0 * k / N);
-    const float cV = (float)(-(0.5 * (A + C) / (den * den)) * 2.0 / (N - 1.0));
-    const float rbar = (float)Rbar;
-    if (g == 0 && tid == 0 && a.loss) *a.loss = (float)(0.5 * (A + C) / den);
+    const LossCoef k = loss_coef(s0, s1, s2, s3, N);
+    if (g == 0 && tid == 0 && a.loss) *a.loss = k.loss;
     // thread -> (user tid / 8 of the group, column quads tid % 8 + 8 j)
     const int su = tid >> 3, sq = tid & 7, r = RC_USERS * g + su;
     const size_t rowP = (size_t)RC_ROWS * g + su;
@@ -368,18 +362,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_dgrad_chain(const DgradChainArg
       if (r < a.B && col < a.L) {
         const f32x4 P = {P4[j].x, P4[j].y, P4[j].z, P4[j].w}, S = {S4[j].x, S4[j].y, S4[j].z, S4[j].w},
                     Q = {Q4[j].x, Q4[j].y, Q4[j].z, Q4[j].w}, X = {X4[j].x, X4[j].y, X4[j].z, X4[j].w};
-        const f32x4 R = P - X;
-        const f32x4 D = (Q - S) * (1.f / MU2) - R;
-        const f32x4 gD = cD * D;
-        const f32x4 gC = cD * (R - S);
-        const f32x4 gV = cV * (R - rbar);
-        const f32x4 gDm = gD * (1.f / MU2);
-        gP = (-gD + gC + gV) * (1.f - P * P);
-        gQ = gDm * (1.f - Q * Q);
-        gS = (-gDm - gC) * (1.f - S * S);
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-          if (col + i >= a.L) { gP[i] = 0.f; gQ[i] = 0.f; gS[i] = 0.f; }
+        loss_seed_quad<true>(P, S, Q, X, k, col, a.L, gP, gS, gQ);
       }
       *reinterpret_cast<float4*>(a.dY + yP) = make_float4(gP[0], gP[1], gP[2], gP[3]);
       *reinterpret_cast<float4*>(a.dY + yS) = make_float4(gS[0], gS[1], gS[2], gS[3]);

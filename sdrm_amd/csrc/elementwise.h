@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "philox.h"
+#include "train_math.h"
 
 namespace sdrm {
 
@@ -31,8 +32,6 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // A layer's activations prelu(v) stand in for its pre-activations v in the row-owned backward (rowchain.h: skip_pre) when the slope
 // is at least this: positive, and far enough from zero that slope * v neither underflows nor loses min(v, 0) to rounding
 constexpr float SLOPE_FROM_ACT_MIN = 1e-6f;
-constexpr float MU = 0.1f;          // score_matching_loss(..., mu=.1), :333
-constexpr float MU2 = 0.01f;        // mu ** 2, :196
 
 // ---------------------------------------------------------------------------------------------
 // Per-step time-embedding tables (only T+1 distinct timesteps exist):
@@ -227,13 +226,7 @@ __global__ __launch_bounds__(256) void k_prep_train(const PrepTrainArgs a) {
     const int rr = r_first + (int)threadIdx.x;
     int t0 = 0;
     if (rr < a.B) {
-      if (a.mode == 0) {
-        t0 = (int)a.t[rr];
-      } else {
-        const U4 w = philox4x32_10((uint32_t)(a.row0 + rr), 0u, PURPOSE_TRAIN_T, a.step, a.seed_lo, a.seed_hi);
-        t0 = 1 + (int)bounded(w.x, (uint32_t)a.T);
-      }
-      t0 = min(max(t0, 0), a.T);
+      t0 = train_timestep(a.mode, a.t, a.row0, rr, a.step, a.seed_lo, a.seed_hi, a.T);
       a.tdev[rr] = t0;   // (rows shared by two blocks are written twice with the same value)
     }
     tts[threadIdx.x] = t0;
@@ -254,23 +247,12 @@ __global__ __launch_bounds__(256) void k_prep_train(const PrepTrainArgs a) {
       const float x_[4] = {X.x, X.y, X.z, X.w};
       float e[4] = {0.f, 0.f, 0.f, 0.f};
       uint32_t bits[4] = {0u, 0u, 0u, 0u};
-      if (a.mode != 0) {
-        // ONE Philox call per group of four columns: (x, y) and (z, w) give two normal pairs (the upper 24 bits of
-        // each word), the low byte of word j carries the three keep bits of column j (integer multiplies are what
-        // this kernel is bound by; the counter is the column quad)
-        const U4 w = philox4x32_10((uint32_t)(a.row0 + r), (uint32_t)(c >> 2), PURPOSE_TRAIN_ELEM, a.step, a.seed_lo, a.seed_hi);
-        box_muller(w.x, w.y, e[0], e[1]);
-        box_muller(w.z, w.w, e[2], e[3]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] *= a.nd;
-        bits[0] = w.x; bits[1] = w.y; bits[2] = w.z; bits[3] = w.w;
-      }
+      // PHILOX mode: ONE call per group of four columns (integer multiplies are what this kernel is bound by)
+      if (a.mode != 0) train_quad_decode(train_quad_draw(a.row0, r, c >> 2, a.step, a.seed_lo, a.seed_hi), a.nd, e, bits);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int cc = c + j;
-        if (cc < a.L) {
-          const size_t idx = (size_t)r * a.L + cc;
-          const float x = x_[j];
+        if (c + j < a.L) {
+          const size_t idx = (size_t)r * a.L + c + j;
           bool k1, k2, k3;
           float ee;
           if (a.mode == 0) {
@@ -279,14 +261,9 @@ __global__ __launch_bounds__(256) void k_prep_train(const PrepTrainArgs a) {
             k1 = a.keep[idx] != 0; k2 = a.keep[BL + idx] != 0; k3 = a.keep[2 * BL + idx] != 0;
           } else {
             ee = e[j];
-            const uint32_t bb = bits[j];
-            k1 = bb & 1u; k2 = (bb >> 1) & 1u; k3 = (bb >> 2) & 1u;
+            k1 = bits[j] & 1u; k2 = (bits[j] >> 1) & 1u; k3 = (bits[j] >> 2) & 1u;
           }
-          const float xp = sa * x + om * ee;
-          const float xq = x + MU * ee;
-          vP[j] = k1 ? 2.f * xp : 0.f;
-          vS[j] = k2 ? 2.f * x : 0.f;
-          vQ[j] = k3 ? 2.f * xq : 0.f;
+          stage_element(x_[j], ee, sa, om, k1, k2, k3, vP[j], vS[j], vQ[j]);
         }
       }
     }
@@ -343,7 +320,7 @@ __global__ __launch_bounds__(256) void k_prep_forward(const PrepFwdArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Loss partial sums (:196-198): R = P - x0, D = (Q-S)/mu^2 - R.
+// Loss partial sums (train_math.h: loss_terms).
 struct LossArgs {
   const float* Y; const float* x0; int B, L, LP;
   double* part;   // [gridDim.x][4]
@@ -407,12 +384,7 @@ __global__ __launch_bounds__(1024) void k_loss_partials(const LossArgs a) {
     float fD = 0.f, fC = 0.f, fR = 0.f, fR2 = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (c + j < a.L) {
-        const float R = p_[j] - x_[j];
-        const float D = (q_[j] - s_[j]) / MU2 - R;
-        const float RS = R - s_[j];
-        fD += D * D; fC += RS * RS; fR += R; fR2 += R * R;
-      }
+      if (c + j < a.L) loss_terms<false>(p_[j], s_[j], q_[j], x_[j], fD, fC, fR, fR2);
     }
     sD += fD; sC += fC; sR += fR; sR2 += fR2;
   }
@@ -438,7 +410,7 @@ __global__ __launch_bounds__(256) void k_loss_sums(const double* part, int nblk,
   if (threadIdx.x == 0) sums[4] = count;
 }
 
-// Loss value and closed-form gradient seeds, times tanh' = 1 - y^2.
+// Loss value and closed-form gradient seeds (train_math.h: loss_coef, loss_seed), per-layer path.
 struct SeedArgs {
   const double* sums; const float* Y; const float* x0; float* dY; float* loss;
   int B, L, LP, MP;
@@ -465,14 +437,7 @@ __global__ __launch_bounds__(256) void k_loss_seed(const SeedArgs a) {
     s0 = tot[0]; s1 = tot[1]; s2 = tot[2]; s3 = tot[3]; N = a.count;
   }
   const int QP = a.LP >> 2;
-  const double A = s0 / N, C = s1 / N, Rbar = s2 / N;
-  // unbiased variance; a single element gives 0/0 = NaN exactly as torch.var does (train_SDRM.py:198)
-  const double V = (N > 1.0) ? (s3 - N * Rbar * Rbar) / (N - 1.0) : __builtin_nan("");
-  const double den = 1e-8 + V;
-  const double k = 0.5 / den;
-  const float cD = (float)(2.0 * k / N);
-  const float cV = (float)(-(0.5 * (A + C) / (den * den)) * 2.0 / (N - 1.0));
-  const float rbar = (float)Rbar;
+  const LossCoef k = loss_coef(s0, s1, s2, s3, N);
   // items: user slots (three rows each), then the padding rows behind them (one row each)
   const int gu = a.grouped == 2 ? 16 : RC_USERS;   // users per group of the grouped orders
   const int nslots = a.grouped ? gu * ((a.B + gu - 1) / gu) : a.B;
@@ -496,7 +461,7 @@ __global__ __launch_bounds__(256) void k_loss_seed(const SeedArgs a) {
       *reinterpret_cast<float4*>(a.dY + yQ) = zero;
       continue;
     }
-    if (r == 0 && c == 0 && a.loss) *a.loss = (float)(0.5 * (A + C) / den);
+    if (r == 0 && c == 0 && a.loss) *a.loss = k.loss;
     float gP[4] = {0.f, 0.f, 0.f, 0.f}, gS[4] = {0.f, 0.f, 0.f, 0.f}, gQ[4] = {0.f, 0.f, 0.f, 0.f};
     if (c < a.L) {
       const float4 P4 = *reinterpret_cast<const float4*>(a.Y + yP);
@@ -507,17 +472,7 @@ __global__ __launch_bounds__(256) void k_loss_seed(const SeedArgs a) {
                   x_[4] = {X4.x, X4.y, X4.z, X4.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (c + j < a.L) {
-          const float P = p_[j], S = s_[j], Q = q_[j];
-          const float R = P - x_[j];
-          const float D = (Q - S) / MU2 - R;
-          const float gD = cD * D;
-          const float gC = cD * (R - S);
-          const float gV = cV * (R - rbar);
-          gP[j] = (-gD + gC + gV) * (1.f - P * P);
-          gQ[j] = (gD / MU2) * (1.f - Q * Q);
-          gS[j] = (-gD / MU2 - gC) * (1.f - S * S);
-        }
+        if (c + j < a.L) loss_seed<false>(p_[j], s_[j], q_[j], x_[j], k, gP[j], gS[j], gQ[j]);
       }
     }
     *reinterpret_cast<float4*>(a.dY + yP) = make_float4(gP[0], gP[1], gP[2], gP[3]);

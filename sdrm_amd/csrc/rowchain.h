@@ -299,13 +299,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd(const RowChainArgs a) {
     const int usr = u0 + tid;
     int t0 = 0;
     if (usr < a.B) {
-      if (a.mode == 0) {
-        t0 = (int)a.t[usr];
-      } else {
-        const U4 w = philox4x32_10((uint32_t)(a.row0 + usr), 0u, PURPOSE_TRAIN_T, a.step, a.seed_lo, a.seed_hi);
-        t0 = 1 + (int)bounded(w.x, (uint32_t)a.T);
-      }
-      t0 = min(max(t0, 0), a.T);
+      t0 = train_timestep(a.mode, a.t, a.row0, usr, a.step, a.seed_lo, a.seed_hi, a.T);
       a.tdev[usr] = t0;
     }
     trow[tid] = t0;
@@ -348,7 +342,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd(const RowChainArgs a) {
     if (a.mode != 0) {
 #pragma unroll
       for (int j = 0; j < NQ; ++j)
-        rw[j] = philox4x32_10((uint32_t)(a.row0 + susr), (uint32_t)(sq + 8 * j), PURPOSE_TRAIN_ELEM, a.step, a.seed_lo, a.seed_hi);
+        rw[j] = train_quad_draw(a.row0, susr, sq + 8 * j, a.step, a.seed_lo, a.seed_hi);
     }
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
@@ -359,12 +353,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd(const RowChainArgs a) {
         float e[4] = {0.f, 0.f, 0.f, 0.f};
         uint32_t bits[4] = {0u, 0u, 0u, 0u};
         if (a.mode != 0) {
-          const U4 w = rw[j];
-          box_muller(w.x, w.y, e[0], e[1]);
-          box_muller(w.z, w.w, e[2], e[3]);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) e[k] *= a.nd;
-          bits[0] = w.x; bits[1] = w.y; bits[2] = w.z; bits[3] = w.w;
+          train_quad_decode(rw[j], a.nd, e, bits);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -381,9 +370,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd(const RowChainArgs a) {
               ee = e[k];
               k1 = bits[k] & 1u; k2 = (bits[k] >> 1) & 1u; k3 = (bits[k] >> 2) & 1u;
             }
-            vP[k] = k1 ? 2.f * (sa * x + om * ee) : 0.f;
-            vS[k] = k2 ? 2.f * x : 0.f;
-            vQ[k] = k3 ? 2.f * (x + MU * ee) : 0.f;
+            stage_element(x, ee, sa, om, k1, k2, k3, vP[k], vS[k], vQ[k]);
           }
         }
       }
@@ -524,12 +511,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd(const RowChainArgs a) {
     gstore4(yw + ct * 64, ybase + 2 * yrt, make_float4(Q[0], Q[1], Q[2], Q[3]));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if (uok && col + i < a.L) {
-        const float R = P[i] - xq[ct][i];
-        const float D = (Q[i] - S[i]) * (1.f / MU2) - R;   // a multiply: an IEEE division is ten instructions, 132 times per lane
-        const float RS = R - S[i];
-        fD += D * D; fC += RS * RS; fR += R; fR2 += R * R;
-      }
+      if (uok && col + i < a.L) loss_terms<true>(P[i], S[i], Q[i], xq[ct][i], fD, fC, fR, fR2);   // a multiply: an IEEE division is ten instructions, 132 times per lane
     }
     sD += fD; sC += fC; sR += fR; sR2 += fR2;
   }

@@ -261,13 +261,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_rows48_fwd(const RowChainArgs a
     const int usr = u0 + tid;
     int ts = 0;
     if (usr < a.B) {
-      if (a.mode == 0) {
-        ts = (int)a.t[usr];
-      } else {
-        const U4 w = philox4x32_10((uint32_t)(a.row0 + usr), 0u, PURPOSE_TRAIN_T, a.step, a.seed_lo, a.seed_hi);
-        ts = 1 + (int)bounded(w.x, (uint32_t)a.T);
-      }
-      ts = min(max(ts, 0), a.T);
+      ts = train_timestep(a.mode, a.t, a.row0, usr, a.step, a.seed_lo, a.seed_hi, a.T);
       if (part == 0) a.tdev[usr] = ts;
     }
     trow[tid] = ts;
@@ -307,7 +301,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_rows48_fwd(const RowChainArgs a
     if (a.mode != 0) {
 #pragma unroll
       for (int j = 0; j < NQ; ++j)
-        rw[j] = philox4x32_10((uint32_t)(a.row0 + susr), (uint32_t)(sq + 16 * j), PURPOSE_TRAIN_ELEM, a.step, a.seed_lo, a.seed_hi);
+        rw[j] = train_quad_draw(a.row0, susr, sq + 16 * j, a.step, a.seed_lo, a.seed_hi);
     }
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
@@ -319,12 +313,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_rows48_fwd(const RowChainArgs a
         float e[4] = {0.f, 0.f, 0.f, 0.f};
         uint32_t bits[4] = {0u, 0u, 0u, 0u};
         if (a.mode != 0) {
-          const U4 w = rw[j];
-          box_muller(w.x, w.y, e[0], e[1]);
-          box_muller(w.z, w.w, e[2], e[3]);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) e[k] *= a.nd;
-          bits[0] = w.x; bits[1] = w.y; bits[2] = w.z; bits[3] = w.w;
+          train_quad_decode(rw[j], a.nd, e, bits);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -341,9 +330,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_rows48_fwd(const RowChainArgs a
               ee = e[k];
               k1 = bits[k] & 1u; k2 = (bits[k] >> 1) & 1u; k3 = (bits[k] >> 2) & 1u;
             }
-            vP[k] = k1 ? 2.f * (sa * x + om * ee) : 0.f;
-            vS[k] = k2 ? 2.f * x : 0.f;
-            vQ[k] = k3 ? 2.f * (x + MU * ee) : 0.f;
+            stage_element(x, ee, sa, om, k1, k2, k3, vP[k], vS[k], vQ[k]);
           }
         }
       }
@@ -549,12 +536,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_rows48_fwd(const RowChainArgs a
     gstore4(yw + ct * 64, ybase + 2 * yrt, make_float4(Q[0], Q[1], Q[2], Q[3]));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      if (uok && col + i < a.L) {
-        const float R = P[i] - xq[ct][i];
-        const float D = (Q[i] - S[i]) * (1.f / MU2) - R;
-        const float RS = R - S[i];
-        fD += D * D; fC += RS * RS; fR += R; fR2 += R * R;
-      }
+      if (uok && col + i < a.L) loss_terms<true>(P[i], S[i], Q[i], xq[ct][i], fD, fC, fR, fR2);
     }
     sD += fD; sC += fC; sR += fR; sR2 += fR2;
   }
@@ -620,14 +602,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_rows48_dgrad_chain(const DgradC
       __syncthreads();
       s0 = tot[0]; s1 = tot[1]; s2 = tot[2]; s3 = tot[3]; N = a.count;
     }
-    const double A = s0 / N, Cc = s1 / N, Rbar = s2 / N;
-    const double V = (N > 1.0) ? (s3 - N * Rbar * Rbar) / (N - 1.0) : __builtin_nan("");
-    const double den = 1e-8 + V;
-    const double k = 0.5 / den;
-    const float cD = (float)(2.0 * k / N);
-    const float cV = (float)(-(0.5 * (A + Cc) / (den * den)) * 2.0 / (N - 1.0));
-    const float rbar = (float)Rbar;
-    if (g == 0 && part == 0 && tid == 0 && a.loss) *a.loss = (float)(0.5 * (A + Cc) / den);
+    const LossCoef k = loss_coef(s0, s1, s2, s3, N);
+    if (g == 0 && part == 0 && tid == 0 && a.loss) *a.loss = k.loss;
     // thread -> (user tid / 16 of the group, column quads tid % 16 + 16 j)
     const int su = tid >> 4, sq = tid & 15, r = R48_USERS * g + su;
     const size_t rowP = (size_t)R48_ROWS * g + su;
@@ -652,18 +628,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_rows48_dgrad_chain(const DgradC
       if (r < a.B && col < a.L) {
         const f32x4 P = {P4[j].x, P4[j].y, P4[j].z, P4[j].w}, S = {S4[j].x, S4[j].y, S4[j].z, S4[j].w},
                     Q = {Q4[j].x, Q4[j].y, Q4[j].z, Q4[j].w}, X = {X4[j].x, X4[j].y, X4[j].z, X4[j].w};
-        const f32x4 R = P - X;
-        const f32x4 D = (Q - S) * (1.f / MU2) - R;
-        const f32x4 gD = cD * D;
-        const f32x4 gC = cD * (R - S);
-        const f32x4 gV = cV * (R - rbar);
-        const f32x4 gDm = gD * (1.f / MU2);
-        gP = (-gD + gC + gV) * (1.f - P * P);
-        gQ = gDm * (1.f - Q * Q);
-        gS = (-gDm - gC) * (1.f - S * S);
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-          if (col + i >= a.L) { gP[i] = 0.f; gQ[i] = 0.f; gS[i] = 0.f; }
+        loss_seed_quad<true>(P, S, Q, X, k, col, a.L, gP, gS, gQ);
       }
       *reinterpret_cast<float4*>(a.dY + yP) = make_float4(gP[0], gP[1], gP[2], gP[3]);
       *reinterpret_cast<float4*>(a.dY + yS) = make_float4(gS[0], gS[1], gS[2], gS[3]);

@@ -174,13 +174,7 @@ __global__ __launch_bounds__(SK4_THREADS) void k_skinny_fwd4(const SkStepArgs a)
       const int uu = u0 + tid;
       int t0 = -1;
       if (tid < SK4_USERS && uu < a.B) {
-        if (a.mode == 0) {
-          t0 = (int)a.t[uu];
-        } else {
-          const U4 w = philox4x32_10((uint32_t)(a.row0 + uu), 0u, PURPOSE_TRAIN_T, a.step, a.seed_lo, a.seed_hi);
-          t0 = 1 + (int)bounded(w.x, (uint32_t)a.T);
-        }
-        t0 = min(max(t0, 0), a.T);
+        t0 = train_timestep(a.mode, a.t, a.row0, uu, a.step, a.seed_lo, a.seed_hi, a.T);
         a.tdev[uu] = t0;
       }
       trow[tid] = t0;
@@ -219,21 +213,15 @@ __global__ __launch_bounds__(SK4_THREADS) void k_skinny_fwd4(const SkStepArgs a)
       if (stg) {
         const int t0 = trow[ur];
         if (a.mode != 0 && c0 < a.L) {
-          const U4 w = philox4x32_10((uint32_t)(a.row0 + usr), (uint32_t)(c0 >> 2), PURPOSE_TRAIN_ELEM, a.step, a.seed_lo, a.seed_hi);
-          box_muller(w.x, w.y, ens[0], ens[1]);
-          box_muller(w.z, w.w, ens[2], ens[3]);
-          const uint32_t bits[4] = {w.x, w.y, w.z, w.w};
+          uint32_t bits[4];
+          train_quad_decode(train_quad_draw(a.row0, usr, c0 >> 2, a.step, a.seed_lo, a.seed_hi), a.nd, ens, bits);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) { ens[j] *= a.nd; kps[j] = (bits[j] >> pass) & 1u; }
+          for (int j = 0; j < 4; ++j) kps[j] = (bits[j] >> pass) & 1u;
         }
         const float sa = a.sqrt_ab[t0], sb = a.one_minus_ab[t0];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          if (c0 + j < a.L) {
-            const float x = xs[j], e1 = ens[j];
-            const float v = pass == 0 ? sa * x + sb * e1 : (pass == 1 ? x : x + MU * e1);
-            uv[j] = kps[j] ? 2.f * v : 0.f;
-          }
+          if (c0 + j < a.L) uv[j] = stage_element_pass(pass, xs[j], ens[j], sa, sb, kps[j]);
         }
       }
       if (c0 < LPk) {
@@ -329,17 +317,13 @@ __global__ __launch_bounds__(SK4_THREADS) void k_skinny_fwd4(const SkStepArgs a)
       }
     }
     lds_barrier();
-    // ---- loss partial sums (:196-198): R = P - x0, D = (Q - S) / mu^2 - R, over the group's users and the real columns
+    // ---- loss partial sums (train_math.h: loss_terms, every element added in double) over the group's users and the real columns
     {
       double sD = 0, sC = 0, sR = 0, sR2 = 0;
       for (int f = tid; f < SK4_USERS * LPk; f += SK4_THREADS) {
         const int uq = f / LPk, c = f - uq * LPk;
         if (u0 + uq < a.B && c < a.L) {
-          const float P = Yt[uq * XS + c], S = Yt[(4 + uq) * XS + c], Q = Yt[(8 + uq) * XS + c];
-          const float R = P - x0s[uq * XS + c];
-          const float D = (Q - S) / MU2 - R;
-          const float RS = R - S;
-          sD += (double)(D * D); sC += (double)(RS * RS); sR += (double)R; sR2 += (double)(R * R);
+          loss_terms<false>(Yt[uq * XS + c], Yt[(4 + uq) * XS + c], Yt[(8 + uq) * XS + c], x0s[uq * XS + c], sD, sC, sR, sR2);
         }
       }
       double v4[4] = {sD, sC, sR, sR2};

@@ -154,13 +154,7 @@ __global__ __launch_bounds__(64 * 3 * (NL > NW ? NL : NW)) void k_skinny_fwd(con
       const int uu = u0 + tid;
       int t0 = -1;
       if (uu < a.B) {
-        if (a.mode == 0) {
-          t0 = (int)a.t[uu];
-        } else {
-          const U4 w = philox4x32_10((uint32_t)(a.row0 + uu), 0u, PURPOSE_TRAIN_T, a.step, a.seed_lo, a.seed_hi);
-          t0 = 1 + (int)bounded(w.x, (uint32_t)a.T);
-        }
-        t0 = min(max(t0, 0), a.T);
+        t0 = train_timestep(a.mode, a.t, a.row0, uu, a.step, a.seed_lo, a.seed_hi, a.T);
         a.tdev[uu] = t0;
       }
       trow[tid] = t0;
@@ -189,21 +183,15 @@ __global__ __launch_bounds__(64 * 3 * (NL > NW ? NL : NW)) void k_skinny_fwd(con
       if (stg) {
         const int t0 = trow[ur];
         if (a.mode != 0 && c0 < a.L) {
-          const U4 w = philox4x32_10((uint32_t)(a.row0 + usr), (uint32_t)(c0 >> 2), PURPOSE_TRAIN_ELEM, a.step, a.seed_lo, a.seed_hi);
-          box_muller(w.x, w.y, ens[0], ens[1]);
-          box_muller(w.z, w.w, ens[2], ens[3]);
-          const uint32_t bits[4] = {w.x, w.y, w.z, w.w};
+          uint32_t bits[4];
+          train_quad_decode(train_quad_draw(a.row0, usr, c0 >> 2, a.step, a.seed_lo, a.seed_hi), a.nd, ens, bits);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) { ens[j] *= a.nd; kps[j] = (bits[j] >> pass) & 1u; }
+          for (int j = 0; j < 4; ++j) kps[j] = (bits[j] >> pass) & 1u;
         }
         const float sa = a.sqrt_ab[t0], sb = a.one_minus_ab[t0];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          if (c0 + j < a.L) {
-            const float x = xs[j], e1 = ens[j];
-            const float v = pass == 0 ? sa * x + sb * e1 : (pass == 1 ? x : x + MU * e1);
-            uv[j] = kps[j] ? 2.f * v : 0.f;
-          }
+          if (c0 + j < a.L) uv[j] = stage_element_pass(pass, xs[j], ens[j], sa, sb, kps[j]);
         }
       }
       *reinterpret_cast<f32x4*>(&tile0[(16 * pass + ur) * SCR + c0]) = uv;
@@ -299,18 +287,14 @@ __global__ __launch_bounds__(64 * 3 * (NL > NW ? NL : NW)) void k_skinny_fwd(con
       }
     }
     lds_barrier();
-    // ---- loss partial sums (:196-198): R = P - x0, D = (Q - S) / mu^2 - R, over the group's users and the real columns
+    // ---- loss partial sums (train_math.h: loss_terms, every element added in double) over the group's users and the real columns
     {
       double sD = 0, sC = 0, sR = 0, sR2 = 0;
       for (int f = tid; f < SK_USERS * C::LPk; f += NTHR) {
         const int ur = f / C::LPk, c = f - ur * C::LPk;
         const int usr = u0 + ur;
         if (usr < a.B && c < a.L) {
-          const float P = oth[ur * SCR + c], S = oth[(16 + ur) * SCR + c], Q = oth[(32 + ur) * SCR + c];
-          const float R = P - x0s[ur * SCR + c];
-          const float D = (Q - S) / MU2 - R;
-          const float RS = R - S;
-          sD += (double)(D * D); sC += (double)(RS * RS); sR += (double)R; sR2 += (double)(R * R);
+          loss_terms<false>(oth[ur * SCR + c], oth[(16 + ur) * SCR + c], oth[(32 + ur) * SCR + c], x0s[ur * SCR + c], sD, sC, sR, sR2);
         }
       }
       double v4[4] = {sD, sC, sR, sR2};
@@ -430,6 +414,7 @@ __global__ __launch_bounds__(64 * 3 * (NL > NW ? NL : NW)) void k_skinny_bwd(con
     lds_barrier();
     s0 = shs[0]; s1 = shs[1]; s2 = shs[2]; s3 = shs[3]; N = a.count;
   }
+  // (train_math.h: loss_coef and loss_seed, written out: through the helpers this kernel takes 8 more bytes of scratch per lane)
   const double A = s0 / N, Cc = s1 / N, Rbar = s2 / N;
   const double V = (N > 1.0) ? (s3 - N * Rbar * Rbar) / (N - 1.0) : __builtin_nan("");
   const double den = 1e-8 + V;
