@@ -325,6 +325,34 @@ int sdrm_vae_encoder_load(sdrm_engine* e, const sdrm_vae_encoder* enc, void* str
 int sdrm_vae_encode(sdrm_engine* e, const float* x, int n, float* z, float* kl, void* stream);
 int sdrm_vae_encode_csr(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows,
                         const int64_t* rows, int64_t row0, int b, float* z, float* kl, void* stream);
+/* The loss head of the VAE pre-stage on the device (reference: train_SDRM.py:141-142,
+ *   neg_ll = -torch.mean(torch.sum(F.log_softmax(out, dim=1) * X, dim=1)), and the gradient autograd derives from it), for the batch
+ * whose interaction rows X are the CSR rows rows[0..b) (or row0 .. row0+b-1 when rows is null) of a device-resident matrix
+ * [n_rows, n_items] under the contract of sdrm_vae_encode_csr (int64 indptr, int32 indices, float32 data or null for all ones;
+ * canonical CSR: no column twice in a row; stored zeros are legal).  No dense X exists.  logits [b, n_items] float32 row-major, its
+ * base 16-byte aligned (rows need not be).  With x_p the stored values of the batch row's CSR row and s_r their sum:
+ *   sdrm_multinomial_nll_csr:       lse[r] = log sum_i exp(logits[r,i])  (max-subtracted, fp32; device float [b]),
+ *                                   *loss  = -(1/b) sum_r sum_p x_p (logits[r, col_p] - lse[r])  (device float; fp32 terms summed in
+ *                                   float64 in a fixed order: per work-group partials, then one work-group; no atomics).
+ *   sdrm_multinomial_nll_csr_grad:  grad[r,i] = scale (exp(logits[r,i] - lse[r]) s_r - X[r,i]) / b, with lse as the first call left it;
+ *                                   scale is a DEVICE float, the upstream gradient (null: 1).
+ * The first call reads the logits once (and the row's stored columns once more for the terms), the second reads them once and writes
+ * grad once.  grad (16-byte aligned) may be the logits buffer itself - exactly it, any other overlap is SDRM_ERR_ARG: every element
+ * is read before it is written, by the thread that writes it.
+ * Bit-level promises: lse[r] and row r of grad are functions of logits row r, CSR row rows[r], b and scale alone - the same bits
+ * wherever the row sits in the batch, with rows or row0 addressing, in place or out of place, and for data == null against explicit
+ * ones; *loss is the same bits from call to call on the same inputs.
+ * Row ids, indptr pairs and column indices are range-checked on the device into the status word sdrm_feed_status reports: an
+ * offending entry contributes nothing to s_r, to the loss or to grad; an offending row counts as an empty row (its term is 0, its
+ * grad row all zeros; its lse is still that of its logits).  No load or store uses an unchecked index.
+ * Envelope: 1 <= b, 1 <= n_items <= 2^20, b * n_items < 2^40 (SDRM_ERR_SHAPE otherwise, and for a contiguous range that ends behind
+ * n_rows); a null required pointer or a misaligned logits / grad is SDRM_ERR_ARG.  Non-finite logits are outside the contract.
+ * Scratch (the float64 partials, a fixed 16 KB of the handle) is library-owned.  Neither call synchronises the stream. */
+int sdrm_multinomial_nll_csr(sdrm_engine* e, const float* logits, const int64_t* indptr, const int32_t* indices, const float* data,
+                             int64_t n_rows, const int64_t* rows, int64_t row0, int b, int n_items, float* lse, float* loss, void* stream);
+int sdrm_multinomial_nll_csr_grad(sdrm_engine* e, const float* logits, const float* lse, const int64_t* indptr, const int32_t* indices,
+                                  const float* data, int64_t n_rows, const int64_t* rows, int64_t row0, int b, int n_items,
+                                  const float* scale, float* grad, void* stream);
 /* Recall@k and NDCG@k of a score matrix against held-out interactions (reference: utilities.py:116-171,
  * mask_training_examples + recall_at_k_batch + NDCG_binary_at_k_batch, as svd_benchmark.py:58-66 chains them).
  * scores [U, I] float32 row-major; held_* / train_* are CSR index arrays over the same U rows (int64 indptr [U+1],

@@ -88,6 +88,10 @@ SIGNATURES = {
     "sdrm_vae_encoder_load": (c_int, [c_void_p, C.POINTER(VaeEncoder), c_void_p]),
     "sdrm_vae_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "sdrm_vae_encode_csr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "sdrm_multinomial_nll_csr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                         c_void_p, c_void_p]),
+    "sdrm_multinomial_nll_csr_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
+                                              c_void_p, c_void_p, c_void_p]),
     "sdrm_equal_sparsity": (c_int, [c_void_p, c_void_p, c_int64, C.c_double, c_void_p, c_void_p, c_void_p]),
     "sdrm_equal_sparsity_csr_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int64, C.c_double, c_int, c_void_p, c_void_p,
                                               C.POINTER(c_int64), c_void_p]),

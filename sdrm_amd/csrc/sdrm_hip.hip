@@ -23,6 +23,7 @@
 #include "exchange.h"
 #include "feed.h"
 #include "gemm.h"
+#include "nll.h"
 #include "rank.h"
 #include "rowchain.h"
 #include "rows48.h"
@@ -220,6 +221,7 @@ struct sdrm_engine {
   size_t enc_cap[ENC_BUFS] = {};
   double* enc_part = nullptr;        // partial sums of the kl (k_encode_kl_rows)
   bool enc_loaded = false;
+  double* nll_part = nullptr;        // partial sums of the multinomial loss (k_nll_rows), [NLL_PARTS]
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
   Exchange xch;                      // RCCL communicator of the user-sharded step (sdrm_comm_init_rank / sdrm_allreduce_init)
   mutable int64_t n_launches = 0;    // kernel launches issued through this handle since sdrm_create
@@ -248,8 +250,10 @@ struct sdrm_engine {
   std::string err;
 };
 
+constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
+
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_COUNT };
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
     "train: gemm_kernel<0,0,0,0,9> fwd layer0 (row-table bias)", "train: gemm_kernel<0,0,1,0,0> fwd hidden (prelu-in, bias)",
@@ -262,7 +266,8 @@ static const char* kProfNames[PC_COUNT] = {
     "train: k_row_fwd row-owned forward (staging + all layers + loss partial sums, one work-group per CU)",
     "train: k_wgrad_strips weight gradients of all layers (strip-owned split-K, one work-group per CU)",
     "train: k_dgrad_chain / k_dgrad_rows input gradients (row-owned, prelu' epilogue, one work-group per CU; the chain: loss seeds + every layer in one launch)",
-    "sample: k_sample_persist reverse steps without kernel boundaries (all layers + reverse update per step, row tiles synchronised through one XCD's L2)"};
+    "sample: k_sample_persist reverse steps without kernel boundaries (all layers + reverse update per step, row tiles synchronised through one XCD's L2)",
+    "loss head: k_nll_rows / k_nll_grad multinomial NLL of logits against CSR rows and its gradient (one work-group per row, HBM-bound)"};
 
 namespace {
 
@@ -1461,6 +1466,7 @@ int sdrm_create(int L, int W, int T, int H, int max_rows, int device_id, sdrm_en
   HIP_TRY(e, dalloc(&e->sel, 1));
   HIP_TRY(e, dalloc(&e->one_dev, 4));
   HIP_TRY(e, dalloc(&e->feed_flag, 4));
+  HIP_TRY(e, dalloc(&e->nll_part, NLL_PARTS));
   if (e->W0f) {
     // column-split row groups (csrc/rows48.h): hand-shake counters, the host-visible abort word, and the check of the one property
     // of the chip the path rests on - work-group b of a launch runs on XCD b & 7 - with a probe launch
@@ -1545,6 +1551,7 @@ int sdrm_destroy(sdrm_engine* e) {
   for (float* b : e->enc_buf)
     if (b) (void)hipFree(b);
   if (e->enc_part) (void)hipFree(e->enc_part);
+  if (e->nll_part) (void)hipFree(e->nll_part);
   if (e->csr_ws) (void)hipFree(e->csr_ws);
   if (e->csr_nnz_host) (void)hipHostFree(e->csr_nnz_host);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -2870,6 +2877,69 @@ int sdrm_vae_encode_csr(sdrm_engine* e, const int64_t* indptr, const int32_t* in
   else rc = launch_encode_csr(e, k_encode_csr<256, 4, 2>, 256, a, st);
   if (rc) return rc;
   return encode_tail(e, b, z, kl, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Loss head of the VAE pre-stage (train_SDRM.py:141-142), csrc/nll.h.
+namespace {
+
+constexpr int NLL_GRAD_BLOCKS = 1 << 16;   // most work-groups of k_nll_grad; either kernel strides over the rows behind its grid
+
+int check_nll(sdrm_engine* e, const char* who, const float* logits, const int64_t* indptr, const int32_t* indices, int64_t n_rows,
+              const int64_t* rows, int64_t row0, int b, int n_items) {
+  const std::string w(who);
+  if (!logits || !indptr || !indices) return fail(e, SDRM_ERR_ARG, w + ": null pointer");
+  if ((uintptr_t)logits & 15u) return fail(e, SDRM_ERR_ARG, w + ": logits must be 16-byte aligned");
+  if (b < 1 || n_items < 1 || n_items > (1 << 20) || (int64_t)b * n_items >= ((int64_t)1 << 40) || row0 < 0 || n_rows < 1)
+    return fail(e, SDRM_ERR_SHAPE, w + ": b < 1, n_items outside 1 .. 2^20, b x n_items >= 2^40, n_rows < 1 or row0 < 0");
+  if (!rows && row0 + b > n_rows) return fail(e, SDRM_ERR_SHAPE, w + ": rows row0 .. row0 + b - 1 end behind the matrix");
+  return SDRM_OK;
+}
+
+NllArgs nll_args(sdrm_engine* e, const float* logits, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows,
+                 const int64_t* rows, int64_t row0, int b, int n_items) {
+  NllArgs a{};
+  a.logits = logits; a.indptr = indptr; a.indices = indices; a.data = data; a.rows = rows; a.row0 = row0; a.n_rows = n_rows;
+  a.b = b; a.n_items = n_items; a.flag = e->feed_flag;
+  return a;
+}
+
+}  // namespace
+
+int sdrm_multinomial_nll_csr(sdrm_engine* e, const float* logits, const int64_t* indptr, const int32_t* indices, const float* data,
+                             int64_t n_rows, const int64_t* rows, int64_t row0, int b, int n_items, float* lse, float* loss, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!lse || !loss) return fail(e, SDRM_ERR_ARG, "sdrm_multinomial_nll_csr: null pointer");
+  if (int rc = check_nll(e, "sdrm_multinomial_nll_csr", logits, indptr, indices, n_rows, rows, row0, b, n_items)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const NllArgs a = nll_args(e, logits, indptr, indices, data, n_rows, rows, row0, b, n_items);
+  const int parts = std::min(b, NLL_PARTS);
+  if (int rc = hip_rc(e, "k_nll_rows", profiled(e, PC_NLL, 0.0, st, [&] {
+        SDRM_LAUNCH(e, k_nll_rows, dim3((unsigned)parts), dim3(256), 0, st, a, lse, e->nll_part);
+        return hipGetLastError();
+      })))
+    return rc;
+  SDRM_LAUNCH(e, k_nll_sum, dim3(1), dim3(256), 0, st, (const double*)e->nll_part, parts, b, loss);
+  HIP_TRY(e, hipGetLastError());
+  return SDRM_OK;
+}
+
+int sdrm_multinomial_nll_csr_grad(sdrm_engine* e, const float* logits, const float* lse, const int64_t* indptr, const int32_t* indices,
+                                  const float* data, int64_t n_rows, const int64_t* rows, int64_t row0, int b, int n_items,
+                                  const float* scale, float* grad, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!lse || !grad) return fail(e, SDRM_ERR_ARG, "sdrm_multinomial_nll_csr_grad: null pointer");
+  if ((uintptr_t)grad & 15u) return fail(e, SDRM_ERR_ARG, "sdrm_multinomial_nll_csr_grad: grad must be 16-byte aligned");
+  if (int rc = check_nll(e, "sdrm_multinomial_nll_csr_grad", logits, indptr, indices, n_rows, rows, row0, b, n_items)) return rc;
+  const uintptr_t lo = (uintptr_t)logits, go = (uintptr_t)grad, bytes = (uintptr_t)b * (uintptr_t)n_items * sizeof(float);
+  if (lo != go && lo < go + bytes && go < lo + bytes)
+    return fail(e, SDRM_ERR_ARG, "sdrm_multinomial_nll_csr_grad: grad overlaps logits (only grad == logits may alias)");
+  hipStream_t st = (hipStream_t)stream;
+  const NllArgs a = nll_args(e, logits, indptr, indices, data, n_rows, rows, row0, b, n_items);
+  return hip_rc(e, "k_nll_grad", profiled(e, PC_NLL, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_nll_grad, dim3((unsigned)std::min(b, NLL_GRAD_BLOCKS)), dim3(256), 0, st, a, lse, scale, grad);
+    return hipGetLastError();
+  }));
 }
 
 int sdrm_equal_sparsity(sdrm_engine* e, const float* x, int64_t n, double q, uint8_t* out, float* threshold, void* stream) {

@@ -573,6 +573,52 @@ class Engine:
             self.feed_status()
         return (z, kl) if return_kl else z
 
+    # ------------------------------------------------------------------ loss head of the VAE pre-stage (csrc/nll.h)
+    def _nll_batch(self, who, logits, csr_dev, rows, b):
+        indptr, indices, data, (n_rows, n_items) = csr_dev
+        if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.device != self.device or not logits.is_contiguous():
+            raise SdrmError(f"{who}: logits must be a contiguous float32 tensor on the engine's device")
+        if rows is not None:
+            rows = self._dev(rows, torch.int64)
+            b = rows.numel()
+        elif b is None:
+            raise SdrmError(f"{who}: give `rows` or `row0` and `b`")
+        if logits.dim() != 2 or tuple(logits.shape) != (b, n_items):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: logits must be [{b},{n_items}], got {tuple(logits.shape)}")
+        if indices.numel() == 0:   # a matrix without an entry: torch gives an empty tensor no address, and the C ABI takes no null array
+            indices = indices.new_zeros(1)
+        return indptr, indices, data, int(n_rows), int(n_items), rows, int(b)
+
+    def multinomial_nll_csr(self, logits, csr_dev, rows=None, row0=0, b=None, check=True):
+        """train_SDRM.py:141-142 on the device, `-mean(sum(log_softmax(logits) * X))` for the X whose rows are the rows `rows` (or
+        row0 .. row0+b-1) of a `csr_to_device` matrix: (loss 0-d float32, lse [b] float32) as device tensors; no dense X exists and
+        nothing is read back.  Range checks and `check` as in `csr_rows_to_dense`."""
+        indptr, indices, data, n_rows, n_items, rows, b = self._nll_batch("multinomial_nll_csr", logits, csr_dev, rows, b)
+        lse = torch.empty(b, dtype=torch.float32, device=self.device)
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        self._check(self.lib.sdrm_multinomial_nll_csr(self._h, _ptr(logits), _ptr(indptr), _ptr(indices), _ptr(data), n_rows, _ptr(rows), int(row0),
+                                                      b, n_items, _ptr(lse), _ptr(loss), _stream()), "sdrm_multinomial_nll_csr")
+        if check:
+            self.feed_status()
+        return loss, lse
+
+    def multinomial_nll_csr_grad(self, logits, lse, csr_dev, rows=None, row0=0, b=None, scale=None, out=None):
+        """Its gradient with respect to the logits, `scale * (softmax(logits) * X.sum(1) - X) / b` [b, n_items], from the `lse` the
+        forward returned.  `scale`: a float32 device tensor of one element (the upstream gradient; None = 1).  `out=logits` writes it
+        in place of the logits; any other `out` must not overlap them.  The range checks land in the status word `feed_status` reads."""
+        indptr, indices, data, n_rows, n_items, rows, b = self._nll_batch("multinomial_nll_csr_grad", logits, csr_dev, rows, b)
+        for name, t, n in (("lse", lse, b), ("scale", scale, 1)):
+            if t is not None and (t.dtype != torch.float32 or t.device != self.device or t.numel() != n or not t.is_contiguous()):
+                raise SdrmError(f"multinomial_nll_csr_grad: {name} must be a contiguous float32 device tensor of {n} element(s)")
+        if out is None:
+            out = torch.empty_like(logits)
+        elif out.dtype != torch.float32 or out.device != self.device or out.shape != logits.shape or not out.is_contiguous():
+            raise SdrmError("multinomial_nll_csr_grad: out must be a contiguous float32 device tensor of the logits' shape")
+        self._check(self.lib.sdrm_multinomial_nll_csr_grad(self._h, _ptr(logits), _ptr(lse), _ptr(indptr), _ptr(indices), _ptr(data), n_rows,
+                                                           _ptr(rows), int(row0), b, n_items, _ptr(scale), _ptr(out), _stream()),
+                    "sdrm_multinomial_nll_csr_grad")
+        return out
+
     def csr_to_device(self, m):
         """(indptr i64, indices i32, data f32 | None for an all-ones matrix, shape) of a scipy sparse matrix, on the device."""
         m = m.tocsr().copy()

@@ -18,7 +18,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import metrics as utilities
-from .engine import utility_engine
+from .engine import SdrmError, utility_engine
 
 
 def _pruned(msg):
@@ -88,31 +88,87 @@ class VAE(nn.Module):
         return self.decode(z).cpu().detach().numpy()
 
 
+class _MultinomialNLL(torch.autograd.Function):
+    """`-mean(sum(log_softmax(logits) * X))` (:141-142) with X given as CSR rows on the device: both directions are launches of
+    csrc/nll.h on the utility engine, once-differentiable, nothing is read back (the range checks wait for `feed_status()`)."""
+
+    @staticmethod
+    def forward(ctx, logits, csr_dev, rows, row0, b):
+        eng = utility_engine(logits.device)
+        logits = logits.detach().contiguous()
+        rows = None if rows is None else eng._dev(rows, torch.int64)
+        loss, lse = eng.multinomial_nll_csr(logits, csr_dev, rows=rows, row0=row0, b=b, check=False)
+        ctx.save_for_backward(logits, lse)
+        ctx.batch = (eng, csr_dev, rows, row0, b)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        logits, lse = ctx.saved_tensors
+        eng, csr_dev, rows, row0, b = ctx.batch
+        scale = grad_output.to(dtype=torch.float32).contiguous()   # its device pointer is the kernel's `scale`
+        return eng.multinomial_nll_csr_grad(logits, lse, csr_dev, rows=rows, row0=row0, b=b, scale=scale), None, None, None, None
+
+
+def multinomial_nll(logits, csr_dev, rows=None, row0=0, b=None):
+    """The pre-stage's loss term (:141-142) as a 0-dim device tensor with autograd: `logits` [b, n_items] float32 on a ROCm device
+    against the rows `rows` (or row0 .. row0+b-1; default all b = logits.shape[0] rows from row0) of a `csr_to_device` matrix.
+    Its backward hands `grad_output` to the gradient kernel as a device scalar.  A CSR out of range surfaces at the next
+    `utility_engine().feed_status()`."""
+    if not logits.is_cuda:
+        raise SdrmError("multinomial_nll: the logits must be on a ROCm device (there is no CPU fallback)")
+    if rows is None and b is None:
+        b = logits.shape[0]
+    return _MultinomialNLL.apply(logits, csr_dev, rows, row0, b)
+
+
 def train_variational_autoencoder(model, train_data, test_data, epochs, batch_size, lr, early_stop_metric="NDCG@50",
-                                  VAE_DIR_PATH="./", verbose=False):
+                                  VAE_DIR_PATH="./", verbose=False, device_feed=False):
     """VAE pre-stage (:115-188): multinomial NLL + annealed KL, early stopping on Recall/NDCG@k of a
-    per-user hold-out of `test_data`, best epoch restored.  Plain PyTorch (not part of the hot path)."""
+    per-user hold-out of `test_data`, best epoch restored.  Plain PyTorch (not part of the hot path) - except, with
+    `device_feed=True` and the model on a ROCm device, the feed and the loss head: the CSR matrices stay in HBM, every train and
+    evaluation batch is densified there (`csr_rows_to_dense`), the NLL term and its gradient are launches of csrc/nll.h
+    (`multinomial_nll`), the per-step losses stay on the device until the epoch's one readback, and the range checks of all those
+    launches are asked for once per epoch.  The layers, dropout, the reparameterisation draw, KL, L2, autograd through the Linears
+    and Adam stay PyTorch.  With the model on the host the keyword is ignored."""
     os.makedirs(os.path.normpath(VAE_DIR_PATH), exist_ok=True)
     dev = next(model.parameters()).device
+    device_feed = bool(device_feed) and dev.type == "cuda"
     anneal_cap, anneal_count = 0.2, 0.0
     best_metric, best_epoch, stale = -np.inf, 0, 0
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
     k = int(early_stop_metric.split("@")[1])
     start = time.time()
+    n = train_data.shape[0]
+    if device_feed:
+        eng = utility_engine(dev)
+        csr = eng.csr_to_device(train_data)
+        order = np.arange(n)   # the rows the reference's cumulative train_data = train_data[perm] holds, as an index array
     for epoch in range(epochs):
         losses = []
         model.train()
         model.is_training = 1
-        train_data = train_data[np.random.permutation(train_data.shape[0])]
-        for lo in range(0, train_data.shape[0], batch_size):
-            hi = min(lo + batch_size, train_data.shape[0])
+        if device_feed:
+            order = order[np.random.permutation(n)]
+            order_dev = torch.from_numpy(order.astype(np.int64)).to(dev)
+        else:
+            train_data = train_data[np.random.permutation(n)]
+        for lo in range(0, n, batch_size):
+            hi = min(lo + batch_size, n)
             anneal = min(anneal_cap, 1.0 * anneal_count / 20_000)
-            X = torch.tensor(train_data[lo:hi].toarray(), dtype=torch.float32, device=dev)
+            if device_feed:
+                X = eng.csr_rows_to_dense(csr, rows=order_dev[lo:hi], check=False)
+            else:
+                X = torch.tensor(train_data[lo:hi].toarray(), dtype=torch.float32, device=dev)
             optimizer.zero_grad()
             out, kl = model(X)
-            neg_ll = -torch.mean(torch.sum(F.log_softmax(out, dim=1) * X, dim=1))
+            if device_feed:
+                neg_ll = multinomial_nll(out, csr, rows=order_dev[lo:hi])
+            else:
+                neg_ll = -torch.mean(torch.sum(F.log_softmax(out, dim=1) * X, dim=1))
             loss = neg_ll + anneal * kl + model.get_l2_reg()
-            losses.append(loss.item())
+            losses.append(loss.detach() if device_feed else loss.item())
             loss.backward()
             optimizer.step()
             anneal_count += 1
@@ -120,11 +176,16 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
         model.is_training = 0
         scores = []
         valid_train, valid_test = utilities.split_train_test_proportion_from_csr_matrix(test_data, batch_size=1000)
+        if device_feed:
+            valid_csr = eng.csr_to_device(valid_train)
         with torch.no_grad():
             for lo in range(0, valid_train.shape[0], 500):
                 hi = min(lo + 500, valid_train.shape[0])
                 X = valid_train[lo:hi]
-                pred, _ = model(torch.tensor(X.toarray(), dtype=torch.float32, device=dev))
+                if device_feed:
+                    pred, _ = model(eng.csr_rows_to_dense(valid_csr, row0=lo, b=hi - lo, check=False))
+                else:
+                    pred, _ = model(torch.tensor(X.toarray(), dtype=torch.float32, device=dev))
                 if dev.type == "cuda":
                     # utilities.py:116-171 on the device (sdrm_rank_metrics): the [500, N_ITEMS] scores stay in HBM
                     rec, ndcg = utility_engine(dev).rank_metrics(pred, valid_test[lo:hi], train=X, ks=(k,))
@@ -133,6 +194,9 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
                     pred = utilities.mask_training_examples(X, pred.cpu().numpy())
                     fn = utilities.recall_at_k_batch if "Recall" in early_stop_metric else utilities.NDCG_binary_at_k_batch
                     scores.append(fn(pred, valid_test[lo:hi], k=k))
+        if device_feed:
+            eng.feed_status()   # the epoch's one verdict on every row id and column index its launches met
+            losses = torch.stack(losses).cpu().numpy().astype(np.float64)   # one readback; the values the .item()s would have been
         avg = np.nanmean(np.concatenate(scores))
         if verbose:
             print(f"Epoch: {epoch}, Loss: {np.round(np.mean(losses), 4)}, {early_stop_metric}: {np.round(avg, 4)}", end="\r")
