@@ -353,6 +353,39 @@ int sdrm_multinomial_nll_csr(sdrm_engine* e, const float* logits, const int64_t*
 int sdrm_multinomial_nll_csr_grad(sdrm_engine* e, const float* logits, const float* lse, const int64_t* indptr, const int32_t* indices,
                                   const float* data, int64_t n_rows, const int64_t* rows, int64_t row0, int b, int n_items,
                                   const float* scale, float* grad, void* stream);
+/* The input layer of the VAE encoder in TRAIN mode, both directions, straight from a device-resident feed (reference:
+ * train_SDRM.py:242-244, `h = self.encoder(self.dropout(F.normalize(x, p=2, dim=1)))` - the normalisation, the dropout and the FIRST
+ * Linear of the encoder - and, of :148 `loss.backward()`, that Linear's weight gradient).  No dense batch exists in either direction.
+ *   x~[r,c]  = keep(R_r, c) * scale * x[r,c] / max(|x[r,:]|_2, 1e-12)     R_r the feed row of batch row r; the norm covers dropped entries
+ *   pre[r,:] = sum_c x~[r,c] W1[:,c] + b1                                  (no tanh: everything behind the pre-activation is the caller's)
+ *   dW1[:,c] = sum_r x~[r,c] dpre[r,:]
+ * Dropout: the keep decision of (feed row R, column c) is word c & 3 of Philox4x32-10 with counter (R, c >> 2, 7, step) and key
+ * `seed` (csrc/philox.h, PURPOSE_VAE_DROP); keep iff word >= thr, thr = floor((double)p_drop * 2^32); kept values are multiplied by
+ * scale = (float)(1 / (1 - (double)p_drop)).  p_drop is a float in [0, 1) (0: nothing is drawn).  The decision depends on (seed,
+ * step, R, c) alone - not on where the row sits in a batch - and the backward regenerates it: no mask is stored.
+ * sdrm_vae_input_layer_fwd: w1 [hidden, n_items], b1 [hidden] as nn.Linear stores them (device, read by this call: W1 is transposed
+ *   into scratch of the handle on EVERY call, it changes with every optimiser step; an encoder staged by sdrm_vae_encoder_load is not
+ *   touched); the batch is the CSR rows rows[0..b) (or row0 .. row0+b-1 when rows is null) of the feed [n_rows, n_items] under the
+ *   contract of sdrm_vae_encode_csr.  Out: pre [b, hidden] contiguous and rowscale [b] = scale / max(|x[r,:]|_2, 1e-12), which the
+ *   backward takes.  A row's pre and rowscale have the same bits at any batch position and batch size, through rows or row0, and for
+ *   data == null against explicit ones.
+ * sdrm_vae_input_layer_wgrad: dpre [b, hidden] contiguous, rowscale [b] as the forward left it; the feed as CSC (int64 colptr
+ *   [n_items + 1], int32 rowidx ascending within a column, float32 data or null); pos int32 [n_rows], the place of every feed row in
+ *   the epoch's order (the inverse of the permutation whose slice lo .. lo+b-1 was the forward's `rows`; null: the identity, batch =
+ *   rows lo .. lo+b-1).  Feed row R is in the batch iff 0 <= pos[R] - lo < b, and that difference is its row of dpre.  Out: dw1
+ *   [hidden, n_items] contiguous, EVERY element written exactly once (zero where the batch has no kept entry): no memset, no atomic.
+ *   A column's sum runs over its members in ascending feed row: the same bits from call to call and under any order of the batch.
+ *   Cost: one walk over the whole feed's rowidx per call, whatever b is.
+ * Range checks, into the status word sdrm_feed_status reports: row ids, indptr / colptr pairs, column and row indices; an offending
+ * entry contributes nothing, an offending row or column counts as empty.  No load or store uses an unchecked index.
+ * Envelope (SDRM_ERR_SHAPE otherwise): 1 <= n_items <= 2^20, 1 <= hidden <= 4096, 1 <= n_rows < 2^31, 1 <= b <= 2^22, row0 / lo >= 0,
+ * a contiguous range inside the feed, p_drop in [0, 1).  A null required pointer is SDRM_ERR_ARG.  Neither call synchronises. */
+int sdrm_vae_input_layer_fwd(sdrm_engine* e, const float* w1, const float* b1, int n_items, int hidden, const int64_t* indptr,
+                             const int32_t* indices, const float* data, int64_t n_rows, const int64_t* rows, int64_t row0, int b,
+                             uint64_t seed, uint32_t step, float p_drop, float* pre, float* rowscale, void* stream);
+int sdrm_vae_input_layer_wgrad(sdrm_engine* e, const float* dpre, const float* rowscale, int hidden, const int64_t* colptr,
+                               const int32_t* rowidx, const float* data, int64_t n_rows, int n_items, const int32_t* pos, int64_t lo,
+                               int b, uint64_t seed, uint32_t step, float p_drop, float* dw1, void* stream);
 /* Recall@k and NDCG@k of a score matrix against held-out interactions (reference: utilities.py:116-171,
  * mask_training_examples + recall_at_k_batch + NDCG_binary_at_k_batch, as svd_benchmark.py:58-66 chains them).
  * scores [U, I] float32 row-major; held_* / train_* are CSR index arrays over the same U rows (int64 indptr [U+1],

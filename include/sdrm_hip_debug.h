@@ -23,6 +23,13 @@ extern "C" {
  * e.g. "gfx950:sramecc+:xnack-") with 256 compute units, SDRM_ERR_DEVICE otherwise.  Pure function: callable without a GPU. */
 int sdrm_debug_device_check(const char* gcn_arch, int compute_units);
 
+/* What sdrm_vae_input_layer_fwd / _wgrad check and derive on the host before any launch: SDRM_ERR_SHAPE outside their envelope
+ * (`first` is row0 / lo; `contiguous` != 0: rows first .. first + b - 1 must lie inside the feed), else SDRM_OK with the dropout
+ * threshold floor((double)p_drop * 2^32) in *thr and the scale (float)(1 / (1 - (double)p_drop)) in *scale (either may be NULL).
+ * Pure function: callable without a GPU. */
+int sdrm_debug_input_layer_args(int n_items, int hidden, int64_t n_rows, int64_t first, int b, int contiguous, float p_drop,
+                                uint32_t* thr, float* scale);
+
 /* Tile shapes of the MFMA GEMM template, as numbered by sdrm_debug_set_tile / the `cfg` arguments below:
  *   0 = 64x64x16 (default), 1 = 64x64x32, 2 = 64x128x16, 3 = 128x128x16 on v_mfma_f32_32x32x2_f32,
  *   4 = 32x32x32 on v_mfma_f32_16x16x4_f32. */

@@ -14,7 +14,8 @@ enum : uint32_t {
   PURPOSE_SAMPLE_XT = 3,   // start noise of a column quad
   PURPOSE_SAMPLE_STEP = 4, // (four z, four dropout bits) of reverse step i (i in bits 8..), column quad
   PURPOSE_SAMPLE_TJ = 5,   // multi-resolution start step of a row
-  PURPOSE_FORWARD = 6      // dropout bits of a plain forward call (column pair)
+  PURPOSE_FORWARD = 6,     // dropout bits of a plain forward call (column pair)
+  PURPOSE_VAE_DROP = 7     // input dropout of the VAE encoder in train mode (csrc/input_layer.h): word c & 3 of (feed row, column quad)
 };
 
 struct U4 { uint32_t x, y, z, w; };

@@ -23,6 +23,7 @@
 #include "exchange.h"
 #include "feed.h"
 #include "gemm.h"
+#include "input_layer.h"
 #include "nll.h"
 #include "rank.h"
 #include "rowchain.h"
@@ -222,6 +223,10 @@ struct sdrm_engine {
   double* enc_part = nullptr;        // partial sums of the kl (k_encode_kl_rows)
   bool enc_loaded = false;
   double* nll_part = nullptr;        // partial sums of the multinomial loss (k_nll_rows), [NLL_PARTS]
+  // grow-only scratch of the train-mode input layer (csrc/input_layer.h); nothing of the loaded encoder above is touched by it
+  enum { IL_W1T = 0, IL_DPRE, IL_BUFS };
+  float* il_buf[IL_BUFS] = {};       // this call's W1^T [items][Hq] | dpre padded to [b][Hq] (hidden off the 16-byte grid only)
+  size_t il_cap[IL_BUFS] = {};
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
   Exchange xch;                      // RCCL communicator of the user-sharded step (sdrm_comm_init_rank / sdrm_allreduce_init)
   mutable int64_t n_launches = 0;    // kernel launches issued through this handle since sdrm_create
@@ -253,7 +258,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_COUNT };
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
     "train: gemm_kernel<0,0,0,0,9> fwd layer0 (row-table bias)", "train: gemm_kernel<0,0,1,0,0> fwd hidden (prelu-in, bias)",
@@ -267,7 +272,8 @@ static const char* kProfNames[PC_COUNT] = {
     "train: k_wgrad_strips weight gradients of all layers (strip-owned split-K, one work-group per CU)",
     "train: k_dgrad_chain / k_dgrad_rows input gradients (row-owned, prelu' epilogue, one work-group per CU; the chain: loss seeds + every layer in one launch)",
     "sample: k_sample_persist reverse steps without kernel boundaries (all layers + reverse update per step, row tiles synchronised through one XCD's L2)",
-    "loss head: k_nll_rows / k_nll_grad multinomial NLL of logits against CSR rows and its gradient (one work-group per row, HBM-bound)"};
+    "loss head: k_nll_rows / k_nll_grad multinomial NLL of logits against CSR rows and its gradient (one work-group per row, HBM-bound)",
+    "input layer: k_input_fwd / k_input_wgrad train-mode first Linear of the VAE encoder from CSR rows and its weight gradient from CSC columns"};
 
 namespace {
 
@@ -1552,6 +1558,8 @@ int sdrm_destroy(sdrm_engine* e) {
     if (b) (void)hipFree(b);
   if (e->enc_part) (void)hipFree(e->enc_part);
   if (e->nll_part) (void)hipFree(e->nll_part);
+  for (float* b : e->il_buf)
+    if (b) (void)hipFree(b);
   if (e->csr_ws) (void)hipFree(e->csr_ws);
   if (e->csr_nnz_host) (void)hipHostFree(e->csr_nnz_host);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -2939,6 +2947,117 @@ int sdrm_multinomial_nll_csr_grad(sdrm_engine* e, const float* logits, const flo
   return hip_rc(e, "k_nll_grad", profiled(e, PC_NLL, 0.0, st, [&] {
     SDRM_LAUNCH(e, k_nll_grad, dim3((unsigned)std::min(b, NLL_GRAD_BLOCKS)), dim3(256), 0, st, a, lse, scale, grad);
     return hipGetLastError();
+  }));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Input layer of the VAE encoder in train mode (train_SDRM.py:242-244, first Linear; its weight's share of :148), csrc/input_layer.h.
+constexpr int IL_MAX_HIDDEN = 4096;
+
+// The host side of both entry points that needs no device: the envelope, and the dropout threshold and scale of a float p_drop.
+int sdrm_debug_input_layer_args(int n_items, int hidden, int64_t n_rows, int64_t first, int b, int contiguous, float p_drop,
+                                uint32_t* thr, float* scale) {
+  if (n_items < 1 || n_items > (1 << 20) || hidden < 1 || hidden > IL_MAX_HIDDEN || n_rows < 1 || n_rows > (int64_t)INT32_MAX ||
+      b < 1 || b > (1 << 22) || first < 0)
+    return SDRM_ERR_SHAPE;
+  if (contiguous && first + b > n_rows) return SDRM_ERR_SHAPE;
+  if (!(p_drop >= 0.f && p_drop < 1.f)) return SDRM_ERR_SHAPE;   // (a NaN fails both compares)
+  const double p = (double)p_drop;
+  if (thr) *thr = (uint32_t)std::floor(p * 4294967296.0);
+  if (scale) *scale = (float)(1.0 / (1.0 - p));
+  return SDRM_OK;
+}
+
+namespace {
+
+int il_grow(sdrm_engine* e, int slot, size_t n) { return grow_scratch(e, e->il_buf, e->il_cap, slot, n); }
+
+DropArgs drop_args(uint64_t seed, uint32_t step, uint32_t thr) {
+  DropArgs d;
+  d.k0 = (uint32_t)seed; d.k1 = (uint32_t)(seed >> 32); d.step = step; d.thr = thr;
+  return d;
+}
+
+extern "C++" template <class Args>
+hipError_t launch_input(sdrm_engine* e, void (*kernel)(const Args), dim3 grid, size_t lds, const Args& a, hipStream_t st) {
+  if (lds) {   // raised once per kernel and process, as allow_full_lds does; the kernel's static LDS (the chunk, 2 KB) comes on top
+    static std::mutex mu;
+    static std::set<const void*> done;
+    std::lock_guard<std::mutex> lock(mu);
+    const void* fn = reinterpret_cast<const void*>(kernel);
+    if (!done.count(fn)) {
+      const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BYTES - 4096);
+      if (rc != hipSuccess) return rc;
+      done.insert(fn);
+    }
+  }
+  SDRM_LAUNCH(e, kernel, grid, dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+int sdrm_vae_input_layer_fwd(sdrm_engine* e, const float* w1, const float* b1, int n_items, int hidden, const int64_t* indptr,
+                             const int32_t* indices, const float* data, int64_t n_rows, const int64_t* rows, int64_t row0, int b,
+                             uint64_t seed, uint32_t step, float p_drop, float* pre, float* rowscale, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!w1 || !b1 || !indptr || !indices || !pre || !rowscale) return fail(e, SDRM_ERR_ARG, "sdrm_vae_input_layer_fwd: null pointer");
+  uint32_t thr;
+  float scale;
+  if (int rc = sdrm_debug_input_layer_args(n_items, hidden, n_rows, row0, b, rows == nullptr, p_drop, &thr, &scale))
+    return fail(e, rc, "sdrm_vae_input_layer_fwd: n_items outside 1 .. 2^20, hidden outside 1 .. 4096, n_rows outside 1 .. 2^31 - 1, b outside "
+                       "1 .. 2^22, row0 < 0, rows row0 .. row0 + b - 1 end behind the matrix, or p_drop outside [0, 1)");
+  hipStream_t st = (hipStream_t)stream;
+  if (int jr = chains_join(e, st)) return jr;
+  const int Hq = round_up(hidden, 4), q = Hq / 4;
+  if (int rc = il_grow(e, sdrm_engine::IL_W1T, (size_t)n_items * Hq)) return rc;
+  // W1 changes with every optimiser step: the transposed copy is this call's
+  SDRM_LAUNCH(e, k_encode_w1t, dim3((unsigned)((n_items + 31) / 32), (unsigned)((Hq + 31) / 32)), dim3(256), 0, st, w1, hidden, n_items,
+              e->il_buf[sdrm_engine::IL_W1T], Hq);
+  HIP_TRY(e, hipGetLastError());
+  InputFwdArgs a{};
+  a.indptr = indptr; a.indices = indices; a.data = data; a.rows = rows; a.row0 = row0; a.n_rows = n_rows; a.b = b; a.n_items = n_items;
+  a.flag = e->feed_flag; a.w1t = e->il_buf[sdrm_engine::IL_W1T]; a.b1 = b1; a.hidden = hidden; a.Hq = Hq;
+  a.drop = drop_args(seed, step, thr); a.scale = scale; a.pre = pre; a.rowscale = rowscale;
+  return hip_rc(e, "k_input_fwd", profiled(e, PC_INPUT_LAYER, 0.0, st, [&] {
+    if (q <= 64) return launch_input(e, k_input_fwd<64, 1, 8>, dim3((unsigned)((b + 3) / 4)), 0, a, st);   // one wave per row
+    if (q <= 256) return launch_input(e, k_input_fwd<256, 1, 8>, dim3((unsigned)b), 0, a, st);              // one work-group per row
+    if (q <= 512) return launch_input(e, k_input_fwd<256, 2, 4>, dim3((unsigned)b), 0, a, st);
+    return launch_input(e, k_input_fwd<256, 4, 2>, dim3((unsigned)b), 0, a, st);
+  }));
+}
+
+int sdrm_vae_input_layer_wgrad(sdrm_engine* e, const float* dpre, const float* rowscale, int hidden, const int64_t* colptr,
+                               const int32_t* rowidx, const float* data, int64_t n_rows, int n_items, const int32_t* pos, int64_t lo,
+                               int b, uint64_t seed, uint32_t step, float p_drop, float* dw1, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!dpre || !rowscale || !colptr || !rowidx || !dw1) return fail(e, SDRM_ERR_ARG, "sdrm_vae_input_layer_wgrad: null pointer");
+  uint32_t thr;
+  float scale;
+  if (int rc = sdrm_debug_input_layer_args(n_items, hidden, n_rows, lo, b, 1, p_drop, &thr, &scale))
+    return fail(e, rc, "sdrm_vae_input_layer_wgrad: n_items outside 1 .. 2^20, hidden outside 1 .. 4096, n_rows outside 1 .. 2^31 - 1, b outside "
+                       "1 .. 2^22, lo < 0, places lo .. lo + b - 1 end behind the feed, or p_drop outside [0, 1)");
+  hipStream_t st = (hipStream_t)stream;
+  if (int jr = chains_join(e, st)) return jr;
+  const int Hq = round_up(hidden, 4), q = Hq / 4;
+  InputWgradArgs a{};
+  a.dpre = dpre; a.ldd = hidden;
+  if ((hidden & 3) || ((uintptr_t)dpre & 15u)) {   // rows off the 16-byte grid: a padded copy [b][Hq]
+    if (int rc = il_grow(e, sdrm_engine::IL_DPRE, (size_t)b * Hq)) return rc;
+    PadList pad;
+    pad.add(dpre, b, hidden, e->il_buf[sdrm_engine::IL_DPRE], b, Hq);
+    if (int rc = pad.launch(e, st)) return rc;
+    a.dpre = e->il_buf[sdrm_engine::IL_DPRE]; a.ldd = Hq;
+  }
+  a.rowscale = rowscale; a.colptr = colptr; a.rowidx = rowidx; a.data = data; a.pos = pos; a.lo = lo; a.n_rows = n_rows; a.b = b;
+  a.n_items = n_items; a.hidden = hidden; a.Hq = Hq; a.flag = e->feed_flag; a.drop = drop_args(seed, step, thr); a.dw1 = dw1;
+  const unsigned tiles = (unsigned)((n_items + IL_CT - 1) / IL_CT);
+  // the LDS tile [16][ld]: ld = the pass's share of Hq + 4 floats (<= 131 KB at 2048 of them)
+  const auto lds = [&](int span) { return (size_t)IL_CT * (size_t)(std::min(Hq, span) + 4) * sizeof(float); };
+  return hip_rc(e, "k_input_wgrad", profiled(e, PC_INPUT_LAYER, 0.0, st, [&] {
+    if (q <= 64) return launch_input(e, k_input_wgrad<64, 1, 4>, dim3(tiles, 1), lds(256), a, st);      // one wave per column
+    if (q <= 256) return launch_input(e, k_input_wgrad<256, 1, 4>, dim3(tiles, 1), lds(1024), a, st);   // the work-group per column
+    return launch_input(e, k_input_wgrad<256, 2, 2>, dim3(tiles, (unsigned)((Hq + 2047) / 2048)), lds(2048), a, st);
   }));
 }
 

@@ -619,6 +619,87 @@ class Engine:
                     "sdrm_multinomial_nll_csr_grad")
         return out
 
+    # ------------------------------------------------------------------ train-mode input layer of the VAE encoder (csrc/input_layer.h)
+    def _f32(self, who, name, t, shape):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+            raise SdrmError(f"{who}: {name} must be a contiguous float32 tensor on the engine's device")
+        if tuple(t.shape) != tuple(shape):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {name} must be {list(shape)}, got {list(t.shape)}")
+        return t
+
+    def _index(self, who, name, t, dtype, n):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous() or t.numel() != n:
+            raise SdrmError(f"{who}: {name} must be a contiguous {dtype} tensor of {n} element(s) on the engine's device")
+        return t
+
+    def vae_input_layer_fwd(self, w1, b1, csr_dev, rows=None, row0=0, b=None, seed=0, step=0, p_drop=0.5, check=True):
+        """train_SDRM.py:242-244 up to the first pre-activation, in train mode, from the rows `rows` (or row0 .. row0+b-1) of a
+        `csr_to_device` matrix: (pre [b, hidden], rowscale [b]) float32 device tensors for w1 [hidden, n_items], b1 [hidden] as
+        `nn.Linear` holds them.  The dropout bits are the engine's Philox draws of (seed, step, feed row, column), not torch's.
+        Range checks and `check` as in `csr_rows_to_dense`."""
+        who = "vae_input_layer_fwd"
+        indptr, indices, data, (n_rows, n_items) = csr_dev
+        if not isinstance(w1, torch.Tensor) or w1.dim() != 2:
+            raise SdrmError(f"{who}: w1 must be a 2-D tensor [hidden, n_items]")
+        hidden = int(w1.shape[0])
+        w1 = self._f32(who, "w1", w1, (hidden, n_items))
+        b1 = self._f32(who, "b1", b1, (hidden,))
+        if rows is not None:
+            rows = self._dev(rows, torch.int64)
+            b = rows.numel()
+        elif b is None:
+            raise SdrmError(f"{who}: give `rows` or `row0` and `b`")
+        if indices.numel() == 0:   # a matrix without an entry: torch gives an empty tensor no address
+            indices = indices.new_zeros(1)
+        pre = torch.empty(int(b), hidden, dtype=torch.float32, device=self.device)
+        rowscale = torch.empty(int(b), dtype=torch.float32, device=self.device)
+        self._check(self.lib.sdrm_vae_input_layer_fwd(self._h, _ptr(w1), _ptr(b1), int(n_items), hidden, _ptr(indptr), _ptr(indices), _ptr(data),
+                                                      int(n_rows), _ptr(rows), int(row0), int(b), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
+                                                      float(p_drop), _ptr(pre), _ptr(rowscale), _stream()), "sdrm_vae_input_layer_fwd")
+        if check:
+            self.feed_status()
+        return pre, rowscale
+
+    def vae_input_layer_wgrad(self, dpre, rowscale, csc_dev, pos=None, lo=0, b=None, seed=0, step=0, p_drop=0.5, out=None, check=True):
+        """The weight gradient of that Linear, dW1 [hidden, n_items], for dpre [b, hidden] and the `rowscale` the forward returned,
+        from a `csc_to_device` matrix: the batch is the feed rows R with 0 <= pos[R] - lo < b (`pos` int32 [n_rows], the inverse of
+        the epoch's order; None: rows lo .. lo+b-1).  Every element of the result is written once - `out` needs no zeroing."""
+        who = "vae_input_layer_wgrad"
+        colptr, rowidx, data, (n_rows, n_items) = csc_dev
+        if not isinstance(dpre, torch.Tensor) or dpre.dim() != 2:
+            raise SdrmError(f"{who}: dpre must be a 2-D tensor [b, hidden]")
+        b = int(dpre.shape[0]) if b is None else int(b)
+        hidden = int(dpre.shape[1])
+        dpre = self._f32(who, "dpre", dpre, (b, hidden))
+        rowscale = self._f32(who, "rowscale", rowscale, (b,))
+        if pos is not None:
+            pos = self._index(who, "pos", pos, torch.int32, int(n_rows))
+        if rowidx.numel() == 0:
+            rowidx = rowidx.new_zeros(1)
+        if out is None:
+            out = torch.empty(hidden, int(n_items), dtype=torch.float32, device=self.device)
+        else:
+            out = self._f32(who, "out", out, (hidden, int(n_items)))
+        self._check(self.lib.sdrm_vae_input_layer_wgrad(self._h, _ptr(dpre), _ptr(rowscale), hidden, _ptr(colptr), _ptr(rowidx), _ptr(data),
+                                                        int(n_rows), int(n_items), _ptr(pos), int(lo), b, int(seed) & (2 ** 64 - 1),
+                                                        int(step) & 0xFFFFFFFF, float(p_drop), _ptr(out), _stream()), "sdrm_vae_input_layer_wgrad")
+        if check:
+            self.feed_status()
+        return out
+
+    def csc_to_device(self, m):
+        """(colptr i64, rowidx i32, data f32 | None for an all-ones matrix, shape) of a scipy sparse matrix, on the device: the
+        matrix `csr_to_device` ships (duplicates summed, indices sorted), by columns, row indices ascending within a column."""
+        m = m.tocsr().copy()
+        m.sum_duplicates()
+        m.sort_indices()
+        shape = m.shape
+        m = m.tocsc()
+        m.sort_indices()
+        data = None if np.all(m.data == 1) else torch.from_numpy(m.data.astype(np.float32)).to(self.device)
+        return (torch.from_numpy(m.indptr.astype(np.int64)).to(self.device),
+                torch.from_numpy(m.indices.astype(np.int32)).to(self.device), data, shape)
+
     def csr_to_device(self, m):
         """(indptr i64, indices i32, data f32 | None for an all-ones matrix, shape) of a scipy sparse matrix, on the device."""
         m = m.tocsr().copy()

@@ -34,7 +34,8 @@ from torch.nn import functional as F
 
 from . import synth
 from .engine import Engine, SdrmError
-from .vae_hooks import VAE, checkpoint, multinomial_nll, resume, train_variational_autoencoder  # noqa: F401  (part of the reference's module surface)
+from .vae_hooks import (VAE, SparseFeed, checkpoint, multinomial_nll, resume, sparse_input_linear,  # noqa: F401  (part of the reference's
+                        train_variational_autoencoder)                                               # module surface)
 
 warnings.filterwarnings("ignore")
 

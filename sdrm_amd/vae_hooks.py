@@ -71,6 +71,17 @@ class VAE(nn.Module):
         eps = torch.randn_like(mu)  # consumed even in eval, like the reference (Q12)
         return mu + self.is_training * eps * torch.exp(0.5 * logvar), kl
 
+    def encode_rows(self, feed, lo, hi, seed, step):
+        """`encode` in train mode for the rows at places lo .. hi-1 of a `SparseFeed`'s order, without a dense batch: normalise,
+        dropout and the first Linear are `sparse_input_linear` (the dropout bits are the engine's Philox draws of (seed, step, feed
+        row, column), `self.dropout` draws nothing); the rest of the encoder, the KL and the reparameterisation are `encode`'s."""
+        pre = sparse_input_linear(self.encoder[0].weight, self.encoder[0].bias, feed, lo, hi, seed, step, self.dropout.p)
+        h = self.encoder[1:](pre)
+        mu, logvar = torch.chunk(h, chunks=2, dim=1)
+        kl = -0.5 * torch.mean(torch.sum(1 + logvar - mu.pow(2) - logvar.exp(), dim=1))
+        eps = torch.randn_like(mu)
+        return mu + self.is_training * eps * torch.exp(0.5 * logvar), kl
+
     def decode(self, z):
         return self.decoder(z)
 
@@ -123,18 +134,93 @@ def multinomial_nll(logits, csr_dev, rows=None, row0=0, b=None):
     return _MultinomialNLL.apply(logits, csr_dev, rows, row0, b)
 
 
+class SparseFeed:
+    """One scipy matrix on the device in both forms the train-mode input layer reads: `csr` (`Engine.csr_to_device`, the forward's
+    rows) and `csc` (`Engine.csc_to_device`, the weight gradient's columns), plus the epoch's order.  `set_order(order)` stores the
+    order (place -> feed row, int64) and its inverse `pos` (feed row -> place, int32) on the device; without one the order is the
+    identity and batches are contiguous row ranges."""
+
+    def __init__(self, m, device=None, engine=None):
+        self.engine = utility_engine(device) if engine is None else engine
+        self.csr = self.engine.csr_to_device(m)
+        self.csc = self.engine.csc_to_device(m)
+        self.shape = tuple(int(v) for v in m.shape)
+        self.order = self.pos = None
+
+    def set_order(self, order):
+        order = np.asarray(order, dtype=np.int64)
+        n = self.shape[0]
+        if order.shape != (n,) or not np.array_equal(np.sort(order), np.arange(n)):
+            raise SdrmError(f"SparseFeed.set_order: the order must be a permutation of the feed's {n} rows")
+        pos = np.empty(n, dtype=np.int32)
+        pos[order] = np.arange(n, dtype=np.int32)
+        self.order = torch.from_numpy(order).to(self.engine.device)
+        self.pos = torch.from_numpy(pos).to(self.engine.device)
+
+
+class _SparseInputLinear(torch.autograd.Function):
+    """`Linear(n_items, hidden)(dropout(normalize(X)))` for the X whose rows are places lo .. hi-1 of a `SparseFeed`: both
+    directions are launches of csrc/input_layer.h, once-differentiable, no dense X and no stored mask."""
+
+    @staticmethod
+    def forward(ctx, w1, b1, feed, lo, hi, seed, step, p_drop):
+        eng = feed.engine
+        rows = None if feed.order is None else feed.order[lo:hi]
+        pre, rowscale = eng.vae_input_layer_fwd(w1.detach().contiguous(), b1.detach().contiguous(), feed.csr, rows=rows, row0=lo, b=hi - lo,
+                                                seed=seed, step=step, p_drop=p_drop, check=False)
+        ctx.save_for_backward(rowscale)
+        ctx.batch = (feed, lo, hi, seed, step, p_drop)
+        return pre
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dpre):
+        (rowscale,) = ctx.saved_tensors
+        feed, lo, hi, seed, step, p_drop = ctx.batch
+        dpre = dpre.to(dtype=torch.float32).contiguous()
+        dw1 = db1 = None
+        if ctx.needs_input_grad[0]:
+            dw1 = feed.engine.vae_input_layer_wgrad(dpre, rowscale, feed.csc, pos=feed.pos, lo=lo, b=hi - lo, seed=seed, step=step,
+                                                    p_drop=p_drop, check=False)
+        if ctx.needs_input_grad[1]:
+            db1 = dpre.sum(0)
+        return dw1, db1, None, None, None, None, None, None
+
+
+def sparse_input_linear(w1, b1, feed, lo, hi, seed, step, p_drop):
+    """The encoder's input layer in train mode (:242-244 up to the first pre-activation) as a device tensor pre [hi - lo, hidden] with
+    gradients for w1 [hidden, n_items] and b1 [hidden]: the batch is the rows at places lo .. hi-1 of `feed`'s order (a
+    `SparseFeed`).  Dropout keeps entry (feed row R, column c) by the engine's Philox draw of (seed, step, R, c) - not torch's
+    generator.  A feed out of range surfaces at the next `feed.engine.feed_status()`."""
+    if not w1.is_cuda:
+        raise SdrmError("sparse_input_linear: the weights must be on a ROCm device (there is no CPU fallback)")
+    if not 0 <= lo < hi <= feed.shape[0]:
+        raise SdrmError(f"sparse_input_linear: SDRM_ERR_SHAPE: places {lo} .. {hi} outside the feed's {feed.shape[0]} rows")
+    return _SparseInputLinear.apply(w1, b1, feed, int(lo), int(hi), int(seed), int(step), float(p_drop))
+
+
+SPARSE_INPUT_MAX_HIDDEN = 4096   # the widest hidden layer csrc/input_layer.h takes
+
+
 def train_variational_autoencoder(model, train_data, test_data, epochs, batch_size, lr, early_stop_metric="NDCG@50",
-                                  VAE_DIR_PATH="./", verbose=False, device_feed=False):
+                                  VAE_DIR_PATH="./", verbose=False, device_feed=False, sparse_input=False):
     """VAE pre-stage (:115-188): multinomial NLL + annealed KL, early stopping on Recall/NDCG@k of a
     per-user hold-out of `test_data`, best epoch restored.  Plain PyTorch (not part of the hot path) - except, with
     `device_feed=True` and the model on a ROCm device, the feed and the loss head: the CSR matrices stay in HBM, every train and
     evaluation batch is densified there (`csr_rows_to_dense`), the NLL term and its gradient are launches of csrc/nll.h
     (`multinomial_nll`), the per-step losses stay on the device until the epoch's one readback, and the range checks of all those
     launches are asked for once per epoch.  The layers, dropout, the reparameterisation draw, KL, L2, autograd through the Linears
-    and Adam stay PyTorch.  With the model on the host the keyword is ignored."""
+    and Adam stay PyTorch.  With the model on the host the keyword is ignored.
+    `sparse_input=True` (with `device_feed=True`, the model on a ROCm device and a hidden layer of at most 4096; ignored otherwise)
+    also takes the dense batch out of the train half: `model.encode_rows` + `model.decode` in place of `csr_rows_to_dense` +
+    `model(X)`, the input layer and its weight gradient being launches of csrc/input_layer.h straight from the feed's CSR rows and
+    CSC columns.  Its dropout bits are the engine's Philox draws keyed by a seed and `anneal_count`, not torch's generator, so such a
+    run is not bit-comparable with `device_feed=True` alone; and the seed is ONE extra draw from `np.random` (`randint(2**63)`), taken
+    before the first epoch's permutation, so numpy's stream is one draw ahead of the other paths'.  The evaluation half is unchanged."""
     os.makedirs(os.path.normpath(VAE_DIR_PATH), exist_ok=True)
     dev = next(model.parameters()).device
     device_feed = bool(device_feed) and dev.type == "cuda"
+    sparse_input = bool(sparse_input) and device_feed and model.encoder[0].out_features <= SPARSE_INPUT_MAX_HIDDEN
     anneal_cap, anneal_count = 0.2, 0.0
     best_metric, best_epoch, stale = -np.inf, 0, 0
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
@@ -143,8 +229,11 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
     n = train_data.shape[0]
     if device_feed:
         eng = utility_engine(dev)
-        csr = eng.csr_to_device(train_data)
+        feed = SparseFeed(train_data, engine=eng) if sparse_input else None
+        csr = feed.csr if sparse_input else eng.csr_to_device(train_data)
         order = np.arange(n)   # the rows the reference's cumulative train_data = train_data[perm] holds, as an index array
+    if sparse_input:
+        drop_seed = int(np.random.randint(2 ** 63, dtype=np.int64))
     for epoch in range(epochs):
         losses = []
         model.train()
@@ -152,17 +241,25 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
         if device_feed:
             order = order[np.random.permutation(n)]
             order_dev = torch.from_numpy(order.astype(np.int64)).to(dev)
+            if sparse_input:
+                feed.set_order(order)
         else:
             train_data = train_data[np.random.permutation(n)]
         for lo in range(0, n, batch_size):
             hi = min(lo + batch_size, n)
             anneal = min(anneal_cap, 1.0 * anneal_count / 20_000)
-            if device_feed:
+            if sparse_input:
+                X = None
+            elif device_feed:
                 X = eng.csr_rows_to_dense(csr, rows=order_dev[lo:hi], check=False)
             else:
                 X = torch.tensor(train_data[lo:hi].toarray(), dtype=torch.float32, device=dev)
             optimizer.zero_grad()
-            out, kl = model(X)
+            if sparse_input:
+                z, kl = model.encode_rows(feed, lo, hi, drop_seed, int(anneal_count))
+                out = model.decode(z)
+            else:
+                out, kl = model(X)
             if device_feed:
                 neg_ll = multinomial_nll(out, csr, rows=order_dev[lo:hi])
             else:
