@@ -386,6 +386,33 @@ int sdrm_vae_input_layer_fwd(sdrm_engine* e, const float* w1, const float* b1, i
 int sdrm_vae_input_layer_wgrad(sdrm_engine* e, const float* dpre, const float* rowscale, int hidden, const int64_t* colptr,
                                const int32_t* rowidx, const float* data, int64_t n_rows, int n_items, const int32_t* pos, int64_t lo,
                                int b, uint64_t seed, uint32_t step, float p_drop, float* dw1, void* stream);
+/* Per-user hold-out split on the device, CSR in, two CSRs out (reference: utilities.py:174-236,
+ * split_train_test_proportion_from_csr_matrix with ignore_zeros=False, which train_SDRM.py:161 calls once per pre-stage epoch): of
+ * the n stored entries of a user with n >= 2, m = ceil(test_prop * n) chosen uniformly without replacement go to the held-out
+ * matrix and the others to the train matrix; both are all ones (there is no data array, in or out: every stored entry of the input
+ * counts as an interaction, stored zeros included) with columns in CSR order.  Where the reference DROPS a user with fewer than two
+ * entries, that user is an EMPTY ROW in both outputs here: row numbers stay the input's, and sdrm_rank_metrics gives such a user nan,
+ * which the pre-stage's nanmean ignores - the same users count.
+ * The reference's MT19937 np.random.choice stream is not reproduced.  The draw is defined by sort keys (csrc/philox.h,
+ * PURPOSE_HOLDOUT = 8): entry p (0-based place inside feed row u) has
+ *   w_p     = word p & 3 of Philox4x32-10 with counter (u, p >> 2, 8, draw) and key `seed`,
+ *   rank(p) = #{q : w_q < w_p or (w_q == w_p and q < p)},   and is held out iff rank(p) < m_u,
+ *   m_u     = n_u < 2 ? 0 : min(n_u, (int64)ceil(test_prop * (double)n_u))      (the product in double: Python's math.ceil(test_prop * n)).
+ * The m smallest of iid keys are a uniform m-subset (the tie-break by place on equal 32-bit words is a bias of order n^2 2^-32).  The
+ * split of row u depends on (seed, draw, u, n_u) and the row's columns alone - not on n_rows or any other row.
+ * In: indptr [n_rows + 1] int64, indices [nnz] int32 (device).  Out: train_indptr, held_indptr [n_rows + 1] int64; train_indices,
+ * held_indices int32 of capacity nnz, filled on [0, x_indptr[n_rows]) and untouched behind (every store is checked against nnz).
+ * The call does not synchronise and reads nothing back; the outputs are the same bits on every call.
+ * Range checks, into the status word sdrm_feed_status reports: a row whose indptr pair is out of order or reaches outside [0, nnz],
+ * that is longer than n_items, or that holds a column outside [0, n_items) is recorded and is an empty row in both outputs.  The
+ * outputs therefore hold checked column indices and ordered offsets only: sdrm_rank_metrics and sdrm_csr_rows_to_dense may take
+ * them as they are.  No load or store uses an unchecked index.
+ * Envelope (SDRM_ERR_SHAPE otherwise): 1 <= n_items <= 2^20, 1 <= n_rows < 2^31, 0 <= nnz < 2^40, 0 < test_prop < 1.  A null
+ * pointer is SDRM_ERR_ARG (with nnz == 0 the index arrays are never touched but must still be given).  Scratch (two counts per
+ * row) is library-owned and grow-only.  The ranking is quadratic in the row length. */
+int sdrm_holdout_split(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int n_items, int64_t nnz,
+                       double test_prop, uint64_t seed, uint32_t draw, int64_t* train_indptr, int32_t* train_indices,
+                       int64_t* held_indptr, int32_t* held_indices, void* stream);
 /* Recall@k and NDCG@k of a score matrix against held-out interactions (reference: utilities.py:116-171,
  * mask_training_examples + recall_at_k_batch + NDCG_binary_at_k_batch, as svd_benchmark.py:58-66 chains them).
  * scores [U, I] float32 row-major; held_* / train_* are CSR index arrays over the same U rows (int64 indptr [U+1],

@@ -30,6 +30,11 @@ int sdrm_debug_device_check(const char* gcn_arch, int compute_units);
 int sdrm_debug_input_layer_args(int n_items, int hidden, int64_t n_rows, int64_t first, int b, int contiguous, float p_drop,
                                 uint32_t* thr, float* scale);
 
+/* What sdrm_holdout_split checks and derives on the host before any launch: SDRM_ERR_SHAPE outside its envelope (1 <= n_items <=
+ * 2^20, 1 <= n_rows < 2^31, 0 <= nnz < 2^40, 0 < test_prop < 1), else SDRM_OK with the held-out count of a row of n_u entries,
+ * n_u < 2 ? 0 : min(n_u, (int64)ceil(test_prop * (double)n_u)), in *m_out (may be NULL).  Pure function: callable without a GPU. */
+int sdrm_debug_holdout_args(int n_items, int64_t n_rows, int64_t nnz, double test_prop, int64_t n_u, int64_t* m_out);
+
 /* Tile shapes of the MFMA GEMM template, as numbered by sdrm_debug_set_tile / the `cfg` arguments below:
  *   0 = 64x64x16 (default), 1 = 64x64x32, 2 = 64x128x16, 3 = 128x128x16 on v_mfma_f32_32x32x2_f32,
  *   4 = 32x32x32 on v_mfma_f32_16x16x4_f32. */

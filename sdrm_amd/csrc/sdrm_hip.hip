@@ -23,6 +23,7 @@
 #include "exchange.h"
 #include "feed.h"
 #include "gemm.h"
+#include "holdout.h"
 #include "input_layer.h"
 #include "nll.h"
 #include "rank.h"
@@ -227,6 +228,8 @@ struct sdrm_engine {
   enum { IL_W1T = 0, IL_DPRE, IL_BUFS };
   float* il_buf[IL_BUFS] = {};       // this call's W1^T [items][Hq] | dpre padded to [b][Hq] (hidden off the 16-byte grid only)
   size_t il_cap[IL_BUFS] = {};
+  uint32_t* hold_cnt = nullptr;      // grow-only scratch of sdrm_holdout_split (csrc/holdout.h): [2][rows] entries n_u and held entries m_u of every row
+  size_t hold_cap = 0;               // in rows
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
   Exchange xch;                      // RCCL communicator of the user-sharded step (sdrm_comm_init_rank / sdrm_allreduce_init)
   mutable int64_t n_launches = 0;    // kernel launches issued through this handle since sdrm_create
@@ -258,7 +261,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_COUNT };
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
     "train: gemm_kernel<0,0,0,0,9> fwd layer0 (row-table bias)", "train: gemm_kernel<0,0,1,0,0> fwd hidden (prelu-in, bias)",
@@ -273,7 +276,8 @@ static const char* kProfNames[PC_COUNT] = {
     "train: k_dgrad_chain / k_dgrad_rows input gradients (row-owned, prelu' epilogue, one work-group per CU; the chain: loss seeds + every layer in one launch)",
     "sample: k_sample_persist reverse steps without kernel boundaries (all layers + reverse update per step, row tiles synchronised through one XCD's L2)",
     "loss head: k_nll_rows / k_nll_grad multinomial NLL of logits against CSR rows and its gradient (one work-group per row, HBM-bound)",
-    "input layer: k_input_fwd / k_input_wgrad train-mode first Linear of the VAE encoder from CSR rows and its weight gradient from CSC columns"};
+    "input layer: k_input_fwd / k_input_wgrad train-mode first Linear of the VAE encoder from CSR rows and its weight gradient from CSC columns",
+    "hold-out: k_holdout_counts / k_holdout_scan / k_holdout_split per-user hold-out split of a CSR matrix into two (keys ranked per row, a wave or a work-group per row)"};
 
 namespace {
 
@@ -1560,6 +1564,7 @@ int sdrm_destroy(sdrm_engine* e) {
   if (e->nll_part) (void)hipFree(e->nll_part);
   for (float* b : e->il_buf)
     if (b) (void)hipFree(b);
+  if (e->hold_cnt) (void)hipFree(e->hold_cnt);
   if (e->csr_ws) (void)hipFree(e->csr_ws);
   if (e->csr_nnz_host) (void)hipHostFree(e->csr_nnz_host);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -2628,6 +2633,9 @@ int sdrm_feed_status(sdrm_engine* e, void* stream) {
   if (flag & FEED_BAD_ROW) msg += " a row id outside [0, n_rows) (its output row is zero);";
   if (flag & FEED_BAD_PTR) msg += " an indptr pair that is negative or not ordered (its output row is zero);";
   if (flag & FEED_BAD_COL) msg += " a column index outside [0, n_items) (that entry was skipped);";
+  if (flag & FEED_HOLD_PTR)
+    msg += " sdrm_holdout_split: an indptr pair that is out of order, reaches outside [0, nnz] or spans more than n_items entries (the row is empty in both outputs);";
+  if (flag & FEED_HOLD_COL) msg += " sdrm_holdout_split: a column index outside [0, n_items) (the row is empty in both outputs);";
   return fail(e, SDRM_ERR_ARG, msg);
 }
 
@@ -3058,6 +3066,48 @@ int sdrm_vae_input_layer_wgrad(sdrm_engine* e, const float* dpre, const float* r
     if (q <= 64) return launch_input(e, k_input_wgrad<64, 1, 4>, dim3(tiles, 1), lds(256), a, st);      // one wave per column
     if (q <= 256) return launch_input(e, k_input_wgrad<256, 1, 4>, dim3(tiles, 1), lds(1024), a, st);   // the work-group per column
     return launch_input(e, k_input_wgrad<256, 2, 2>, dim3(tiles, (unsigned)((Hq + 2047) / 2048)), lds(2048), a, st);
+  }));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Per-user hold-out split of the VAE pre-stage's evaluation half (utilities.py:174-236), csrc/holdout.h.
+
+// The host side that needs no device: the envelope, and m_u of a row of n_u entries.
+int sdrm_debug_holdout_args(int n_items, int64_t n_rows, int64_t nnz, double test_prop, int64_t n_u, int64_t* m_out) {
+  if (n_items < 1 || n_items > (1 << 20) || n_rows < 1 || n_rows > (int64_t)INT32_MAX || nnz < 0 || nnz >= ((int64_t)1 << 40))
+    return SDRM_ERR_SHAPE;
+  if (!(test_prop > 0.0 && test_prop < 1.0)) return SDRM_ERR_SHAPE;   // (a NaN fails both compares)
+  if (m_out) *m_out = holdout_m(test_prop, n_u);
+  return SDRM_OK;
+}
+
+int sdrm_holdout_split(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int n_items, int64_t nnz,
+                       double test_prop, uint64_t seed, uint32_t draw, int64_t* train_indptr, int32_t* train_indices,
+                       int64_t* held_indptr, int32_t* held_indices, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!indptr || !indices || !train_indptr || !train_indices || !held_indptr || !held_indices)
+    return fail(e, SDRM_ERR_ARG, "sdrm_holdout_split: null pointer");
+  if (int rc = sdrm_debug_holdout_args(n_items, n_rows, nnz, test_prop, 0, nullptr))
+    return fail(e, rc, "sdrm_holdout_split: n_items outside 1 .. 2^20, n_rows outside 1 .. 2^31 - 1, nnz outside 0 .. 2^40 - 1 or test_prop outside (0, 1)");
+  hipStream_t st = (hipStream_t)stream;
+  if ((size_t)n_rows > e->hold_cap) {
+    if (e->hold_cnt) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(e->hold_cnt)); e->hold_cnt = nullptr; e->hold_cap = 0; }
+    HIP_TRY(e, dalloc(&e->hold_cnt, 2 * (size_t)n_rows));
+    e->hold_cap = (size_t)n_rows;
+  }
+  HoldoutArgs a{};
+  a.indptr = indptr; a.indices = indices; a.n_rows = n_rows; a.nnz = nnz; a.n_items = n_items; a.test_prop = test_prop;
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.draw = draw; a.cnt = e->hold_cnt;
+  a.train_indptr = train_indptr; a.train_indices = train_indices; a.held_indptr = held_indptr; a.held_indices = held_indices;
+  a.flag = e->feed_flag;
+  const unsigned waves = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 1 << 20);   // the kernels stride over the rows behind their grids
+  const unsigned groups = (unsigned)std::min<int64_t>(n_rows, 1 << 16);
+  return hip_rc(e, "k_holdout_split", profiled(e, PC_HOLDOUT, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_holdout_counts, dim3(waves), dim3(256), 0, st, a);
+    SDRM_LAUNCH(e, k_holdout_scan, dim3(2), dim3(256), 0, st, a);
+    SDRM_LAUNCH(e, k_holdout_split<64>, dim3(waves), dim3(256), 0, st, a);    // rows of at most HOLD_WAVE_MAX entries: a wave each
+    SDRM_LAUNCH(e, k_holdout_split<256>, dim3(groups), dim3(256), 0, st, a);  // longer rows: a work-group each
+    return hipGetLastError();
   }));
 }
 

@@ -65,6 +65,7 @@ class Engine:
         self._loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.gradient_buckets = 2 if os.environ.get("SDRM_AR_BUCKETS", "1").strip() == "2" else 1   # of train_step_sharded
         self._keepalive = None
+        self._rank_cache = {}             # rank_metrics, device form: (ks, tp, idcg) per cut-off list
         self._n_views = 0                 # spans handed out by params_view() that some tensor's storage still holds
         self._close_pending = False
 
@@ -732,12 +733,59 @@ class Engine:
         """Raises if any `csr_rows_to_dense` launch since the last call met a row id / column index outside the matrix."""
         self._check(self.lib.sdrm_feed_status(self._h, _stream()), "sdrm_feed_status")
 
-    def rank_metrics(self, scores, heldout, train=None, ks=(1, 3, 5, 10, 20, 50)):
+    def holdout_split(self, csr_dev, test_prop=0.2, seed=0, draw=0, check=True, out=None):
+        """utilities.py:174-236 on the device (sdrm_holdout_split, csrc/holdout.h): the per-user hold-out split of a `csr_to_device`
+        matrix as (train_csr_dev, held_csr_dev), each an `(indptr, indices, None, shape)` tuple like `csr_to_device`'s - all ones,
+        the input's row numbering, users with fewer than two entries as empty rows in both.  Per user with n >= 2 entries,
+        ceil(test_prop * n) go to the held part, chosen by the engine's Philox keys of (seed, draw, row, place) - not numpy's
+        generator.  The index tensors have the input's nnz as capacity and are filled up to indptr[-1].  Nothing is read back;
+        range checks and `check` as in `csr_rows_to_dense`.  `out`: a pair of int32 device tensors of nnz elements to fill."""
+        who = "holdout_split"
+        indptr, indices, _, (n_rows, n_items) = csr_dev
+        n_rows, n_items, nnz = int(n_rows), int(n_items), int(indices.numel())
+        indptr = self._index(who, "indptr", indptr, torch.int64, n_rows + 1)
+        indices = self._index(who, "indices", indices, torch.int32, nnz)
+        if out is None:
+            out = (torch.empty(nnz, dtype=torch.int32, device=self.device), torch.empty(nnz, dtype=torch.int32, device=self.device))
+        tr_idx, he_idx = (self._index(who, "out", t, torch.int32, nnz) for t in out)
+        tr_ptr = torch.empty(n_rows + 1, dtype=torch.int64, device=self.device)
+        he_ptr = torch.empty(n_rows + 1, dtype=torch.int64, device=self.device)
+        # a matrix without an entry: torch gives an empty tensor no address, and the C ABI takes no null array
+        spare = [indices.new_zeros(1) for _ in range(3)] if nnz == 0 else (indices, tr_idx, he_idx)
+        self._check(self.lib.sdrm_holdout_split(self._h, _ptr(indptr), _ptr(spare[0]), n_rows, n_items, nnz, float(test_prop),
+                                                int(seed) & (2 ** 64 - 1), int(draw) & 0xFFFFFFFF, _ptr(tr_ptr), _ptr(spare[1]),
+                                                _ptr(he_ptr), _ptr(spare[2]), _stream()), "sdrm_holdout_split")
+        if check:
+            self.feed_status()
+        return (tr_ptr, tr_idx, None, (n_rows, n_items)), (he_ptr, he_idx, None, (n_rows, n_items))
+
+    def _rank_tables(self, ks):
+        """(ks int32 host array, tp, idcg float64 device tables) of a cut-off list, made once per list and engine."""
+        key = tuple(int(k) for k in ks)
+        hit = self._rank_cache.get(key)
+        if hit is None:
+            ks_h = np.asarray(key, dtype=np.int32)
+            kmax = int(ks_h.max())
+            tp = 1.0 / np.log2(np.arange(2, kmax + 2))                                   # utilities.py:145
+            idcg = np.asarray([tp[:m].sum() for m in range(kmax + 1)], dtype=np.float64)   # utilities.py:149-150
+            hit = self._rank_cache[key] = (ks_h, torch.from_numpy(tp).to(self.device), torch.from_numpy(idcg).to(self.device))
+        return hit
+
+    def rank_metrics(self, scores, heldout, train=None, ks=(1, 3, 5, 10, 20, 50), row0=0):
         """utilities.py:116-171 on the device: (recall[nk,U], ndcg[nk,U]) float64 device tensors for a score matrix
         [U, I] (device or host) against the held-out CSR matrix, with the items of the `train` CSR matrix masked out
-        (-inf).  `heldout` / `train` are scipy.sparse matrices (or anything with tocsr())."""
+        (-inf).  `heldout` / `train` are scipy.sparse matrices (or anything with tocsr()) of the scores' shape - or device CSR
+        tuples (`csr_to_device`, `holdout_split`) of [n_rows, I]: the batch's U rows are then rows row0 .. row0+U-1 of them, the
+        discount tables come from a per-`ks` cache on the engine, and the call uploads nothing.  The device form trusts its column
+        indices (`holdout_split` delivers checked ones)."""
         scores = self._dev(scores, torch.float32)
         U, I = scores.shape
+        if isinstance(heldout, tuple):
+            return self._rank_metrics_dev(scores, heldout, train, ks, int(row0))
+        if isinstance(train, tuple):
+            raise SdrmError("rank_metrics: heldout and train must both be scipy matrices or both device CSR tuples")
+        if row0:
+            raise SdrmError("rank_metrics: row0 goes with device CSR tuples only")
         ks = np.asarray(ks, dtype=np.int32)
         kmax = int(ks.max())
         tp = 1.0 / np.log2(np.arange(2, kmax + 2))                                   # utilities.py:145
@@ -758,6 +806,34 @@ class Engine:
                                                ks.ctypes.data_as(C.c_void_p), len(ks), _ptr(tp_d), _ptr(idcg_d),
                                                _ptr(recall), _ptr(ndcg), _stream()), "sdrm_rank_metrics")
         self._keepalive = (scores, hp, hi, tr, tp_d, idcg_d)
+        return recall, ndcg
+
+    def _rank_metrics_dev(self, scores, heldout, train, ks, row0):
+        U, I = scores.shape
+        if train is not None and not isinstance(train, tuple):
+            raise SdrmError("rank_metrics: heldout and train must both be scipy matrices or both device CSR tuples")
+
+        def rows(name, csr_dev):
+            indptr, indices, _, (n_rows, width) = csr_dev
+            if int(width) != I:
+                raise SdrmError(f"rank_metrics: SDRM_ERR_SHAPE: the {name} matrix has {width} columns, the scores {I}")
+            if row0 < 0 or row0 + U > int(n_rows):
+                raise SdrmError(f"rank_metrics: SDRM_ERR_SHAPE: rows {row0} .. {row0 + U - 1} end behind the {name} matrix's {n_rows} rows")
+            indptr = self._index("rank_metrics", f"{name} indptr", indptr, torch.int64, int(n_rows) + 1)
+            if indices.dtype != torch.int32 or indices.device != self.device or not indices.is_contiguous():
+                raise SdrmError(f"rank_metrics: {name} indices must be a contiguous int32 tensor on the engine's device")
+            if indices.numel() == 0:
+                indices = indices.new_zeros(1)
+            return indptr[row0:], indices   # indptr holds absolute offsets: a row range is a pointer offset
+        hp, hi = rows("held-out", heldout)
+        tr = rows("train", train) if train is not None else (None, None)
+        ks_h, tp_d, idcg_d = self._rank_tables(ks)
+        recall = torch.empty(len(ks_h), U, dtype=torch.float64, device=self.device)
+        ndcg = torch.empty(len(ks_h), U, dtype=torch.float64, device=self.device)
+        self._check(self.lib.sdrm_rank_metrics(self._h, _ptr(scores), U, I, _ptr(hp), _ptr(hi), _ptr(tr[0]), _ptr(tr[1]),
+                                               ks_h.ctypes.data_as(C.c_void_p), len(ks_h), _ptr(tp_d), _ptr(idcg_d),
+                                               _ptr(recall), _ptr(ndcg), _stream()), "sdrm_rank_metrics")
+        self._keepalive = (scores, hp, hi, tr)
         return recall, ndcg
 
     def perturb_input(self, x, t, noise):

@@ -202,8 +202,30 @@ def sparse_input_linear(w1, b1, feed, lo, hi, seed, step, p_drop):
 SPARSE_INPUT_MAX_HIDDEN = 4096   # the widest hidden layer csrc/input_layer.h takes
 
 
+def evaluate_holdout(model, eng, test_csr_dev, seed, draw, early_stop_metric, batch=500):
+    """The evaluation half of one pre-stage epoch (:160-177) on the device: the per-user hold-out split of `test_csr_dev` (a
+    `csr_to_device` matrix) by `eng.holdout_split(seed=seed, draw=draw)`, then per batch of `batch` users the dense train part
+    (`csr_rows_to_dense`), `model(...)` in eval mode under `no_grad`, and Recall@k / NDCG@k of its scores against the held part with
+    the train part masked (`rank_metrics`, device form).  Returns the per-user scores as a float64 device tensor [n_rows] - nan for a
+    user with fewer than two entries, whom the reference's split drops.  Nothing is read back; a feed out of range surfaces at the
+    next `eng.feed_status()`.  The model is left in eval mode with `is_training = 0`."""
+    k = int(early_stop_metric.split("@")[1])
+    which = 0 if "Recall" in early_stop_metric else 1
+    n = int(test_csr_dev[3][0])
+    model.eval()
+    model.is_training = 0
+    valid_train, held = eng.holdout_split(test_csr_dev, seed=seed, draw=draw, check=False)
+    scores = torch.empty(n, dtype=torch.float64, device=eng.device)
+    with torch.no_grad():
+        for lo in range(0, n, batch):
+            hi = min(lo + batch, n)
+            pred, _ = model(eng.csr_rows_to_dense(valid_train, row0=lo, b=hi - lo, check=False))
+            scores[lo:hi] = eng.rank_metrics(pred, held, train=valid_train, ks=(k,), row0=lo)[which][0]
+    return scores
+
+
 def train_variational_autoencoder(model, train_data, test_data, epochs, batch_size, lr, early_stop_metric="NDCG@50",
-                                  VAE_DIR_PATH="./", verbose=False, device_feed=False, sparse_input=False):
+                                  VAE_DIR_PATH="./", verbose=False, device_feed=False, sparse_input=False, device_holdout=False):
     """VAE pre-stage (:115-188): multinomial NLL + annealed KL, early stopping on Recall/NDCG@k of a
     per-user hold-out of `test_data`, best epoch restored.  Plain PyTorch (not part of the hot path) - except, with
     `device_feed=True` and the model on a ROCm device, the feed and the loss head: the CSR matrices stay in HBM, every train and
@@ -216,11 +238,19 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
     `model(X)`, the input layer and its weight gradient being launches of csrc/input_layer.h straight from the feed's CSR rows and
     CSC columns.  Its dropout bits are the engine's Philox draws keyed by a seed and `anneal_count`, not torch's generator, so such a
     run is not bit-comparable with `device_feed=True` alone; and the seed is ONE extra draw from `np.random` (`randint(2**63)`), taken
-    before the first epoch's permutation, so numpy's stream is one draw ahead of the other paths'.  The evaluation half is unchanged."""
+    before the first epoch's permutation, so numpy's stream is one draw ahead of the other paths'.  The evaluation half is unchanged.
+    `device_holdout=True` (with `device_feed=True` and the model on a ROCm device; ignored otherwise) puts the evaluation half on the
+    engine (`evaluate_holdout`): `test_data` is uploaded once before the first epoch, epoch e splits it on the device with
+    `holdout_split(seed=holdout_seed, draw=e)`, and the epoch's scores come back in the one readback of the losses.  Such a run's
+    split is the engine's Philox split (csrc/holdout.h), not numpy's: `holdout_seed` is ONE extra draw from `np.random`
+    (`randint(2**63)`, taken before the first permutation, after `sparse_input`'s seed when both are on), numpy's stream no longer
+    advances by one `choice` per user per epoch, and the "skipping user" warning is not printed (such users are empty rows whose nan
+    score `np.nanmean` ignores, so the same users count).  The run is therefore not bit-comparable with the other paths."""
     os.makedirs(os.path.normpath(VAE_DIR_PATH), exist_ok=True)
     dev = next(model.parameters()).device
     device_feed = bool(device_feed) and dev.type == "cuda"
     sparse_input = bool(sparse_input) and device_feed and model.encoder[0].out_features <= SPARSE_INPUT_MAX_HIDDEN
+    device_holdout = bool(device_holdout) and device_feed
     anneal_cap, anneal_count = 0.2, 0.0
     best_metric, best_epoch, stale = -np.inf, 0, 0
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
@@ -234,6 +264,9 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
         order = np.arange(n)   # the rows the reference's cumulative train_data = train_data[perm] holds, as an index array
     if sparse_input:
         drop_seed = int(np.random.randint(2 ** 63, dtype=np.int64))
+    if device_holdout:
+        test_dev = eng.csr_to_device(test_data)
+        holdout_seed = int(np.random.randint(2 ** 63, dtype=np.int64))
     for epoch in range(epochs):
         losses = []
         model.train()
@@ -272,26 +305,33 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
         model.eval()
         model.is_training = 0
         scores = []
-        valid_train, valid_test = utilities.split_train_test_proportion_from_csr_matrix(test_data, batch_size=1000)
-        if device_feed:
-            valid_csr = eng.csr_to_device(valid_train)
-        with torch.no_grad():
-            for lo in range(0, valid_train.shape[0], 500):
-                hi = min(lo + 500, valid_train.shape[0])
-                X = valid_train[lo:hi]
-                if device_feed:
-                    pred, _ = model(eng.csr_rows_to_dense(valid_csr, row0=lo, b=hi - lo, check=False))
-                else:
-                    pred, _ = model(torch.tensor(X.toarray(), dtype=torch.float32, device=dev))
-                if dev.type == "cuda":
-                    # utilities.py:116-171 on the device (sdrm_rank_metrics): the [500, N_ITEMS] scores stay in HBM
-                    rec, ndcg = utility_engine(dev).rank_metrics(pred, valid_test[lo:hi], train=X, ks=(k,))
-                    scores.append((rec if "Recall" in early_stop_metric else ndcg)[0].cpu().numpy())
-                else:
-                    pred = utilities.mask_training_examples(X, pred.cpu().numpy())
-                    fn = utilities.recall_at_k_batch if "Recall" in early_stop_metric else utilities.NDCG_binary_at_k_batch
-                    scores.append(fn(pred, valid_test[lo:hi], k=k))
-        if device_feed:
+        if device_holdout:
+            scores_dev = evaluate_holdout(model, eng, test_dev, holdout_seed, epoch, early_stop_metric)
+        else:
+            valid_train, valid_test = utilities.split_train_test_proportion_from_csr_matrix(test_data, batch_size=1000)
+            if device_feed:
+                valid_csr = eng.csr_to_device(valid_train)
+            with torch.no_grad():
+                for lo in range(0, valid_train.shape[0], 500):
+                    hi = min(lo + 500, valid_train.shape[0])
+                    X = valid_train[lo:hi]
+                    if device_feed:
+                        pred, _ = model(eng.csr_rows_to_dense(valid_csr, row0=lo, b=hi - lo, check=False))
+                    else:
+                        pred, _ = model(torch.tensor(X.toarray(), dtype=torch.float32, device=dev))
+                    if dev.type == "cuda":
+                        # utilities.py:116-171 on the device (sdrm_rank_metrics): the [500, N_ITEMS] scores stay in HBM
+                        rec, ndcg = utility_engine(dev).rank_metrics(pred, valid_test[lo:hi], train=X, ks=(k,))
+                        scores.append((rec if "Recall" in early_stop_metric else ndcg)[0].cpu().numpy())
+                    else:
+                        pred = utilities.mask_training_examples(X, pred.cpu().numpy())
+                        fn = utilities.recall_at_k_batch if "Recall" in early_stop_metric else utilities.NDCG_binary_at_k_batch
+                        scores.append(fn(pred, valid_test[lo:hi], k=k))
+        if device_holdout:
+            eng.feed_status()
+            both = torch.cat([torch.stack(losses).double(), scores_dev]).cpu().numpy()   # one readback: the losses and the scores
+            losses, scores = both[:len(losses)], [both[len(losses):]]
+        elif device_feed:
             eng.feed_status()   # the epoch's one verdict on every row id and column index its launches met
             losses = torch.stack(losses).cpu().numpy().astype(np.float64)   # one readback; the values the .item()s would have been
         avg = np.nanmean(np.concatenate(scores))
