@@ -10,7 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "feed.h"
+#include "csr_batch.h"
 #include "gemm.h"
 
 namespace sdrm {
@@ -66,10 +66,7 @@ __global__ __launch_bounds__(256) void k_encode_norm_rows(const float* __restric
 }
 
 struct EncodeCsrArgs {
-  const int64_t* indptr; const int32_t* indices; const float* data;   // CSR of the whole feed [n_rows, n_items] (data null: all ones)
-  const int64_t* rows;     // [b] row ids of this batch (null: rows row0 .. row0+b-1)
-  int64_t row0, n_rows; int b, n_items;
-  unsigned* flag;          // the handle's feed status word (csrc/feed.h)
+  CsrBatch csr;
   const float* w1t;        // W1^T [n_items][Hq]
   const float* b1;         // [>= Hq], zero behind hidden
   int Hq, Hp;              // hidden rounded up to 4 / to the GEMM's 32
@@ -88,21 +85,10 @@ __global__ __launch_bounds__(256) void k_encode_csr(const EncodeCsrArgs a) {
   __shared__ int2 ent[RPW][TPR];
   const int g = threadIdx.x / TPR, slot = threadIdx.x % TPR;
   const int r = blockIdx.x * RPW + g;
-  const bool row_ok = r < a.b;     // (uniform over the TPR threads of a row; with TPR == 256 over the work-group, so the barriers below are too)
+  const bool row_ok = r < a.csr.b;     // (uniform over the TPR threads of a row; with TPR == 256 over the work-group, so the barriers below are too)
   const int q = a.Hq >> 2;
-  int64_t p0 = 0, p1 = 0;
-  if (row_ok) {
-    const int64_t src = a.rows ? a.rows[r] : a.row0 + r;
-    if (src < 0 || src >= a.n_rows) {
-      if (slot == 0) atomicOr(a.flag, (unsigned)FEED_BAD_ROW);
-    } else {
-      p0 = a.indptr[src]; p1 = a.indptr[src + 1];
-      if (p0 < 0 || p1 < p0) {
-        if (slot == 0) atomicOr(a.flag, (unsigned)FEED_BAD_PTR);
-        p0 = p1 = 0;
-      }
-    }
-  }
+  const CsrSpan s = row_ok ? csr_row_span(a.csr, r, slot) : CsrSpan{0, 0, 0};
+  const int64_t p0 = s.p0, p1 = s.p1;
   float4 acc[NV];
 #pragma unroll
   for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -118,39 +104,21 @@ __global__ __launch_bounds__(256) void k_encode_csr(const EncodeCsrArgs a) {
     {
       int2 e2 = make_int2(0, 0);   // (column 0, value +0.0f): what pads the chunk to a multiple of U
       if (slot < cnt) {
-        const int32_t c = a.indices[p + slot];
-        if (c < 0 || c >= a.n_items) bad = true;
-        else e2 = make_int2(c, __float_as_int(a.data ? a.data[p + slot] : 1.f));
+        const int32_t c = a.csr.indices[p + slot];
+        if (c < 0 || c >= a.csr.n_items) bad = true;
+        else e2 = make_int2(c, __float_as_int(a.csr.data ? a.csr.data[p + slot] : 1.f));
       }
       ent[g][slot] = e2;
     }
-    if (TPR == 256) __syncthreads();
-    else { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
+    chunk_barrier<TPR>();
     for (int j = 0; j < cnt; j += U) {   // (TPR is a multiple of U: j + u stays inside the chunk's LDS row, padded with zero-valued entries)
-      float4 w[U][NV];
       float val[U];
+      gather_fma<NV, U>(ent[g], j, wt, (size_t)q, sl, acc, val);
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int2 e2 = ent[g][j + u];
-        val[u] = __int_as_float(e2.y);
-        const float4* wrow = wt + (size_t)e2.x * q;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) w[u][v] = wrow[sl[v]];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        ss = fmaf(val[u], val[u], ss);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          acc[v].x = fmaf(val[u], w[u][v].x, acc[v].x);
-          acc[v].y = fmaf(val[u], w[u][v].y, acc[v].y);
-          acc[v].z = fmaf(val[u], w[u][v].z, acc[v].z);
-          acc[v].w = fmaf(val[u], w[u][v].w, acc[v].w);
-        }
-      }
+      for (int u = 0; u < U; ++u) ss = fmaf(val[u], val[u], ss);
     }
   }
-  if (bad) atomicOr(a.flag, (unsigned)FEED_BAD_COL);
+  if (bad) atomicOr(a.csr.flag, (unsigned)FEED_BAD_COL);
   if (!row_ok) return;
   const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
   float4* out = reinterpret_cast<float4*>(a.hid + (size_t)r * a.Hp);

@@ -23,12 +23,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "feed.h"
+#include "csr_batch.h"
 #include "philox.h"
 
 namespace sdrm {
-
-enum { FEED_HOLD_PTR = 8u, FEED_HOLD_COL = 16u };   // further bits of the feed status word (csrc/feed.h holds bits 0 .. 2)
 
 constexpr int HOLD_WAVE_MAX = 256;    // longest row of the wave form: four entries per lane
 constexpr int HOLD_TILE = 2048;       // keys of an LDS tile of the work-group form (16 KB)

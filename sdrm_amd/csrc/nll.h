@@ -17,34 +17,13 @@
 #include <stdint.h>
 
 #include "encode.h"
-#include "feed.h"
 
 namespace sdrm {
 
 struct NllArgs {
   const float* logits;     // [b, n_items], base 16-byte aligned
-  const int64_t* indptr; const int32_t* indices; const float* data;   // CSR of the whole feed [n_rows, n_items] (data null: all ones)
-  const int64_t* rows;     // [b] row ids of this batch (null: rows row0 .. row0+b-1)
-  int64_t row0, n_rows; int b, n_items;
-  unsigned* flag;          // the handle's feed status word (csrc/feed.h)
+  CsrBatch csr;
 };
-
-// CSR stretch [p0, p1) of batch row r, range-checked: a row id outside the matrix or an indptr pair out of order raises the
-// status word and leaves the empty stretch.  (Uniform over the work-group: no barrier is skipped.)
-__device__ __forceinline__ void nll_row_span(const NllArgs& a, int r, int64_t& p0, int64_t& p1) {
-  p0 = p1 = 0;
-  const int64_t src = a.rows ? a.rows[r] : a.row0 + r;
-  if (src < 0 || src >= a.n_rows) {
-    if (threadIdx.x == 0) atomicOr(a.flag, (unsigned)FEED_BAD_ROW);
-    return;
-  }
-  const int64_t q0 = a.indptr[src], q1 = a.indptr[src + 1];
-  if (q0 < 0 || q1 < q0) {
-    if (threadIdx.x == 0) atomicOr(a.flag, (unsigned)FEED_BAD_PTR);
-    return;
-  }
-  p0 = q0; p1 = q1;
-}
 
 // Forward.  Block k takes rows k, k + gridDim.x, ..  Per row: every thread keeps a running (max, sum of exp(o - max)) over its
 // columns c = t, t + 256, .. (four loads in flight, one rescale per four), a fixed tree over LDS joins the 256 pairs, and
@@ -56,17 +35,17 @@ __global__ __launch_bounds__(256) void k_nll_rows(const NllArgs a, float* __rest
   const int t = threadIdx.x;
   double acc = 0.0;
   bool bad = false;
-  for (int r = blockIdx.x; r < a.b; r += gridDim.x) {
-    const float* __restrict__ o = a.logits + (size_t)r * a.n_items;
+  for (int r = blockIdx.x; r < a.csr.b; r += gridDim.x) {
+    const float* __restrict__ o = a.logits + (size_t)r * a.csr.n_items;
     float m = -FLT_MAX, s = 0.f;
     int c = t;
-    for (; c + 768 < a.n_items; c += 1024) {
+    for (; c + 768 < a.csr.n_items; c += 1024) {
       const float v0 = o[c], v1 = o[c + 256], v2 = o[c + 512], v3 = o[c + 768];
       const float mn = fmaxf(m, fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)));
       s = s * expf(m - mn) + ((expf(v0 - mn) + expf(v1 - mn)) + (expf(v2 - mn) + expf(v3 - mn)));
       m = mn;
     }
-    for (; c < a.n_items; c += 256) {
+    for (; c < a.csr.n_items; c += 256) {
       const float v = o[c];
       const float mn = fmaxf(m, v);
       s = s * expf(m - mn) + expf(v - mn);
@@ -86,15 +65,15 @@ __global__ __launch_bounds__(256) void k_nll_rows(const NllArgs a, float* __rest
     }
     const float l = red_m[0] + logf(red_s[0]);
     if (t == 0) lse[r] = l;
-    int64_t p0, p1;
-    nll_row_span(a, r, p0, p1);
+    const CsrSpan sp = csr_row_span(a.csr, r, t);   // (uniform over the work-group: no barrier is skipped)
+    const int64_t p0 = sp.p0, p1 = sp.p1;
     for (int64_t p = p0 + t; p < p1; p += 256) {
-      const int32_t col = a.indices[p];
-      if (col < 0 || col >= a.n_items) bad = true;
-      else acc += (double)((a.data ? a.data[p] : 1.f) * (o[col] - l));
+      const int32_t col = a.csr.indices[p];
+      if (col < 0 || col >= a.csr.n_items) bad = true;
+      else acc += (double)((a.csr.data ? a.csr.data[p] : 1.f) * (o[col] - l));
     }
   }
-  if (bad) atomicOr(a.flag, (unsigned)FEED_BAD_COL);
+  if (bad) atomicOr(a.csr.flag, (unsigned)FEED_BAD_COL);
   acc = encode_block_sum(acc, red_d);
   if (t == 0) part[blockIdx.x] = acc;
 }
@@ -118,26 +97,26 @@ __device__ __forceinline__ float nll_soft(float v, float l, float sr, float k) {
 __global__ __launch_bounds__(256) void k_nll_grad(const NllArgs a, const float* __restrict__ lse, const float* __restrict__ scale, float* g) {
   __shared__ double red[256];
   const int t = threadIdx.x;
-  const float k = (scale ? *scale : 1.f) / (float)a.b;
+  const float k = (scale ? *scale : 1.f) / (float)a.csr.b;
   bool bad = false;
-  for (int r = blockIdx.x; r < a.b; r += gridDim.x) {
-    int64_t p0, p1;
-    nll_row_span(a, r, p0, p1);
+  for (int r = blockIdx.x; r < a.csr.b; r += gridDim.x) {
+    const CsrSpan sp = csr_row_span(a.csr, r, t);   // (uniform over the work-group: no barrier is skipped)
+    const int64_t p0 = sp.p0, p1 = sp.p1;
     double sd = 0.0;
     for (int64_t p = p0 + t; p < p1; p += 256) {
-      const int32_t col = a.indices[p];
-      if (col < 0 || col >= a.n_items) bad = true;
-      else sd += (double)(a.data ? a.data[p] : 1.f);
+      const int32_t col = a.csr.indices[p];
+      if (col < 0 || col >= a.csr.n_items) bad = true;
+      else sd += (double)(a.csr.data ? a.csr.data[p] : 1.f);
     }
     const float sr = (float)encode_block_sum(sd, red);
     const float l = lse[r];
-    const float* o = a.logits + (size_t)r * a.n_items;
-    float* d = g + (size_t)r * a.n_items;
+    const float* o = a.logits + (size_t)r * a.csr.n_items;
+    float* d = g + (size_t)r * a.csr.n_items;
     // both bases are 16-byte aligned, so the two rows share one misalignment: peel to a 16-byte boundary
     const int head = (int)(((16 - ((uintptr_t)d & 15)) & 15) >> 2);
-    const int h = head < a.n_items ? head : a.n_items;
+    const int h = head < a.csr.n_items ? head : a.csr.n_items;
     if (t < h) d[t] = nll_soft(o[t], l, sr, k);
-    const int nv = (a.n_items - h) >> 2;
+    const int nv = (a.csr.n_items - h) >> 2;
     const float4* o4 = reinterpret_cast<const float4*>(o + h);
     float4* d4 = reinterpret_cast<float4*>(d + h);
     for (int i = t; i < nv; i += 512) {   // two loads in flight (the compiler may not move a load over a store: the buffers may alias)
@@ -147,14 +126,14 @@ __global__ __launch_bounds__(256) void k_nll_grad(const NllArgs a, const float* 
       d4[i] = make_float4(nll_soft(v.x, l, sr, k), nll_soft(v.y, l, sr, k), nll_soft(v.z, l, sr, k), nll_soft(v.w, l, sr, k));
       if (two) d4[i + 256] = make_float4(nll_soft(w.x, l, sr, k), nll_soft(w.y, l, sr, k), nll_soft(w.z, l, sr, k), nll_soft(w.w, l, sr, k));
     }
-    for (int i = h + 4 * nv + t; i < a.n_items; i += 256) d[i] = nll_soft(o[i], l, sr, k);
+    for (int i = h + 4 * nv + t; i < a.csr.n_items; i += 256) d[i] = nll_soft(o[i], l, sr, k);
     __syncthreads();   // the entries below land on this work-group's own stores above (same row)
     for (int64_t p = p0 + t; p < p1; p += 256) {
-      const int32_t col = a.indices[p];
-      if (col >= 0 && col < a.n_items) d[col] = d[col] - k * (a.data ? a.data[p] : 1.f);
+      const int32_t col = a.csr.indices[p];
+      if (col >= 0 && col < a.csr.n_items) d[col] = d[col] - k * (a.csr.data ? a.csr.data[p] : 1.f);
     }
   }
-  if (bad) atomicOr(a.flag, (unsigned)FEED_BAD_COL);
+  if (bad) atomicOr(a.csr.flag, (unsigned)FEED_BAD_COL);
 }
 
 }  // namespace sdrm

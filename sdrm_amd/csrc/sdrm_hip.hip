@@ -229,7 +229,7 @@ struct sdrm_engine {
   float* il_buf[IL_BUFS] = {};       // this call's W1^T [items][Hq] | dpre padded to [b][Hq] (hidden off the 16-byte grid only)
   size_t il_cap[IL_BUFS] = {};
   uint32_t* hold_cnt = nullptr;      // grow-only scratch of sdrm_holdout_split (csrc/holdout.h): [2][rows] entries n_u and held entries m_u of every row
-  size_t hold_cap = 0;               // in rows
+  size_t hold_cap = 0;               // in elements
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
   Exchange xch;                      // RCCL communicator of the user-sharded step (sdrm_comm_init_rank / sdrm_allreduce_init)
   mutable int64_t n_launches = 0;    // kernel launches issued through this handle since sdrm_create
@@ -302,18 +302,29 @@ int fail(sdrm_engine* e, int code, const std::string& msg) {
   return code;
 }
 
+// The batch of CSR rows of an entry point (csrc/csr_batch.h): the checks that all of them make, and the kernels' descriptor.  The
+// caller has looked at `e` and keeps the limits that are its own.
+int csr_batch(sdrm_engine* e, const char* who, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows,
+              const int64_t* rows, int64_t row0, int b, int n_items, CsrBatch* out) {
+  if (!indptr || !indices) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (b < 1 || n_items < 1 || n_rows < 1 || row0 < 0) return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": b < 1, n_items < 1, n_rows < 1 or row0 < 0");
+  if (!rows && row0 + b > n_rows) return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": rows row0 .. row0 + b - 1 end behind the matrix");
+  *out = CsrBatch{indptr, indices, data, rows, row0, n_rows, b, n_items, e->feed_flag};
+  return SDRM_OK;
+}
+
 constexpr size_t SLACK = 4096;  // elements of zeroed tail on every buffer: unguarded tile loads may run past a matrix
 
-// Dynamic LDS above 48 KB needs the kernel's limit raised.  Raised ONCE per kernel and process, to the whole 160 KB of a CU: a
-// per-launch call is host time on every step of the narrow nets, and a per-engine value would let a second engine with a smaller
-// image lower the limit under a first one with a larger image.
+// Dynamic LDS above 48 KB needs the kernel's limit raised.  Raised ONCE per kernel and process, to the whole 160 KB of a CU (less
+// what a kernel declares statically: its caller says so in `bytes`): a per-launch call is host time on every step of the narrow
+// nets, and a per-engine value would let a second engine with a smaller image lower the limit under a first one with a larger image.
 constexpr int LDS_MAX_BYTES = 160 * 1024;
-hipError_t allow_full_lds(const void* kernel) {
+hipError_t allow_full_lds(const void* kernel, int bytes = LDS_MAX_BYTES) {
   static std::mutex mu;
   static std::set<const void*> done;
   std::lock_guard<std::mutex> lock(mu);
   if (done.count(kernel)) return hipSuccess;
-  const hipError_t st = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BYTES);
+  const hipError_t st = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (st == hipSuccess) done.insert(kernel);
   return st;
 }
@@ -323,6 +334,17 @@ hipError_t dalloc(Tp** p, size_t n) {
   hipError_t st = hipMalloc((void**)p, (n + SLACK) * sizeof(Tp));
   if (st != hipSuccess) return st;
   return hipMemset(*p, 0, (n + SLACK) * sizeof(Tp));
+}
+
+// Grow-only device scratch: *p holds n elements afterwards.  A buffer that is too small is freed behind a device synchronise (a
+// launch may still read it) and its contents are not kept.
+template <typename Tp>
+int grow(sdrm_engine* e, Tp** p, size_t* cap, size_t n) {
+  if (n <= *cap) return SDRM_OK;
+  if (*p) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(*p)); *p = nullptr; *cap = 0; }
+  HIP_TRY(e, dalloc(p, n));
+  *cap = n;
+  return SDRM_OK;
 }
 
 float* pre_buf(sdrm_engine* e, int k) { return e->pre + (size_t)k * e->MPmax * e->WP; }
@@ -2609,13 +2631,10 @@ int sdrm_get_preacts(const sdrm_engine* e, int layer, float* out, void* stream) 
 // Sparse batch feed (dataloaders.py:46-79, train_SDRM.py:323), csrc/feed.h.
 int sdrm_csr_rows_to_dense(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows,
                            const int64_t* rows, int64_t row0, int b, int n_items, float* out, void* stream) {
-  if (!e || !indptr || !indices || !out) return fail(e, SDRM_ERR_ARG, "sdrm_csr_rows_to_dense: null pointer");
-  if (b < 1 || n_items < 1 || row0 < 0 || n_rows < 1)
-    return fail(e, SDRM_ERR_SHAPE, "sdrm_csr_rows_to_dense: b < 1, n_items < 1, n_rows < 1 or row0 < 0");
-  if (!rows && row0 + b > n_rows) return fail(e, SDRM_ERR_SHAPE, "sdrm_csr_rows_to_dense: rows row0 .. row0 + b - 1 end behind the matrix");
+  if (!e || !out) return fail(e, SDRM_ERR_ARG, "sdrm_csr_rows_to_dense: null pointer");
   FeedArgs a{};
-  a.indptr = indptr; a.indices = indices; a.data = data; a.rows = rows; a.row0 = row0; a.n_rows = n_rows; a.b = b; a.n_items = n_items;
-  a.out = out; a.flag = e->feed_flag;
+  if (int rc = csr_batch(e, "sdrm_csr_rows_to_dense", indptr, indices, data, n_rows, rows, row0, b, n_items, &a.csr)) return rc;
+  a.out = out;
   SDRM_LAUNCH(e, k_csr_rows_to_dense, dim3(b), dim3(256), 0, (hipStream_t)stream, a);
   HIP_TRY(e, hipGetLastError());
   return SDRM_OK;
@@ -2629,13 +2648,9 @@ int sdrm_feed_status(sdrm_engine* e, void* stream) {
   HIP_TRY(e, hipStreamSynchronize((hipStream_t)stream));
   if (!flag) return SDRM_OK;
   HIP_TRY(e, hipMemsetAsync(e->feed_flag, 0, sizeof(flag), (hipStream_t)stream));
-  std::string msg = "sdrm_csr_rows_to_dense:";
-  if (flag & FEED_BAD_ROW) msg += " a row id outside [0, n_rows) (its output row is zero);";
-  if (flag & FEED_BAD_PTR) msg += " an indptr pair that is negative or not ordered (its output row is zero);";
-  if (flag & FEED_BAD_COL) msg += " a column index outside [0, n_items) (that entry was skipped);";
-  if (flag & FEED_HOLD_PTR)
-    msg += " sdrm_holdout_split: an indptr pair that is out of order, reaches outside [0, nnz] or spans more than n_items entries (the row is empty in both outputs);";
-  if (flag & FEED_HOLD_COL) msg += " sdrm_holdout_split: a column index outside [0, n_items) (the row is empty in both outputs);";
+  std::string msg = "the CSR feed met";
+  for (const FeedStatusText& t : FEED_STATUS_TEXT)
+    if (flag & t.bit) msg += t.text;
   return fail(e, SDRM_ERR_ARG, msg);
 }
 
@@ -2680,15 +2695,8 @@ int select_and_binarize(sdrm_engine* e, const float* x, int64_t n, float gamma, 
   return SDRM_OK;
 }
 
-int grow_scratch(sdrm_engine* e, float** buf, size_t* cap, int slot, size_t n) {
-  if (n <= cap[slot]) return SDRM_OK;
-  if (buf[slot]) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(buf[slot])); buf[slot] = nullptr; cap[slot] = 0; }
-  HIP_TRY(e, dalloc(&buf[slot], n));
-  cap[slot] = n;
-  return SDRM_OK;
-}
-int dec_grow(sdrm_engine* e, int slot, size_t n) { return grow_scratch(e, e->dec_buf, e->dec_cap, slot, n); }
-int enc_grow(sdrm_engine* e, int slot, size_t n) { return grow_scratch(e, e->enc_buf, e->enc_cap, slot, n); }
+int dec_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->dec_buf[slot], &e->dec_cap[slot], n); }
+int enc_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->enc_buf[slot], &e->enc_cap[slot], n); }
 
 // The segments of ONE k_pad2d launch: src [rows, cols] -> dst [rowsP, colsP], zero-padded
 struct PadList {
@@ -2813,11 +2821,20 @@ int encode_dense_launches(sdrm_engine* e, const float* x, int n, float* z, float
   return encode_tail(e, n, z, kl, st);
 }
 
-int launch_encode_csr(sdrm_engine* e, void (*kernel)(const EncodeCsrArgs), int tpr, const EncodeCsrArgs& a, hipStream_t st) {
-  const int rpw = 256 / tpr;
-  SDRM_LAUNCH(e, kernel, dim3((unsigned)((a.b + rpw - 1) / rpw)), dim3(256), 0, st, a);
-  HIP_TRY(e, hipGetLastError());
-  return SDRM_OK;
+// One launch of a row-owned gather kernel (csrc/csr_batch.h) over the rows of a batch.  The gather shape goes by the q float4 slices
+// of the hidden vector alone: TPR threads own a row, NV slices each, U entries in flight.  kernel_of(TPR, NV, U) names the kernel.
+extern "C++" template <class Args, class KernelOf>
+hipError_t launch_gather_rows(sdrm_engine* e, int q, const Args& a, hipStream_t st, KernelOf&& kernel_of) {
+  const auto go = [&](auto tpr, auto nv, auto u) {
+    constexpr int rpw = 256 / VAL(tpr);
+    SDRM_LAUNCH(e, kernel_of(tpr, nv, u), dim3((unsigned)((a.csr.b + rpw - 1) / rpw)), dim3(256), 0, st, a);
+    return hipGetLastError();
+  };
+  using std::integral_constant;
+  if (q <= 64) return go(integral_constant<int, 64>{}, integral_constant<int, 1>{}, integral_constant<int, 8>{});   // one wave per row, four rows per work-group (ADM: hidden 200)
+  if (q <= 256) return go(integral_constant<int, 256>{}, integral_constant<int, 1>{}, integral_constant<int, 8>{});   // one work-group per row (ML-1M 600, ML-100k 930)
+  if (q <= 512) return go(integral_constant<int, 256>{}, integral_constant<int, 2>{}, integral_constant<int, 4>{});
+  return go(integral_constant<int, 256>{}, integral_constant<int, 4>{}, integral_constant<int, 2>{});
 }
 
 int check_encoder(sdrm_engine* e, const sdrm_vae_encoder* d, const char* who) {
@@ -2868,10 +2885,11 @@ int sdrm_vae_encode(sdrm_engine* e, const float* x, int n, float* z, float* kl, 
 int sdrm_vae_encode_csr(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows,
                         const int64_t* rows, int64_t row0, int b, float* z, float* kl, void* stream) {
   if (!e) return SDRM_ERR_ARG;
-  if (!indptr || !indices || !z) return fail(e, SDRM_ERR_ARG, "sdrm_vae_encode_csr: null pointer");
+  if (!z) return fail(e, SDRM_ERR_ARG, "sdrm_vae_encode_csr: null pointer");
   if (!e->enc_loaded) return fail(e, SDRM_ERR_STATE, "sdrm_vae_encode_csr: no encoder loaded (sdrm_vae_encoder_load)");
-  if (b < 1 || b > (1 << 22) || row0 < 0 || n_rows < 1) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode_csr: b outside 1 .. 2^22, n_rows < 1 or row0 < 0");
-  if (!rows && row0 + b > n_rows) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode_csr: rows row0 .. row0 + b - 1 end behind the matrix");
+  EncodeCsrArgs a{};
+  if (int rc = csr_batch(e, "sdrm_vae_encode_csr", indptr, indices, data, n_rows, rows, row0, b, e->enc_items, &a.csr)) return rc;
+  if (b > (1 << 22)) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode_csr: b outside 1 .. 2^22");
   hipStream_t st = (hipStream_t)stream;
   if (int jr = chains_join(e, st)) return jr;
   const EncDims d = enc_dims(e->enc_items, e->enc_hidden, e->enc_latent);
@@ -2882,16 +2900,9 @@ int sdrm_vae_encode_csr(sdrm_engine* e, const int64_t* indptr, const int32_t* in
     return encode_dense_launches(e, e->enc_buf[sdrm_engine::ENC_DENSE], b, z, kl, st);
   }
   if (int rc = enc_grow(e, sdrm_engine::ENC_HID, (size_t)round_up(b, 128) * d.Hp)) return rc;
-  EncodeCsrArgs a{};
-  a.indptr = indptr; a.indices = indices; a.data = data; a.rows = rows; a.row0 = row0; a.n_rows = n_rows; a.b = b; a.n_items = e->enc_items;
-  a.flag = e->feed_flag; a.w1t = e->enc_buf[sdrm_engine::ENC_W1T]; a.b1 = e->enc_buf[sdrm_engine::ENC_B1]; a.Hq = d.Hq; a.Hp = d.Hp;
+  a.w1t = e->enc_buf[sdrm_engine::ENC_W1T]; a.b1 = e->enc_buf[sdrm_engine::ENC_B1]; a.Hq = d.Hq; a.Hp = d.Hp;
   a.hid = e->enc_buf[sdrm_engine::ENC_HID];
-  int rc;
-  if (q <= 64) rc = launch_encode_csr(e, k_encode_csr<64, 1, 8>, 64, a, st);          // one wave per row, four rows per work-group (ADM: hidden 200)
-  else if (q <= 256) rc = launch_encode_csr(e, k_encode_csr<256, 1, 8>, 256, a, st);   // one work-group per row (ML-1M 600, ML-100k 930)
-  else if (q <= 512) rc = launch_encode_csr(e, k_encode_csr<256, 2, 4>, 256, a, st);
-  else rc = launch_encode_csr(e, k_encode_csr<256, 4, 2>, 256, a, st);
-  if (rc) return rc;
+  HIP_TRY(e, launch_gather_rows(e, q, a, st, [](auto tpr, auto nv, auto u) { return k_encode_csr<VAL(tpr), VAL(nv), VAL(u)>; }));
   return encode_tail(e, b, z, kl, st);
 }
 
@@ -2901,23 +2912,17 @@ namespace {
 
 constexpr int NLL_GRAD_BLOCKS = 1 << 16;   // most work-groups of k_nll_grad; either kernel strides over the rows behind its grid
 
-int check_nll(sdrm_engine* e, const char* who, const float* logits, const int64_t* indptr, const int32_t* indices, int64_t n_rows,
-              const int64_t* rows, int64_t row0, int b, int n_items) {
+// the checks of both entry points, and their kernels' arguments
+int nll_args(sdrm_engine* e, const char* who, const float* logits, const int64_t* indptr, const int32_t* indices, const float* data,
+             int64_t n_rows, const int64_t* rows, int64_t row0, int b, int n_items, NllArgs* a) {
   const std::string w(who);
-  if (!logits || !indptr || !indices) return fail(e, SDRM_ERR_ARG, w + ": null pointer");
+  if (!logits) return fail(e, SDRM_ERR_ARG, w + ": null pointer");
   if ((uintptr_t)logits & 15u) return fail(e, SDRM_ERR_ARG, w + ": logits must be 16-byte aligned");
-  if (b < 1 || n_items < 1 || n_items > (1 << 20) || (int64_t)b * n_items >= ((int64_t)1 << 40) || row0 < 0 || n_rows < 1)
-    return fail(e, SDRM_ERR_SHAPE, w + ": b < 1, n_items outside 1 .. 2^20, b x n_items >= 2^40, n_rows < 1 or row0 < 0");
-  if (!rows && row0 + b > n_rows) return fail(e, SDRM_ERR_SHAPE, w + ": rows row0 .. row0 + b - 1 end behind the matrix");
+  if (int rc = csr_batch(e, who, indptr, indices, data, n_rows, rows, row0, b, n_items, &a->csr)) return rc;
+  if (n_items > (1 << 20) || (int64_t)b * n_items >= ((int64_t)1 << 40))
+    return fail(e, SDRM_ERR_SHAPE, w + ": n_items outside 1 .. 2^20 or b x n_items >= 2^40");
+  a->logits = logits;
   return SDRM_OK;
-}
-
-NllArgs nll_args(sdrm_engine* e, const float* logits, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows,
-                 const int64_t* rows, int64_t row0, int b, int n_items) {
-  NllArgs a{};
-  a.logits = logits; a.indptr = indptr; a.indices = indices; a.data = data; a.rows = rows; a.row0 = row0; a.n_rows = n_rows;
-  a.b = b; a.n_items = n_items; a.flag = e->feed_flag;
-  return a;
 }
 
 }  // namespace
@@ -2926,9 +2931,9 @@ int sdrm_multinomial_nll_csr(sdrm_engine* e, const float* logits, const int64_t*
                              int64_t n_rows, const int64_t* rows, int64_t row0, int b, int n_items, float* lse, float* loss, void* stream) {
   if (!e) return SDRM_ERR_ARG;
   if (!lse || !loss) return fail(e, SDRM_ERR_ARG, "sdrm_multinomial_nll_csr: null pointer");
-  if (int rc = check_nll(e, "sdrm_multinomial_nll_csr", logits, indptr, indices, n_rows, rows, row0, b, n_items)) return rc;
+  NllArgs a{};
+  if (int rc = nll_args(e, "sdrm_multinomial_nll_csr", logits, indptr, indices, data, n_rows, rows, row0, b, n_items, &a)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const NllArgs a = nll_args(e, logits, indptr, indices, data, n_rows, rows, row0, b, n_items);
   const int parts = std::min(b, NLL_PARTS);
   if (int rc = hip_rc(e, "k_nll_rows", profiled(e, PC_NLL, 0.0, st, [&] {
         SDRM_LAUNCH(e, k_nll_rows, dim3((unsigned)parts), dim3(256), 0, st, a, lse, e->nll_part);
@@ -2946,12 +2951,12 @@ int sdrm_multinomial_nll_csr_grad(sdrm_engine* e, const float* logits, const flo
   if (!e) return SDRM_ERR_ARG;
   if (!lse || !grad) return fail(e, SDRM_ERR_ARG, "sdrm_multinomial_nll_csr_grad: null pointer");
   if ((uintptr_t)grad & 15u) return fail(e, SDRM_ERR_ARG, "sdrm_multinomial_nll_csr_grad: grad must be 16-byte aligned");
-  if (int rc = check_nll(e, "sdrm_multinomial_nll_csr_grad", logits, indptr, indices, n_rows, rows, row0, b, n_items)) return rc;
+  NllArgs a{};
+  if (int rc = nll_args(e, "sdrm_multinomial_nll_csr_grad", logits, indptr, indices, data, n_rows, rows, row0, b, n_items, &a)) return rc;
   const uintptr_t lo = (uintptr_t)logits, go = (uintptr_t)grad, bytes = (uintptr_t)b * (uintptr_t)n_items * sizeof(float);
   if (lo != go && lo < go + bytes && go < lo + bytes)
     return fail(e, SDRM_ERR_ARG, "sdrm_multinomial_nll_csr_grad: grad overlaps logits (only grad == logits may alias)");
   hipStream_t st = (hipStream_t)stream;
-  const NllArgs a = nll_args(e, logits, indptr, indices, data, n_rows, rows, row0, b, n_items);
   return hip_rc(e, "k_nll_grad", profiled(e, PC_NLL, 0.0, st, [&] {
     SDRM_LAUNCH(e, k_nll_grad, dim3((unsigned)std::min(b, NLL_GRAD_BLOCKS)), dim3(256), 0, st, a, lse, scale, grad);
     return hipGetLastError();
@@ -2978,7 +2983,7 @@ int sdrm_debug_input_layer_args(int n_items, int hidden, int64_t n_rows, int64_t
 
 namespace {
 
-int il_grow(sdrm_engine* e, int slot, size_t n) { return grow_scratch(e, e->il_buf, e->il_cap, slot, n); }
+int il_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->il_buf[slot], &e->il_cap[slot], n); }
 
 DropArgs drop_args(uint64_t seed, uint32_t step, uint32_t thr) {
   DropArgs d;
@@ -2986,19 +2991,9 @@ DropArgs drop_args(uint64_t seed, uint32_t step, uint32_t thr) {
   return d;
 }
 
-extern "C++" template <class Args>
-hipError_t launch_input(sdrm_engine* e, void (*kernel)(const Args), dim3 grid, size_t lds, const Args& a, hipStream_t st) {
-  if (lds) {   // raised once per kernel and process, as allow_full_lds does; the kernel's static LDS (the chunk, 2 KB) comes on top
-    static std::mutex mu;
-    static std::set<const void*> done;
-    std::lock_guard<std::mutex> lock(mu);
-    const void* fn = reinterpret_cast<const void*>(kernel);
-    if (!done.count(fn)) {
-      const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX_BYTES - 4096);
-      if (rc != hipSuccess) return rc;
-      done.insert(fn);
-    }
-  }
+hipError_t launch_input_wgrad(sdrm_engine* e, void (*kernel)(const InputWgradArgs), dim3 grid, size_t lds, const InputWgradArgs& a, hipStream_t st) {
+  // the kernel's static LDS (the chunk, 2 KB) comes on top of the tile
+  if (const hipError_t rc = allow_full_lds(reinterpret_cast<const void*>(kernel), LDS_MAX_BYTES - 4096)) return rc;
   SDRM_LAUNCH(e, kernel, grid, dim3(256), lds, st, a);
   return hipGetLastError();
 }
@@ -3009,7 +3004,9 @@ int sdrm_vae_input_layer_fwd(sdrm_engine* e, const float* w1, const float* b1, i
                              const int32_t* indices, const float* data, int64_t n_rows, const int64_t* rows, int64_t row0, int b,
                              uint64_t seed, uint32_t step, float p_drop, float* pre, float* rowscale, void* stream) {
   if (!e) return SDRM_ERR_ARG;
-  if (!w1 || !b1 || !indptr || !indices || !pre || !rowscale) return fail(e, SDRM_ERR_ARG, "sdrm_vae_input_layer_fwd: null pointer");
+  if (!w1 || !b1 || !pre || !rowscale) return fail(e, SDRM_ERR_ARG, "sdrm_vae_input_layer_fwd: null pointer");
+  InputFwdArgs a{};
+  if (int rc = csr_batch(e, "sdrm_vae_input_layer_fwd", indptr, indices, data, n_rows, rows, row0, b, n_items, &a.csr)) return rc;
   uint32_t thr;
   float scale;
   if (int rc = sdrm_debug_input_layer_args(n_items, hidden, n_rows, row0, b, rows == nullptr, p_drop, &thr, &scale))
@@ -3023,15 +3020,10 @@ int sdrm_vae_input_layer_fwd(sdrm_engine* e, const float* w1, const float* b1, i
   SDRM_LAUNCH(e, k_encode_w1t, dim3((unsigned)((n_items + 31) / 32), (unsigned)((Hq + 31) / 32)), dim3(256), 0, st, w1, hidden, n_items,
               e->il_buf[sdrm_engine::IL_W1T], Hq);
   HIP_TRY(e, hipGetLastError());
-  InputFwdArgs a{};
-  a.indptr = indptr; a.indices = indices; a.data = data; a.rows = rows; a.row0 = row0; a.n_rows = n_rows; a.b = b; a.n_items = n_items;
-  a.flag = e->feed_flag; a.w1t = e->il_buf[sdrm_engine::IL_W1T]; a.b1 = b1; a.hidden = hidden; a.Hq = Hq;
+  a.w1t = e->il_buf[sdrm_engine::IL_W1T]; a.b1 = b1; a.hidden = hidden; a.Hq = Hq;
   a.drop = drop_args(seed, step, thr); a.scale = scale; a.pre = pre; a.rowscale = rowscale;
   return hip_rc(e, "k_input_fwd", profiled(e, PC_INPUT_LAYER, 0.0, st, [&] {
-    if (q <= 64) return launch_input(e, k_input_fwd<64, 1, 8>, dim3((unsigned)((b + 3) / 4)), 0, a, st);   // one wave per row
-    if (q <= 256) return launch_input(e, k_input_fwd<256, 1, 8>, dim3((unsigned)b), 0, a, st);              // one work-group per row
-    if (q <= 512) return launch_input(e, k_input_fwd<256, 2, 4>, dim3((unsigned)b), 0, a, st);
-    return launch_input(e, k_input_fwd<256, 4, 2>, dim3((unsigned)b), 0, a, st);
+    return launch_gather_rows(e, q, a, st, [](auto tpr, auto nv, auto u) { return k_input_fwd<VAL(tpr), VAL(nv), VAL(u)>; });
   }));
 }
 
@@ -3063,9 +3055,9 @@ int sdrm_vae_input_layer_wgrad(sdrm_engine* e, const float* dpre, const float* r
   // the LDS tile [16][ld]: ld = the pass's share of Hq + 4 floats (<= 131 KB at 2048 of them)
   const auto lds = [&](int span) { return (size_t)IL_CT * (size_t)(std::min(Hq, span) + 4) * sizeof(float); };
   return hip_rc(e, "k_input_wgrad", profiled(e, PC_INPUT_LAYER, 0.0, st, [&] {
-    if (q <= 64) return launch_input(e, k_input_wgrad<64, 1, 4>, dim3(tiles, 1), lds(256), a, st);      // one wave per column
-    if (q <= 256) return launch_input(e, k_input_wgrad<256, 1, 4>, dim3(tiles, 1), lds(1024), a, st);   // the work-group per column
-    return launch_input(e, k_input_wgrad<256, 2, 2>, dim3(tiles, (unsigned)((Hq + 2047) / 2048)), lds(2048), a, st);
+    if (q <= 64) return launch_input_wgrad(e, k_input_wgrad<64, 1, 4>, dim3(tiles, 1), lds(256), a, st);      // one wave per column
+    if (q <= 256) return launch_input_wgrad(e, k_input_wgrad<256, 1, 4>, dim3(tiles, 1), lds(1024), a, st);   // the work-group per column
+    return launch_input_wgrad(e, k_input_wgrad<256, 2, 2>, dim3(tiles, (unsigned)((Hq + 2047) / 2048)), lds(2048), a, st);
   }));
 }
 
@@ -3090,11 +3082,7 @@ int sdrm_holdout_split(sdrm_engine* e, const int64_t* indptr, const int32_t* ind
   if (int rc = sdrm_debug_holdout_args(n_items, n_rows, nnz, test_prop, 0, nullptr))
     return fail(e, rc, "sdrm_holdout_split: n_items outside 1 .. 2^20, n_rows outside 1 .. 2^31 - 1, nnz outside 0 .. 2^40 - 1 or test_prop outside (0, 1)");
   hipStream_t st = (hipStream_t)stream;
-  if ((size_t)n_rows > e->hold_cap) {
-    if (e->hold_cnt) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(e->hold_cnt)); e->hold_cnt = nullptr; e->hold_cap = 0; }
-    HIP_TRY(e, dalloc(&e->hold_cnt, 2 * (size_t)n_rows));
-    e->hold_cap = (size_t)n_rows;
-  }
+  if (int rc = grow(e, &e->hold_cnt, &e->hold_cap, 2 * (size_t)n_rows)) return rc;
   HoldoutArgs a{};
   a.indptr = indptr; a.indices = indices; a.n_rows = n_rows; a.nnz = nnz; a.n_items = n_items; a.test_prop = test_prop;
   a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.draw = draw; a.cnt = e->hold_cnt;
@@ -3145,11 +3133,7 @@ int sdrm_equal_sparsity_csr_begin(sdrm_engine* e, const float* x, int64_t n_rows
   e->csr.active = false;   // a second begin replaces a pending one
   const size_t words = (size_t)(n_rows * wpr), off_ptr = words, off_cnt = off_ptr + (size_t)n_rows + 1;
   const size_t need = off_cnt + ((size_t)n_rows + 1) / 2;
-  if (need > e->csr_ws_cap) {
-    if (e->csr_ws) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(e->csr_ws)); e->csr_ws = nullptr; e->csr_ws_cap = 0; }
-    HIP_TRY(e, dalloc(&e->csr_ws, need));
-    e->csr_ws_cap = need;
-  }
+  if (int rc = grow(e, &e->csr_ws, &e->csr_ws_cap, need)) return rc;
   if (!e->csr_nnz_host) {
     HIP_TRY(e, hipHostMalloc((void**)&e->csr_nnz_host, sizeof(int64_t), hipHostMallocMapped));
     HIP_TRY(e, hipHostGetDevicePointer((void**)&e->csr_nnz_dev, e->csr_nnz_host, 0));

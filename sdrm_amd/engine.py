@@ -111,6 +111,20 @@ class Engine:
             t = torch.from_numpy(np.ascontiguousarray(a)).to(device=self.device, dtype=dtype)
         return t.contiguous()
 
+    def _csr_batch(self, who, csr_dev, rows, row0, b):
+        """A batch of rows of a `csr_to_device` matrix, `rows` (int64, moved to the device) or row0 .. row0+b-1, as the C ABI takes
+        it: (n_rows, n_items, b, the seven leading arguments indptr, indices, data, n_rows, rows, row0, b)."""
+        indptr, indices, data, (n_rows, n_items) = csr_dev
+        if rows is not None:
+            rows = self._dev(rows, torch.int64)
+            b = rows.numel()
+        elif b is None:
+            raise SdrmError(f"{who}: give `rows` or `row0` and `b`")
+        if indices.numel() == 0:   # a matrix without an entry: torch gives an empty tensor no address, and the C ABI takes no null array
+            indices = indices.new_zeros(1)
+        self._feed_keep = (rows, indices)   # what this call made itself, alive until the launch is issued
+        return int(n_rows), int(n_items), int(b), (_ptr(indptr), _ptr(indices), _ptr(data), int(n_rows), _ptr(rows), int(row0), int(b))
+
     def debug_set(self, tile=None, skinny=None, fused_reverse=None, chains=None, nt32_rows=None, nt32_rows_train=None,
                   gradient_buckets=None, rowchain=None, wgrad_strips=None, dgrad_rows=None, rows48=None, rows48_split=None, sample_persist=None, rows48_share=None):
         """Test / tuning hooks of THIS engine (include/sdrm_hip_debug.h): force a GEMM tile shape (-1 = automatic),
@@ -558,47 +572,34 @@ class Engine:
         """The same z straight from the rows `rows` (or row0 .. row0+b-1) of a `csr_to_device` matrix: the first Linear is a gather
         of W1's columns, no dense batch exists.  Range checks and `check` as in `csr_rows_to_dense`."""
         n_items, _, latent = self._encoder_dims("sdrm_vae_encode_csr")
-        indptr, indices, data, (n_rows, width) = csr_dev
+        _, width, b, batch = self._csr_batch("vae_encode_csr", csr_dev, rows, row0, b)
         if width != n_items:
             raise SdrmError(f"sdrm_vae_encode_csr: SDRM_ERR_SHAPE: the matrix has {width} columns, the encoder {n_items}")
-        if rows is not None:
-            rows = self._dev(rows, torch.int64)
-            b = rows.numel()
-        elif b is None:
-            raise SdrmError("vae_encode_csr: give `rows` or `row0` and `b`")
         z = torch.empty(b, latent, dtype=torch.float32, device=self.device)
         kl = self._kl_out(return_kl)
-        self._check(self.lib.sdrm_vae_encode_csr(self._h, _ptr(indptr), _ptr(indices), _ptr(data), int(n_rows), _ptr(rows), int(row0), int(b),
-                                                 _ptr(z), _ptr(kl), _stream()), "sdrm_vae_encode_csr")
+        self._check(self.lib.sdrm_vae_encode_csr(self._h, *batch, _ptr(z), _ptr(kl), _stream()), "sdrm_vae_encode_csr")
         if check:
             self.feed_status()
         return (z, kl) if return_kl else z
 
     # ------------------------------------------------------------------ loss head of the VAE pre-stage (csrc/nll.h)
-    def _nll_batch(self, who, logits, csr_dev, rows, b):
-        indptr, indices, data, (n_rows, n_items) = csr_dev
+    def _nll_batch(self, who, logits, csr_dev, rows, row0, b):
         if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.device != self.device or not logits.is_contiguous():
             raise SdrmError(f"{who}: logits must be a contiguous float32 tensor on the engine's device")
-        if rows is not None:
-            rows = self._dev(rows, torch.int64)
-            b = rows.numel()
-        elif b is None:
-            raise SdrmError(f"{who}: give `rows` or `row0` and `b`")
+        _, n_items, b, batch = self._csr_batch(who, csr_dev, rows, row0, b)
         if logits.dim() != 2 or tuple(logits.shape) != (b, n_items):
             raise SdrmError(f"{who}: SDRM_ERR_SHAPE: logits must be [{b},{n_items}], got {tuple(logits.shape)}")
-        if indices.numel() == 0:   # a matrix without an entry: torch gives an empty tensor no address, and the C ABI takes no null array
-            indices = indices.new_zeros(1)
-        return indptr, indices, data, int(n_rows), int(n_items), rows, int(b)
+        return n_items, b, batch
 
     def multinomial_nll_csr(self, logits, csr_dev, rows=None, row0=0, b=None, check=True):
         """train_SDRM.py:141-142 on the device, `-mean(sum(log_softmax(logits) * X))` for the X whose rows are the rows `rows` (or
         row0 .. row0+b-1) of a `csr_to_device` matrix: (loss 0-d float32, lse [b] float32) as device tensors; no dense X exists and
         nothing is read back.  Range checks and `check` as in `csr_rows_to_dense`."""
-        indptr, indices, data, n_rows, n_items, rows, b = self._nll_batch("multinomial_nll_csr", logits, csr_dev, rows, b)
+        n_items, b, batch = self._nll_batch("multinomial_nll_csr", logits, csr_dev, rows, row0, b)
         lse = torch.empty(b, dtype=torch.float32, device=self.device)
         loss = torch.empty((), dtype=torch.float32, device=self.device)
-        self._check(self.lib.sdrm_multinomial_nll_csr(self._h, _ptr(logits), _ptr(indptr), _ptr(indices), _ptr(data), n_rows, _ptr(rows), int(row0),
-                                                      b, n_items, _ptr(lse), _ptr(loss), _stream()), "sdrm_multinomial_nll_csr")
+        self._check(self.lib.sdrm_multinomial_nll_csr(self._h, _ptr(logits), *batch, n_items, _ptr(lse), _ptr(loss), _stream()),
+                    "sdrm_multinomial_nll_csr")
         if check:
             self.feed_status()
         return loss, lse
@@ -607,7 +608,7 @@ class Engine:
         """Its gradient with respect to the logits, `scale * (softmax(logits) * X.sum(1) - X) / b` [b, n_items], from the `lse` the
         forward returned.  `scale`: a float32 device tensor of one element (the upstream gradient; None = 1).  `out=logits` writes it
         in place of the logits; any other `out` must not overlap them.  The range checks land in the status word `feed_status` reads."""
-        indptr, indices, data, n_rows, n_items, rows, b = self._nll_batch("multinomial_nll_csr_grad", logits, csr_dev, rows, b)
+        n_items, b, batch = self._nll_batch("multinomial_nll_csr_grad", logits, csr_dev, rows, row0, b)
         for name, t, n in (("lse", lse, b), ("scale", scale, 1)):
             if t is not None and (t.dtype != torch.float32 or t.device != self.device or t.numel() != n or not t.is_contiguous()):
                 raise SdrmError(f"multinomial_nll_csr_grad: {name} must be a contiguous float32 device tensor of {n} element(s)")
@@ -615,8 +616,7 @@ class Engine:
             out = torch.empty_like(logits)
         elif out.dtype != torch.float32 or out.device != self.device or out.shape != logits.shape or not out.is_contiguous():
             raise SdrmError("multinomial_nll_csr_grad: out must be a contiguous float32 device tensor of the logits' shape")
-        self._check(self.lib.sdrm_multinomial_nll_csr_grad(self._h, _ptr(logits), _ptr(lse), _ptr(indptr), _ptr(indices), _ptr(data), n_rows,
-                                                           _ptr(rows), int(row0), b, n_items, _ptr(scale), _ptr(out), _stream()),
+        self._check(self.lib.sdrm_multinomial_nll_csr_grad(self._h, _ptr(logits), _ptr(lse), *batch, n_items, _ptr(scale), _ptr(out), _stream()),
                     "sdrm_multinomial_nll_csr_grad")
         return out
 
@@ -639,24 +639,17 @@ class Engine:
         `nn.Linear` holds them.  The dropout bits are the engine's Philox draws of (seed, step, feed row, column), not torch's.
         Range checks and `check` as in `csr_rows_to_dense`."""
         who = "vae_input_layer_fwd"
-        indptr, indices, data, (n_rows, n_items) = csr_dev
+        _, n_items, b, batch = self._csr_batch(who, csr_dev, rows, row0, b)
         if not isinstance(w1, torch.Tensor) or w1.dim() != 2:
             raise SdrmError(f"{who}: w1 must be a 2-D tensor [hidden, n_items]")
         hidden = int(w1.shape[0])
         w1 = self._f32(who, "w1", w1, (hidden, n_items))
         b1 = self._f32(who, "b1", b1, (hidden,))
-        if rows is not None:
-            rows = self._dev(rows, torch.int64)
-            b = rows.numel()
-        elif b is None:
-            raise SdrmError(f"{who}: give `rows` or `row0` and `b`")
-        if indices.numel() == 0:   # a matrix without an entry: torch gives an empty tensor no address
-            indices = indices.new_zeros(1)
-        pre = torch.empty(int(b), hidden, dtype=torch.float32, device=self.device)
-        rowscale = torch.empty(int(b), dtype=torch.float32, device=self.device)
-        self._check(self.lib.sdrm_vae_input_layer_fwd(self._h, _ptr(w1), _ptr(b1), int(n_items), hidden, _ptr(indptr), _ptr(indices), _ptr(data),
-                                                      int(n_rows), _ptr(rows), int(row0), int(b), int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF,
-                                                      float(p_drop), _ptr(pre), _ptr(rowscale), _stream()), "sdrm_vae_input_layer_fwd")
+        pre = torch.empty(b, hidden, dtype=torch.float32, device=self.device)
+        rowscale = torch.empty(b, dtype=torch.float32, device=self.device)
+        self._check(self.lib.sdrm_vae_input_layer_fwd(self._h, _ptr(w1), _ptr(b1), n_items, hidden, *batch, int(seed) & (2 ** 64 - 1),
+                                                      int(step) & 0xFFFFFFFF, float(p_drop), _ptr(pre), _ptr(rowscale), _stream()),
+                    "sdrm_vae_input_layer_fwd")
         if check:
             self.feed_status()
         return pre, rowscale
@@ -716,21 +709,15 @@ class Engine:
         Row ids and column indices are range-checked ON THE DEVICE (an offending row / entry stays zero, never a stray store);
         `check=True` reads the verdict back at once (one stream sync) and raises, `check=False` leaves it to a later
         `feed_status()` - what an epoch loop wants (`pipeline.DeviceFeed` asks once per epoch)."""
-        indptr, indices, data, (n_rows, n_items) = csr_dev
-        if rows is not None:
-            rows = self._dev(rows, torch.int64)
-            b = rows.numel()
-        elif b is None:
-            raise SdrmError("csr_rows_to_dense: give `rows` or `row0` and `b`")
+        _, n_items, b, batch = self._csr_batch("csr_rows_to_dense", csr_dev, rows, row0, b)
         out = torch.empty(b, n_items, dtype=torch.float32, device=self.device)
-        self._check(self.lib.sdrm_csr_rows_to_dense(self._h, _ptr(indptr), _ptr(indices), _ptr(data), int(n_rows), _ptr(rows), int(row0),
-                                                    int(b), int(n_items), _ptr(out), _stream()), "sdrm_csr_rows_to_dense")
+        self._check(self.lib.sdrm_csr_rows_to_dense(self._h, *batch, n_items, _ptr(out), _stream()), "sdrm_csr_rows_to_dense")
         if check:
             self.feed_status()
         return out
 
     def feed_status(self):
-        """Raises if any `csr_rows_to_dense` launch since the last call met a row id / column index outside the matrix."""
+        """Raises if any launch on the CSR feed since the last call met a row id, column index or indptr pair outside the matrix."""
         self._check(self.lib.sdrm_feed_status(self._h, _stream()), "sdrm_feed_status")
 
     def holdout_split(self, csr_dev, test_prop=0.2, seed=0, draw=0, check=True, out=None):

@@ -107,3 +107,58 @@ def test_out_of_range_csr_is_caught_on_the_device_not_written_out_of_bounds(engi
         engine.feed_status()
     good = engine.csr_rows_to_dense((indptr, indices, data, shape), row0=0, b=12).cpu().numpy()
     np.testing.assert_array_equal(good, dense)
+
+
+@pytest.mark.gpu
+def test_a_matrix_without_entries_goes_through_every_feed_entry(engine):
+    """A `csr_to_device` matrix with nnz = 0 has an empty `indices` tensor, to which torch gives no address: every entry point on the
+    feed takes it all the same, and delivers what a batch of empty rows is - zeros, the bias, a loss of zero."""
+    from vae_encode_ref import rel_l2, rel_max
+    from test_vae_encode import TOL
+    n_rows, n_items, hidden = 5, 70, 24
+    empty = engine.csr_to_device(csr_matrix((n_rows, n_items), dtype=np.float32))
+    assert empty[1].numel() == 0
+    dense = engine.csr_rows_to_dense(empty, row0=0, b=n_rows, check=False)
+    assert dense.shape == (n_rows, n_items) and not dense.any()
+    # train-mode input layer: the accumulator is +0 and fmaf(0, rs, b) is b; the norm is 0, so rowscale = scale / 1e-12 in float32
+    w1, b1, w2, b2 = tensors = synth.synth_vae_encoder(n_items, hidden, 6, seed=51)
+    b1_d = torch.from_numpy(b1).cuda()
+    pre, rowscale = engine.vae_input_layer_fwd(torch.from_numpy(w1).cuda(), b1_d, empty, row0=0, b=n_rows, seed=3, step=1, p_drop=0.5, check=False)
+    assert torch.equal(pre.view(torch.int32), b1_d.expand(n_rows, hidden).contiguous().view(torch.int32))
+    want_rs = np.float32(1.0 / (1.0 - 0.5)) / np.float32(1e-12)
+    assert want_rs == np.float32(2.0 / 1e-12)
+    np.testing.assert_array_equal(rowscale.cpu().numpy(), np.full(n_rows, want_rs, np.float32))
+    # loss head: no entry, no term; lse does not read the CSR
+    logits = torch.from_numpy(np.random.RandomState(52).standard_normal((n_rows, n_items)).astype(np.float32)).cuda()
+    full = engine.csr_to_device(synth.synth_feed_csr(n_rows, n_items, 0.2, seed=53))
+    loss, lse = engine.multinomial_nll_csr(logits, empty, row0=0, b=n_rows, check=False)
+    _, lse_full = engine.multinomial_nll_csr(logits, full, row0=0, b=n_rows, check=False)
+    assert float(loss) == 0.0
+    assert torch.equal(lse.view(torch.int32), lse_full.view(torch.int32))
+    # frozen encode hook: the CSR form against the dense form of a zero batch
+    engine.vae_encoder_load(*tensors)
+    z_csr = engine.vae_encode_csr(empty, row0=0, b=n_rows, check=False).cpu().numpy()
+    z_dense = engine.vae_encode(torch.zeros(n_rows, n_items)).cpu().numpy()
+    print(f"empty matrix, csr vs dense encode: rel_max {rel_max(z_csr, z_dense):.2e} rel_l2 {rel_l2(z_csr, z_dense):.2e}")
+    assert rel_max(z_csr, z_dense) <= TOL and rel_l2(z_csr, z_dense) <= TOL
+    engine.feed_status()   # nothing was raised
+
+
+@pytest.mark.gpu
+def test_rows_or_row0_and_b(engine):
+    """Each method that takes a batch of the feed, called with neither `rows` nor `b`, says so under its own name."""
+    from sdrm_amd.engine import SdrmError
+    dev = engine.csr_to_device(csr_matrix(np.eye(5, dtype=np.float32)))
+    logits = torch.zeros(5, 5, device="cuda")
+    w1, b1, w2, b2 = (torch.from_numpy(t).cuda() for t in synth.synth_vae_encoder(5, 8, 2, seed=61))
+    engine.vae_encoder_load(w1, b1, w2, b2)
+    calls = {
+        "csr_rows_to_dense": lambda: engine.csr_rows_to_dense(dev),
+        "vae_encode_csr": lambda: engine.vae_encode_csr(dev),
+        "multinomial_nll_csr": lambda: engine.multinomial_nll_csr(logits, dev),
+        "multinomial_nll_csr_grad": lambda: engine.multinomial_nll_csr_grad(logits, torch.zeros(5, device="cuda"), dev),
+        "vae_input_layer_fwd": lambda: engine.vae_input_layer_fwd(w1, b1, dev),
+    }
+    for name, call in calls.items():
+        with pytest.raises(SdrmError, match=rf"\b{name}: give `rows` or `row0` and `b`"):
+            call()
