@@ -386,6 +386,39 @@ int sdrm_vae_input_layer_fwd(sdrm_engine* e, const float* w1, const float* b1, i
 int sdrm_vae_input_layer_wgrad(sdrm_engine* e, const float* dpre, const float* rowscale, int hidden, const int64_t* colptr,
                                const int32_t* rowidx, const float* data, int64_t n_rows, int n_items, const int32_t* pos, int64_t lo,
                                int b, uint64_t seed, uint32_t step, float p_drop, float* dw1, void* stream);
+/* The VAE encoder BEHIND its first pre-activation in TRAIN mode, both directions (reference: train_SDRM.py:244-250 with is_training == 1 -
+ * the Tanh and the second Linear of `self.encoder`, `chunk`, the KL line and `mu + eps * exp(0.5 * logvar)` - and their share of :148).
+ * It takes the `pre` that sdrm_vae_input_layer_fwd left; float32 throughout, L = latent, H = hidden, R_r the feed row of batch row r:
+ *   h1   = tanh(pre)                                    [b, H]
+ *   out2 = h1 W2^T + b2 = [mu | lv]                     [b, 2L]      W2 [2L, H], b2 [2L] as nn.Linear stores them
+ *   eps[r, j] = normal j & 3 of the column quad j >> 2: words = Philox4x32-10 with counter (R_r, j >> 2, 9, step) and key `seed`
+ *          (csrc/philox.h, PURPOSE_VAE_EPS); (n0, n1) = box_muller(x, y), (n2, n3) = box_muller(z, w)
+ *   z    = mu + eps exp(0.5 lv)                         [b, L]
+ *   kl   = -0.5 / b sum_r sum_j (lv - mu^2 - expm1(lv))  fp32 terms summed in float64 in a fixed order (per-work-group partials, then
+ *          one work-group): no floating-point atomic
+ *   dmu  = gz + gkl mu / b        dlv = 0.5 gz eps exp(0.5 lv) + 0.5 gkl expm1(lv) / b        dout2 = [dmu | dlv]
+ *   dW2  = dout2^T h1             db2 = sum_r dout2[r, :]                                      dpre  = (dout2 W2) (1 - h1^2)
+ * The draw depends on (seed, step, R_r, j) alone - not on where the row sits in a batch, on the batch size or on torch's generator.
+ * sdrm_vae_latent_fwd: pre [b, hidden], w2 [2 latent, hidden], b2 [2 latent] contiguous (device, read by this call: W2 and b2 are
+ *   padded into scratch of the handle on EVERY call, they change with every optimiser step; an encoder staged by
+ *   sdrm_vae_encoder_load is not touched).  rows: int64 device array [b] of feed rows, or null for row0 .. row0 + b - 1; it names the
+ *   rows for the Philox counter only - no feed is read.  draw != 0: eps [b, latent] is drawn and WRITTEN; draw == 0: eps is an INPUT
+ *   and is not written (how tests, and callers who want torch's draws, inject their own; rows, row0, seed and step are then unused).
+ *   Out, all caller-owned and contiguous: h1 [b, hidden], out2 [b, 2 latent], eps, z [b, latent], kl (one device float).  The
+ *   backward takes h1, out2 and eps from the caller, so two forwards may precede their backwards.
+ * sdrm_vae_latent_bwd: h1, out2, eps as a forward left them, w2 as that forward read it; gz [b, latent] and gkl (ONE device float),
+ *   the upstream gradients of z and kl - either may be null, which means zero.  Out: dpre [b, hidden], dw2 [2 latent, hidden], db2
+ *   [2 latent] contiguous, EVERY element written exactly once: no memset, no atomic, the same bits from call to call.
+ * Launches: 4 forward (staging, GEMM, reparameterisation + KL partials, KL sum), 5 backward (staging, seed, weight-gradient GEMM,
+ * dgrad GEMM, unpadding); the GEMMs are csrc/gemm.h's fp32 MFMA family and follow sdrm_debug_set_tile.
+ * Envelope (SDRM_ERR_SHAPE otherwise): 1 <= hidden <= 4096, 1 <= latent <= 4096, 1 <= b <= 2^22, feed rows in [0, 2^31) (row0 .. row0
+ * + b - 1 is checked on the host; an id of `rows` outside that range raises the feed status word's row bit, sdrm_feed_status, and its
+ * counter is the id's low 32 bits).  A null required pointer is SDRM_ERR_ARG.  Neither call synchronises or reads back. */
+int sdrm_vae_latent_fwd(sdrm_engine* e, const float* pre, const float* w2, const float* b2, int hidden, int latent, const int64_t* rows,
+                        int64_t row0, int b, uint64_t seed, uint32_t step, int draw, float* h1, float* out2, float* eps, float* z, float* kl,
+                        void* stream);
+int sdrm_vae_latent_bwd(sdrm_engine* e, const float* h1, const float* out2, const float* eps, const float* w2, int hidden, int latent, int b,
+                        const float* gz, const float* gkl, float* dpre, float* dw2, float* db2, void* stream);
 /* Per-user hold-out split on the device, CSR in, two CSRs out (reference: utilities.py:174-236,
  * split_train_test_proportion_from_csr_matrix with ignore_zeros=False, which train_SDRM.py:161 calls once per pre-stage epoch): of
  * the n stored entries of a user with n >= 2, m = ceil(test_prop * n) chosen uniformly without replacement go to the held-out

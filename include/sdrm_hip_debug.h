@@ -30,6 +30,11 @@ int sdrm_debug_device_check(const char* gcn_arch, int compute_units);
 int sdrm_debug_input_layer_args(int n_items, int hidden, int64_t n_rows, int64_t first, int b, int contiguous, float p_drop,
                                 uint32_t* thr, float* scale);
 
+/* What sdrm_vae_latent_fwd / _bwd check on the host before any launch: SDRM_ERR_SHAPE outside their envelope (1 <= hidden <= 4096,
+ * 1 <= latent <= 4096, 1 <= b <= 2^22; `contiguous` != 0, the forward without a `rows` array: the feed rows row0 .. row0 + b - 1 must
+ * lie in [0, 2^31)), else SDRM_OK.  Pure function: callable without a GPU. */
+int sdrm_debug_latent_args(int hidden, int latent, int b, int64_t row0, int contiguous);
+
 /* What sdrm_holdout_split checks and derives on the host before any launch: SDRM_ERR_SHAPE outside its envelope (1 <= n_items <=
  * 2^20, 1 <= n_rows < 2^31, 0 <= nnz < 2^40, 0 < test_prop < 1), else SDRM_OK with the held-out count of a row of n_u entries,
  * n_u < 2 ? 0 : min(n_u, (int64)ceil(test_prop * (double)n_u)), in *m_out (may be NULL).  Pure function: callable without a GPU. */

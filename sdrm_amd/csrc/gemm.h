@@ -55,9 +55,11 @@ enum : int {
   EPI_BIAS_G = 7,        // C = acc + bias[n], bounds-checked into an unpadded caller buffer (VAE decode output layer)
   EPI_BIAS_ROWTAB = 9,   // C = acc + tab[t(row)][n]: layer 0 of the train step, whose bias + time-embedding term b0 + C0[t] is a
                          // row of the per-step table B0tab picked by the row's timestep (the stacked passes P, S, Q share t)
-  EPI_BIAS_PRELU = 10    // C = prelu(acc + bias[n]; slopeE): the sampler's hidden layers store the ACTIVATION - nothing reads their
+  EPI_BIAS_PRELU = 10,   // C = prelu(acc + bias[n]; slopeE): the sampler's hidden layers store the ACTIVATION - nothing reads their
                          // pre-activations again (no backward), and the next layer then loads its operand without the PReLU-on-load
                          // transform, which costs the 5429-row launches ~1.5 us each (12.7 us plain against 16 us with it)
+  EPI_DTANH_G = 11       // C = acc * (1 - aux^2), bounds-checked into an unpadded caller buffer: the dgrad through a stored tanh
+                         // ACTIVATION aux (csrc/latent.h: d loss / d pre of the VAE encoder's hidden layer)
 };
 
 constexpr int NTHREADS = 256;
@@ -775,6 +777,16 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
         for (int r = 0; r < NR; ++r) {
           const int row = rbase + rowoff(r);
           if (row < p.rows_valid && col < p.cols_valid) Cp[(size_t)row * p.ldc + col] = acc[a][b][r] + bias;
+        }
+      } else if (EPI == EPI_DTANH_G) {
+        const float* __restrict__ auxp = p.aux;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          const int row = rbase + rowoff(r);
+          if (row < p.rows_valid && col < p.cols_valid) {
+            const float h = auxp[(size_t)row * p.ldaux + col];
+            Cp[(size_t)row * p.ldc + col] = acc[a][b][r] * fmaf(-h, h, 1.f);
+          }
         }
       } else if (EPI == EPI_DPRELU) {
         const float* __restrict__ auxp = p.aux;

@@ -25,6 +25,7 @@
 #include "gemm.h"
 #include "holdout.h"
 #include "input_layer.h"
+#include "latent.h"
 #include "nll.h"
 #include "rank.h"
 #include "rowchain.h"
@@ -144,6 +145,8 @@ struct ChainSched {
   bool hold_marked = false;    // ev_hold is recorded behind its weight gradients
 };
 
+constexpr int PROF_SLOTS = 32;   // room for the profile classes (ProfClass below holds PC_COUNT to it)
+
 struct sdrm_engine {
   int L, W, T, H, max_rows, device;
   Tuning tune;
@@ -228,6 +231,12 @@ struct sdrm_engine {
   enum { IL_W1T = 0, IL_DPRE, IL_BUFS };
   float* il_buf[IL_BUFS] = {};       // this call's W1^T [items][Hq] | dpre padded to [b][Hq] (hidden off the 16-byte grid only)
   size_t il_cap[IL_BUFS] = {};
+  // grow-only scratch of the train-mode latent head (csrc/latent.h): this call's operands, nothing of a loaded encoder or of a forward
+  // that still waits for its backward (h1, out2, eps are the caller's)
+  enum { LAT_H = 0, LAT_W2, LAT_B2, LAT_W2T, LAT_DOUT2, LAT_SLAB, LAT_DBIAS, LAT_BUFS };
+  float* lat_buf[LAT_BUFS] = {};     // h1 [MP][Hp] | W2 [L2r][Hp], b2 [L2r] | W2^T [Hr][L2p] | dout2 [MP][L2p] | weight-gradient slabs [S][L2p][Hp], bias sums [S][L2p]
+  size_t lat_cap[LAT_BUFS] = {};
+  double* lat_part = nullptr;        // partial sums of its kl (k_latent_reparam), [ENC_KL_PARTS]
   uint32_t* hold_cnt = nullptr;      // grow-only scratch of sdrm_holdout_split (csrc/holdout.h): [2][rows] entries n_u and held entries m_u of every row
   size_t hold_cap = 0;               // in elements
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
@@ -252,16 +261,17 @@ struct sdrm_engine {
   std::vector<hipEvent_t> prof_ev;      // 2 per recorded launch
   std::vector<int> prof_cls;
   std::vector<double> prof_flops;
-  double prof_ms[16] = {0};
-  double prof_fl[16] = {0};
-  int64_t prof_n[16] = {0};
+  double prof_ms[PROF_SLOTS] = {0};
+  double prof_fl[PROF_SLOTS] = {0};
+  int64_t prof_n[PROF_SLOTS] = {0};
   std::string err;
 };
 
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_COUNT };
+static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
     "train: gemm_kernel<0,0,0,0,9> fwd layer0 (row-table bias)", "train: gemm_kernel<0,0,1,0,0> fwd hidden (prelu-in, bias)",
@@ -277,7 +287,8 @@ static const char* kProfNames[PC_COUNT] = {
     "sample: k_sample_persist reverse steps without kernel boundaries (all layers + reverse update per step, row tiles synchronised through one XCD's L2)",
     "loss head: k_nll_rows / k_nll_grad multinomial NLL of logits against CSR rows and its gradient (one work-group per row, HBM-bound)",
     "input layer: k_input_fwd / k_input_wgrad train-mode first Linear of the VAE encoder from CSR rows and its weight gradient from CSC columns",
-    "hold-out: k_holdout_counts / k_holdout_scan / k_holdout_split per-user hold-out split of a CSR matrix into two (keys ranked per row, a wave or a work-group per row)"};
+    "hold-out: k_holdout_counts / k_holdout_scan / k_holdout_split per-user hold-out split of a CSR matrix into two (keys ranked per row, a wave or a work-group per row)",
+    "latent head: k_latent_stage / gemm_kernel<0,0,0,0,7> / k_latent_reparam forward, k_latent_stage_bwd / k_latent_seed / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / k_latent_unpad backward of the VAE encoder behind its first pre-activation in train mode"};
 
 namespace {
 
@@ -1586,6 +1597,9 @@ int sdrm_destroy(sdrm_engine* e) {
   if (e->nll_part) (void)hipFree(e->nll_part);
   for (float* b : e->il_buf)
     if (b) (void)hipFree(b);
+  for (float* b : e->lat_buf)
+    if (b) (void)hipFree(b);
+  if (e->lat_part) (void)hipFree(e->lat_part);
   if (e->hold_cnt) (void)hipFree(e->hold_cnt);
   if (e->csr_ws) (void)hipFree(e->csr_ws);
   if (e->csr_nnz_host) (void)hipHostFree(e->csr_nnz_host);
@@ -2907,6 +2921,150 @@ int sdrm_vae_encode_csr(sdrm_engine* e, const int64_t* indptr, const int32_t* in
 }
 
 // ---------------------------------------------------------------------------------------------
+// The VAE encoder behind its first pre-activation in TRAIN mode (train_SDRM.py:244-250 with is_training == 1: Tanh, the second Linear,
+// chunk, the KL, the reparameterisation; and their share of :148), csrc/latent.h.  The frozen encoder above is not touched.
+constexpr int LATENT_MAX_HIDDEN = 4096, LATENT_MAX_LATENT = 4096;
+constexpr int LATENT_WGRAD_KCHUNK = 8192;   // most batch rows of one weight-gradient slab (the pre-stage's batches are a few hundred: one slab)
+
+// The host side of both entry points that needs no device: the envelope (`contiguous` != 0: the feed rows are row0 .. row0 + b - 1).
+int sdrm_debug_latent_args(int hidden, int latent, int b, int64_t row0, int contiguous) {
+  if (hidden < 1 || hidden > LATENT_MAX_HIDDEN || latent < 1 || latent > LATENT_MAX_LATENT || b < 1 || b > (1 << 22)) return SDRM_ERR_SHAPE;
+  if (contiguous && (row0 < 0 || row0 + b > ((int64_t)1 << 31))) return SDRM_ERR_SHAPE;
+  return SDRM_OK;
+}
+
+namespace {
+
+int lat_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->lat_buf[slot], &e->lat_cap[slot], n); }
+
+// padded extents: K and N of the GEMMs to 32, operand rows to the largest tile (128), the batch to 64 (the launches' M)
+struct LatDims { int Hp, Hr, L2, L2p, L2r, MP, rows64; };
+LatDims lat_dims(int hidden, int latent, int b) {
+  LatDims d;
+  d.Hp = round_up(hidden, 32); d.Hr = round_up(d.Hp, 128);
+  d.L2 = 2 * latent; d.L2p = round_up(d.L2, 32); d.L2r = round_up(d.L2p, 128);
+  d.MP = round_up(b, 128); d.rows64 = round_up(b, BM);
+  return d;
+}
+
+unsigned lat_blocks(int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (items + 255) / 256)); }
+
+const char* const kLatentEnvelope = ": hidden outside 1 .. 4096, latent outside 1 .. 4096, b outside 1 .. 2^22, or feed rows row0 .. row0 + b - 1 "
+                                    "outside [0, 2^31)";
+
+}  // namespace
+
+int sdrm_vae_latent_fwd(sdrm_engine* e, const float* pre, const float* w2, const float* b2, int hidden, int latent, const int64_t* rows,
+                        int64_t row0, int b, uint64_t seed, uint32_t step, int draw, float* h1, float* out2, float* eps, float* z, float* kl,
+                        void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!pre || !w2 || !b2 || !h1 || !out2 || !eps || !z || !kl) return fail(e, SDRM_ERR_ARG, "sdrm_vae_latent_fwd: null pointer");
+  if (int rc = sdrm_debug_latent_args(hidden, latent, b, row0, rows == nullptr)) return fail(e, rc, std::string("sdrm_vae_latent_fwd") + kLatentEnvelope);
+  hipStream_t st = (hipStream_t)stream;
+  if (int jr = chains_join(e, st)) return jr;
+  const LatDims d = lat_dims(hidden, latent, b);
+  int rc;
+  if ((rc = lat_grow(e, sdrm_engine::LAT_H, (size_t)d.MP * d.Hp)) || (rc = lat_grow(e, sdrm_engine::LAT_W2, (size_t)d.L2r * d.Hp)) ||
+      (rc = lat_grow(e, sdrm_engine::LAT_B2, d.L2r)))
+    return rc;
+  if (!e->lat_part) HIP_TRY(e, dalloc(&e->lat_part, ENC_KL_PARTS));
+  // 1: h1 = tanh(pre) into the caller's buffer and the padded operand; W2 and b2 padded (they change with every optimiser step)
+  LatentStageArgs sa{};
+  sa.pre = pre; sa.h1 = h1; sa.hp = e->lat_buf[sdrm_engine::LAT_H]; sa.b = b; sa.H = hidden; sa.MP = d.MP; sa.Hp = d.Hp;
+  sa.w2 = w2; sa.w2p = e->lat_buf[sdrm_engine::LAT_W2]; sa.L2 = d.L2; sa.L2r = d.L2r;
+  sa.b2 = b2; sa.b2p = e->lat_buf[sdrm_engine::LAT_B2];
+  if ((rc = hip_rc(e, "k_latent_stage", profiled(e, PC_LATENT, 0.0, st, [&] {
+         SDRM_LAUNCH(e, k_latent_stage, dim3(lat_blocks((int64_t)std::max(d.MP, d.L2r) * (d.Hp / 4)), 3), dim3(256), 0, st, sa);
+         return hipGetLastError();
+       }))))
+    return rc;
+  // 2: out2 = h1 W2^T + b2, bounds-checked into the caller's [b][2L]
+  {
+    GemmArgs a{};
+    a.C = out2; a.ldc = d.L2; a.bias = e->lat_buf[sdrm_engine::LAT_B2];
+    a.rows_valid = b; a.cols_valid = d.L2;
+    HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, e->lat_buf[sdrm_engine::LAT_H], d.Hp, e->lat_buf[sdrm_engine::LAT_W2], d.Hp, d.rows64, d.L2p,
+                                                   d.Hp, st, Prof{e, PC_LATENT, 2.0 * b * d.L2 * hidden},
+                                                   choose_cfg(e->tune, d.rows64, e->tune.nt32_max_rows))));
+  }
+  // 3: the draw, z and the KL partials; 4: their sum
+  const int parts = std::min(b, ENC_KL_PARTS);
+  LatentReparamArgs ra{};
+  ra.out2 = out2; ra.rows = rows; ra.row0 = row0; ra.b = b; ra.L = latent;
+  ra.k0 = (uint32_t)seed; ra.k1 = (uint32_t)(seed >> 32); ra.step = step; ra.draw = draw;
+  ra.eps = eps; ra.z = z; ra.part = e->lat_part; ra.flag = e->feed_flag;
+  if ((rc = hip_rc(e, "k_latent_reparam", profiled(e, PC_LATENT, 0.0, st, [&] {
+         SDRM_LAUNCH(e, k_latent_reparam, dim3((unsigned)parts), dim3(256), 0, st, ra);
+         return hipGetLastError();
+       }))))
+    return rc;
+  return hip_rc(e, "k_encode_kl_sum", profiled(e, PC_LATENT, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_encode_kl_sum, dim3(1), dim3(256), 0, st, (const double*)e->lat_part, parts, b, kl);
+    return hipGetLastError();
+  }));
+}
+
+int sdrm_vae_latent_bwd(sdrm_engine* e, const float* h1, const float* out2, const float* eps, const float* w2, int hidden, int latent, int b,
+                        const float* gz, const float* gkl, float* dpre, float* dw2, float* db2, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!h1 || !out2 || !eps || !w2 || !dpre || !dw2 || !db2) return fail(e, SDRM_ERR_ARG, "sdrm_vae_latent_bwd: null pointer");
+  if (int rc = sdrm_debug_latent_args(hidden, latent, b, 0, 0)) return fail(e, rc, std::string("sdrm_vae_latent_bwd") + kLatentEnvelope);
+  hipStream_t st = (hipStream_t)stream;
+  if (int jr = chains_join(e, st)) return jr;
+  const LatDims d = lat_dims(hidden, latent, b);
+  const int Kb = round_up(b, 32), kchunk = std::min(Kb, LATENT_WGRAD_KCHUNK), S = (Kb + kchunk - 1) / kchunk;
+  int rc;
+  if ((rc = lat_grow(e, sdrm_engine::LAT_H, (size_t)d.MP * d.Hp)) || (rc = lat_grow(e, sdrm_engine::LAT_W2T, (size_t)d.Hr * d.L2p)) ||
+      (rc = lat_grow(e, sdrm_engine::LAT_DOUT2, (size_t)d.MP * d.L2p)) || (rc = lat_grow(e, sdrm_engine::LAT_SLAB, (size_t)S * d.L2p * d.Hp)) ||
+      (rc = lat_grow(e, sdrm_engine::LAT_DBIAS, (size_t)S * d.L2p)))
+    return rc;
+  float* hp = e->lat_buf[sdrm_engine::LAT_H];
+  float* w2t = e->lat_buf[sdrm_engine::LAT_W2T];
+  float* dp = e->lat_buf[sdrm_engine::LAT_DOUT2];
+  float* slab = e->lat_buf[sdrm_engine::LAT_SLAB];
+  float* dbias = e->lat_buf[sdrm_engine::LAT_DBIAS];
+  // 1: W2^T (the NT dgrad's operand) and the padded h1 (the weight gradient's operand, the dgrad epilogue's aux)
+  LatentStageBwdArgs sa{};
+  sa.w2 = w2; sa.w2t = w2t; sa.L2 = d.L2; sa.H = hidden; sa.L2p = d.L2p; sa.Hr = d.Hr;
+  sa.h1 = h1; sa.hp = hp; sa.b = b; sa.MP = d.MP; sa.Hp = d.Hp;
+  sa.tiles_l = d.L2p / 32; sa.tiles = (d.Hr / 32) * sa.tiles_l;
+  if ((rc = hip_rc(e, "k_latent_stage_bwd", profiled(e, PC_LATENT, 0.0, st, [&] {
+         SDRM_LAUNCH(e, k_latent_stage_bwd, dim3((unsigned)sa.tiles + lat_blocks((int64_t)d.MP * (d.Hp / 4))), dim3(256), 0, st, sa);
+         return hipGetLastError();
+       }))))
+    return rc;
+  // 2: dout2 = [dmu | dlv], padded
+  LatentSeedArgs ga{};
+  ga.out2 = out2; ga.eps = eps; ga.gz = gz; ga.gkl = gkl; ga.b = b; ga.L = latent; ga.MP = d.MP; ga.L2p = d.L2p; ga.dp = dp;
+  if ((rc = hip_rc(e, "k_latent_seed", profiled(e, PC_LATENT, 0.0, st, [&] {
+         SDRM_LAUNCH(e, k_latent_seed, dim3(lat_blocks((int64_t)d.MP * (d.L2p / 4))), dim3(256), 0, st, ga);
+         return hipGetLastError();
+       }))))
+    return rc;
+  // 3: dW2 = dout2^T h1 into slabs, db2 = column sums of dout2 (the reduction runs over the batch rows: M-contiguous operands)
+  HIP_TRY(e, (gemm_wgrad<XF_NONE>(dp, d.L2p, d.L2p, hp, d.Hp, d.Hp, nullptr, Kb, S, kchunk, slab, dbias, st,
+                                  Prof{e, PC_LATENT, 2.0 * b * d.L2 * hidden}, pick_cfg(e->tune))));
+  // 4: dpre = (dout2 W2) (1 - h1^2), bounds-checked into the caller's [b][hidden]
+  {
+    GemmArgs a{};
+    a.A = dp; a.lda = d.L2p; a.limA = d.rows64;
+    a.B = w2t; a.ldb = d.L2p; a.limB = d.Hp;
+    a.C = dpre; a.ldc = hidden; a.rows_valid = b; a.cols_valid = hidden;
+    a.K = d.L2p; a.kchunk = d.L2p;
+    a.aux = hp; a.ldaux = d.Hp;
+    HIP_TRY(e, (launch_gemm<LD_KCONTIG, LD_KCONTIG, XF_NONE, XF_NONE, EPI_DTANH_G>(a, d.rows64, d.Hp, 1, st, Prof{e, PC_LATENT, 2.0 * b * d.L2 * hidden},
+                                                                                    choose_cfg(e->tune, d.rows64, e->tune.nt32_max_rows))));
+  }
+  // 5: the slabs and bias sums into the caller's dw2 [2L][hidden] and db2 [2L]
+  LatentUnpadArgs ua{};
+  ua.slab = slab; ua.dbias = dbias; ua.S = S; ua.L2 = d.L2; ua.H = hidden; ua.L2p = d.L2p; ua.Hp = d.Hp; ua.dw2 = dw2; ua.db2 = db2;
+  return hip_rc(e, "k_latent_unpad", profiled(e, PC_LATENT, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_latent_unpad, dim3(lat_blocks((int64_t)d.L2 * ((hidden + 3) / 4) + d.L2)), dim3(256), 0, st, ua);
+    return hipGetLastError();
+  }));
+}
+
+// ---------------------------------------------------------------------------------------------
 // Loss head of the VAE pre-stage (train_SDRM.py:141-142), csrc/nll.h.
 namespace {
 
@@ -3234,7 +3392,7 @@ int sdrm_profile_begin(sdrm_engine* e, int capacity) {
   e->prof_cap = capacity;
   e->prof_cls.clear();
   e->prof_flops.clear();
-  for (int i = 0; i < 16; ++i) { e->prof_ms[i] = 0; e->prof_fl[i] = 0; e->prof_n[i] = 0; }
+  for (int i = 0; i < PROF_SLOTS; ++i) { e->prof_ms[i] = 0; e->prof_fl[i] = 0; e->prof_n[i] = 0; }
   e->prof_on = true;
   return SDRM_OK;
 }

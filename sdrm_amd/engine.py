@@ -681,6 +681,59 @@ class Engine:
             self.feed_status()
         return out
 
+    # ------------------------------------------------------------------ train-mode latent head of the VAE encoder (csrc/latent.h)
+    def vae_latent_fwd(self, pre, w2, b2, rows=None, row0=0, seed=0, step=0, eps=None):
+        """train_SDRM.py:244-250 behind the first pre-activation, in train mode: (z [b, latent], kl 0-d, saved) float32 device tensors
+        for pre [b, hidden] (what `vae_input_layer_fwd` left), w2 [2 latent, hidden], b2 [2 latent] as `nn.Linear` holds them.
+        `eps=None` draws the reparameterisation noise on the device, the engine's Philox draw of (seed, step, feed row, column) with the
+        feed rows `rows` (int64) or row0 .. row0+b-1 - not torch's generator; a given float32 [b, latent] device tensor is used as it
+        is and not written.  `saved` = (h1, out2, eps) is what `vae_latent_bwd` takes; nothing is read back."""
+        who = "vae_latent_fwd"
+        if not isinstance(pre, torch.Tensor) or pre.dim() != 2 or not isinstance(w2, torch.Tensor) or w2.dim() != 2 or w2.shape[0] % 2:
+            raise SdrmError(f"{who}: pre must be a 2-D tensor [b, hidden] and w2 a 2-D tensor [2 latent, hidden]")
+        b, hidden, latent = int(pre.shape[0]), int(pre.shape[1]), int(w2.shape[0]) // 2
+        pre = self._f32(who, "pre", pre, (b, hidden))
+        w2 = self._f32(who, "w2", w2, (2 * latent, hidden))
+        b2 = self._f32(who, "b2", b2, (2 * latent,))
+        if rows is not None:
+            rows = self._index(who, "rows", rows, torch.int64, b)
+        draw = eps is None
+        eps = torch.empty(b, latent, dtype=torch.float32, device=self.device) if draw else self._f32(who, "eps", eps, (b, latent))
+        h1 = torch.empty(b, hidden, dtype=torch.float32, device=self.device)
+        out2 = torch.empty(b, 2 * latent, dtype=torch.float32, device=self.device)
+        z = torch.empty(b, latent, dtype=torch.float32, device=self.device)
+        kl = torch.empty((), dtype=torch.float32, device=self.device)
+        self._check(self.lib.sdrm_vae_latent_fwd(self._h, _ptr(pre), _ptr(w2), _ptr(b2), hidden, latent, _ptr(rows), int(row0), b,
+                                                 int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, int(draw), _ptr(h1), _ptr(out2), _ptr(eps),
+                                                 _ptr(z), _ptr(kl), _stream()), "sdrm_vae_latent_fwd")
+        return z, kl, (h1, out2, eps)
+
+    def vae_latent_bwd(self, saved, w2, gz, gkl, out=None):
+        """Its backward: (dpre [b, hidden], dw2 [2 latent, hidden], db2 [2 latent]) for `saved` as the forward returned it, the w2 that
+        forward read, and the upstream gradients gz [b, latent] and gkl (a float32 device tensor of ONE element) - either may be None,
+        which means zero.  Every element of the three results is written once: `out` = (dpre, dw2, db2) needs no zeroing."""
+        who = "vae_latent_bwd"
+        if not isinstance(saved, (tuple, list)) or len(saved) != 3 or not all(isinstance(t, torch.Tensor) and t.dim() == 2 for t in saved):
+            raise SdrmError(f"{who}: saved must be the (h1, out2, eps) a vae_latent_fwd returned")
+        h1, out2, eps = saved
+        b, hidden, latent = int(h1.shape[0]), int(h1.shape[1]), int(eps.shape[1])
+        h1 = self._f32(who, "h1", h1, (b, hidden))
+        out2 = self._f32(who, "out2", out2, (b, 2 * latent))
+        eps = self._f32(who, "eps", eps, (b, latent))
+        w2 = self._f32(who, "w2", w2, (2 * latent, hidden))
+        if gz is not None:
+            gz = self._f32(who, "gz", gz, (b, latent))
+        if gkl is not None and (not isinstance(gkl, torch.Tensor) or gkl.dtype != torch.float32 or gkl.device != self.device or gkl.numel() != 1):
+            raise SdrmError(f"{who}: gkl must be a float32 device tensor of 1 element")
+        shapes = ((b, hidden), (2 * latent, hidden), (2 * latent,))
+        if out is None:
+            out = tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
+        else:
+            out = tuple(self._f32(who, name, t, s) for name, t, s in zip(("dpre", "dw2", "db2"), out, shapes))
+        self._check(self.lib.sdrm_vae_latent_bwd(self._h, _ptr(h1), _ptr(out2), _ptr(eps), _ptr(w2), hidden, latent, b, _ptr(gz), _ptr(gkl),
+                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()), "sdrm_vae_latent_bwd")
+        return out
+
     def csc_to_device(self, m):
         """(colptr i64, rowidx i32, data f32 | None for an all-ones matrix, shape) of a scipy sparse matrix, on the device: the
         matrix `csr_to_device` ships (duplicates summed, indices sorted), by columns, row indices ascending within a column."""

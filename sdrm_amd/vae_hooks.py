@@ -71,11 +71,17 @@ class VAE(nn.Module):
         eps = torch.randn_like(mu)  # consumed even in eval, like the reference (Q12)
         return mu + self.is_training * eps * torch.exp(0.5 * logvar), kl
 
-    def encode_rows(self, feed, lo, hi, seed, step):
+    def encode_rows(self, feed, lo, hi, seed, step, latent_seed=None):
         """`encode` in train mode for the rows at places lo .. hi-1 of a `SparseFeed`'s order, without a dense batch: normalise,
         dropout and the first Linear are `sparse_input_linear` (the dropout bits are the engine's Philox draws of (seed, step, feed
-        row, column), `self.dropout` draws nothing); the rest of the encoder, the KL and the reparameterisation are `encode`'s."""
+        row, column), `self.dropout` draws nothing); the rest of the encoder, the KL and the reparameterisation are `encode`'s.
+        With `latent_seed` given that rest is `latent_head` instead - launches of csrc/latent.h, the reparameterisation noise being
+        the engine's Philox draw of (latent_seed, step, feed row, column) for the feed rows `feed.order[lo:hi]` (lo .. without an
+        order): torch's generator is not consumed."""
         pre = sparse_input_linear(self.encoder[0].weight, self.encoder[0].bias, feed, lo, hi, seed, step, self.dropout.p)
+        if latent_seed is not None:
+            rows = None if feed.order is None else feed.order[lo:hi]
+            return latent_head(pre, self.encoder[2].weight, self.encoder[2].bias, rows, lo, latent_seed, step)
         h = self.encoder[1:](pre)
         mu, logvar = torch.chunk(h, chunks=2, dim=1)
         kl = -0.5 * torch.mean(torch.sum(1 + logvar - mu.pow(2) - logvar.exp(), dim=1))
@@ -199,7 +205,45 @@ def sparse_input_linear(w1, b1, feed, lo, hi, seed, step, p_drop):
     return _SparseInputLinear.apply(w1, b1, feed, int(lo), int(hi), int(seed), int(step), float(p_drop))
 
 
+class _LatentHead(torch.autograd.Function):
+    """`encode`'s tail in train mode - tanh, the second Linear, chunk, the KL, mu + eps * exp(0.5 * logvar) - for a pre-activation
+    on the device: both directions are launches of csrc/latent.h on the utility engine, once-differentiable, nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, pre, w2, b2, rows, row0, seed, step, eps):
+        eng = utility_engine(pre.device)
+        w2d = w2.detach().contiguous()
+        z, kl, saved = eng.vae_latent_fwd(pre.detach().contiguous(), w2d, b2.detach().contiguous(), rows=rows, row0=row0, seed=seed,
+                                          step=step, eps=eps)
+        ctx.save_for_backward(w2d, *saved)
+        ctx.eng = eng
+        ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None and is passed as null
+        return z, kl
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gz, gkl):
+        w2d, h1, out2, eps = ctx.saved_tensors
+        gz = None if gz is None else gz.to(dtype=torch.float32).contiguous()
+        gkl = None if gkl is None else gkl.to(dtype=torch.float32).contiguous()   # its device pointer is the kernel's `gkl`
+        dpre, dw2, db2 = ctx.eng.vae_latent_bwd((h1, out2, eps), w2d, gz, gkl)
+        need = ctx.needs_input_grad
+        return dpre if need[0] else None, dw2 if need[1] else None, db2 if need[2] else None, None, None, None, None, None
+
+
+def latent_head(pre, w2, b2, rows, row0, seed, step, eps=None):
+    """The encoder behind its first pre-activation in train mode (:244-250 with is_training == 1) as device tensors (z [b, latent],
+    kl 0-dim) with gradients for pre [b, hidden], w2 [2 latent, hidden] and b2 [2 latent].  `eps=None`: the reparameterisation noise
+    of (batch row r, column j) is the engine's Philox draw of (seed, step, feed row, j), the feed rows being `rows` (int64 device
+    tensor [b]) or row0 .. row0+b-1 - not torch's generator; a float32 device tensor `eps` [b, latent] is used as it is.  The
+    backward hands `kl`'s `grad_output` to the kernel as a device scalar; a `None` gradient of either output is passed as null."""
+    if not pre.is_cuda:
+        raise SdrmError("latent_head: the pre-activation must be on a ROCm device (there is no CPU fallback)")
+    return _LatentHead.apply(pre, w2, b2, rows, int(row0), int(seed), int(step), eps)
+
+
 SPARSE_INPUT_MAX_HIDDEN = 4096   # the widest hidden layer csrc/input_layer.h takes
+LATENT_HEAD_MAX_LATENT = 4096    # the widest latent layer csrc/latent.h takes
 
 
 def evaluate_holdout(model, eng, test_csr_dev, seed, draw, early_stop_metric, batch=500):
@@ -225,7 +269,8 @@ def evaluate_holdout(model, eng, test_csr_dev, seed, draw, early_stop_metric, ba
 
 
 def train_variational_autoencoder(model, train_data, test_data, epochs, batch_size, lr, early_stop_metric="NDCG@50",
-                                  VAE_DIR_PATH="./", verbose=False, device_feed=False, sparse_input=False, device_holdout=False):
+                                  VAE_DIR_PATH="./", verbose=False, device_feed=False, sparse_input=False, device_holdout=False,
+                                  device_latent=False):
     """VAE pre-stage (:115-188): multinomial NLL + annealed KL, early stopping on Recall/NDCG@k of a
     per-user hold-out of `test_data`, best epoch restored.  Plain PyTorch (not part of the hot path) - except, with
     `device_feed=True` and the model on a ROCm device, the feed and the loss head: the CSR matrices stay in HBM, every train and
@@ -245,12 +290,20 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
     split is the engine's Philox split (csrc/holdout.h), not numpy's: `holdout_seed` is ONE extra draw from `np.random`
     (`randint(2**63)`, taken before the first permutation, after `sparse_input`'s seed when both are on), numpy's stream no longer
     advances by one `choice` per user per epoch, and the "skipping user" warning is not printed (such users are empty rows whose nan
-    score `np.nanmean` ignores, so the same users count).  The run is therefore not bit-comparable with the other paths."""
+    score `np.nanmean` ignores, so the same users count).  The run is therefore not bit-comparable with the other paths.
+    `device_latent=True` (with `device_feed=True`, `sparse_input=True` in effect, the model on a ROCm device and a latent layer of at
+    most 4096; ignored otherwise) also puts everything behind the first pre-activation of the train half's encode on the engine:
+    `model.encode_rows(..., latent_seed=...)`, whose tanh, second Linear, KL and reparameterisation are `latent_head` (csrc/latent.h)
+    in both directions.  Its reparameterisation noise is the engine's Philox draw keyed by `latent_seed`, `step = int(anneal_count)`
+    and the feed row, not `torch.randn_like`: such a run no longer consumes torch's generator in the train half (the evaluation half's
+    `encode` still does) and is not bit-comparable with the other paths.  `latent_seed` is ONE extra draw from `np.random`
+    (`randint(2**63)`), taken after `sparse_input`'s and `device_holdout`'s seeds and before the first permutation."""
     os.makedirs(os.path.normpath(VAE_DIR_PATH), exist_ok=True)
     dev = next(model.parameters()).device
     device_feed = bool(device_feed) and dev.type == "cuda"
     sparse_input = bool(sparse_input) and device_feed and model.encoder[0].out_features <= SPARSE_INPUT_MAX_HIDDEN
     device_holdout = bool(device_holdout) and device_feed
+    device_latent = bool(device_latent) and sparse_input and model.latent_dim <= LATENT_HEAD_MAX_LATENT
     anneal_cap, anneal_count = 0.2, 0.0
     best_metric, best_epoch, stale = -np.inf, 0, 0
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
@@ -267,6 +320,7 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
     if device_holdout:
         test_dev = eng.csr_to_device(test_data)
         holdout_seed = int(np.random.randint(2 ** 63, dtype=np.int64))
+    latent_seed = int(np.random.randint(2 ** 63, dtype=np.int64)) if device_latent else None
     for epoch in range(epochs):
         losses = []
         model.train()
@@ -289,7 +343,10 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
                 X = torch.tensor(train_data[lo:hi].toarray(), dtype=torch.float32, device=dev)
             optimizer.zero_grad()
             if sparse_input:
-                z, kl = model.encode_rows(feed, lo, hi, drop_seed, int(anneal_count))
+                if device_latent:
+                    z, kl = model.encode_rows(feed, lo, hi, drop_seed, int(anneal_count), latent_seed=latent_seed)
+                else:
+                    z, kl = model.encode_rows(feed, lo, hi, drop_seed, int(anneal_count))
                 out = model.decode(z)
             else:
                 out, kl = model(X)
