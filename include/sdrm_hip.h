@@ -419,6 +419,42 @@ int sdrm_vae_latent_fwd(sdrm_engine* e, const float* pre, const float* w2, const
                         void* stream);
 int sdrm_vae_latent_bwd(sdrm_engine* e, const float* h1, const float* out2, const float* eps, const float* w2, int hidden, int latent, int b,
                         const float* gz, const float* gkl, float* dpre, float* dw2, float* db2, void* stream);
+/* The VAE decoder and the multinomial loss in TRAIN mode, both directions (reference: train_SDRM.py:252-254 `decode`, :141-142 the loss
+ * line, and their share of :148), for the batch whose interaction rows are the CSR rows rows[0..b) (or row0 .. row0+b-1 when rows is null)
+ * of a device-resident matrix [n_rows, n_items] under the contract of sdrm_multinomial_nll_csr.  float32 throughout, L = latent,
+ * H = hidden, I = n_items; `dec` is sdrm_vae_decode's struct: w1 = W3 [H, L], b1 = b3 [H], w2 = W4 [I, H], b2 = b4 [I] as nn.Linear
+ * stores them:
+ *   h3     = tanh(z W3^T + b3)                         [b, H]
+ *   logits = h3 W4^T + b4                              [b, I]
+ *   lse[r] = log sum_i exp(logits[r,i])                (max-subtracted, fp32, over exactly I columns)
+ *   loss   = -(1/b) sum_r sum_p x_p (logits[r,col_p] - lse[r])      (fp32 terms, float64 sums in a fixed order)
+ *   g      = scale (exp(logits - lse) s_r - X) / b     [b, I]       s_r = sum_p x_p;  scale: ONE device float or null (= 1)
+ *   dW4 = g^T h3     db4 = sum_r g[r,:]     dpre3 = (g W4)(1 - h3^2)
+ *   dW3 = dpre3^T z  db3 = sum_r dpre3[r,:] dz    = dpre3 W3
+ * sdrm_vae_decoder_nll_fwd: z [b, L] contiguous.  Out, all caller-owned and contiguous: h3 [b, H], logits [b, I] (base 16-byte
+ *   aligned), lse [b], loss (one device float).  The four tensors are read and padded into scratch of the handle on EVERY call (they
+ *   change with every optimiser step); the scratch of sdrm_vae_decode and an encoder staged by sdrm_vae_encoder_load are not touched.
+ * sdrm_vae_decoder_nll_bwd: z, h3, logits, lse as a forward left them, W3 and W4 as that forward read them (b1 / b2 of `dec` are not
+ *   read), the same batch - so two forwards may precede their backwards.  The inputs are not written; g and dpre3 live in padded
+ *   scratch of the handle, whose padding this call writes itself.  Out: dz [b, L] (may be null: then the last dgrad is not launched),
+ *   dw3 [H, L], db3 [H], dw4 [I, H], db4 [I] contiguous, EVERY element written exactly once: no memset, no atomic, the same bits
+ *   from call to call on the same inputs.
+ * Range checks as in sdrm_multinomial_nll_csr: an offending entry contributes nothing to s_r, the loss or g; an offending row counts
+ * as an empty row (its g row is zero, its lse still that of its logits); the verdict waits in the word sdrm_feed_status reports.
+ * Launches: 6 forward (staging, GEMM + tanh, h3 unpadded, GEMM + bias, loss rows, loss sum), 7 backward (staging with both weight
+ * transposes, loss gradient, weight-gradient GEMM of W4, dgrad GEMM through the tanh, weight-gradient GEMM of W3, dgrad GEMM to z,
+ * unpadding) - 6 without dz; the GEMMs are csrc/gemm.h's fp32 MFMA family and follow sdrm_debug_set_tile.  A batch of more rows than
+ * one weight-gradient K chunk (8192, fewer where (chunk + 64) x n_items padded to 32 x 4 bytes would reach 2^32) makes one slab per
+ * chunk, added in slab order; a product beyond the exact range of the GEMM's tile arithmetic goes out in bands, one launch each.
+ * Envelope (SDRM_ERR_SHAPE otherwise, before any launch): 1 <= latent <= 4096, 1 <= hidden <= 4096, 1 <= n_items <= 2^20, 1 <= b <=
+ * 2^22, b x n_items < 2^40, n_rows >= 1, row0 >= 0 and a contiguous range inside the matrix.  A null required pointer or a logits
+ * base off 16 bytes is SDRM_ERR_ARG.  Both calls join the sampler's chains; neither synchronises or reads back. */
+int sdrm_vae_decoder_nll_fwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z, const int64_t* indptr, const int32_t* indices,
+                             const float* data, int64_t n_rows, const int64_t* rows, int64_t row0, int b, float* h3, float* logits,
+                             float* lse, float* loss, void* stream);
+int sdrm_vae_decoder_nll_bwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z, const float* h3, const float* logits, const float* lse,
+                             const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, const int64_t* rows,
+                             int64_t row0, int b, const float* scale, float* dz, float* dw3, float* db3, float* dw4, float* db4, void* stream);
 /* Per-user hold-out split on the device, CSR in, two CSRs out (reference: utilities.py:174-236,
  * split_train_test_proportion_from_csr_matrix with ignore_zeros=False, which train_SDRM.py:161 calls once per pre-stage epoch): of
  * the n stored entries of a user with n >= 2, m = ceil(test_prop * n) chosen uniformly without replacement go to the held-out

@@ -35,6 +35,13 @@ int sdrm_debug_input_layer_args(int n_items, int hidden, int64_t n_rows, int64_t
  * lie in [0, 2^31)), else SDRM_OK.  Pure function: callable without a GPU. */
 int sdrm_debug_latent_args(int hidden, int latent, int b, int64_t row0, int contiguous);
 
+/* What sdrm_vae_decoder_nll_fwd / _bwd check on the host before any launch: SDRM_ERR_SHAPE outside their envelope (1 <= latent <= 4096,
+ * 1 <= hidden <= 4096, 1 <= n_items <= 2^20, 1 <= b <= 2^22, b x n_items < 2^40, n_rows >= 1, row0 >= 0; `contiguous` != 0, a call
+ * without a `rows` array: row0 + b <= n_rows) and for anything a later GEMM launch would refuse on any tile - with the weight
+ * gradient's K chunk chosen from n_items and the launches banded as the entry points do, nothing inside the envelope is - else
+ * SDRM_OK.  Pure function: callable without a GPU. */
+int sdrm_debug_decoder_nll_args(int latent, int hidden, int n_items, int b, int64_t row0, int64_t n_rows, int contiguous);
+
 /* What sdrm_holdout_split checks and derives on the host before any launch: SDRM_ERR_SHAPE outside its envelope (1 <= n_items <=
  * 2^20, 1 <= n_rows < 2^31, 0 <= nnz < 2^40, 0 < test_prop < 1), else SDRM_OK with the held-out count of a row of n_u entries,
  * n_u < 2 ? 0 : min(n_u, (int64)ceil(test_prop * (double)n_u)), in *m_out (may be NULL).  Pure function: callable without a GPU. */

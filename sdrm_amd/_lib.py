@@ -100,6 +100,10 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_vae_latent_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
+    "sdrm_vae_decoder_nll_fwd": (c_int, [c_void_p, C.POINTER(VaeDecoder), c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdrm_vae_decoder_nll_bwd": (c_int, [c_void_p, C.POINTER(VaeDecoder), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_holdout_split": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, C.c_double, c_uint64, C.c_uint32, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
     "sdrm_equal_sparsity": (c_int, [c_void_p, c_void_p, c_int64, C.c_double, c_void_p, c_void_p, c_void_p]),
@@ -114,6 +118,7 @@ SIGNATURES = {
     "sdrm_debug_device_check": (c_int, [C.c_char_p, c_int]),
     "sdrm_debug_input_layer_args": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, c_float, C.POINTER(C.c_uint32), C.POINTER(c_float)]),
     "sdrm_debug_latent_args": (c_int, [c_int, c_int, c_int, c_int64, c_int]),
+    "sdrm_debug_decoder_nll_args": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int]),
     "sdrm_debug_holdout_args": (c_int, [c_int, c_int64, c_int64, C.c_double, c_int64, C.POINTER(c_int64)]),
     "sdrm_debug_set_tile": (c_int, [c_void_p, c_int]),
     "sdrm_debug_set_nt32_rows": (c_int, [c_void_p, c_int, c_int]),

@@ -18,6 +18,7 @@
 #include "../../include/sdrm_hip_debug.h"
 #include "compact.h"
 #include "decode.h"
+#include "decoder_train.h"
 #include "elementwise.h"
 #include "encode.h"
 #include "exchange.h"
@@ -237,6 +238,12 @@ struct sdrm_engine {
   float* lat_buf[LAT_BUFS] = {};     // h1 [MP][Hp] | W2 [L2r][Hp], b2 [L2r] | W2^T [Hr][L2p] | dout2 [MP][L2p] | weight-gradient slabs [S][L2p][Hp], bias sums [S][L2p]
   size_t lat_cap[LAT_BUFS] = {};
   double* lat_part = nullptr;        // partial sums of its kl (k_latent_reparam), [ENC_KL_PARTS]
+  // grow-only scratch of the train-mode decoder and loss head (csrc/decoder_train.h): this call's operands, every one written by the
+  // call that reads it; nothing of sdrm_vae_decode's dec_buf or of a forward that still waits for its backward (h3, logits, lse are the caller's)
+  enum { DH_Z = 0, DH_W3, DH_B3, DH_H3, DH_W4, DH_B4, DH_W4T, DH_W3T, DH_ZB, DH_G, DH_DP3, DH_SLAB4, DH_DB4, DH_SLAB3, DH_DB3, DH_BUFS };
+  float* dh_buf[DH_BUFS] = {};       // z [MP][Lp], W3 [Hr][Lp], b3 [Hr], h3 [MP][Hp], W4 [Ir][Hp], b4 [Ir] | W4^T [Hr][Ip], W3^T [Lr][Hp], zero bias [Lr],
+                                     // g [MP][Ip], dpre3 [MP][Hp], slabs [S][Ip][Hp] + bias sums [S][Ip] of dW4, slabs [S][Hp][Lp] + bias sums [S][Hp] of dW3
+  size_t dh_cap[DH_BUFS] = {};
   uint32_t* hold_cnt = nullptr;      // grow-only scratch of sdrm_holdout_split (csrc/holdout.h): [2][rows] entries n_u and held entries m_u of every row
   size_t hold_cap = 0;               // in elements
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
@@ -270,7 +277,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -288,7 +295,8 @@ static const char* kProfNames[PC_COUNT] = {
     "loss head: k_nll_rows / k_nll_grad multinomial NLL of logits against CSR rows and its gradient (one work-group per row, HBM-bound)",
     "input layer: k_input_fwd / k_input_wgrad train-mode first Linear of the VAE encoder from CSR rows and its weight gradient from CSC columns",
     "hold-out: k_holdout_counts / k_holdout_scan / k_holdout_split per-user hold-out split of a CSR matrix into two (keys ranked per row, a wave or a work-group per row)",
-    "latent head: k_latent_stage / gemm_kernel<0,0,0,0,7> / k_latent_reparam forward, k_latent_stage_bwd / k_latent_seed / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / k_latent_unpad backward of the VAE encoder behind its first pre-activation in train mode"};
+    "latent head: k_latent_stage / gemm_kernel<0,0,0,0,7> / k_latent_reparam forward, k_latent_stage_bwd / k_latent_seed / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / k_latent_unpad backward of the VAE encoder behind its first pre-activation in train mode",
+    "decoder head: k_pad2d / gemm_kernel<0,0,0,0,1> / k_dechead_h3 / gemm_kernel<0,0,0,0,7> / k_nll_rows / k_nll_sum forward, k_dechead_stage_bwd / k_dechead_grad / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / gemm_kernel<0,0,0,0,7> / k_dechead_unpad backward of the VAE decoder and the multinomial loss in train mode"};
 
 namespace {
 
@@ -1600,6 +1608,8 @@ int sdrm_destroy(sdrm_engine* e) {
   for (float* b : e->lat_buf)
     if (b) (void)hipFree(b);
   if (e->lat_part) (void)hipFree(e->lat_part);
+  for (float* b : e->dh_buf)
+    if (b) (void)hipFree(b);
   if (e->hold_cnt) (void)hipFree(e->hold_cnt);
   if (e->csr_ws) (void)hipFree(e->csr_ws);
   if (e->csr_nnz_host) (void)hipHostFree(e->csr_nnz_host);
@@ -3060,6 +3070,283 @@ int sdrm_vae_latent_bwd(sdrm_engine* e, const float* h1, const float* out2, cons
   ua.slab = slab; ua.dbias = dbias; ua.S = S; ua.L2 = d.L2; ua.H = hidden; ua.L2p = d.L2p; ua.Hp = d.Hp; ua.dw2 = dw2; ua.db2 = db2;
   return hip_rc(e, "k_latent_unpad", profiled(e, PC_LATENT, 0.0, st, [&] {
     SDRM_LAUNCH(e, k_latent_unpad, dim3(lat_blocks((int64_t)d.L2 * ((hidden + 3) / 4) + d.L2)), dim3(256), 0, st, ua);
+    return hipGetLastError();
+  }));
+}
+
+// ---------------------------------------------------------------------------------------------
+// The VAE decoder and the multinomial loss head in TRAIN mode (train_SDRM.py:252-254 and :141-142, and their share of :148),
+// csrc/decoder_train.h.  The scratch of sdrm_vae_decode and a loaded frozen encoder are not touched.
+constexpr int DECHEAD_MAX_HIDDEN = 4096, DECHEAD_MAX_LATENT = 4096;
+constexpr int DECHEAD_WGRAD_KCHUNK = 8192;   // most batch rows of one weight-gradient slab (the pre-stage's batches are a few hundred: one slab)
+
+namespace {
+
+int dh_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->dh_buf[slot], &e->dh_cap[slot], n); }
+
+// padded extents: K and N of the GEMMs to 32, operand rows to the largest tile (128), the batch to 64 (the launches' M)
+struct DhDims { int Lp, Lr, Hp, Hr, Ip, Ir, MP, rows64, Kb, kc4, S4, kc3, S3; };
+
+// Batch rows of one slab of the dW4 weight gradient: launch_gemm_cfg refuses a launch whose K chunk (+ 64) times the operand's row
+// stride reaches 2^32 bytes, and g's stride is Ip - so the chunk follows from Ip (8192 up to Ip = 130048, 928 at Ip = 2^20).
+int dh_kchunk4(int Ip) {
+  const int64_t kc = (((int64_t)1 << 30) - 1) / Ip - 64;   // (kc + 64) * Ip * 4 < 2^32
+  return (int)std::min<int64_t>(DECHEAD_WGRAD_KCHUNK, kc / 32 * 32);
+}
+
+DhDims dh_dims(int latent, int hidden, int n_items, int b) {
+  DhDims d;
+  d.Lp = round_up(latent, 32); d.Lr = round_up(d.Lp, 128);
+  d.Hp = round_up(hidden, 32); d.Hr = round_up(d.Hp, 128);
+  d.Ip = round_up(n_items, 32); d.Ir = round_up(d.Ip, 128);
+  d.MP = round_up(b, 128); d.rows64 = round_up(b, BM); d.Kb = round_up(b, 32);
+  d.kc4 = std::min(d.Kb, dh_kchunk4(d.Ip)); d.S4 = (d.Kb + d.kc4 - 1) / d.kc4;
+  d.kc3 = std::min(d.Kb, DECHEAD_WGRAD_KCHUNK); d.S3 = (d.Kb + d.kc3 - 1) / d.kc3;
+  return d;
+}
+
+// gemm_set_grid keeps a launch's tile count inside the exact range of its magic divisions (nb < 2^31, nb x tiles_n < 2^32,
+// nb^2 x slices < 2^32).  A product of the decoder's envelope can leave that range - 2^22 rows, or 2^20 output columns - so these two
+// give the most rows (NT launch, N columns) / output columns (split-K launch, Kin columns, S slices) of ONE launch on tile `cfg`, whole
+// tiles, and the helpers below send a larger product out in bands of that size.  0: not even one tile row fits.
+int dh_nt_band(int cfg, int N) {
+  const uint64_t tn = (uint64_t)((N + kCfgBN[cfg] - 1) / kCfgBN[cfg]);
+  const uint64_t t = std::min<uint64_t>(65535 / tn, ((1ull << 32) - 1) / (tn * tn));
+  return (int)t * kCfgBM[cfg];
+}
+int dh_wgrad_band(int cfg, int Kin, int S) {
+  const uint64_t tn = (uint64_t)((Kin + kCfgBN[cfg] - 1) / kCfgBN[cfg]);
+  uint64_t nb = (uint64_t)std::sqrt((double)((1ull << 32) - 1) / (double)S);   // the most tiles with nb^2 x S < 2^32
+  while (nb * nb * (uint64_t)S >= (1ull << 32)) --nb;
+  while ((nb + 1) * (nb + 1) * (uint64_t)S < (1ull << 32)) ++nb;
+  return (int)std::min<uint64_t>(nb / tn, 1u << 20) * kCfgBM[cfg];
+}
+// launch_gemm_cfg's own test of a tile x K-chunk span, for a launch on tile `cfg`
+bool dh_span_ok(int cfg, bool kcontig, int lda, int ldb, int kchunk) {
+  const uint64_t kc = (uint64_t)std::max(kchunk, 1) + 64;
+  const uint64_t spanA = kcontig ? ((uint64_t)kCfgBM[cfg] * lda + kc) : kc * lda;
+  const uint64_t spanB = kcontig ? ((uint64_t)kCfgBN[cfg] * ldb + kc) : kc * ldb;
+  return spanA * 4 < (1ull << 32) && spanB * 4 < (1ull << 32);
+}
+
+// C[M, N] = epilogue(A[M, K] B[N, K]^T) in row bands; `a` carries B, C, K and the epilogue's operands, rows_valid counts from row 0
+extern "C++" template <int EPI>
+int dh_nt(sdrm_engine* e, const GemmArgs& a, const float* A, int lda, int M, int N, int rows_valid, hipStream_t st, Prof pr, int cfg) {
+  const int band = dh_nt_band(cfg, N);
+  if (band < 1) return fail(e, SDRM_ERR_SHAPE, "decoder head: no tile row of this product fits one launch");
+  for (int m0 = 0; m0 < M; m0 += band) {
+    GemmArgs x = a;
+    const int m = std::min(band, M - m0);
+    x.A = A + (size_t)m0 * lda; x.lda = lda; x.limA = m; x.limB = N;
+    x.C = a.C + (size_t)m0 * a.ldc;
+    if (a.aux) x.aux = a.aux + (size_t)m0 * a.ldaux;
+    x.kchunk = a.K;
+    x.rows_valid = std::max(0, std::min(rows_valid - m0, m));
+    HIP_TRY(e, (launch_gemm<LD_KCONTIG, LD_KCONTIG, XF_NONE, XF_NONE, EPI>(x, m, N, 1, st, pr, cfg)));
+  }
+  return SDRM_OK;
+}
+
+// gemm_wgrad in bands of output columns: slab [S][Nout][Kin] and dbias [S][Nout] keep their whole strides
+int dh_wgrad(sdrm_engine* e, const float* dC, int Nout, const float* Act, int Kin, int Mrows, int S, int kchunk, float* slab, float* dbias,
+             hipStream_t st, Prof pr, int cfg) {
+  const int band = dh_wgrad_band(cfg, Kin, S);
+  if (band < 1) return fail(e, SDRM_ERR_SHAPE, "decoder head: no tile row of this weight gradient fits one launch");
+  for (int n0 = 0; n0 < Nout; n0 += band) {
+    GemmArgs a{};
+    a.A = dC + n0; a.lda = Nout; a.limA = std::min(band, Nout - n0);
+    a.B = Act; a.ldb = Kin; a.limB = Kin;
+    a.C = slab + (size_t)n0 * Kin; a.ldc = Kin;
+    a.K = Mrows; a.kchunk = kchunk;
+    a.slab_stride = (size_t)Nout * Kin;
+    a.dbias = dbias + n0; a.dbias_stride = Nout;
+    HIP_TRY(e, (launch_gemm<LD_MCONTIG, LD_MCONTIG, XF_NONE, XF_NONE, EPI_SLAB>(a, a.limA, Kin, S, st, pr, cfg)));
+  }
+  return SDRM_OK;
+}
+
+const char* const kDecheadEnvelope = ": latent outside 1 .. 4096, hidden outside 1 .. 4096, n_items outside 1 .. 2^20, b outside 1 .. 2^22, b x n_items >= 2^40, "
+                                     "n_rows < 1, row0 < 0, or rows row0 .. row0 + b - 1 end behind the matrix";
+
+}  // namespace
+
+// The host side of both entry points that needs no device: the envelope, and every test a later launch would make on any tile
+// (`contiguous` != 0: the batch is the feed rows row0 .. row0 + b - 1).
+int sdrm_debug_decoder_nll_args(int latent, int hidden, int n_items, int b, int64_t row0, int64_t n_rows, int contiguous) {
+  if (latent < 1 || latent > DECHEAD_MAX_LATENT || hidden < 1 || hidden > DECHEAD_MAX_HIDDEN || n_items < 1 || n_items > (1 << 20) || b < 1 ||
+      b > (1 << 22) || (int64_t)b * n_items >= ((int64_t)1 << 40) || n_rows < 1 || row0 < 0)
+    return SDRM_ERR_SHAPE;
+  if (contiguous && row0 + b > n_rows) return SDRM_ERR_SHAPE;
+  const DhDims d = dh_dims(latent, hidden, n_items, b);
+  if (d.kc4 < 32) return SDRM_ERR_SHAPE;
+  for (int cfg = 0; cfg < N_TILE_CFGS; ++cfg) {
+    // forward: z W3^T, h3 W4^T; backward: g W4 (K = Ip), dpre3 W3 (K = Hp); the two weight gradients
+    if (dh_nt_band(cfg, d.Hp) < 1 || dh_nt_band(cfg, d.Ip) < 1 || dh_nt_band(cfg, d.Lp) < 1) return SDRM_ERR_SHAPE;
+    if (!dh_span_ok(cfg, true, d.Lp, d.Lp, d.Lp) || !dh_span_ok(cfg, true, d.Hp, d.Hp, d.Hp) || !dh_span_ok(cfg, true, d.Ip, d.Ip, d.Ip))
+      return SDRM_ERR_SHAPE;
+    if (dh_wgrad_band(cfg, d.Hp, d.S4) < 1 || dh_wgrad_band(cfg, d.Lp, d.S3) < 1) return SDRM_ERR_SHAPE;
+    if (!dh_span_ok(cfg, false, d.Ip, d.Hp, d.kc4) || !dh_span_ok(cfg, false, d.Hp, d.Lp, d.kc3)) return SDRM_ERR_SHAPE;
+  }
+  return SDRM_OK;
+}
+
+int sdrm_vae_decoder_nll_fwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z, const int64_t* indptr, const int32_t* indices,
+                             const float* data, int64_t n_rows, const int64_t* rows, int64_t row0, int b, float* h3, float* logits,
+                             float* lse, float* loss, void* stream) {
+  const char* who = "sdrm_vae_decoder_nll_fwd";
+  if (!e) return SDRM_ERR_ARG;
+  if (!dec || !dec->w1 || !dec->b1 || !dec->w2 || !dec->b2 || !z || !indptr || !indices || !h3 || !logits || !lse || !loss)
+    return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if ((uintptr_t)logits & 15u) return fail(e, SDRM_ERR_ARG, std::string(who) + ": logits must be 16-byte aligned");
+  const int L = dec->latent, H = dec->hidden, I = dec->n_items;
+  if (int rc = sdrm_debug_decoder_nll_args(L, H, I, b, row0, n_rows, rows == nullptr)) return fail(e, rc, std::string(who) + kDecheadEnvelope);
+  NllArgs na{};
+  if (int rc = csr_batch(e, who, indptr, indices, data, n_rows, rows, row0, b, I, &na.csr)) return rc;
+  na.logits = logits;
+  hipStream_t st = (hipStream_t)stream;
+  if (int jr = chains_join(e, st)) return jr;
+  const DhDims d = dh_dims(L, H, I, b);
+  int rc;
+  if ((rc = dh_grow(e, sdrm_engine::DH_Z, (size_t)d.MP * d.Lp)) || (rc = dh_grow(e, sdrm_engine::DH_W3, (size_t)d.Hr * d.Lp)) ||
+      (rc = dh_grow(e, sdrm_engine::DH_B3, d.Hr)) || (rc = dh_grow(e, sdrm_engine::DH_H3, (size_t)d.MP * d.Hp)) ||
+      (rc = dh_grow(e, sdrm_engine::DH_W4, (size_t)d.Ir * d.Hp)) || (rc = dh_grow(e, sdrm_engine::DH_B4, d.Ir)))
+    return rc;
+  float* zp = e->dh_buf[sdrm_engine::DH_Z];
+  float* w3p = e->dh_buf[sdrm_engine::DH_W3];
+  float* b3p = e->dh_buf[sdrm_engine::DH_B3];
+  float* h3p = e->dh_buf[sdrm_engine::DH_H3];
+  float* w4p = e->dh_buf[sdrm_engine::DH_W4];
+  float* b4p = e->dh_buf[sdrm_engine::DH_B4];
+  const auto pad_launch = [&](const PadList& pad) {
+    return hip_rc(e, "k_pad2d", profiled(e, PC_DECODER, 0.0, st, [&] {
+      SDRM_LAUNCH(e, k_pad2d, dim3((unsigned)std::min<int64_t>(2048, (pad.most + 255) / 256), (unsigned)pad.k), dim3(256), 0, st, pad.sg);
+      return hipGetLastError();
+    }));
+  };
+  // 1: z and the four tensors padded (the weights change with every optimiser step)
+  {
+    PadList pad;
+    pad.add(z, b, L, zp, d.MP, d.Lp);
+    pad.add(dec->w1, H, L, w3p, d.Hr, d.Lp);
+    pad.add(dec->b1, 1, H, b3p, 1, d.Hr);
+    pad.add(dec->w2, I, H, w4p, d.Ir, d.Hp);
+    pad.add(dec->b2, 1, I, b4p, 1, d.Ir);
+    if ((rc = pad_launch(pad))) return rc;
+  }
+  const int cfg = choose_cfg(e->tune, d.rows64, e->tune.nt32_max_rows);
+  // 2: h3 = tanh(z W3^T + b3) into the padded [MP][Hp], the second GEMM's A operand (the launch decode_launches makes; columns behind
+  //    H are tanh(0) = 0 - W3's pad rows and b3's pad are zero -, rows behind b feed only output rows that 4 drops)
+  {
+    GemmArgs a{};
+    a.B = w3p; a.ldb = d.Lp; a.C = h3p; a.ldc = d.Hp; a.K = d.Lp; a.bias = b3p;
+    if ((rc = dh_nt<EPI_BIAS_TANH>(e, a, zp, d.Lp, d.rows64, d.Hp, b, st, Prof{e, PC_DECODER, 2.0 * b * (double)H * L}, cfg))) return rc;
+  }
+  // 3: its b rows and H columns into the caller's h3 [b][H]
+  {
+    const DecH3Args ha{h3p, h3, b, H, d.Hp};
+    if ((rc = hip_rc(e, "k_dechead_h3", profiled(e, PC_DECODER, 0.0, st, [&] {
+           SDRM_LAUNCH(e, k_dechead_h3, dim3(lat_blocks((int64_t)b * ((H + 3) / 4))), dim3(256), 0, st, ha);
+           return hipGetLastError();
+         }))))
+      return rc;
+  }
+  // 4: logits = h3 W4^T + b4, bounds-checked into the caller's [b][I]
+  {
+    GemmArgs a{};
+    a.B = w4p; a.ldb = d.Hp; a.C = logits; a.ldc = I; a.K = d.Hp; a.bias = b4p; a.cols_valid = I;
+    if ((rc = dh_nt<EPI_BIAS_G>(e, a, h3p, d.Hp, d.rows64, d.Ip, b, st, Prof{e, PC_DECODER, 2.0 * b * (double)I * H}, cfg))) return rc;
+  }
+  // 5: lse and the loss terms over exactly I columns of the caller's logits (csrc/nll.h); 6: their sum
+  const int parts = std::min(b, NLL_PARTS);
+  if ((rc = hip_rc(e, "k_nll_rows", profiled(e, PC_DECODER, 0.0, st, [&] {
+         SDRM_LAUNCH(e, k_nll_rows, dim3((unsigned)parts), dim3(256), 0, st, na, lse, e->nll_part);
+         return hipGetLastError();
+       }))))
+    return rc;
+  return hip_rc(e, "k_nll_sum", profiled(e, PC_DECODER, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_nll_sum, dim3(1), dim3(256), 0, st, (const double*)e->nll_part, parts, b, loss);
+    return hipGetLastError();
+  }));
+}
+
+int sdrm_vae_decoder_nll_bwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z, const float* h3, const float* logits, const float* lse,
+                             const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, const int64_t* rows,
+                             int64_t row0, int b, const float* scale, float* dz, float* dw3, float* db3, float* dw4, float* db4, void* stream) {
+  const char* who = "sdrm_vae_decoder_nll_bwd";
+  if (!e) return SDRM_ERR_ARG;
+  if (!dec || !dec->w1 || !dec->w2 || !z || !h3 || !logits || !lse || !indptr || !indices || !dw3 || !db3 || !dw4 || !db4)
+    return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if ((uintptr_t)logits & 15u) return fail(e, SDRM_ERR_ARG, std::string(who) + ": logits must be 16-byte aligned");
+  const int L = dec->latent, H = dec->hidden, I = dec->n_items;
+  if (int rc = sdrm_debug_decoder_nll_args(L, H, I, b, row0, n_rows, rows == nullptr)) return fail(e, rc, std::string(who) + kDecheadEnvelope);
+  DecGradArgs ga{};
+  if (int rc = csr_batch(e, who, indptr, indices, data, n_rows, rows, row0, b, I, &ga.csr)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (int jr = chains_join(e, st)) return jr;
+  const DhDims d = dh_dims(L, H, I, b);
+  int rc;
+  if ((rc = dh_grow(e, sdrm_engine::DH_Z, (size_t)d.MP * d.Lp)) || (rc = dh_grow(e, sdrm_engine::DH_H3, (size_t)d.MP * d.Hp)) ||
+      (rc = dh_grow(e, sdrm_engine::DH_W4T, (size_t)d.Hr * d.Ip)) || (rc = dh_grow(e, sdrm_engine::DH_W3T, (size_t)d.Lr * d.Hp)) ||
+      (rc = dh_grow(e, sdrm_engine::DH_ZB, d.Lr)) || (rc = dh_grow(e, sdrm_engine::DH_G, (size_t)d.MP * d.Ip)) ||
+      (rc = dh_grow(e, sdrm_engine::DH_DP3, (size_t)d.MP * d.Hp)) || (rc = dh_grow(e, sdrm_engine::DH_SLAB4, (size_t)d.S4 * d.Ip * d.Hp)) ||
+      (rc = dh_grow(e, sdrm_engine::DH_DB4, (size_t)d.S4 * d.Ip)) || (rc = dh_grow(e, sdrm_engine::DH_SLAB3, (size_t)d.S3 * d.Hp * d.Lp)) ||
+      (rc = dh_grow(e, sdrm_engine::DH_DB3, (size_t)d.S3 * d.Hp)))
+    return rc;
+  float* zp = e->dh_buf[sdrm_engine::DH_Z];
+  float* h3p = e->dh_buf[sdrm_engine::DH_H3];
+  float* w4t = e->dh_buf[sdrm_engine::DH_W4T];
+  float* w3t = e->dh_buf[sdrm_engine::DH_W3T];
+  float* zb = e->dh_buf[sdrm_engine::DH_ZB];
+  float* g = e->dh_buf[sdrm_engine::DH_G];
+  float* dp3 = e->dh_buf[sdrm_engine::DH_DP3];
+  float* slab4 = e->dh_buf[sdrm_engine::DH_SLAB4];
+  float* dbs4 = e->dh_buf[sdrm_engine::DH_DB4];
+  float* slab3 = e->dh_buf[sdrm_engine::DH_SLAB3];
+  float* dbs3 = e->dh_buf[sdrm_engine::DH_DB3];
+  // 1: W4^T and W3^T (the NT dgrads' operands), h3 and z padded (the weight gradients' operands), the last dgrad's zero bias
+  DecStageBwdArgs sa{};
+  sa.t4 = DecTranspose{dec->w2, w4t, I, H, d.Ip, d.Ip / 32};
+  sa.t3 = DecTranspose{dec->w1, w3t, H, L, d.Hp, d.Hp / 32};
+  sa.tiles4 = (int64_t)(d.Hr / 32) * (d.Ip / 32); sa.tiles = sa.tiles4 + (int64_t)(d.Lr / 32) * (d.Hp / 32);
+  sa.h3 = h3; sa.h3p = h3p; sa.b = b; sa.H = H; sa.MP = d.MP; sa.Hp = d.Hp;
+  sa.z = z; sa.zp = zp; sa.L = L; sa.Lp = d.Lp;
+  sa.zb = zb; sa.Lr = d.Lr;
+  if ((rc = hip_rc(e, "k_dechead_stage_bwd", profiled(e, PC_DECODER, 0.0, st, [&] {
+         SDRM_LAUNCH(e, k_dechead_stage_bwd, dim3((unsigned)sa.tiles + lat_blocks((int64_t)d.MP * ((d.Hp + d.Lp) / 4) + d.Lr / 4)), dim3(256), 0, st, sa);
+         return hipGetLastError();
+       }))))
+    return rc;
+  // 2: g = scale (softmax s_r - X) / b into [MP][Ip], zero behind b rows / I columns
+  ga.logits = logits; ga.lse = lse; ga.scale = scale; ga.g = g; ga.MP = d.MP; ga.Ip = d.Ip;
+  if ((rc = hip_rc(e, "k_dechead_grad", profiled(e, PC_DECODER, 0.0, st, [&] {
+         SDRM_LAUNCH(e, k_dechead_grad, dim3((unsigned)std::min(d.MP, 1 << 16)), dim3(256), 0, st, ga);
+         return hipGetLastError();
+       }))))
+    return rc;
+  const int cfg_w = pick_cfg(e->tune), cfg = choose_cfg(e->tune, d.rows64, e->tune.nt32_max_rows);
+  // 3: dW4 = g^T h3 into slabs, db4 = column sums of g (the reduction runs over the batch rows: M-contiguous operands)
+  if ((rc = dh_wgrad(e, g, d.Ip, h3p, d.Hp, d.Kb, d.S4, d.kc4, slab4, dbs4, st, Prof{e, PC_DECODER, 2.0 * b * (double)I * H}, cfg_w))) return rc;
+  // 4: dpre3 = (g W4)(1 - h3^2) into [MP][Hp]: all rows64 rows and Hp columns are stored - behind b rows g is zero, behind H columns
+  //    W4^T is: the products are zeros, written by this call
+  {
+    GemmArgs a{};
+    a.B = w4t; a.ldb = d.Ip; a.C = dp3; a.ldc = d.Hp; a.K = d.Ip; a.aux = h3p; a.ldaux = d.Hp; a.cols_valid = d.Hp;
+    if ((rc = dh_nt<EPI_DTANH_G>(e, a, g, d.Ip, d.rows64, d.Hp, d.rows64, st, Prof{e, PC_DECODER, 2.0 * b * (double)I * H}, cfg))) return rc;
+  }
+  // 5: dW3 = dpre3^T z into slabs, db3 = column sums of dpre3
+  if ((rc = dh_wgrad(e, dp3, d.Hp, zp, d.Lp, d.Kb, d.S3, d.kc3, slab3, dbs3, st, Prof{e, PC_DECODER, 2.0 * b * (double)H * L}, cfg_w))) return rc;
+  // 6: dz = dpre3 W3, bounds-checked into the caller's [b][L] (the bias epilogue on a bias of zeros)
+  if (dz) {
+    GemmArgs a{};
+    a.B = w3t; a.ldb = d.Hp; a.C = dz; a.ldc = L; a.K = d.Hp; a.bias = zb; a.cols_valid = L;
+    if ((rc = dh_nt<EPI_BIAS_G>(e, a, dp3, d.Hp, d.rows64, d.Lp, b, st, Prof{e, PC_DECODER, 2.0 * b * (double)H * L}, cfg))) return rc;
+  }
+  // 7: the slabs and bias sums into the caller's dw4 [I][H], db4 [I], dw3 [H][L], db3 [H]
+  DecUnpadArgs ua{};
+  ua.seg[0] = DecUnpadSeg{slab4, dbs4, d.S4, I, H, d.Ip, d.Hp, dw4, db4};
+  ua.seg[1] = DecUnpadSeg{slab3, dbs3, d.S3, H, L, d.Hp, d.Lp, dw3, db3};
+  return hip_rc(e, "k_dechead_unpad", profiled(e, PC_DECODER, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_dechead_unpad, dim3(lat_blocks((int64_t)I * ((H + 3) / 4) + I), 2), dim3(256), 0, st, ua);
     return hipGetLastError();
   }));
 }

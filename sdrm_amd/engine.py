@@ -734,6 +734,67 @@ class Engine:
                                                  _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()), "sdrm_vae_latent_bwd")
         return out
 
+    # ------------------------------------------------------------------ train-mode decoder and loss head (csrc/decoder_train.h)
+    def _decoder_head(self, who, z, w3, b3, w4, b4, csr_dev, rows, row0, b):
+        _, n_items, b, batch = self._csr_batch(who, csr_dev, rows, row0, b)
+        if not isinstance(w3, torch.Tensor) or w3.dim() != 2:
+            raise SdrmError(f"{who}: w3 must be a 2-D tensor [hidden, latent]")
+        hidden, latent = int(w3.shape[0]), int(w3.shape[1])
+        z = self._f32(who, "z", z, (b, latent))
+        w3 = self._f32(who, "w3", w3, (hidden, latent))
+        b3 = self._f32(who, "b3", b3, (hidden,))
+        w4 = self._f32(who, "w4", w4, (n_items, hidden))
+        b4 = self._f32(who, "b4", b4, (n_items,))
+        dec = _lib.VaeDecoder(w3.data_ptr(), b3.data_ptr(), w4.data_ptr(), b4.data_ptr(), latent, hidden, n_items)
+        return dec, z, (b, latent, hidden, n_items), batch
+
+    def vae_decoder_nll_fwd(self, z, w3, b3, w4, b4, csr_dev, rows=None, row0=0, b=None, check=True):
+        """train_SDRM.py:252-254 and :141-142 in train mode: `-mean(sum(log_softmax(decoder(z)) * X))` for z [b, latent], the decoder's
+        four tensors w3 [hidden, latent], b3 [hidden], w4 [n_items, hidden], b4 [n_items] as `nn.Linear` holds them, and the X whose
+        rows are the rows `rows` (or row0 .. row0+b-1) of a `csr_to_device` matrix.  Returns (loss 0-d, saved) float32 device tensors,
+        `saved` = (h3 [b, hidden], logits [b, n_items], lse [b]) being what `vae_decoder_nll_bwd` takes; nothing is read back.  Range
+        checks and `check` as in `csr_rows_to_dense`."""
+        who = "vae_decoder_nll_fwd"
+        dec, z, (b, latent, hidden, n_items), batch = self._decoder_head(who, z, w3, b3, w4, b4, csr_dev, rows, row0, b)
+        h3 = torch.empty(b, hidden, dtype=torch.float32, device=self.device)
+        logits = torch.empty(b, n_items, dtype=torch.float32, device=self.device)
+        lse = torch.empty(b, dtype=torch.float32, device=self.device)
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        self._check(self.lib.sdrm_vae_decoder_nll_fwd(self._h, C.byref(dec), _ptr(z), *batch, _ptr(h3), _ptr(logits), _ptr(lse), _ptr(loss),
+                                                      _stream()), "sdrm_vae_decoder_nll_fwd")
+        if check:
+            self.feed_status()
+        return loss, (h3, logits, lse)
+
+    def vae_decoder_nll_bwd(self, saved, z, w3, b3, w4, b4, csr_dev, rows=None, row0=0, b=None, scale=None, need_dz=True, out=None):
+        """Its backward: (dz [b, latent] | None, dw3, db3, dw4, db4) for `saved` as the forward returned it, the z and the tensors that
+        forward read and the same batch.  `scale`: a float32 device tensor of one element (the upstream gradient; None = 1).
+        `need_dz=False` skips the gradient of z (returned as None).  Every element of the results is written once: `out` = (dz | None,
+        dw3, db3, dw4, db4) needs no zeroing.  The range checks land in the status word `feed_status` reads."""
+        who = "vae_decoder_nll_bwd"
+        if not isinstance(saved, (tuple, list)) or len(saved) != 3 or not all(isinstance(t, torch.Tensor) for t in saved):
+            raise SdrmError(f"{who}: saved must be the (h3, logits, lse) a vae_decoder_nll_fwd returned")
+        dec, z, (b, latent, hidden, n_items), batch = self._decoder_head(who, z, w3, b3, w4, b4, csr_dev, rows, row0, b)
+        h3 = self._f32(who, "h3", saved[0], (b, hidden))
+        logits = self._f32(who, "logits", saved[1], (b, n_items))
+        lse = self._f32(who, "lse", saved[2], (b,))
+        if scale is not None:
+            scale = self._index(who, "scale", scale, torch.float32, 1)
+        names = ("dz", "dw3", "db3", "dw4", "db4")
+        shapes = ((b, latent), (hidden, latent), (hidden,), (n_items, hidden), (n_items,))
+        if out is None:
+            out = tuple(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes)
+        else:
+            out = tuple(None if (name == "dz" and (t is None or not need_dz)) else self._f32(who, name, t, s)
+                        for name, t, s in zip(names, out, shapes))
+            if need_dz and out[0] is None:
+                raise SdrmError(f"{who}: out[0] (dz) is None but need_dz is set")
+        dz = out[0] if need_dz else None
+        self._check(self.lib.sdrm_vae_decoder_nll_bwd(self._h, C.byref(dec), _ptr(z), _ptr(h3), _ptr(logits), _ptr(lse), *batch, _ptr(scale),
+                                                      _ptr(dz), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _stream()),
+                    "sdrm_vae_decoder_nll_bwd")
+        return (dz,) + tuple(out[1:])
+
     def csc_to_device(self, m):
         """(colptr i64, rowidx i32, data f32 | None for an all-ones matrix, shape) of a scipy sparse matrix, on the device: the
         matrix `csr_to_device` ships (duplicates summed, indices sorted), by columns, row indices ascending within a column."""

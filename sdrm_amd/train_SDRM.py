@@ -34,7 +34,7 @@ from torch.nn import functional as F
 
 from . import synth
 from .engine import Engine, SdrmError
-from .vae_hooks import (VAE, SparseFeed, checkpoint, evaluate_holdout, latent_head, multinomial_nll, resume,  # noqa: F401  (part of the
+from .vae_hooks import (VAE, SparseFeed, checkpoint, decoder_nll, evaluate_holdout, latent_head, multinomial_nll, resume,  # noqa: F401  (part of the
                         sparse_input_linear, train_variational_autoencoder)                                   # reference's module surface)
 
 warnings.filterwarnings("ignore")

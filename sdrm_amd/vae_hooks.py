@@ -91,6 +91,12 @@ class VAE(nn.Module):
     def decode(self, z):
         return self.decoder(z)
 
+    def decode_nll(self, z, csr_dev, rows=None, row0=0, b=None):
+        """`multinomial_nll(self.decode(z), ...)` in train mode without a torch Linear: the decoder, the loss against the rows `rows`
+        (or row0 .. row0+b-1) of a `csr_to_device` matrix and the backward of both are `decoder_nll` (csrc/decoder_train.h)."""
+        return decoder_nll(z, self.decoder[0].weight, self.decoder[0].bias, self.decoder[2].weight, self.decoder[2].bias, csr_dev,
+                           rows=rows, row0=row0, b=b)
+
     def forward(self, x):
         z, kl = self.encode(x)
         return self.decode(z), kl
@@ -242,8 +248,48 @@ def latent_head(pre, w2, b2, rows, row0, seed, step, eps=None):
     return _LatentHead.apply(pre, w2, b2, rows, int(row0), int(seed), int(step), eps)
 
 
+class _DecoderNLL(torch.autograd.Function):
+    """`-mean(sum(log_softmax(decoder(z)) * X))` (:252-254, :141-142) for decoder = Linear -> Tanh -> Linear given as its four tensors
+    and X given as CSR rows on the device: both directions are launches of csrc/decoder_train.h on the utility engine,
+    once-differentiable, nothing is read back (the range checks wait for `feed_status()`)."""
+
+    @staticmethod
+    def forward(ctx, z, w3, b3, w4, b4, csr_dev, rows, row0, b):
+        eng = utility_engine(z.device)
+        tensors = tuple(t.detach().contiguous() for t in (z, w3, b3, w4, b4))
+        rows = None if rows is None else eng._dev(rows, torch.int64)
+        loss, saved = eng.vae_decoder_nll_fwd(*tensors, csr_dev, rows=rows, row0=row0, b=b, check=False)
+        ctx.save_for_backward(*tensors, *saved)
+        ctx.batch = (eng, csr_dev, rows, row0, b)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        z, w3, b3, w4, b4, h3, logits, lse = ctx.saved_tensors
+        eng, csr_dev, rows, row0, b = ctx.batch
+        scale = grad_output.to(dtype=torch.float32).contiguous()   # its device pointer is the kernel's `scale`
+        need = ctx.needs_input_grad
+        grads = eng.vae_decoder_nll_bwd((h3, logits, lse), z, w3, b3, w4, b4, csr_dev, rows=rows, row0=row0, b=b, scale=scale, need_dz=need[0])
+        return tuple(g if n else None for g, n in zip(grads, need[:5])) + (None, None, None, None)
+
+
+def decoder_nll(z, w3, b3, w4, b4, csr_dev, rows=None, row0=0, b=None):
+    """The decoder and the loss term of the pre-stage's train half (:252-254, :141-142) as a 0-dim device tensor with gradients for z
+    [b, latent], w3 [hidden, latent], b3 [hidden], w4 [n_items, hidden] and b4 [n_items] (float32 on a ROCm device), against the rows
+    `rows` (or row0 .. row0+b-1; default all b = z.shape[0] rows from row0) of a `csr_to_device` matrix.  No [b, n_items] tensor passes
+    through torch's autograd; the backward hands `grad_output` to the gradient kernel as a device scalar and skips the gradient of a z
+    that needs none.  A CSR out of range surfaces at the next `utility_engine().feed_status()`."""
+    if not z.is_cuda:
+        raise SdrmError("decoder_nll: z must be on a ROCm device (there is no CPU fallback)")
+    if rows is None and b is None:
+        b = z.shape[0]
+    return _DecoderNLL.apply(z, w3, b3, w4, b4, csr_dev, rows, int(row0), b)
+
+
 SPARSE_INPUT_MAX_HIDDEN = 4096   # the widest hidden layer csrc/input_layer.h takes
 LATENT_HEAD_MAX_LATENT = 4096    # the widest latent layer csrc/latent.h takes
+DECODER_HEAD_MAX_HIDDEN = 4096   # the widest hidden and latent layers csrc/decoder_train.h takes
 
 
 def evaluate_holdout(model, eng, test_csr_dev, seed, draw, early_stop_metric, batch=500):
@@ -270,7 +316,7 @@ def evaluate_holdout(model, eng, test_csr_dev, seed, draw, early_stop_metric, ba
 
 def train_variational_autoencoder(model, train_data, test_data, epochs, batch_size, lr, early_stop_metric="NDCG@50",
                                   VAE_DIR_PATH="./", verbose=False, device_feed=False, sparse_input=False, device_holdout=False,
-                                  device_latent=False):
+                                  device_latent=False, device_decoder=False):
     """VAE pre-stage (:115-188): multinomial NLL + annealed KL, early stopping on Recall/NDCG@k of a
     per-user hold-out of `test_data`, best epoch restored.  Plain PyTorch (not part of the hot path) - except, with
     `device_feed=True` and the model on a ROCm device, the feed and the loss head: the CSR matrices stay in HBM, every train and
@@ -297,13 +343,21 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
     in both directions.  Its reparameterisation noise is the engine's Philox draw keyed by `latent_seed`, `step = int(anneal_count)`
     and the feed row, not `torch.randn_like`: such a run no longer consumes torch's generator in the train half (the evaluation half's
     `encode` still does) and is not bit-comparable with the other paths.  `latent_seed` is ONE extra draw from `np.random`
-    (`randint(2**63)`), taken after `sparse_input`'s and `device_holdout`'s seeds and before the first permutation."""
+    (`randint(2**63)`), taken after `sparse_input`'s and `device_holdout`'s seeds and before the first permutation.
+    `device_decoder=True` (with `device_feed=True`, the model on a ROCm device and hidden and latent layers of at most 4096; ignored
+    otherwise) puts the decoder and the loss term of the train half on the engine: `model.decode_nll(z, csr, rows=...)` in place of
+    `model.decode(z)` + `multinomial_nll`, both directions being `decoder_nll` (csrc/decoder_train.h) - no [batch, n_items] tensor
+    passes through torch's autograd and, with all five flags on, the train half runs no torch `Linear`.  `z` comes from `encode_rows`
+    (with `sparse_input`) or from `model.encode(X)` (dense feed).  The decoder draws nothing: the flag adds no draw from `np.random` or
+    torch, and differs from the same run without it by fp32 rounding alone.  The evaluation half, `decode` and `forward` are unchanged."""
     os.makedirs(os.path.normpath(VAE_DIR_PATH), exist_ok=True)
     dev = next(model.parameters()).device
     device_feed = bool(device_feed) and dev.type == "cuda"
     sparse_input = bool(sparse_input) and device_feed and model.encoder[0].out_features <= SPARSE_INPUT_MAX_HIDDEN
     device_holdout = bool(device_holdout) and device_feed
     device_latent = bool(device_latent) and sparse_input and model.latent_dim <= LATENT_HEAD_MAX_LATENT
+    device_decoder = (bool(device_decoder) and device_feed and model.decoder[0].out_features <= DECODER_HEAD_MAX_HIDDEN
+                      and model.latent_dim <= DECODER_HEAD_MAX_HIDDEN)
     anneal_cap, anneal_count = 0.2, 0.0
     best_metric, best_epoch, stale = -np.inf, 0, 0
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
@@ -347,10 +401,14 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
                     z, kl = model.encode_rows(feed, lo, hi, drop_seed, int(anneal_count), latent_seed=latent_seed)
                 else:
                     z, kl = model.encode_rows(feed, lo, hi, drop_seed, int(anneal_count))
-                out = model.decode(z)
+                out = None if device_decoder else model.decode(z)
+            elif device_decoder:
+                z, kl = model.encode(X)
             else:
                 out, kl = model(X)
-            if device_feed:
+            if device_decoder:
+                neg_ll = model.decode_nll(z, csr, rows=order_dev[lo:hi])
+            elif device_feed:
                 neg_ll = multinomial_nll(out, csr, rows=order_dev[lo:hi])
             else:
                 neg_ll = -torch.mean(torch.sum(F.log_softmax(out, dim=1) * X, dim=1))
