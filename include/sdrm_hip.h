@@ -455,6 +455,36 @@ int sdrm_vae_decoder_nll_fwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const 
 int sdrm_vae_decoder_nll_bwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z, const float* h3, const float* logits, const float* lse,
                              const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, const int64_t* rows,
                              int64_t row0, int b, const float* scale, float* dz, float* dw3, float* db3, float* dw4, float* db4, void* stream);
+/* Adam over caller-owned tensors in ONE launch, and the loss value of a pre-stage step (reference: train_SDRM.py:126
+ * `torch.optim.Adam(model.parameters(), lr)`, :143-150 `loss = neg_ll + anneal * kl + model.get_l2_reg()` ... `optimizer.step()`, :262-268
+ * get_l2_reg).  Per tensor p, g, m, v: float32, contiguous, n elements each, on the device; p, m, v are updated in place, g is read only:
+ *   g' = g + 2 l2_coef p        (the gradient of the loss term l2_coef * sum(p^2), folded in; l2_coef = weight_decay for a `.weight`, 0 for a bias)
+ *   m = beta1 m + (1 - beta1) g'        v = beta2 v + (1 - beta2) g'^2
+ *   p -= (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * torch.optim.Adam's update in its default form (no amsgrad, not maximize), in fp32 with contraction off and the hardware's sqrt / rcp
+ * (1 ulp each: csrc/elementwise.h adam_math, the eps-net's own); the two bias corrections are formed on the host in double from the
+ * float betas.  `step` >= 1 is the count AFTER this update and is the caller's number: nothing of the optimizer lives in the handle,
+ * two optimizers may share an engine.  Work is dealt in chunks of 4096 elements, one work-group each: a tensor of n elements is
+ * ceil(n / 4096) chunks, 16 tensors go into one launch, more go out as successive launches of the same kernel.  A tensor whose four
+ * pointers are 16-byte aligned is read and written with 16-byte accesses (its last partial quad by dwords), any other by dwords; no
+ * access falls outside [ptr, ptr + n).
+ * l2_partials (device, float64, l2_capacity elements; may be null): when given and some l2_coef > 0, slot c of it receives sum(p^2) over
+ * chunk c of the table - the weights BEFORE the update, 0 for a chunk of a tensor with l2_coef == 0 - summed in float64 in a fixed order
+ * (no atomic): every slot below the chunk count is written, none is read, the buffer needs no zeroing.  With every l2_coef == 0 nothing
+ * is summed and the buffer is not touched.
+ * sdrm_vae_loss_slot: *out = (*neg_ll + anneal * *kl) + (float)(weight_decay * sum(l2_partials[0 .. n_partials))) from device scalars, in
+ * torch's parenthesisation of `neg_ll + anneal * kl + l2` on float32 with contraction off; the partials are added in float64 in a fixed
+ * order by one work-group.  l2_partials == null: the last term is +0.0f (what get_l2_reg returns for weight_decay == 0), and the value
+ * equals torch's for the same two scalars to the bit.  `out` is ONE float on the device, e.g. a slot of a per-epoch loss buffer.
+ * Refusals, before any launch: a null pointer, step < 1, a negative l2_coef, or two of the 4 x n_tensors ranges [ptr, ptr + n) sharing
+ * a byte (ranges that only touch are fine) are SDRM_ERR_ARG; n_tensors <= 0, n outside 1 .. 2^40, more than 2^30 chunks, l2_capacity
+ * below the chunk count while l2_partials is given and some l2_coef > 0, or n_partials < 1 with l2_partials given are SDRM_ERR_SHAPE.
+ * Both calls are deterministic from call to call, use no atomics, do not synchronise and read nothing back. */
+typedef struct sdrm_vae_adam_tensor { float* p; const float* g; float* m; float* v; int64_t n; float l2_coef; } sdrm_vae_adam_tensor;
+int sdrm_vae_adam_step(sdrm_engine* e, const sdrm_vae_adam_tensor* t, int n_tensors, int64_t step, float lr, float beta1, float beta2,
+                       float eps, double* l2_partials, int64_t l2_capacity, void* stream);
+int sdrm_vae_loss_slot(sdrm_engine* e, const float* neg_ll, const float* kl, float anneal, const double* l2_partials, int64_t n_partials,
+                       float weight_decay, float* out, void* stream);
 /* Per-user hold-out split on the device, CSR in, two CSRs out (reference: utilities.py:174-236,
  * split_train_test_proportion_from_csr_matrix with ignore_zeros=False, which train_SDRM.py:161 calls once per pre-stage epoch): of
  * the n stored entries of a user with n >= 2, m = ceil(test_prop * n) chosen uniformly without replacement go to the held-out

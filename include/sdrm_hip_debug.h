@@ -42,6 +42,15 @@ int sdrm_debug_latent_args(int hidden, int latent, int b, int64_t row0, int cont
  * SDRM_OK.  Pure function: callable without a GPU. */
 int sdrm_debug_decoder_nll_args(int latent, int hidden, int n_items, int b, int64_t row0, int64_t n_rows, int contiguous);
 
+/* What sdrm_vae_adam_step checks on the host before any launch, on integers: addr [4 n_tensors] holds the addresses p, g, m, v of every
+ * tensor, n [n_tensors] their element counts, l2_coef [n_tensors] their L2 coefficients; `has_partials` != 0: an l2_partials buffer of
+ * l2_capacity elements is given.  The refusals are that entry point's (SDRM_ERR_ARG: a null array or address, step < 1, a negative
+ * l2_coef, two of the ranges [addr, addr + 4 n) sharing a byte; SDRM_ERR_SHAPE: n_tensors <= 0, n outside 1 .. 2^40, more than 2^30
+ * chunks, l2_capacity below the chunk count while some l2_coef > 0), else SDRM_OK with the chunk count of the table, sum over the
+ * tensors of ceil(n / 4096), in *chunks_out (may be NULL).  Pure function: callable without a GPU. */
+int sdrm_debug_vae_adam_args(const uint64_t* addr, const int64_t* n, const float* l2_coef, int n_tensors, int64_t step, int has_partials,
+                             int64_t l2_capacity, int64_t* chunks_out);
+
 /* What sdrm_holdout_split checks and derives on the host before any launch: SDRM_ERR_SHAPE outside its envelope (1 <= n_items <=
  * 2^20, 1 <= n_rows < 2^31, 0 <= nnz < 2^40, 0 < test_prop < 1), else SDRM_OK with the held-out count of a row of n_u entries,
  * n_u < 2 ? 0 : min(n_u, (int64)ceil(test_prop * (double)n_u)), in *m_out (may be NULL).  Pure function: callable without a GPU. */

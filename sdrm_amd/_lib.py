@@ -23,6 +23,10 @@ class VaeDecoder(C.Structure):
                 ("n_items", c_int)]
 
 
+class VaeAdamTensor(C.Structure):
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64), ("l2_coef", c_float)]
+
+
 class VaeEncoder(C.Structure):
     _fields_ = [("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("n_items", c_int), ("hidden", c_int),
                 ("latent", c_int)]
@@ -104,6 +108,9 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_vae_decoder_nll_bwd": (c_int, [c_void_p, C.POINTER(VaeDecoder), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdrm_vae_adam_step": (c_int, [c_void_p, C.POINTER(VaeAdamTensor), c_int, c_int64, c_float, c_float, c_float, c_float, c_void_p, c_int64,
+                                   c_void_p]),
+    "sdrm_vae_loss_slot": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "sdrm_holdout_split": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, C.c_double, c_uint64, C.c_uint32, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
     "sdrm_equal_sparsity": (c_int, [c_void_p, c_void_p, c_int64, C.c_double, c_void_p, c_void_p, c_void_p]),
@@ -119,6 +126,8 @@ SIGNATURES = {
     "sdrm_debug_input_layer_args": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, c_float, C.POINTER(C.c_uint32), C.POINTER(c_float)]),
     "sdrm_debug_latent_args": (c_int, [c_int, c_int, c_int, c_int64, c_int]),
     "sdrm_debug_decoder_nll_args": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int]),
+    "sdrm_debug_vae_adam_args": (c_int, [C.POINTER(c_uint64), C.POINTER(c_int64), C.POINTER(c_float), c_int, c_int64, c_int, c_int64,
+                                         C.POINTER(c_int64)]),
     "sdrm_debug_holdout_args": (c_int, [c_int, c_int64, c_int64, C.c_double, c_int64, C.POINTER(c_int64)]),
     "sdrm_debug_set_tile": (c_int, [c_void_p, c_int]),
     "sdrm_debug_set_nt32_rows": (c_int, [c_void_p, c_int, c_int]),

@@ -37,6 +37,7 @@
 #include "skinny_step.h"
 #include "skinny_fwd4.h"
 #include "tail.h"
+#include "vae_adam.h"
 #include "dgrad_rows.h"
 #include "wgrad2.h"
 
@@ -277,7 +278,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -296,7 +297,8 @@ static const char* kProfNames[PC_COUNT] = {
     "input layer: k_input_fwd / k_input_wgrad train-mode first Linear of the VAE encoder from CSR rows and its weight gradient from CSC columns",
     "hold-out: k_holdout_counts / k_holdout_scan / k_holdout_split per-user hold-out split of a CSR matrix into two (keys ranked per row, a wave or a work-group per row)",
     "latent head: k_latent_stage / gemm_kernel<0,0,0,0,7> / k_latent_reparam forward, k_latent_stage_bwd / k_latent_seed / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / k_latent_unpad backward of the VAE encoder behind its first pre-activation in train mode",
-    "decoder head: k_pad2d / gemm_kernel<0,0,0,0,1> / k_dechead_h3 / gemm_kernel<0,0,0,0,7> / k_nll_rows / k_nll_sum forward, k_dechead_stage_bwd / k_dechead_grad / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / gemm_kernel<0,0,0,0,7> / k_dechead_unpad backward of the VAE decoder and the multinomial loss in train mode"};
+    "decoder head: k_pad2d / gemm_kernel<0,0,0,0,1> / k_dechead_h3 / gemm_kernel<0,0,0,0,7> / k_nll_rows / k_nll_sum forward, k_dechead_stage_bwd / k_dechead_grad / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / gemm_kernel<0,0,0,0,7> / k_dechead_unpad backward of the VAE decoder and the multinomial loss in train mode",
+    "optimizer: k_vae_adam / k_vae_loss_slot Adam over the VAE pre-stage's parameter tensors in one launch (with the L2 partial sums) and the step's loss value into its slot"};
 
 namespace {
 
@@ -657,11 +659,11 @@ void build_jobs(sdrm_engine* e, JobTable& tab) {
   tab.n = n;
 }
 
-// Adam's bias corrections of step e->adam_t (train_SDRM.py:337; torch.optim.Adam: step_size = lr / (1 - b1^k), denominators
+// Adam's bias corrections of step `step` >= 1 for the given betas (the eps-net's: e->adam_t, 0.9, 0.999 - train_SDRM.py:337; torch.optim.Adam: step_size = lr / (1 - b1^k), denominators
 // scaled by sqrt(1 - b2^k))
-void adam_scalars(const sdrm_engine* e, float lr, float& step_size, float& bc2_sqrt) {
-  const double k = (double)e->adam_t;
-  const double bc1 = 1.0 - std::pow(0.9, k), bc2 = 1.0 - std::pow(0.999, k);
+void adam_scalars(int64_t step, float lr, double beta1, double beta2, float& step_size, float& bc2_sqrt) {
+  const double k = (double)step;
+  const double bc1 = 1.0 - std::pow(beta1, k), bc2 = 1.0 - std::pow(beta2, k);
   step_size = (float)((double)lr / bc1);
   bc2_sqrt = (float)std::sqrt(bc2);
 }
@@ -672,7 +674,7 @@ int launch_adam(sdrm_engine* e, const float* grad, float lr, int update, hipStre
   AdamArgs a{};
   a.p = e->p; a.m = e->m; a.v = e->v; a.g = grad ? grad : e->g;
   a.b1 = 0.9f; a.b2 = 0.999f; a.eps = 1e-8f; a.wd = 1e-4f; a.update = update;
-  if (update) adam_scalars(e, lr, a.step_size, a.bc2_sqrt);
+  if (update) adam_scalars(e->adam_t, lr, 0.9, 0.999, a.step_size, a.bc2_sqrt);
   // enough work-groups that the largest tensor is one or two passes per thread (a pass is a chain of dependent loads)
   int64_t biggest = 0;
   for (int k = 0; k < tab.n; ++k) biggest = std::max<int64_t>(biggest, (int64_t)tab.j[k].rows * tab.j[k].cols);
@@ -2027,7 +2029,7 @@ int backward_tail(sdrm_engine* e, float* gout, int which, bool update, float lr,
   a.off_we = e->off_we; a.off_be = e->off_be; a.off_w0 = e->off_w0; a.off_b0 = e->off_b0;
   a.Mred = e->Mred; a.snap = e->snap; a.WeP = e->WeP; a.W0eP = e->W0eP; a.TPe = e->TPe;
   a.b1 = 0.9f; a.b2 = 0.999f; a.eps = 1e-8f; a.wd = 1e-4f; a.update = update ? 1 : 0;
-  if (update) adam_scalars(e, lr, a.step_size, a.bc2_sqrt);
+  if (update) adam_scalars(e->adam_t, lr, 0.9, 0.999, a.step_size, a.bc2_sqrt);
   int per_lane = 0;   // most slabs any lane of a weight job sums
   for (int q = 0; q < n; ++q)
     if (a.j[q].kind == TJ_MAT) per_lane = std::max(per_lane, (a.j[q].nslabs + a.j[q].lanes - 1) / a.j[q].lanes);
@@ -3347,6 +3349,104 @@ int sdrm_vae_decoder_nll_bwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const 
   ua.seg[1] = DecUnpadSeg{slab3, dbs3, d.S3, H, L, d.Hp, d.Lp, dw3, db3};
   return hip_rc(e, "k_dechead_unpad", profiled(e, PC_DECODER, 0.0, st, [&] {
     SDRM_LAUNCH(e, k_dechead_unpad, dim3(lat_blocks((int64_t)I * ((H + 3) / 4) + I), 2), dim3(256), 0, st, ua);
+    return hipGetLastError();
+  }));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Adam over caller-owned tensors and the loss value of a pre-stage step (train_SDRM.py:126, :143-150), csrc/vae_adam.h.
+// The host side that needs no device: every refusal of sdrm_vae_adam_step, on integers, and the chunk count of the table.
+int sdrm_debug_vae_adam_args(const uint64_t* addr, const int64_t* n, const float* l2_coef, int n_tensors, int64_t step, int has_partials,
+                             int64_t l2_capacity, int64_t* chunks_out) {
+  if (!addr || !n || !l2_coef) return SDRM_ERR_ARG;
+  if (n_tensors <= 0) return SDRM_ERR_SHAPE;
+  if (step < 1) return SDRM_ERR_ARG;
+  int64_t chunks = 0;
+  bool any_l2 = false;
+  for (int i = 0; i < n_tensors; ++i) {
+    for (int j = 0; j < 4; ++j)
+      if (addr[4 * i + j] == 0) return SDRM_ERR_ARG;
+    if (n[i] <= 0 || n[i] > ((int64_t)1 << 40)) return SDRM_ERR_SHAPE;
+    if (!(l2_coef[i] >= 0.f)) return SDRM_ERR_ARG;   // (a nan as well)
+    any_l2 = any_l2 || l2_coef[i] > 0.f;
+    chunks += (n[i] + VADAM_CHUNK - 1) / VADAM_CHUNK;
+    if (chunks > ((int64_t)1 << 30)) return SDRM_ERR_SHAPE;
+  }
+  if (has_partials && any_l2 && l2_capacity < chunks) return SDRM_ERR_SHAPE;
+  // no two of the 4 x n_tensors ranges [ptr, ptr + n) may share a byte (ranges that only touch are fine)
+  std::vector<std::pair<uint64_t, uint64_t>> span((size_t)4 * n_tensors);
+  for (int i = 0; i < n_tensors; ++i)
+    for (int j = 0; j < 4; ++j) {
+      const uint64_t lo = addr[4 * i + j], bytes = (uint64_t)n[i] * sizeof(float);
+      if (lo + bytes < lo) return SDRM_ERR_ARG;   // wraps the address space
+      span[(size_t)4 * i + j] = {lo, lo + bytes};
+    }
+  std::sort(span.begin(), span.end());
+  for (size_t k = 1; k < span.size(); ++k)
+    if (span[k].first < span[k - 1].second) return SDRM_ERR_ARG;
+  if (chunks_out) *chunks_out = chunks;
+  return SDRM_OK;
+}
+
+int sdrm_vae_adam_step(sdrm_engine* e, const sdrm_vae_adam_tensor* t, int n_tensors, int64_t step, float lr, float beta1, float beta2,
+                       float eps, double* l2_partials, int64_t l2_capacity, void* stream) {
+  const char* who = "sdrm_vae_adam_step";
+  if (!e) return SDRM_ERR_ARG;
+  if (!t) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (n_tensors <= 0) return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": n_tensors <= 0");
+  std::vector<uint64_t> addr((size_t)4 * n_tensors);
+  std::vector<int64_t> n(n_tensors);
+  std::vector<float> coef(n_tensors);
+  for (int i = 0; i < n_tensors; ++i) {
+    addr[4 * i] = (uint64_t)(uintptr_t)t[i].p; addr[4 * i + 1] = (uint64_t)(uintptr_t)t[i].g;
+    addr[4 * i + 2] = (uint64_t)(uintptr_t)t[i].m; addr[4 * i + 3] = (uint64_t)(uintptr_t)t[i].v;
+    n[i] = t[i].n; coef[i] = t[i].l2_coef;
+  }
+  int64_t chunks = 0;
+  if (int rc = sdrm_debug_vae_adam_args(addr.data(), n.data(), coef.data(), n_tensors, step, l2_partials != nullptr, l2_capacity, &chunks))
+    return fail(e, rc, std::string(who) + ": a null pointer, step < 1, a negative l2_coef or two of the ranges [ptr, ptr + n) overlapping (SDRM_ERR_ARG); "
+                                          "n outside 1 .. 2^40, more than 2^30 chunks of 4096 elements, or l2_capacity below the chunk count (SDRM_ERR_SHAPE)");
+  bool any_l2 = false;
+  for (int i = 0; i < n_tensors; ++i) any_l2 = any_l2 || coef[i] > 0.f;
+  VAdamArgs a{};
+  adam_scalars(step, lr, (double)beta1, (double)beta2, a.step_size, a.bc2_sqrt);
+  a.b1 = beta1; a.b2 = beta2; a.eps = eps;
+  a.l2_partials = any_l2 ? l2_partials : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned chunk0 = 0;
+  for (int i0 = 0; i0 < n_tensors; i0 += VADAM_MAX_TENSORS) {
+    VAdamTable tab{};
+    tab.n = std::min(VADAM_MAX_TENSORS, n_tensors - i0);
+    unsigned c = 0;
+    for (int k = 0; k < tab.n; ++k) {
+      const sdrm_vae_adam_tensor& s = t[i0 + k];
+      VAdamTensor& d = tab.t[k];
+      d.p = s.p; d.g = s.g; d.m = s.m; d.v = s.v; d.n = s.n;
+      d.wd2 = 2.f * s.l2_coef;
+      d.first_chunk = c;
+      d.vector_ok = (((uintptr_t)s.p | (uintptr_t)s.g | (uintptr_t)s.m | (uintptr_t)s.v) & 15u) == 0;
+      c += (unsigned)((s.n + VADAM_CHUNK - 1) / VADAM_CHUNK);
+    }
+    a.chunk0 = chunk0;
+    if (int rc = hip_rc(e, "k_vae_adam", profiled(e, PC_VAE_ADAM, 0.0, st, [&] {
+          SDRM_LAUNCH(e, k_vae_adam, dim3(c), dim3(256), 0, st, tab, a);
+          return hipGetLastError();
+        })))
+      return rc;
+    chunk0 += c;
+  }
+  return SDRM_OK;
+}
+
+int sdrm_vae_loss_slot(sdrm_engine* e, const float* neg_ll, const float* kl, float anneal, const double* l2_partials, int64_t n_partials,
+                       float weight_decay, float* out, void* stream) {
+  const char* who = "sdrm_vae_loss_slot";
+  if (!e) return SDRM_ERR_ARG;
+  if (!neg_ll || !kl || !out) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (l2_partials && n_partials < 1) return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": l2_partials given with n_partials < 1");
+  hipStream_t st = (hipStream_t)stream;
+  return hip_rc(e, "k_vae_loss_slot", profiled(e, PC_VAE_ADAM, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_vae_loss_slot, dim3(1), dim3(256), 0, st, neg_ll, kl, anneal, l2_partials, n_partials, weight_decay, out);
     return hipGetLastError();
   }));
 }

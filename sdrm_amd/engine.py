@@ -795,6 +795,62 @@ class Engine:
                     "sdrm_vae_decoder_nll_bwd")
         return (dz,) + tuple(out[1:])
 
+    # ------------------------------------------------------------------ Adam over caller-owned tensors, the step's loss value (csrc/vae_adam.h)
+    def vae_adam_step(self, params, grads, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, l2_coefs=None, l2_partials=None):
+        """`torch.optim.Adam.step()` in its default form (train_SDRM.py:126, :150) for lists of float32 device tensors in ONE launch per
+        16 tensors (sdrm_vae_adam_step): `params`, `exp_avg`, `exp_avg_sq` are updated in place, `grads` are read.  `step` >= 1 is the
+        count after this update - the caller's number, the engine keeps nothing of the optimizer.  `l2_coefs`: per tensor the
+        coefficient c of a loss term c * sum(p^2) whose gradient 2 c p is folded into the update (None: none); `l2_partials`: a
+        float64 device tensor with one element per 4096-element chunk of the tensors, which then receives sum(p^2) of the weights
+        before the update per chunk of every tensor with a coefficient (what `vae_loss_slot` adds up).  Returns nothing."""
+        who = "vae_adam_step"
+        k = len(params)
+        if not (len(grads) == len(exp_avg) == len(exp_avg_sq) == k) or (l2_coefs is not None and len(l2_coefs) != k):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: params, grads, exp_avg, exp_avg_sq (and l2_coefs) must have one entry per tensor")
+        if k == 0:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: n_tensors <= 0")
+        dev, f32 = self.device, torch.float32
+        tab = (_lib.VaeAdamTensor * k)()
+        for i in range(k):
+            p = params[i]
+            n = p.numel()
+            row = tab[i]
+            for name, t in (("p", p), ("g", grads[i]), ("m", exp_avg[i]), ("v", exp_avg_sq[i])):
+                if not isinstance(t, torch.Tensor) or t.dtype != f32 or t.device != dev or not t.is_contiguous() or t.numel() != n:
+                    raise SdrmError(f"{who}: tensor {i}: {name} must be a contiguous float32 tensor of {n} element(s) on the engine's device")
+                setattr(row, name, t.data_ptr())
+            row.n = n
+            row.l2_coef = 0.0 if l2_coefs is None else float(l2_coefs[i])
+        cap = 0
+        if l2_partials is not None:
+            if (not isinstance(l2_partials, torch.Tensor) or l2_partials.dtype != torch.float64 or l2_partials.device != dev
+                    or not l2_partials.is_contiguous()):
+                raise SdrmError(f"{who}: l2_partials must be a contiguous float64 tensor on the engine's device")
+            cap = l2_partials.numel()
+        self._check(self.lib.sdrm_vae_adam_step(self._h, tab, k, int(step), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                                _ptr(l2_partials), cap, _stream()), "sdrm_vae_adam_step")
+
+    def vae_loss_slot(self, neg_ll, kl, anneal, out, slot, l2_partials=None, weight_decay=0.0):
+        """`out[slot] = neg_ll + anneal * kl + weight_decay * sum(l2_partials)` (train_SDRM.py:143) from two float32 device scalars, in
+        torch's order of operations (sdrm_vae_loss_slot): `out` is a float32 device vector, e.g. an epoch's loss buffer, of which only
+        element `slot` is written.  Without `l2_partials` the last term is +0.0, and the value is torch's to the bit.  Returns nothing."""
+        who = "vae_loss_slot"
+        for name, t in (("neg_ll", neg_ll), ("kl", kl)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device or t.numel() != 1:
+                raise SdrmError(f"{who}: {name} must be a float32 device tensor of 1 element")
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != self.device or out.dim() != 1 or not out.is_contiguous():
+            raise SdrmError(f"{who}: out must be a contiguous float32 vector on the engine's device")
+        slot = int(slot)
+        if not 0 <= slot < out.numel():
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: slot {slot} outside the buffer's {out.numel()} element(s)")
+        n_part = 0
+        if l2_partials is not None:
+            if l2_partials.dtype != torch.float64 or l2_partials.device != self.device or not l2_partials.is_contiguous():
+                raise SdrmError(f"{who}: l2_partials must be a contiguous float64 tensor on the engine's device")
+            n_part = l2_partials.numel()
+        self._check(self.lib.sdrm_vae_loss_slot(self._h, _ptr(neg_ll), _ptr(kl), float(anneal), _ptr(l2_partials), n_part, float(weight_decay),
+                                                C.c_void_p(out.data_ptr() + 4 * slot), _stream()), "sdrm_vae_loss_slot")
+
     def csc_to_device(self, m):
         """(colptr i64, rowidx i32, data f32 | None for an all-ones matrix, shape) of a scipy sparse matrix, on the device: the
         matrix `csr_to_device` ships (duplicates summed, indices sorted), by columns, row indices ascending within a column."""

@@ -34,8 +34,8 @@ from torch.nn import functional as F
 
 from . import synth
 from .engine import Engine, SdrmError
-from .vae_hooks import (VAE, SparseFeed, checkpoint, decoder_nll, evaluate_holdout, latent_head, multinomial_nll, resume,  # noqa: F401  (part of the
-                        sparse_input_linear, train_variational_autoencoder)                                   # reference's module surface)
+from .vae_hooks import (VAE, DeviceAdam, SparseFeed, checkpoint, decoder_nll, evaluate_holdout, latent_head, multinomial_nll, resume,  # noqa: F401  (part of the
+                        sparse_input_linear, train_variational_autoencoder, vae_train_step)                                   # reference's module surface)
 
 warnings.filterwarnings("ignore")
 
@@ -267,7 +267,8 @@ def _set_schedule_globals(eng):
 def train_SDRM(dl, N_ITEMS, VAE_HIDDEN, VAE_LATENT, VAE_BATCH_SIZE, VAE_LR, DIFF_LATENT, N_HIDDEN_MLP_LAYERS, DIFF_LR,
                DIFF_TRAINING_EPOCHS, TIMESTEPS, noise_divider, VAE_DIR_PATH, TRAIN_PARTIAL_VALID_DATA, VALID_DATA,
                OPTIMIZATION_OBJECTIVE, verbose=False, variational_ae=None, cache_latents=False, engine_encode=False,
-               vae_device_feed=False, vae_device_holdout=False):
+               vae_device_feed=False, vae_device_holdout=False, vae_sparse_input=False, vae_device_latent=False, vae_device_decoder=False,
+               vae_device_optimizer=False):
     """(:271-340) Train the VAE (PyTorch), freeze it, then train the eps-net on its latents in the HIP
     engine.  `dl` yields `(x, _)` with x a sparse/dense [b, N_ITEMS] tensor.  Extras (keyword-only in
     spirit): `variational_ae` = an already trained VAE to reuse; `cache_latents` = encode the feed once
@@ -278,7 +279,10 @@ def train_SDRM(dl, N_ITEMS, VAE_HIDDEN, VAE_LATENT, VAE_BATCH_SIZE, VAE_LR, DIFF
     called as the module it is; `vae_device_feed` = the `device_feed` of `train_variational_autoencoder` for the pre-stage (CSR
     resident in HBM, batches densified there, the NLL term and its gradient on the engine); `vae_device_holdout` = its
     `device_holdout` (the per-epoch hold-out split and the evaluation half on the engine; takes effect only beside
-    `vae_device_feed`).  All off by default: nothing existing changes by a bit."""
+    `vae_device_feed`); `vae_sparse_input`, `vae_device_latent`, `vae_device_decoder`, `vae_device_optimizer` = its `sparse_input`,
+    `device_latent`, `device_decoder` and `device_optimizer` (the train half's input layer, latent head, decoder and loss head, and
+    Adam on the engine; each takes effect under the conditions given there, and with all six the train step runs without autograd).
+    All off by default: nothing existing changes by a bit."""
     if not torch.cuda.is_available():
         raise SdrmError("train_SDRM needs a ROCm device (no CPU fallback)")
     if variational_ae is None:
@@ -286,7 +290,9 @@ def train_SDRM(dl, N_ITEMS, VAE_HIDDEN, VAE_LATENT, VAE_BATCH_SIZE, VAE_LR, DIFF
         train_variational_autoencoder(variational_ae, train_data=TRAIN_PARTIAL_VALID_DATA, test_data=VALID_DATA,
                                       epochs=500, batch_size=VAE_BATCH_SIZE, lr=VAE_LR,
                                       early_stop_metric=OPTIMIZATION_OBJECTIVE, VAE_DIR_PATH=VAE_DIR_PATH, verbose=verbose,
-                                      device_feed=vae_device_feed, device_holdout=vae_device_holdout)
+                                      device_feed=vae_device_feed, device_holdout=vae_device_holdout, sparse_input=vae_sparse_input,
+                                      device_latent=vae_device_latent, device_decoder=vae_device_decoder,
+                                      device_optimizer=vae_device_optimizer)
     assert variational_ae.model_is_trained
     for p in variational_ae.parameters():
         p.requires_grad = False

@@ -292,6 +292,142 @@ LATENT_HEAD_MAX_LATENT = 4096    # the widest latent layer csrc/latent.h takes
 DECODER_HEAD_MAX_HIDDEN = 4096   # the widest hidden and latent layers csrc/decoder_train.h takes
 
 
+ADAM_CHUNK = 4096   # elements per work-group of csrc/vae_adam.h: one float64 L2 partial per chunk of every tensor
+DIRECT_STEP = True   # train_variational_autoencoder takes `vae_train_step` when all six flags are in effect (False: the autograd path)
+
+
+class DeviceAdam:
+    """`torch.optim.Adam(params, lr, betas, eps)` in its default form with the update of all tensors in ONE launch
+    (`Engine.vae_adam_step`, csrc/vae_adam.h), for float32 parameters on a ROCm device.  `weight_decay` is `VAE.weight_decay`, the
+    factor of `get_l2_reg`'s `weight_decay * sum ||W||^2` over the `.weight` tensors (:262-268) - NOT torch.optim.Adam's coupled decay
+    of every parameter: its gradient 2 weight_decay W is folded into the update of the weights, so autograd differentiates the loss
+    without that term, and the term's value comes out of the same launch as float64 partial sums (`l2_partials`, what
+    `Engine.vae_loss_slot` adds).  `named_params`: (name, parameter) pairs, e.g. `model.named_parameters()`.  The moments are allocated
+    once, zero.  `state_dict()` / `load_state_dict()` speak `torch.optim.Adam`'s layout: a state moves between the two optimizers in
+    either direction (torch's own `weight_decay` entry stays 0 there: the L2 term is the loss's, as in the reference)."""
+
+    def __init__(self, named_params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, engine=None):
+        named = list(named_params)
+        if not named:
+            raise SdrmError("DeviceAdam: no parameters")
+        self.names = [n for n, _ in named]
+        self.params = [p for _, p in named]
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.step_count = 0
+        self.engine = engine
+        self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.l2_coefs = [self.weight_decay if n.endswith(".weight") else 0.0 for n in self.names]
+        self.l2_partials = None
+        if self.weight_decay > 0:
+            chunks = sum(-(-p.numel() // ADAM_CHUNK) for p in self.params)
+            self.l2_partials = torch.zeros(chunks, dtype=torch.float64, device=self.params[0].device)
+        self._grad_flat = self._grad_views = None
+
+    def zero_grad(self, set_to_none=True):
+        """Sets every parameter's `.grad` to None (no launch: `step` reads whole gradients, it accumulates nothing)."""
+        for p in self.params:
+            p.grad = None
+
+    def grad_buffers(self):
+        """One gradient buffer per parameter, of its shape, as views of ONE flat float32 vector allocated at the first call (each view
+        on a 64-byte boundary): what `vae_train_step` has the engine's backward calls write through their `out=` arguments."""
+        if self._grad_views is None:
+            offs, total = [], 0
+            for p in self.params:
+                offs.append(total)
+                total += -(-p.numel() // 16) * 16
+            self._grad_flat = torch.zeros(total, dtype=torch.float32, device=self.params[0].device)
+            self._grad_views = [self._grad_flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, self.params)]
+        return self._grad_views
+
+    def step(self, grads=None):
+        """One update from `grads` (a list, one tensor per parameter; default each parameter's `.grad`).  A missing or non-contiguous
+        gradient raises - it is not skipped."""
+        if grads is None:
+            grads = [p.grad for p in self.params]
+        if len(grads) != len(self.params):
+            raise SdrmError("DeviceAdam.step: one gradient per parameter")
+        for name, g in zip(self.names, grads):
+            if g is None or not g.is_contiguous():
+                raise SdrmError(f"DeviceAdam.step: the gradient of {name} is {'None' if g is None else 'not contiguous'}")
+        if self.engine is None:
+            if not self.params[0].is_cuda:
+                raise SdrmError("DeviceAdam.step: the parameters must be on a ROCm device (there is no CPU fallback)")
+            self.engine = utility_engine(self.params[0].device)
+        with torch.no_grad():
+            self.engine.vae_adam_step(self.params, grads, self.exp_avg, self.exp_avg_sq, self.step_count + 1, self.lr,
+                                      betas=self.betas, eps=self.eps, l2_coefs=self.l2_coefs if self.weight_decay > 0 else None,
+                                      l2_partials=self.l2_partials)
+        self.step_count += 1
+
+    def state_dict(self):
+        """`torch.optim.Adam.state_dict()`'s layout: state[i] = {step, exp_avg, exp_avg_sq} (empty before the first step, like torch's)
+        and one param group."""
+        group = torch.optim.Adam([torch.zeros(1)], lr=self.lr, betas=self.betas, eps=self.eps).state_dict()["param_groups"][0]
+        group["params"] = list(range(len(self.params)))
+        state = {}
+        if self.step_count > 0:
+            state = {i: {"step": torch.tensor(float(self.step_count), dtype=torch.float32), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+                     for i, (m, v) in enumerate(zip(self.exp_avg, self.exp_avg_sq))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(self.params):
+            raise SdrmError("DeviceAdam.load_state_dict: one param group over this optimizer's parameters is expected")
+        g = groups[0]
+        if g.get("amsgrad") or g.get("maximize") or g.get("weight_decay"):
+            raise SdrmError("DeviceAdam.load_state_dict: amsgrad, maximize and torch's coupled weight_decay have no counterpart here")
+        state, ids = sd["state"], g["params"]
+        steps = {int(float(state[i]["step"])) for i in ids if i in state}
+        if len(steps) > 1 or (state and len([i for i in ids if i in state]) != len(ids)):
+            raise SdrmError("DeviceAdam.load_state_dict: every parameter must carry a state, all at one step (or none)")
+        with torch.no_grad():
+            for k, i in enumerate(ids):
+                if i in state:
+                    self.exp_avg[k].copy_(state[i]["exp_avg"])
+                    self.exp_avg_sq[k].copy_(state[i]["exp_avg_sq"])
+                else:
+                    self.exp_avg[k].zero_()
+                    self.exp_avg_sq[k].zero_()
+        self.step_count = steps.pop() if steps else 0
+        self.lr, self.betas, self.eps = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"])
+
+
+def vae_train_step(model, feed, lo, hi, drop_seed, latent_seed, step, anneal, opt, loss_out, slot):
+    """One train step of the pre-stage (:139-150) for the rows at places lo .. hi-1 of `feed`'s order (a `SparseFeed` with an order
+    set), as a fixed chain of engine calls under `no_grad`: no `autograd.Function`, no `.grad`, no torch arithmetic but the one
+    reduction `db1 = dpre.sum(0)`.  The calls, their arguments, seeds and `step` are those the autograd path makes
+    (`encode_rows(..., latent_seed=...)` + `decode_nll` + `backward()`), in the order autograd walks them: input layer, latent head,
+    decoder and loss forward; decoder backward (null scale: 1), latent backward with gz = dz and gkl = anneal, input-layer weight
+    gradient; then `opt.step(grads=...)` (a `DeviceAdam`) on gradients written through `out=` into `opt.grad_buffers()`, and the
+    loss `neg_ll + anneal * kl + l2` into `loss_out[slot]` (`Engine.vae_loss_slot`).  `anneal`: a pair (the float, a one-element
+    float32 device tensor holding it - a view of the epoch's uploaded values), or the float alone, which is then uploaded here."""
+    eng = feed.engine
+    if isinstance(anneal, tuple):
+        anneal, anneal_dev = anneal
+    else:
+        anneal_dev = torch.full((1,), float(anneal), dtype=torch.float32, device=eng.device)
+    with torch.no_grad():
+        w1, b1, w2, b2 = model.encoder[0].weight, model.encoder[0].bias, model.encoder[2].weight, model.encoder[2].bias
+        w3, b3, w4, b4 = model.decoder[0].weight, model.decoder[0].bias, model.decoder[2].weight, model.decoder[2].bias
+        dw1, db1, dw2, db2, dw3, db3, dw4, db4 = grads = opt.grad_buffers()
+        rows = feed.order[lo:hi]
+        b, p_drop = hi - lo, model.dropout.p
+        pre, rowscale = eng.vae_input_layer_fwd(w1, b1, feed.csr, rows=rows, row0=lo, b=b, seed=drop_seed, step=step, p_drop=p_drop, check=False)
+        z, kl, saved_lat = eng.vae_latent_fwd(pre, w2, b2, rows=rows, row0=lo, seed=latent_seed, step=step)
+        neg_ll, saved_dec = eng.vae_decoder_nll_fwd(z, w3, b3, w4, b4, feed.csr, rows=rows, check=False)
+        dz = torch.empty_like(z)
+        eng.vae_decoder_nll_bwd(saved_dec, z, w3, b3, w4, b4, feed.csr, rows=rows, scale=None, need_dz=True, out=(dz, dw3, db3, dw4, db4))
+        dpre = torch.empty_like(pre)
+        eng.vae_latent_bwd(saved_lat, w2, dz, anneal_dev, out=(dpre, dw2, db2))
+        eng.vae_input_layer_wgrad(dpre, rowscale, feed.csc, pos=feed.pos, lo=lo, b=b, seed=drop_seed, step=step, p_drop=p_drop, out=dw1, check=False)
+        torch.sum(dpre, 0, out=db1)
+        opt.step(grads=grads)
+        eng.vae_loss_slot(neg_ll, kl, anneal, loss_out, slot, l2_partials=opt.l2_partials, weight_decay=opt.weight_decay)
+
+
 def evaluate_holdout(model, eng, test_csr_dev, seed, draw, early_stop_metric, batch=500):
     """The evaluation half of one pre-stage epoch (:160-177) on the device: the per-user hold-out split of `test_csr_dev` (a
     `csr_to_device` matrix) by `eng.holdout_split(seed=seed, draw=draw)`, then per batch of `batch` users the dense train part
@@ -316,7 +452,7 @@ def evaluate_holdout(model, eng, test_csr_dev, seed, draw, early_stop_metric, ba
 
 def train_variational_autoencoder(model, train_data, test_data, epochs, batch_size, lr, early_stop_metric="NDCG@50",
                                   VAE_DIR_PATH="./", verbose=False, device_feed=False, sparse_input=False, device_holdout=False,
-                                  device_latent=False, device_decoder=False):
+                                  device_latent=False, device_decoder=False, device_optimizer=False):
     """VAE pre-stage (:115-188): multinomial NLL + annealed KL, early stopping on Recall/NDCG@k of a
     per-user hold-out of `test_data`, best epoch restored.  Plain PyTorch (not part of the hot path) - except, with
     `device_feed=True` and the model on a ROCm device, the feed and the loss head: the CSR matrices stay in HBM, every train and
@@ -349,7 +485,17 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
     `model.decode(z)` + `multinomial_nll`, both directions being `decoder_nll` (csrc/decoder_train.h) - no [batch, n_items] tensor
     passes through torch's autograd and, with all five flags on, the train half runs no torch `Linear`.  `z` comes from `encode_rows`
     (with `sparse_input`) or from `model.encode(X)` (dense feed).  The decoder draws nothing: the flag adds no draw from `np.random` or
-    torch, and differs from the same run without it by fp32 rounding alone.  The evaluation half, `decode` and `forward` are unchanged."""
+    torch, and differs from the same run without it by fp32 rounding alone.  The evaluation half, `decode` and `forward` are unchanged.
+    `device_optimizer=True` (with `device_feed=True`, the model on a ROCm device and float32 parameters; ignored otherwise) puts the
+    optimizer and the loss value on the engine: `DeviceAdam` in place of `torch.optim.Adam` - one launch of csrc/vae_adam.h over the
+    eight tensors per step, `zero_grad()` without a launch - autograd differentiates `neg_ll + anneal * kl` only (the gradient of
+    `get_l2_reg` is folded into the update), and the step's loss `neg_ll + anneal * kl + l2` goes through `vae_loss_slot` into a
+    per-epoch device buffer that the epoch's one readback takes, in place of `losses.append(loss.detach())` + `torch.stack`.  With
+    `weight_decay == 0`, the reference's only value, the first step's loss has the bits of the same run without the flag; the updates
+    differ from torch's by the rounding of `adam_math`'s hardware `rcp` / `sqrt` (about 1e-7 of an update).  With all six flags in
+    effect the step is `vae_train_step`: the same engine calls in the same order with the same arguments, under `no_grad`, without
+    an `autograd.Function`, a `.grad` or a torch `Linear` - bit-equal to the autograd path of the same flags (`DIRECT_STEP = False`
+    keeps that one) - and the epoch's anneal values are uploaded once per epoch.  The flag adds no draw from `np.random` or torch."""
     os.makedirs(os.path.normpath(VAE_DIR_PATH), exist_ok=True)
     dev = next(model.parameters()).device
     device_feed = bool(device_feed) and dev.type == "cuda"
@@ -358,9 +504,14 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
     device_latent = bool(device_latent) and sparse_input and model.latent_dim <= LATENT_HEAD_MAX_LATENT
     device_decoder = (bool(device_decoder) and device_feed and model.decoder[0].out_features <= DECODER_HEAD_MAX_HIDDEN
                       and model.latent_dim <= DECODER_HEAD_MAX_HIDDEN)
+    device_optimizer = bool(device_optimizer) and device_feed and all(p.dtype == torch.float32 for p in model.parameters())
+    direct_step = DIRECT_STEP and device_optimizer and device_holdout and device_latent and device_decoder
     anneal_cap, anneal_count = 0.2, 0.0
     best_metric, best_epoch, stale = -np.inf, 0, 0
-    optimizer = torch.optim.Adam(model.parameters(), lr=lr)
+    if device_optimizer:
+        optimizer = DeviceAdam(model.named_parameters(), lr=lr, weight_decay=getattr(model, "weight_decay", 0.0), engine=utility_engine(dev))
+    else:
+        optimizer = torch.optim.Adam(model.parameters(), lr=lr)
     k = int(early_stop_metric.split("@")[1])
     start = time.time()
     n = train_data.shape[0]
@@ -386,9 +537,20 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
                 feed.set_order(order)
         else:
             train_data = train_data[np.random.permutation(n)]
+        if device_optimizer:
+            n_steps = -(-n // batch_size)
+            loss_buf = torch.empty(n_steps, dtype=torch.float32, device=dev)   # the epoch's losses, one slot per step
+        if direct_step:
+            anneal_dev = torch.tensor([min(anneal_cap, 1.0 * (anneal_count + i) / 20_000) for i in range(n_steps)], dtype=torch.float32, device=dev)
         for lo in range(0, n, batch_size):
             hi = min(lo + batch_size, n)
             anneal = min(anneal_cap, 1.0 * anneal_count / 20_000)
+            if direct_step:
+                slot = lo // batch_size
+                vae_train_step(model, feed, lo, hi, drop_seed, latent_seed, int(anneal_count), (anneal, anneal_dev[slot:slot + 1]), optimizer,
+                               loss_buf, slot)
+                anneal_count += 1
+                continue
             if sparse_input:
                 X = None
             elif device_feed:
@@ -412,6 +574,13 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
                 neg_ll = multinomial_nll(out, csr, rows=order_dev[lo:hi])
             else:
                 neg_ll = -torch.mean(torch.sum(F.log_softmax(out, dim=1) * X, dim=1))
+            if device_optimizer:
+                (neg_ll + anneal * kl).backward()
+                optimizer.step()
+                eng.vae_loss_slot(neg_ll.detach(), kl.detach(), anneal, loss_buf, lo // batch_size, l2_partials=optimizer.l2_partials,
+                                  weight_decay=optimizer.weight_decay)
+                anneal_count += 1
+                continue
             loss = neg_ll + anneal * kl + model.get_l2_reg()
             losses.append(loss.detach() if device_feed else loss.item())
             loss.backward()
@@ -444,11 +613,13 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
                         scores.append(fn(pred, valid_test[lo:hi], k=k))
         if device_holdout:
             eng.feed_status()
-            both = torch.cat([torch.stack(losses).double(), scores_dev]).cpu().numpy()   # one readback: the losses and the scores
-            losses, scores = both[:len(losses)], [both[len(losses):]]
+            losses_dev = loss_buf if device_optimizer else torch.stack(losses)
+            both = torch.cat([losses_dev.double(), scores_dev]).cpu().numpy()   # one readback: the losses and the scores
+            losses, scores = both[:losses_dev.numel()], [both[losses_dev.numel():]]
         elif device_feed:
             eng.feed_status()   # the epoch's one verdict on every row id and column index its launches met
-            losses = torch.stack(losses).cpu().numpy().astype(np.float64)   # one readback; the values the .item()s would have been
+            losses_dev = loss_buf if device_optimizer else torch.stack(losses)
+            losses = losses_dev.cpu().numpy().astype(np.float64)   # one readback; the values the .item()s would have been
         avg = np.nanmean(np.concatenate(scores))
         if verbose:
             print(f"Epoch: {epoch}, Loss: {np.round(np.mean(losses), 4)}, {early_stop_metric}: {np.round(avg, 4)}", end="\r")
