@@ -525,6 +525,34 @@ int sdrm_rank_metrics(sdrm_engine* e, const float* scores, int U, int I, const i
                       const int32_t* held_indices, const int64_t* train_indptr, const int32_t* train_indices,
                       const int32_t* ks_host, int nk, const double* tp, const double* idcg, double* recall, double* ndcg,
                       void* stream);
+/* The evaluation half of a VAE pre-stage epoch on the device (reference: train_SDRM.py:160-177 with is_training == 0 and dropout
+ * off), one call for all users of a hold-out split.  enc / dec are the eight LIVE nn.Linear tensors as nn.Linear stores them (their
+ * n_items, hidden and latent must agree); train_* / held_* are the two CSR index pairs sdrm_holdout_split leaves (int64 indptr
+ * [n_rows + 1], int32 indices of capacity *_nnz; every stored entry counts as 1).  For user u, with T_u the columns of the train
+ * part and H_u those of the held part:
+ *   x = 1_{T_u} / max(sqrt(|T_u|), 1e-12),  h1 = tanh(W1 x + b1),  z = W2[:L] h1 + b2[:L],  h3 = tanh(W3 z + b3),  s = W4 h3 + b4,
+ *   scores[u] = Recall@k (metric 0) or NDCG@k (metric 1) of s against H_u with the items of T_u at -inf
+ * - the last line being sdrm_rank_metrics' definition (tie rule, nan for a user with nothing held out, tp [k] and idcg [k + 1] float64
+ * device tables as that call takes them).  The logvar rows of W2, the KL and the reparameterisation draw are never computed.
+ * scores: float64 [n_rows], every element written exactly once.  logits: null, or float32 [n_rows, n_items] contiguous, which then
+ * receives s of every user; when null, nothing of that size leaves the handle's scratch.
+ * The weights are staged ONCE per call (two launches: seven tensors padded, W1 transposed) into scratch of their own - an encoder
+ * staged by sdrm_vae_encoder_load and the scratch of the train-mode entry points are not touched -, then the call loops over batches
+ * of `batch` users (the last may be short), five launches each: the eval-mode gather of the first Linear straight from the train
+ * part's rows (no dense input batch), three MFMA GEMMs (they follow sdrm_debug_set_tile) and the ranking.  A GEMM of more than 65535
+ * tiles goes out in row bands, one launch each.  The call does not synchronise, reads nothing back, joins the sampler chains like its
+ * neighbours, and gives the same bits on every call.
+ * Range checks, into the status word sdrm_feed_status reports: no load or store uses an unchecked index.  An indptr pair that is
+ * negative, out of order or reaches behind *_nnz is an empty row, in the gather and in the ranking alike (such a user's logits are
+ * those of a user without train entries, and nothing of that user is masked); a train entry with a column outside [0, n_items)
+ * contributes nothing and masks nothing; a held entry outside it is neither ranked nor counted.
+ * Envelope (SDRM_ERR_SHAPE otherwise): 1 <= n_items <= 36864 (the ranking's LDS row), 1 <= hidden, latent <= 4096, 1 <= n_rows <
+ * 2^31, 1 <= batch <= 2^22, 1 <= k <= min(128, n_items), metric in {0, 1}, *_nnz >= 0, every tile x K span of the GEMMs below 2^32
+ * bytes.  A null required pointer is SDRM_ERR_ARG.  No launch is made by a refused call. */
+int sdrm_vae_eval_holdout(sdrm_engine* e, const sdrm_vae_encoder* enc, const sdrm_vae_decoder* dec, const int64_t* train_indptr,
+                          const int32_t* train_indices, int64_t train_nnz, const int64_t* held_indptr, const int32_t* held_indices,
+                          int64_t held_nnz, int64_t n_rows, int batch, int k, const double* tp, const double* idcg, int metric,
+                          double* scores, float* logits, void* stream);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,12 @@ int sdrm_debug_vae_adam_args(const uint64_t* addr, const int64_t* n, const float
  * n_u < 2 ? 0 : min(n_u, (int64)ceil(test_prop * (double)n_u)), in *m_out (may be NULL).  Pure function: callable without a GPU. */
 int sdrm_debug_holdout_args(int n_items, int64_t n_rows, int64_t nnz, double test_prop, int64_t n_u, int64_t* m_out);
 
+/* What sdrm_vae_eval_holdout checks on the host before any launch: SDRM_ERR_SHAPE outside its envelope (1 <= n_items <= 36864,
+ * 1 <= hidden <= 4096, 1 <= latent <= 4096, 1 <= n_rows < 2^31, 1 <= batch <= 2^22, 1 <= k <= min(128, n_items), metric 0 or 1) and
+ * for anything a later GEMM launch would refuse on any tile - with the launches banded as the entry point does, nothing inside the
+ * envelope is - else SDRM_OK.  Pure function: callable without a GPU. */
+int sdrm_debug_vae_eval_args(int n_items, int hidden, int latent, int64_t n_rows, int batch, int k, int metric);
+
 /* Tile shapes of the MFMA GEMM template, as numbered by sdrm_debug_set_tile / the `cfg` arguments below:
  *   0 = 64x64x16 (default), 1 = 64x64x32, 2 = 64x128x16, 3 = 128x128x16 on v_mfma_f32_32x32x2_f32,
  *   4 = 32x32x32 on v_mfma_f32_16x16x4_f32. */

@@ -113,6 +113,8 @@ SIGNATURES = {
     "sdrm_vae_loss_slot": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "sdrm_holdout_split": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, C.c_double, c_uint64, C.c_uint32, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
+    "sdrm_vae_eval_holdout": (c_int, [c_void_p, C.POINTER(VaeEncoder), C.POINTER(VaeDecoder), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                      c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "sdrm_equal_sparsity": (c_int, [c_void_p, c_void_p, c_int64, C.c_double, c_void_p, c_void_p, c_void_p]),
     "sdrm_equal_sparsity_csr_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int64, C.c_double, c_int, c_void_p, c_void_p,
                                               C.POINTER(c_int64), c_void_p]),
@@ -128,6 +130,7 @@ SIGNATURES = {
     "sdrm_debug_decoder_nll_args": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int64, c_int]),
     "sdrm_debug_vae_adam_args": (c_int, [C.POINTER(c_uint64), C.POINTER(c_int64), C.POINTER(c_float), c_int, c_int64, c_int, c_int64,
                                          C.POINTER(c_int64)]),
+    "sdrm_debug_vae_eval_args": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int, c_int]),
     "sdrm_debug_holdout_args": (c_int, [c_int, c_int64, c_int64, C.c_double, c_int64, C.POINTER(c_int64)]),
     "sdrm_debug_set_tile": (c_int, [c_void_p, c_int]),
     "sdrm_debug_set_nt32_rows": (c_int, [c_void_p, c_int, c_int]),

@@ -10,8 +10,8 @@ namespace sdrm {
 
 // dst[rowsP][colsP] (row-major, colsP a multiple of 4) = src[rows][cols] zero-padded; the five operands of a decode (latents, two
 // weights, two biases) in ONE launch: segment = blockIdx.y (five launches of a few microseconds each were most of the decode's
-// time at the small shapes, where the engine's decode lost to the PyTorch module)
-struct PadSegs { const float* src[5]; float* dst[5]; int rows[5], cols[5], rowsP[5], colsP[5]; };
+// time at the small shapes, where the engine's decode lost to the PyTorch module); up to eight (the seven tensors sdrm_vae_eval_holdout pads)
+struct PadSegs { const float* src[8]; float* dst[8]; int rows[8], cols[8], rowsP[8], colsP[8]; };
 __global__ __launch_bounds__(256) void k_pad2d(const PadSegs sg) {
   const int k = blockIdx.y;
   const float* __restrict__ src = sg.src[k];

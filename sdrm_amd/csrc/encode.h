@@ -71,6 +71,7 @@ struct EncodeCsrArgs {
   const float* b1;         // [>= Hq], zero behind hidden
   int Hq, Hp;              // hidden rounded up to 4 / to the GEMM's 32
   float* hid;              // [>= b][Hp] hidden activations, the second-layer GEMM's operand
+  int64_t nnz;             // entries of csr.indices; looked at by the CHECKED form alone (k_encode_csr_checked, csrc/eval_half.h)
 };
 
 // First Linear + normalise + tanh by gather.  TPR threads own one batch row (a work-group of 256: one row, or one row per wave for a narrow
@@ -79,8 +80,10 @@ struct EncodeCsrArgs {
 // LDS reads, U entries at a time: the U x NV 16-byte loads of W1^T rows are issued before the FMAs that consume them.  Every thread adds the
 // entries in CSR order, so a row's result is a function of that row alone (bit-reproducible, wherever the row sits in the batch).  An entry
 // with a column outside [0, n_items) becomes (column 0, value 0): no stray load, and it adds +0.  sum(value^2) runs alongside in every thread.
-template <int TPR, int NV, int U>
-__global__ __launch_bounds__(256) void k_encode_csr(const EncodeCsrArgs a) {
+// CHECKED == false is k_encode_csr as it always was: the upper end of an indptr pair is the caller's (the feed entry points are given
+// no nnz).  CHECKED == true also holds it against a.nnz: a pair that reaches behind the index array is the empty row and raises FEED_BAD_PTR.
+template <int TPR, int NV, int U, bool CHECKED>
+__device__ __forceinline__ void encode_csr_rows(const EncodeCsrArgs& a) {
   constexpr int RPW = 256 / TPR;   // rows per work-group
   __shared__ int2 ent[RPW][TPR];
   const int g = threadIdx.x / TPR, slot = threadIdx.x % TPR;
@@ -88,7 +91,11 @@ __global__ __launch_bounds__(256) void k_encode_csr(const EncodeCsrArgs a) {
   const bool row_ok = r < a.csr.b;     // (uniform over the TPR threads of a row; with TPR == 256 over the work-group, so the barriers below are too)
   const int q = a.Hq >> 2;
   const CsrSpan s = row_ok ? csr_row_span(a.csr, r, slot) : CsrSpan{0, 0, 0};
-  const int64_t p0 = s.p0, p1 = s.p1;
+  int64_t p0 = s.p0, p1 = s.p1;
+  if (CHECKED && p1 > a.nnz) {
+    if (slot == 0) atomicOr(a.csr.flag, (unsigned)FEED_BAD_PTR);
+    p0 = p1 = 0;
+  }
   float4 acc[NV];
 #pragma unroll
   for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -134,6 +141,9 @@ __global__ __launch_bounds__(256) void k_encode_csr(const EncodeCsrArgs a) {
   }
   for (int s = q + slot; s < (a.Hp >> 2); s += TPR) out[s] = make_float4(0.f, 0.f, 0.f, 0.f);   // the GEMM's K padding
 }
+
+template <int TPR, int NV, int U>
+__global__ __launch_bounds__(256) void k_encode_csr(const EncodeCsrArgs a) { encode_csr_rows<TPR, NV, U, false>(a); }
 
 // kl, first launch: block k takes rows k, k + gridDim.x, ..: copies mu = out2[row][0 .. L) to z[row] and leaves its share of
 // sum(1 + logvar - mu^2 - exp(logvar)) in part[k] (float64; every thread in a fixed order, then the tree).  1 - exp(lv) is taken as

@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "csr_batch.h"
+
 namespace sdrm {
 
 constexpr int RANK_MAX_K = 128;   // numpy's pairwise block: one level, no recursion
@@ -49,7 +51,15 @@ __device__ inline double np_pairwise_sum(const double* a, int n) {
   return res;
 }
 
-__global__ __launch_bounds__(256) void k_rank_metrics(const RankArgs a) {
+// What the CHECKED form (k_rank_metrics_checked, csrc/eval_half.h) knows beside RankArgs: the capacities of the two index arrays and
+// the feed status word (csrc/csr_batch.h).  It trusts no offset and no column: an indptr pair that is out of order or reaches outside
+// [0, nnz] is an empty row, an entry with a column outside [0, I) is skipped (a held one does not count as held), and either raises
+// FEED_BAD_PTR / FEED_BAD_COL.  It writes the metrics whose pointer is not null.
+struct RankCheck { int64_t held_nnz, train_nnz; unsigned* flag; };
+
+// One work-group, one user.  CHECKED == false is k_rank_metrics as it always was: `ck` is not looked at.
+template <bool CHECKED>
+__device__ __forceinline__ void rank_metrics_user(const RankArgs& a, const RankCheck& ck) {
   extern __shared__ float row[];            // [I] scores of this user, then the reduction scratch
   __shared__ int red[4];
   __shared__ double vec[RANK_MAX_K];        // hit * discount by rank
@@ -59,15 +69,23 @@ __global__ __launch_bounds__(256) void k_rank_metrics(const RankArgs a) {
   for (int i = tid; i < a.I; i += 256) row[i] = src[i];
   for (int r = tid; r < RANK_MAX_K; r += 256) hit[r] = 0;
   __syncthreads();
+  unsigned bad = 0;
   if (a.train_indptr) {
-    const int64_t t0 = a.train_indptr[u], t1 = a.train_indptr[u + 1];
-    for (int64_t t = t0 + tid; t < t1; t += 256) row[a.train_indices[t]] = -INFINITY;
+    int64_t t0 = a.train_indptr[u], t1 = a.train_indptr[u + 1];
+    if (CHECKED && (t0 < 0 || t1 < t0 || t1 > ck.train_nnz)) { bad |= (unsigned)FEED_BAD_PTR; t0 = t1 = 0; }
+    for (int64_t t = t0 + tid; t < t1; t += 256) {
+      const int c = a.train_indices[t];
+      if (CHECKED && (c < 0 || c >= a.I)) { bad |= (unsigned)FEED_BAD_COL; continue; }
+      row[c] = -INFINITY;
+    }
     __syncthreads();
   }
-  const int64_t h0 = a.held_indptr[u], h1 = a.held_indptr[u + 1];
-  const int n_true = (int)(h1 - h0);
+  int64_t h0 = a.held_indptr[u], h1 = a.held_indptr[u + 1];
+  if (CHECKED && (h0 < 0 || h1 < h0 || h1 > ck.held_nnz)) { bad |= (unsigned)FEED_BAD_PTR; h0 = h1 = 0; }
+  int n_true = (int)(h1 - h0);
   for (int64_t h = h0; h < h1; ++h) {
     const int j = a.held_indices[h];
+    if (CHECKED && (j < 0 || j >= a.I)) { bad |= (unsigned)FEED_BAD_COL; --n_true; continue; }   // (uniform over the work-group: every thread reads entry h)
     const float v = row[j];
     int c = 0;
     for (int i = tid; i < a.I; i += 256) {
@@ -94,10 +112,13 @@ __global__ __launch_bounds__(256) void k_rank_metrics(const RankArgs a) {
       }
       const double dcg = np_pairwise_sum(vec, k);
       const int m = n_true < k ? n_true : k;
-      a.recall[(size_t)q * a.U + u] = (double)hits / (double)m;          // 0/0 -> nan, like the reference
-      a.ndcg[(size_t)q * a.U + u] = dcg / a.idcg[m];                      // idcg[0] = 0 -> nan
+      if (!CHECKED || a.recall) a.recall[(size_t)q * a.U + u] = (double)hits / (double)m;          // 0/0 -> nan, like the reference
+      if (!CHECKED || a.ndcg) a.ndcg[(size_t)q * a.U + u] = dcg / a.idcg[m];                      // idcg[0] = 0 -> nan
     }
   }
+  if (CHECKED && bad) atomicOr(ck.flag, bad);
 }
+
+__global__ __launch_bounds__(256) void k_rank_metrics(const RankArgs a) { rank_metrics_user<false>(a, RankCheck{}); }
 
 }  // namespace sdrm

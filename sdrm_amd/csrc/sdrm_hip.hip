@@ -21,6 +21,7 @@
 #include "decoder_train.h"
 #include "elementwise.h"
 #include "encode.h"
+#include "eval_half.h"
 #include "exchange.h"
 #include "feed.h"
 #include "gemm.h"
@@ -245,6 +246,11 @@ struct sdrm_engine {
   float* dh_buf[DH_BUFS] = {};       // z [MP][Lp], W3 [Hr][Lp], b3 [Hr], h3 [MP][Hp], W4 [Ir][Hp], b4 [Ir] | W4^T [Hr][Ip], W3^T [Lr][Hp], zero bias [Lr],
                                      // g [MP][Ip], dpre3 [MP][Hp], slabs [S][Ip][Hp] + bias sums [S][Ip] of dW4, slabs [S][Hp][Lp] + bias sums [S][Hp] of dW3
   size_t dh_cap[DH_BUFS] = {};
+  // sdrm_vae_eval_holdout (csrc/eval_half.h: EvalBuf): the live weights staged by that call and its batches' hand-overs, grow-only;
+  // nothing of the loaded encoder (enc_buf) or of the train-mode entry points' scratch (il_buf, lat_buf, dh_buf) is touched by it
+  float* ev_buf[EV_BUFS] = {};       // W1^T [items][Hq], b1 [Hr], W2[:L] [Lr][Hp], b2[:L] [Lr], W3 [Hr][Lp], b3 [Hr], W4 [Ir][Hp], b4 [Ir] |
+                                     // h1 [MP][Hp], z [MP][Lp], h3 [MP][Hp], logits [batch][items] (when the caller gives none)
+  size_t ev_cap[EV_BUFS] = {};
   uint32_t* hold_cnt = nullptr;      // grow-only scratch of sdrm_holdout_split (csrc/holdout.h): [2][rows] entries n_u and held entries m_u of every row
   size_t hold_cap = 0;               // in elements
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
@@ -278,7 +284,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -298,7 +304,8 @@ static const char* kProfNames[PC_COUNT] = {
     "hold-out: k_holdout_counts / k_holdout_scan / k_holdout_split per-user hold-out split of a CSR matrix into two (keys ranked per row, a wave or a work-group per row)",
     "latent head: k_latent_stage / gemm_kernel<0,0,0,0,7> / k_latent_reparam forward, k_latent_stage_bwd / k_latent_seed / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / k_latent_unpad backward of the VAE encoder behind its first pre-activation in train mode",
     "decoder head: k_pad2d / gemm_kernel<0,0,0,0,1> / k_dechead_h3 / gemm_kernel<0,0,0,0,7> / k_nll_rows / k_nll_sum forward, k_dechead_stage_bwd / k_dechead_grad / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / gemm_kernel<0,0,0,0,7> / k_dechead_unpad backward of the VAE decoder and the multinomial loss in train mode",
-    "optimizer: k_vae_adam / k_vae_loss_slot Adam over the VAE pre-stage's parameter tensors in one launch (with the L2 partial sums) and the step's loss value into its slot"};
+    "optimizer: k_vae_adam / k_vae_loss_slot Adam over the VAE pre-stage's parameter tensors in one launch (with the L2 partial sums) and the step's loss value into its slot",
+    "evaluation half: k_pad2d / k_encode_w1t staging once per call, then per batch k_encode_csr_checked / gemm_kernel<0,0,0,0,0> / gemm_kernel<0,0,0,0,1> / gemm_kernel<0,0,0,0,7> / k_rank_metrics_checked: the VAE's eval-mode forward from the CSR rows of a hold-out split and Recall@k / NDCG@k of its scores"};
 
 namespace {
 
@@ -1611,6 +1618,8 @@ int sdrm_destroy(sdrm_engine* e) {
     if (b) (void)hipFree(b);
   if (e->lat_part) (void)hipFree(e->lat_part);
   for (float* b : e->dh_buf)
+    if (b) (void)hipFree(b);
+  for (float* b : e->ev_buf)
     if (b) (void)hipFree(b);
   if (e->hold_cnt) (void)hipFree(e->hold_cnt);
   if (e->csr_ws) (void)hipFree(e->csr_ws);
@@ -3761,6 +3770,149 @@ int sdrm_rank_metrics(sdrm_engine* e, const float* scores, int U, int I, const i
     HIP_TRY(e, hipFuncSetAttribute((const void*)k_rank_metrics, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   SDRM_LAUNCH(e, k_rank_metrics, dim3(U), dim3(256), lds, (hipStream_t)stream, a);
   HIP_TRY(e, hipGetLastError());
+  return SDRM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The evaluation half of a VAE pre-stage epoch (train_SDRM.py:160-177), csrc/eval_half.h: the live weights staged once, then per
+// batch of users the eval-mode forward straight from the train part's CSR rows and the ranking against the held part.
+namespace {
+
+constexpr int EVAL_MAX_ITEMS = 36864;   // k_rank_metrics' LDS row
+constexpr int EVAL_MAX_HIDDEN = 4096, EVAL_MAX_LATENT = 4096;   // (hidden: ENC_GATHER_MAX_Q float4 slices in k_encode_csr's registers)
+
+int ev_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->ev_buf[slot], &e->ev_cap[slot], n); }
+
+// padded extents: K and N of the GEMMs to 32, operand rows to the largest tile (128), the batch to 64 (the launches' M)
+struct EvDims { int Hq, Hp, Hr, Lp, Lr, Ip, Ir, MP, rows64; };
+EvDims ev_dims(int n_items, int hidden, int latent, int batch) {
+  EvDims d;
+  d.Hq = round_up(hidden, 4); d.Hp = round_up(hidden, 32); d.Hr = round_up(d.Hp, 128);
+  d.Lp = round_up(latent, 32); d.Lr = round_up(d.Lp, 128);
+  d.Ip = round_up(n_items, 32); d.Ir = round_up(d.Ip, 128);
+  d.MP = round_up(batch, 128); d.rows64 = round_up(batch, BM);
+  return d;
+}
+
+const char* const kEvalEnvelope = ": n_items outside 1 .. 36864, hidden or latent outside 1 .. 4096, n_rows outside 1 .. 2^31 - 1, batch outside 1 .. 2^22, "
+                                  "k outside 1 .. min(128, n_items), metric not 0 (recall) or 1 (ndcg), a negative nnz, or the encoder's and the decoder's sizes differ";
+
+}  // namespace
+
+// The host side that needs no device: the envelope, and the tests that the three GEMM launches of sdrm_vae_eval_holdout make on any
+// tile (A's stride equal to K, as those launches have it; a launch of another form added to the call needs its own line here).
+int sdrm_debug_vae_eval_args(int n_items, int hidden, int latent, int64_t n_rows, int batch, int k, int metric) {
+  if (n_items < 1 || n_items > EVAL_MAX_ITEMS || hidden < 1 || hidden > EVAL_MAX_HIDDEN || latent < 1 || latent > EVAL_MAX_LATENT || n_rows < 1 ||
+      n_rows > (int64_t)INT32_MAX || batch < 1 || batch > (1 << 22) || k < 1 || k > RANK_MAX_K || k > n_items || (metric != 0 && metric != 1))
+    return SDRM_ERR_SHAPE;
+  const EvDims d = ev_dims(n_items, hidden, latent, batch);
+  for (int cfg = 0; cfg < N_TILE_CFGS; ++cfg) {
+    // h1 W2[:L]^T (K = Hp), z W3^T (K = Lp), h3 W4^T (K = Hp): a row band of each fits a launch, and a tile x K span stays below 2^32 bytes
+    if (dh_nt_band(cfg, d.Lp) < 1 || dh_nt_band(cfg, d.Hp) < 1 || dh_nt_band(cfg, d.Ip) < 1) return SDRM_ERR_SHAPE;
+    if (!dh_span_ok(cfg, true, d.Hp, d.Hp, d.Hp) || !dh_span_ok(cfg, true, d.Lp, d.Lp, d.Lp)) return SDRM_ERR_SHAPE;
+  }
+  return SDRM_OK;
+}
+
+int sdrm_vae_eval_holdout(sdrm_engine* e, const sdrm_vae_encoder* enc, const sdrm_vae_decoder* dec, const int64_t* train_indptr,
+                          const int32_t* train_indices, int64_t train_nnz, const int64_t* held_indptr, const int32_t* held_indices,
+                          int64_t held_nnz, int64_t n_rows, int batch, int k, const double* tp, const double* idcg, int metric, double* scores,
+                          float* logits, void* stream) {
+  const char* who = "sdrm_vae_eval_holdout";
+  if (!e) return SDRM_ERR_ARG;
+  if (!enc || !dec || !enc->w1 || !enc->b1 || !enc->w2 || !enc->b2 || !dec->w1 || !dec->b1 || !dec->w2 || !dec->b2 || !train_indptr ||
+      !train_indices || !held_indptr || !held_indices || !tp || !idcg || !scores)
+    return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  const int I = enc->n_items, H = enc->hidden, L = enc->latent;
+  if (dec->n_items != I || dec->hidden != H || dec->latent != L || train_nnz < 0 || held_nnz < 0)
+    return fail(e, SDRM_ERR_SHAPE, std::string(who) + kEvalEnvelope);
+  if (int rc = sdrm_debug_vae_eval_args(I, H, L, n_rows, batch, k, metric)) return fail(e, rc, std::string(who) + kEvalEnvelope);
+  hipStream_t st = (hipStream_t)stream;
+  if (int jr = chains_join(e, st)) return jr;
+  const int bmax = (int)std::min<int64_t>(batch, n_rows);
+  const EvDims d = ev_dims(I, H, L, bmax);
+  int rc;
+  if ((rc = ev_grow(e, EV_W1T, (size_t)I * d.Hq)) || (rc = ev_grow(e, EV_B1, d.Hr)) || (rc = ev_grow(e, EV_W2, (size_t)d.Lr * d.Hp)) ||
+      (rc = ev_grow(e, EV_B2, d.Lr)) || (rc = ev_grow(e, EV_W3, (size_t)d.Hr * d.Lp)) || (rc = ev_grow(e, EV_B3, d.Hr)) ||
+      (rc = ev_grow(e, EV_W4, (size_t)d.Ir * d.Hp)) || (rc = ev_grow(e, EV_B4, d.Ir)) || (rc = ev_grow(e, EV_H1, (size_t)d.MP * d.Hp)) ||
+      (rc = ev_grow(e, EV_Z, (size_t)d.MP * d.Lp)) || (rc = ev_grow(e, EV_H3, (size_t)d.MP * d.Hp)))
+    return rc;
+  if (!logits && (rc = ev_grow(e, EV_LOGITS, (size_t)bmax * I))) return rc;
+  float* const* ev = e->ev_buf;
+  const size_t lds = (size_t)I * sizeof(float);
+  if (lds > 48 * 1024) HIP_TRY(e, allow_full_lds((const void*)k_rank_metrics_checked, EVAL_MAX_ITEMS * (int)sizeof(float)));
+  // staging, once per call (the weights change with every optimiser step): seven tensors padded in one launch, W1 transposed in a second
+  {
+    PadList pad;
+    pad.add(enc->b1, 1, H, ev[EV_B1], 1, d.Hr);
+    pad.add(enc->w2, L, H, ev[EV_W2], d.Lr, d.Hp);   // the mu rows: the first L of [2 L][H]
+    pad.add(enc->b2, 1, L, ev[EV_B2], 1, d.Lr);
+    pad.add(dec->w1, H, L, ev[EV_W3], d.Hr, d.Lp);
+    pad.add(dec->b1, 1, H, ev[EV_B3], 1, d.Hr);
+    pad.add(dec->w2, I, H, ev[EV_W4], d.Ir, d.Hp);
+    pad.add(dec->b2, 1, I, ev[EV_B4], 1, d.Ir);
+    if ((rc = hip_rc(e, "k_pad2d", profiled(e, PC_EVAL_HALF, 0.0, st, [&] {
+           SDRM_LAUNCH(e, k_pad2d, dim3((unsigned)std::min<int64_t>(2048, (pad.most + 255) / 256), (unsigned)pad.k), dim3(256), 0, st, pad.sg);
+           return hipGetLastError();
+         }))))
+      return rc;
+    if ((rc = hip_rc(e, "k_encode_w1t", profiled(e, PC_EVAL_HALF, 0.0, st, [&] {
+           SDRM_LAUNCH(e, k_encode_w1t, dim3((unsigned)((I + 31) / 32), (unsigned)((d.Hq + 31) / 32)), dim3(256), 0, st, enc->w1, H, I, ev[EV_W1T], d.Hq);
+           return hipGetLastError();
+         }))))
+      return rc;
+  }
+  for (int64_t row0 = 0; row0 < n_rows; row0 += batch) {
+    const int b = (int)std::min<int64_t>(batch, n_rows - row0);
+    const int rows64 = round_up(b, BM);
+    const int cfg = choose_cfg(e->tune, rows64, e->tune.nt32_max_rows);
+    // 1: h1 = tanh(W1 x / |x| + b1) by gather from the train part's rows, into the padded operand (columns behind H: zero)
+    {
+      EncodeCsrArgs a{};
+      a.csr = CsrBatch{train_indptr, train_indices, nullptr, nullptr, row0, n_rows, b, I, e->feed_flag};
+      a.w1t = ev[EV_W1T]; a.b1 = ev[EV_B1]; a.Hq = d.Hq; a.Hp = d.Hp; a.hid = ev[EV_H1]; a.nnz = train_nnz;
+      if ((rc = hip_rc(e, "k_encode_csr_checked", profiled(e, PC_EVAL_HALF, 0.0, st, [&] {
+             return launch_gather_rows(e, d.Hq / 4, a, st, [](auto tpr, auto nv, auto u) { return k_encode_csr_checked<VAL(tpr), VAL(nv), VAL(u)>; });
+           }))))
+        return rc;
+    }
+    // 2: z = h1 W2[:L]^T + b2[:L] into the padded [MP][Lp] (W2's pad rows and b2's pad are zero: columns behind L are 0)
+    {
+      GemmArgs a{};
+      a.B = ev[EV_W2]; a.ldb = d.Hp; a.C = ev[EV_Z]; a.ldc = d.Lp; a.K = d.Hp; a.bias = ev[EV_B2];
+      if ((rc = dh_nt<EPI_BIAS>(e, a, ev[EV_H1], d.Hp, rows64, d.Lp, b, st, Prof{e, PC_EVAL_HALF, 2.0 * b * (double)L * H}, cfg))) return rc;
+    }
+    // 3: h3 = tanh(z W3^T + b3) into the padded [MP][Hp]
+    {
+      GemmArgs a{};
+      a.B = ev[EV_W3]; a.ldb = d.Lp; a.C = ev[EV_H3]; a.ldc = d.Hp; a.K = d.Lp; a.bias = ev[EV_B3];
+      if ((rc = dh_nt<EPI_BIAS_TANH>(e, a, ev[EV_Z], d.Lp, rows64, d.Hp, b, st, Prof{e, PC_EVAL_HALF, 2.0 * b * (double)H * L}, cfg))) return rc;
+    }
+    // 4: s = h3 W4^T + b4, bounds-checked into the batch's [b][I]: the scratch, or the caller's rows row0 ..
+    float* s_out = logits ? logits + (size_t)row0 * I : ev[EV_LOGITS];
+    {
+      GemmArgs a{};
+      a.B = ev[EV_W4]; a.ldb = d.Hp; a.C = s_out; a.ldc = I; a.K = d.Hp; a.bias = ev[EV_B4]; a.cols_valid = I;
+      if ((rc = dh_nt<EPI_BIAS_G>(e, a, ev[EV_H3], d.Hp, rows64, d.Ip, b, st, Prof{e, PC_EVAL_HALF, 2.0 * b * (double)I * H}, cfg))) return rc;
+    }
+    // 5: the chosen metric of the batch's users into scores[row0 ..] (the indptr arrays hold absolute offsets: a row range is a pointer offset)
+    {
+      RankArgs a{};
+      a.scores = s_out; a.U = b; a.I = I;
+      a.held_indptr = held_indptr + row0; a.held_indices = held_indices;
+      a.train_indptr = train_indptr + row0; a.train_indices = train_indices;
+      a.nk = 1; a.kmax = k; a.ks[0] = k;
+      a.tp = tp; a.idcg = idcg;
+      a.recall = metric == 0 ? scores + row0 : nullptr;
+      a.ndcg = metric == 1 ? scores + row0 : nullptr;
+      const RankCheck ck{held_nnz, train_nnz, e->feed_flag};
+      if ((rc = hip_rc(e, "k_rank_metrics_checked", profiled(e, PC_EVAL_HALF, 0.0, st, [&] {
+             SDRM_LAUNCH(e, k_rank_metrics_checked, dim3((unsigned)b), dim3(256), lds, st, a, ck);
+             return hipGetLastError();
+           }))))
+        return rc;
+    }
+  }
   return SDRM_OK;
 }
 

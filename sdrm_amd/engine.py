@@ -993,6 +993,70 @@ class Engine:
         self._keepalive = (scores, hp, hi, tr)
         return recall, ndcg
 
+    # ------------------------------------------------------------------ evaluation half of the VAE pre-stage (csrc/eval_half.h)
+    def vae_eval_holdout(self, w1, b1, w2, b2, w3, b3, w4, b4, train_csr_dev, held_csr_dev, k, metric, batch=500, out=None, logits=None,
+                         check=False):
+        """train_SDRM.py:160-177 in eval mode for every user of a hold-out split, in one engine call (sdrm_vae_eval_holdout): the VAE's
+        forward - normalise, encoder (mu rows only; no KL, no draw), decoder - straight from the rows of `train_csr_dev`, and `metric`
+        ("recall" / 0 or "ndcg" / 1) at cut-off `k` of its scores against `held_csr_dev` with the train items at -inf, as `rank_metrics`
+        defines it.  The eight tensors are the live `nn.Linear` weights and biases (encoder[0], encoder[2], decoder[0], decoder[2]),
+        float32 and contiguous on the engine's device; the two CSRs are `(indptr, indices, None, shape)` tuples as `holdout_split`
+        returns them.  The weights are staged once, the call loops over batches of `batch` users itself, and no dense input batch exists.
+        Returns the float64 device tensor [n_rows] of per-user scores (`out`, when given) - nan for a user with nothing held out.
+        `logits`: a float32 device tensor [n_rows, n_items] that receives the scores of every item; without it nothing of that size is
+        allocated.  Nothing is read back; `check=True` asks `feed_status()` at once."""
+        who = "vae_eval_holdout"
+        if isinstance(metric, str) and metric in ("recall", "Recall"):
+            metric = 0
+        elif isinstance(metric, str) and metric in ("ndcg", "NDCG"):
+            metric = 1
+        elif isinstance(metric, (bool, str)) or not isinstance(metric, (int, np.integer)) or int(metric) not in (0, 1):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: metric = {metric!r} is none of \"recall\" / 0 and \"ndcg\" / 1")
+        tr_ptr, tr_idx, _, (n_rows, n_items) = train_csr_dev
+        he_ptr, he_idx, _, he_shape = held_csr_dev
+        n_rows, n_items = int(n_rows), int(n_items)
+        if (int(he_shape[0]), int(he_shape[1])) != (n_rows, n_items):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: the held part is {tuple(he_shape)}, the train part {(n_rows, n_items)}")
+        if not isinstance(w1, torch.Tensor) or w1.dim() != 2 or not isinstance(w3, torch.Tensor) or w3.dim() != 2:
+            raise SdrmError(f"{who}: w1 must be a 2-D tensor [hidden, n_items] and w3 one [hidden, latent]")
+        hidden, latent = int(w3.shape[0]), int(w3.shape[1])
+        w1 = self._f32(who, "w1", w1.detach(), (hidden, n_items))
+        b1 = self._f32(who, "b1", b1.detach(), (hidden,))
+        w2 = self._f32(who, "w2", w2.detach(), (2 * latent, hidden))
+        b2 = self._f32(who, "b2", b2.detach(), (2 * latent,))
+        w3 = self._f32(who, "w3", w3.detach(), (hidden, latent))
+        b3 = self._f32(who, "b3", b3.detach(), (hidden,))
+        w4 = self._f32(who, "w4", w4.detach(), (n_items, hidden))
+        b4 = self._f32(who, "b4", b4.detach(), (n_items,))
+        tr_ptr = self._index(who, "train indptr", tr_ptr, torch.int64, n_rows + 1)
+        he_ptr = self._index(who, "held indptr", he_ptr, torch.int64, n_rows + 1)
+        nnz = []
+        idx = []
+        for name, t in (("train", tr_idx), ("held", he_idx)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous():
+                raise SdrmError(f"{who}: {name} indices must be a contiguous int32 tensor on the engine's device")
+            nnz.append(int(t.numel()))
+            idx.append(t.new_zeros(1) if t.numel() == 0 else t)   # torch gives an empty tensor no address, and the C ABI takes no null array
+        if out is None:
+            out = torch.empty(n_rows, dtype=torch.float64, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous() \
+                or tuple(out.shape) != (n_rows,):
+            raise SdrmError(f"{who}: out must be a contiguous float64 tensor [{n_rows}] on the engine's device")
+        if logits is not None:
+            logits = self._f32(who, "logits", logits, (n_rows, n_items))
+        if not 1 <= int(k) <= min(128, n_items):   # (the tables below are made for k: the C call's own refusal would come too late)
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: k = {k} outside 1 .. min(128, n_items)")
+        _, tp_d, idcg_d = self._rank_tables((int(k),))
+        enc = _lib.VaeEncoder(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), n_items, hidden, latent)
+        dec = _lib.VaeDecoder(w3.data_ptr(), b3.data_ptr(), w4.data_ptr(), b4.data_ptr(), latent, hidden, n_items)
+        self._check(self.lib.sdrm_vae_eval_holdout(self._h, C.byref(enc), C.byref(dec), _ptr(tr_ptr), _ptr(idx[0]), nnz[0], _ptr(he_ptr),
+                                                   _ptr(idx[1]), nnz[1], n_rows, int(batch), int(k), _ptr(tp_d), _ptr(idcg_d), int(metric),
+                                                   _ptr(out), _ptr(logits), _stream()), "sdrm_vae_eval_holdout")
+        self._keepalive = (w1, b1, w2, b2, w3, b3, w4, b4, idx)
+        if check:
+            self.feed_status()
+        return out
+
     def perturb_input(self, x, t, noise):
         x, t, noise = self._dev(x, torch.float32), self._dev(t, torch.int64), self._dev(noise, torch.float32)
         out = torch.empty_like(x)

@@ -139,8 +139,15 @@ def compute_mf_results(training_dataset, testing_dataset, synthetic_data, only_s
     return np.array(rec), np.array(ndcg)
 
 
+# the pre-stage's opt-in flags that `hp` may carry, under `train_SDRM`'s keyword names
+VAE_FLAGS = ("vae_device_feed", "vae_device_holdout", "vae_sparse_input", "vae_device_latent", "vae_device_decoder", "vae_device_optimizer",
+             "vae_device_eval")
+
+
 def run_experiment(split, hp, seed, vae_dir, verbose=False):
-    """One run of main.py's loop body with the MI355X engine; returns {"M": (recall, ndcg), "F": ..., "V": ...}."""
+    """One run of main.py's loop body with the MI355X engine; returns {"M": (recall, ndcg), "F": ..., "V": ...}.  `hp` may carry the
+    seven flags of the VAE pre-stage under the keys `VAE_FLAGS` (each False when absent): those that are set are handed to `train_SDRM`
+    under the same names, and an `hp` without them makes the call it always made."""
     from . import train_SDRM as ts
     train, train_partial, valid = split
     n_users, n_items = train.shape
@@ -153,7 +160,8 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
                              VAE_LR=hp["vae_lr"], DIFF_LATENT=hp["latent"], N_HIDDEN_MLP_LAYERS=hp["H"], DIFF_LR=hp["lr"],
                              DIFF_TRAINING_EPOCHS=hp["epochs"], TIMESTEPS=hp["T"], noise_divider=hp["nd"], VAE_DIR_PATH=vae_dir,
                              TRAIN_PARTIAL_VALID_DATA=train_partial, VALID_DATA=valid, OPTIMIZATION_OBJECTIVE="Recall@10",
-                             verbose=verbose, cache_latents=hp.get("cache_latents", False), engine_encode=hp.get("engine_encode", False))
+                             verbose=verbose, cache_latents=hp.get("cache_latents", False), engine_encode=hp.get("engine_encode", False),
+                             **{flag: True for flag in VAE_FLAGS if hp.get(flag, False)})
     out = {}
     M = ts.sample_ddpm(n_users, net, vae, hp["latent"], hp["nd"], timesteps="random", n_timesteps=hp["T"]).detach()
     F = ts.sample_ddpm(n_users, net, vae, hp["latent"], hp["nd"], n_timesteps=hp["T"]).detach()

@@ -268,7 +268,7 @@ def train_SDRM(dl, N_ITEMS, VAE_HIDDEN, VAE_LATENT, VAE_BATCH_SIZE, VAE_LR, DIFF
                DIFF_TRAINING_EPOCHS, TIMESTEPS, noise_divider, VAE_DIR_PATH, TRAIN_PARTIAL_VALID_DATA, VALID_DATA,
                OPTIMIZATION_OBJECTIVE, verbose=False, variational_ae=None, cache_latents=False, engine_encode=False,
                vae_device_feed=False, vae_device_holdout=False, vae_sparse_input=False, vae_device_latent=False, vae_device_decoder=False,
-               vae_device_optimizer=False):
+               vae_device_optimizer=False, vae_device_eval=False):
     """(:271-340) Train the VAE (PyTorch), freeze it, then train the eps-net on its latents in the HIP
     engine.  `dl` yields `(x, _)` with x a sparse/dense [b, N_ITEMS] tensor.  Extras (keyword-only in
     spirit): `variational_ae` = an already trained VAE to reuse; `cache_latents` = encode the feed once
@@ -281,7 +281,9 @@ def train_SDRM(dl, N_ITEMS, VAE_HIDDEN, VAE_LATENT, VAE_BATCH_SIZE, VAE_LR, DIFF
     `device_holdout` (the per-epoch hold-out split and the evaluation half on the engine; takes effect only beside
     `vae_device_feed`); `vae_sparse_input`, `vae_device_latent`, `vae_device_decoder`, `vae_device_optimizer` = its `sparse_input`,
     `device_latent`, `device_decoder` and `device_optimizer` (the train half's input layer, latent head, decoder and loss head, and
-    Adam on the engine; each takes effect under the conditions given there, and with all six the train step runs without autograd).
+    Adam on the engine; each takes effect under the conditions given there, and with all six the train step runs without autograd);
+    `vae_device_eval` = its `device_eval` (the evaluation half's forward in one engine call, `Engine.vae_eval_holdout`; beside
+    `vae_device_feed` and `vae_device_holdout` only).
     All off by default: nothing existing changes by a bit."""
     if not torch.cuda.is_available():
         raise SdrmError("train_SDRM needs a ROCm device (no CPU fallback)")
@@ -292,7 +294,7 @@ def train_SDRM(dl, N_ITEMS, VAE_HIDDEN, VAE_LATENT, VAE_BATCH_SIZE, VAE_LR, DIFF
                                       early_stop_metric=OPTIMIZATION_OBJECTIVE, VAE_DIR_PATH=VAE_DIR_PATH, verbose=verbose,
                                       device_feed=vae_device_feed, device_holdout=vae_device_holdout, sparse_input=vae_sparse_input,
                                       device_latent=vae_device_latent, device_decoder=vae_device_decoder,
-                                      device_optimizer=vae_device_optimizer)
+                                      device_optimizer=vae_device_optimizer, device_eval=vae_device_eval)
     assert variational_ae.model_is_trained
     for p in variational_ae.parameters():
         p.requires_grad = False

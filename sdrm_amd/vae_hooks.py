@@ -18,6 +18,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import metrics as utilities
+from . import _lib
 from .engine import SdrmError, utility_engine
 
 
@@ -428,19 +429,36 @@ def vae_train_step(model, feed, lo, hi, drop_seed, latent_seed, step, anneal, op
         eng.vae_loss_slot(neg_ll, kl, anneal, loss_out, slot, l2_partials=opt.l2_partials, weight_decay=opt.weight_decay)
 
 
-def evaluate_holdout(model, eng, test_csr_dev, seed, draw, early_stop_metric, batch=500):
+EVAL_BATCH = 500                # users per batch of the evaluation half (:166)
+
+
+def eval_half_supported(model, n_rows, k, batch=EVAL_BATCH):
+    """Whether `Engine.vae_eval_holdout` takes this model, `n_rows` users and cut-off `k`: the C library's own host-side argument check
+    (`sdrm_debug_vae_eval_args`, which needs no device), so the envelope is stated once, in csrc/sdrm_hip.hip."""
+    rc = _lib.load().sdrm_debug_vae_eval_args(int(model.encoder[0].in_features), int(model.encoder[0].out_features), int(model.latent_dim),
+                                              int(n_rows), int(batch), int(k), 0)
+    return rc == 0
+
+
+def evaluate_holdout(model, eng, test_csr_dev, seed, draw, early_stop_metric, batch=EVAL_BATCH, device_forward=False):
     """The evaluation half of one pre-stage epoch (:160-177) on the device: the per-user hold-out split of `test_csr_dev` (a
     `csr_to_device` matrix) by `eng.holdout_split(seed=seed, draw=draw)`, then per batch of `batch` users the dense train part
     (`csr_rows_to_dense`), `model(...)` in eval mode under `no_grad`, and Recall@k / NDCG@k of its scores against the held part with
     the train part masked (`rank_metrics`, device form).  Returns the per-user scores as a float64 device tensor [n_rows] - nan for a
     user with fewer than two entries, whom the reference's split drops.  Nothing is read back; a feed out of range surfaces at the
-    next `eng.feed_status()`.  The model is left in eval mode with `is_training = 0`."""
+    next `eng.feed_status()`.  The model is left in eval mode with `is_training = 0`.
+    `device_forward=True`: the loop over the batches is ONE engine call, `eng.vae_eval_holdout` (csrc/eval_half.h), on the model's live
+    weights - no dense batch, no torch `Linear`, no KL and no `randn_like`; its scores differ from the torch forward's by fp32 rounding."""
     k = int(early_stop_metric.split("@")[1])
     which = 0 if "Recall" in early_stop_metric else 1
     n = int(test_csr_dev[3][0])
     model.eval()
     model.is_training = 0
     valid_train, held = eng.holdout_split(test_csr_dev, seed=seed, draw=draw, check=False)
+    if device_forward:
+        enc0, enc2, dec0, dec2 = model.encoder[0], model.encoder[2], model.decoder[0], model.decoder[2]
+        return eng.vae_eval_holdout(enc0.weight, enc0.bias, enc2.weight, enc2.bias, dec0.weight, dec0.bias, dec2.weight, dec2.bias,
+                                    valid_train, held, k, which, batch=batch, check=False)
     scores = torch.empty(n, dtype=torch.float64, device=eng.device)
     with torch.no_grad():
         for lo in range(0, n, batch):
@@ -452,7 +470,7 @@ def evaluate_holdout(model, eng, test_csr_dev, seed, draw, early_stop_metric, ba
 
 def train_variational_autoencoder(model, train_data, test_data, epochs, batch_size, lr, early_stop_metric="NDCG@50",
                                   VAE_DIR_PATH="./", verbose=False, device_feed=False, sparse_input=False, device_holdout=False,
-                                  device_latent=False, device_decoder=False, device_optimizer=False):
+                                  device_latent=False, device_decoder=False, device_optimizer=False, device_eval=False):
     """VAE pre-stage (:115-188): multinomial NLL + annealed KL, early stopping on Recall/NDCG@k of a
     per-user hold-out of `test_data`, best epoch restored.  Plain PyTorch (not part of the hot path) - except, with
     `device_feed=True` and the model on a ROCm device, the feed and the loss head: the CSR matrices stay in HBM, every train and
@@ -495,7 +513,16 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
     differ from torch's by the rounding of `adam_math`'s hardware `rcp` / `sqrt` (about 1e-7 of an update).  With all six flags in
     effect the step is `vae_train_step`: the same engine calls in the same order with the same arguments, under `no_grad`, without
     an `autograd.Function`, a `.grad` or a torch `Linear` - bit-equal to the autograd path of the same flags (`DIRECT_STEP = False`
-    keeps that one) - and the epoch's anneal values are uploaded once per epoch.  The flag adds no draw from `np.random` or torch."""
+    keeps that one) - and the epoch's anneal values are uploaded once per epoch.  The flag adds no draw from `np.random` or torch.
+    `device_eval=True` (with `device_feed=True` and `device_holdout=True` in effect, the model on a ROCm device, float32 parameters,
+    and what `sdrm_debug_vae_eval_args` accepts - at most 36864 items, hidden and latent layers of at most 4096 and a cut-off
+    k <= min(128, n_items) -, asked through `eval_half_supported`; ignored otherwise) puts the
+    forward of the evaluation half on the engine too: `evaluate_holdout(..., device_forward=True)`, one `Engine.vae_eval_holdout`
+    call per epoch on the live weights (csrc/eval_half.h) in place of `csr_rows_to_dense` + `model(...)` + `rank_metrics` per 500
+    users - with it on top of the six flags an epoch runs no torch `Linear` in either half.  The flag adds no draw from `np.random`.
+    With it the evaluation half no longer consumes torch's generator: without it `encode` draws a `randn_like` it multiplies by 0.
+    Its scores differ from the torch forward's by fp32 rounding, so a near-tie at the cut-off can move a user's metric (and with it
+    the epoch's mean and, rarely, the epoch that is restored); the train half is not fed by the evaluation half and does not change."""
     os.makedirs(os.path.normpath(VAE_DIR_PATH), exist_ok=True)
     dev = next(model.parameters()).device
     device_feed = bool(device_feed) and dev.type == "cuda"
@@ -506,13 +533,15 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
                       and model.latent_dim <= DECODER_HEAD_MAX_HIDDEN)
     device_optimizer = bool(device_optimizer) and device_feed and all(p.dtype == torch.float32 for p in model.parameters())
     direct_step = DIRECT_STEP and device_optimizer and device_holdout and device_latent and device_decoder
+    k = int(early_stop_metric.split("@")[1])
+    device_eval = (bool(device_eval) and device_holdout and all(p.dtype == torch.float32 for p in model.parameters())
+                   and eval_half_supported(model, test_data.shape[0], k))
     anneal_cap, anneal_count = 0.2, 0.0
     best_metric, best_epoch, stale = -np.inf, 0, 0
     if device_optimizer:
         optimizer = DeviceAdam(model.named_parameters(), lr=lr, weight_decay=getattr(model, "weight_decay", 0.0), engine=utility_engine(dev))
     else:
         optimizer = torch.optim.Adam(model.parameters(), lr=lr)
-    k = int(early_stop_metric.split("@")[1])
     start = time.time()
     n = train_data.shape[0]
     if device_feed:
@@ -590,7 +619,7 @@ def train_variational_autoencoder(model, train_data, test_data, epochs, batch_si
         model.is_training = 0
         scores = []
         if device_holdout:
-            scores_dev = evaluate_holdout(model, eng, test_dev, holdout_seed, epoch, early_stop_metric)
+            scores_dev = evaluate_holdout(model, eng, test_dev, holdout_seed, epoch, early_stop_metric, device_forward=device_eval)
         else:
             valid_train, valid_test = utilities.split_train_test_proportion_from_csr_matrix(test_data, batch_size=1000)
             if device_feed:
