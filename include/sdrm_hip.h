@@ -554,6 +554,43 @@ int sdrm_vae_eval_holdout(sdrm_engine* e, const sdrm_vae_encoder* enc, const sdr
                           int64_t held_nnz, int64_t n_rows, int batch, int k, const double* tp, const double* idcg, int metric,
                           double* scores, float* logits, void* stream);
 
+/* Rank-k truncated SVD of a sparse matrix on the device, and the scores of its rank-k reconstruction (reference: svd_benchmark.py:17-70,
+ * `TruncatedSVD(n_components=20, n_iter=100)` fitted on the stacked matrix, `inverse_transform(fit_transform(.))` as the score matrix).
+ * sklearn's randomized SVD is a subspace iteration; this is the same iteration on a panel of 32 columns (csrc/svd_eval.h):
+ *   Q [n, 32] = the start panel;  n_iter times: Y = A Q, Y <- orth(Y), Q = A^T Y, Q <- orth(Q);  then Y = A Q, Y <- orth(Y), Z = A^T Y
+ *   host, float64: the eigenvectors of Z^T Z (= B B^T for B = Y^T A) rotate Z into the top k right singular directions; normalised, they
+ *   are the rows of components, and singular_values are the square roots of the eigenvalues.
+ * The products are gathers in float32, every output element summed in the order of its row's entries (no atomic: the same bits on every
+ * call); orth is CholeskyQR applied twice with the Gram matrix, the factorisation and the sums of Y R^-1 in float64.  7 launches per
+ * half-iteration.  The sign of a component is whatever the iteration leaves (sklearn's svd_flip is not applied).
+ * sdrm_svd_fit: the matrix A [m, n] in BOTH forms, device-resident under the contract of sdrm_csr_rows_to_dense - CSR (indptr [m + 1]
+ *   int64, indices [nnz] int32, data [nnz] float32 or null for all ones) and CSC (colptr [n + 1], rowidx [nnz], cdata: the CSR of the
+ *   transpose; data and cdata are both given or both null).  q0: null - the start panel is drawn on the device, normals 4 j .. 4 j + 3 of
+ *   row i from Philox4x32-10 with counter (i, j, 10, draw) and key `seed` -, or a device float32 [n, 32] that is used instead (how tests
+ *   inject theirs; seed and draw are then unused).  Out: components [k, n] float32 on the device, singular_values_host [k] float64 on the
+ *   HOST, descending.  The call synchronises `stream`: ONE read-back (Z, 128 n bytes, with the status word), the small problem on the host,
+ *   one upload of components.
+ *   SDRM_ERR_SHAPE, before any launch: k < 1, k + 10 > 32 (the reference's 10 oversampling columns must fit the panel), min(m, n) < 32,
+ *   m or n above 2^22, nnz outside 0 .. 2^40 - 1, n_iter outside 0 .. 10000.  A null required pointer is SDRM_ERR_ARG.
+ *   BREAKDOWN is SDRM_ERR_ARG as well (the matrix handed in cannot be factored; the message says so): a panel whose columns are numerically
+ *   dependent - a matrix of rank < 32, or values that are not finite - shows as a Cholesky pivot at or below 2^-40 of the largest diagonal
+ *   entry of the Gram matrix (the derivation is in csrc/svd_eval.h).  It raises a status word on the device and zeroes the panel, so the
+ *   rest of the fit meets no NaN and stores nothing outside the handle's scratch; components and singular_values_host are not written.
+ *   The word is cleared by the refusal and by the next fit: the next call on the same handle works.
+ * sdrm_svd_scores: scores [b, n_items] float32 contiguous = (A_rows V^T) V for the CSR rows rows[0..b) (or row0 .. row0+b-1 when rows is
+ *   null) of a device-resident matrix [n_rows, n_items] and V = components [k, n_items]: V is transposed into scratch, the rows' k
+ *   coordinates are gathered by the fit's product kernel, and the expansion writes every element of scores exactly once.  Three launches,
+ *   no synchronisation.  Seen items are NOT masked: sdrm_rank_metrics does that.
+ *   SDRM_ERR_SHAPE: k outside 1 .. 22, b or n_items above 2^22, b x n_items at or above 2^40, a contiguous range that ends behind n_rows.
+ * Range checks of both calls, into the status word sdrm_feed_status reports: row ids, indptr / colptr pairs (negative, out of order or
+ * reaching behind nnz: the row is empty), column / row indices outside the matrix (the entry is skipped).  A row that fails is a zero
+ * row of the product and of scores.  No load or store uses an unchecked index.  Scratch is library-owned and grow-only. */
+int sdrm_svd_fit(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, const int64_t* colptr, const int32_t* rowidx,
+                 const float* cdata, int64_t m, int64_t n, int64_t nnz, int k, int n_iter, uint64_t seed, uint32_t draw, const float* q0,
+                 float* components, double* singular_values_host, void* stream);
+int sdrm_svd_scores(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, int64_t nnz,
+                    const int64_t* rows, int64_t row0, int b, int n_items, const float* components, int k, float* scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,16 @@ int sdrm_debug_gemm(int variant, int cfg, const float* A, const float* B, float*
  * `stream` (tools/gemm_tune.py). */
 int sdrm_debug_gemm_time(int variant, int cfg, int M, int N, int K, int reps, float* us_out, void* stream);
 
+/* The host side of sdrm_svd_fit that needs no device: SDRM_OK, or SDRM_ERR_SHAPE for a call outside its envelope (k < 1, k + 10 > 32,
+ * min of m and n below 32, m or n above 2^22, nnz outside 0 .. 2^40 - 1, n_iter outside 0 .. 10000). */
+int sdrm_debug_svd_args(int64_t m, int64_t n, int64_t nnz, int k, int n_iter);
+/* One stage of the fit on the caller's panels (csrc/svd_eval.h), for the stage tests: y_prod [n_rows, 32] = A q for the CSR matrix
+ * A [n_rows, n_cols] (data null: all ones; hand in the CSC arrays with n_rows and n_cols swapped for the product with the transpose) and
+ * q [n_cols, 32]; y_orth [n_rows, 32] = y_prod orthonormalised (CholeskyQR twice).  All three panels float32 on the device, 16-byte
+ * aligned.  Synchronises `stream`; a breakdown is SDRM_ERR_ARG as in the fit (y_orth is then all zeros). */
+int sdrm_debug_svd_stage(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, int64_t n_cols,
+                         int64_t nnz, const float* q, float* y_prod, float* y_orth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

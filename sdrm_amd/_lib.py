@@ -121,6 +121,10 @@ SIGNATURES = {
     "sdrm_equal_sparsity_csr_end": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "sdrm_rank_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdrm_svd_fit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_uint64,
+                             C.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdrm_svd_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p,
+                                c_void_p]),
     "sdrm_source_hash": (C.c_char_p, []),
     # include/sdrm_hip_debug.h (test / tuning hooks; every setter acts on one handle)
     "sdrm_debug_philox_draws": (c_int, [c_void_p, c_uint64, C.c_uint32, C.c_uint32, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -131,6 +135,8 @@ SIGNATURES = {
     "sdrm_debug_vae_adam_args": (c_int, [C.POINTER(c_uint64), C.POINTER(c_int64), C.POINTER(c_float), c_int, c_int64, c_int, c_int64,
                                          C.POINTER(c_int64)]),
     "sdrm_debug_vae_eval_args": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int, c_int]),
+    "sdrm_debug_svd_args": (c_int, [c_int64, c_int64, c_int64, c_int, c_int]),
+    "sdrm_debug_svd_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_debug_holdout_args": (c_int, [c_int, c_int64, c_int64, C.c_double, c_int64, C.POINTER(c_int64)]),
     "sdrm_debug_set_tile": (c_int, [c_void_p, c_int]),
     "sdrm_debug_set_nt32_rows": (c_int, [c_void_p, c_int, c_int]),

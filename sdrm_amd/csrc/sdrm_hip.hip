@@ -37,6 +37,7 @@
 #include "skinny.h"
 #include "skinny_step.h"
 #include "skinny_fwd4.h"
+#include "svd_eval.h"
 #include "tail.h"
 #include "vae_adam.h"
 #include "dgrad_rows.h"
@@ -253,6 +254,12 @@ struct sdrm_engine {
   size_t ev_cap[EV_BUFS] = {};
   uint32_t* hold_cnt = nullptr;      // grow-only scratch of sdrm_holdout_split (csrc/holdout.h): [2][rows] entries n_u and held entries m_u of every row
   size_t hold_cap = 0;               // in elements
+  // sdrm_svd_fit / sdrm_svd_scores (csrc/svd_eval.h), grow-only: the fit's panels Q [n][32] | Y [m][32]; the scores' V^T [n][32] | T [b][32];
+  // the Gram partials [SVD_GRAM_PARTS][32][32] with R^-1 [32][32] behind them (float64), and the fit's status word (bit 0: breakdown)
+  float *svd_panel = nullptr, *svd_vt = nullptr;
+  size_t svd_panel_cap = 0, svd_vt_cap = 0;
+  double* svd_part = nullptr;
+  unsigned* svd_flag = nullptr;
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
   Exchange xch;                      // RCCL communicator of the user-sharded step (sdrm_comm_init_rank / sdrm_allreduce_init)
   mutable int64_t n_launches = 0;    // kernel launches issued through this handle since sdrm_create
@@ -284,7 +291,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -305,7 +312,12 @@ static const char* kProfNames[PC_COUNT] = {
     "latent head: k_latent_stage / gemm_kernel<0,0,0,0,7> / k_latent_reparam forward, k_latent_stage_bwd / k_latent_seed / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / k_latent_unpad backward of the VAE encoder behind its first pre-activation in train mode",
     "decoder head: k_pad2d / gemm_kernel<0,0,0,0,1> / k_dechead_h3 / gemm_kernel<0,0,0,0,7> / k_nll_rows / k_nll_sum forward, k_dechead_stage_bwd / k_dechead_grad / gemm_kernel<1,1,0,0,4> / gemm_kernel<0,0,0,0,11> / gemm_kernel<0,0,0,0,7> / k_dechead_unpad backward of the VAE decoder and the multinomial loss in train mode",
     "optimizer: k_vae_adam / k_vae_loss_slot Adam over the VAE pre-stage's parameter tensors in one launch (with the L2 partial sums) and the step's loss value into its slot",
-    "evaluation half: k_pad2d / k_encode_w1t staging once per call, then per batch k_encode_csr_checked / gemm_kernel<0,0,0,0,0> / gemm_kernel<0,0,0,0,1> / gemm_kernel<0,0,0,0,7> / k_rank_metrics_checked: the VAE's eval-mode forward from the CSR rows of a hold-out split and Recall@k / NDCG@k of its scores"};
+    "evaluation half: k_pad2d / k_encode_w1t staging once per call, then per batch k_encode_csr_checked / gemm_kernel<0,0,0,0,0> / gemm_kernel<0,0,0,0,1> / gemm_kernel<0,0,0,0,7> / k_rank_metrics_checked: the VAE's eval-mode forward from the CSR rows of a hold-out split and Recall@k / NDCG@k of its scores",
+    "svd evaluator: k_svd_spmm sparse x [., 32] panel product from CSR / CSC rows (fixed summation order)",
+    "svd evaluator: k_svd_gram float64 partials of the panel's Gram matrix",
+    "svd evaluator: k_svd_chol partials summed, 32 x 32 Cholesky factor and its inverse in float64 (one work-group)",
+    "svd evaluator: k_svd_apply panel times R^-1, row by row",
+    "svd evaluator: k_svd_start / k_svd_vt / k_svd_expand start panel, V^T staging and the rank-k expansion into dense scores"};
 
 namespace {
 
@@ -1622,6 +1634,8 @@ int sdrm_destroy(sdrm_engine* e) {
   for (float* b : e->ev_buf)
     if (b) (void)hipFree(b);
   if (e->hold_cnt) (void)hipFree(e->hold_cnt);
+  for (void* b : {(void*)e->svd_panel, (void*)e->svd_vt, (void*)e->svd_part, (void*)e->svd_flag})
+    if (b) (void)hipFree(b);
   if (e->csr_ws) (void)hipFree(e->csr_ws);
   if (e->csr_nnz_host) (void)hipHostFree(e->csr_nnz_host);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -3771,6 +3785,236 @@ int sdrm_rank_metrics(sdrm_engine* e, const float* scores, int U, int I, const i
   SDRM_LAUNCH(e, k_rank_metrics, dim3(U), dim3(256), lds, (hipStream_t)stream, a);
   HIP_TRY(e, hipGetLastError());
   return SDRM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Rank-k truncated SVD of a sparse matrix and the scores of its reconstruction (svd_benchmark.py:17-70), csrc/svd_eval.h.
+namespace {
+
+constexpr int64_t SVD_MAX_DIM = (int64_t)1 << 22;
+const char* const kSvdEnvelope = ": k outside 1 .. 22 (k + 10 columns must fit the panel of 32), min(m, n) < 32, m or n above 2^22, nnz outside 0 .. 2^40 - 1 "
+                                 "or n_iter outside 0 .. 10000";
+
+int svd_scratch(sdrm_engine* e) {
+  if (!e->svd_part) HIP_TRY(e, dalloc(&e->svd_part, (size_t)(SVD_GRAM_PARTS + 1) * SVD_PW * SVD_PW));
+  if (!e->svd_flag) HIP_TRY(e, dalloc(&e->svd_flag, 4));
+  return SDRM_OK;
+}
+
+// y [c.b][32] = (the rows of c) q
+hipError_t svd_spmm(sdrm_engine* e, const CsrBatch& c, int64_t nnz, const float* q, float* y, hipStream_t st) {
+  const SvdSpmmArgs a{c, nnz, q, y};
+  return profiled(e, PC_SVD_SPMM, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_svd_spmm, dim3((unsigned)((c.b + 31) / 32)), dim3(256), 0, st, a);
+    return hipGetLastError();
+  });
+}
+
+// y [rows][32] <- orth(y): CholeskyQR twice, three launches each
+hipError_t svd_orth(sdrm_engine* e, float* y, int rows, hipStream_t st) {
+  const int parts = std::min(SVD_GRAM_PARTS, (rows + SVD_GRAM_ROWS - 1) / SVD_GRAM_ROWS);
+  double* rinv = e->svd_part + (size_t)SVD_GRAM_PARTS * SVD_PW * SVD_PW;
+  hipError_t rc = hipSuccess;
+  for (int pass = 0; pass < 2 && rc == hipSuccess; ++pass) {
+    rc = profiled(e, PC_SVD_GRAM, 0.0, st, [&] {
+      SDRM_LAUNCH(e, k_svd_gram, dim3((unsigned)parts), dim3(256), 0, st, (const float*)y, rows, e->svd_part);
+      return hipGetLastError();
+    });
+    if (rc == hipSuccess)
+      rc = profiled(e, PC_SVD_CHOL, 0.0, st, [&] {
+        SDRM_LAUNCH(e, k_svd_chol, dim3(1), dim3(256), 0, st, (const double*)e->svd_part, parts, rinv, e->svd_flag);
+        return hipGetLastError();
+      });
+    if (rc == hipSuccess)
+      rc = profiled(e, PC_SVD_APPLY, 0.0, st, [&] {
+        SDRM_LAUNCH(e, k_svd_apply, dim3((unsigned)((rows + 31) / 32)), dim3(256), 0, st, y, rows, (const double*)rinv);
+        return hipGetLastError();
+      });
+  }
+  return rc;
+}
+
+// Eigen-decomposition of the symmetric a [n][n] by cyclic Jacobi rotations (float64): the eigenvalues end on a's diagonal, column j of v
+// is the eigenvector of a[j][j].
+void jacobi_eigh(std::vector<double>& a, std::vector<double>& v, int n) {
+  v.assign((size_t)n * n, 0.0);
+  for (int i = 0; i < n; ++i) v[(size_t)i * n + i] = 1.0;
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    double off = 0.0, diag = 0.0;
+    for (int p = 0; p < n; ++p) {
+      diag += a[(size_t)p * n + p] * a[(size_t)p * n + p];
+      for (int q = p + 1; q < n; ++q) off += a[(size_t)p * n + q] * a[(size_t)p * n + q];
+    }
+    if (!(off > 1e-32 * diag)) break;
+    for (int p = 0; p < n; ++p)
+      for (int q = p + 1; q < n; ++q) {
+        const double apq = a[(size_t)p * n + q];
+        if (apq == 0.0) continue;
+        const double theta = (a[(size_t)q * n + q] - a[(size_t)p * n + p]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < n; ++k) {
+          const double akp = a[(size_t)k * n + p], akq = a[(size_t)k * n + q];
+          a[(size_t)k * n + p] = c * akp - s * akq;
+          a[(size_t)k * n + q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < n; ++k) {
+          const double apk = a[(size_t)p * n + k], aqk = a[(size_t)q * n + k];
+          a[(size_t)p * n + k] = c * apk - s * aqk;
+          a[(size_t)q * n + k] = s * apk + c * aqk;
+        }
+        for (int k = 0; k < n; ++k) {
+          const double vkp = v[(size_t)k * n + p], vkq = v[(size_t)k * n + q];
+          v[(size_t)k * n + p] = c * vkp - s * vkq;
+          v[(size_t)k * n + q] = s * vkp + c * vkq;
+        }
+      }
+  }
+}
+
+// The closing small problem on the host, float64: z [n][32] = A^T Y = B^T.  eigh(B B^T = z^T z), the top k eigenvectors u rotated into
+// the rows z u of V and normalised (float32 [k][n]), sigma = sqrt(eigenvalue).  False when a direction has no length or is not finite.
+bool svd_close(const std::vector<float>& z, int64_t n, int k, std::vector<float>& V, double* sigma) {
+  std::vector<double> g((size_t)SVD_PW * SVD_PW, 0.0), u;
+  for (int64_t r = 0; r < n; ++r) {
+    const float* zr = &z[(size_t)r * SVD_PW];
+    for (int i = 0; i < SVD_PW; ++i)
+      for (int j = i; j < SVD_PW; ++j) g[(size_t)i * SVD_PW + j] += (double)zr[i] * (double)zr[j];
+  }
+  for (int i = 0; i < SVD_PW; ++i)
+    for (int j = 0; j < i; ++j) g[(size_t)i * SVD_PW + j] = g[(size_t)j * SVD_PW + i];
+  for (double x : g)
+    if (!std::isfinite(x)) return false;
+  jacobi_eigh(g, u, SVD_PW);
+  int order[SVD_PW];
+  for (int i = 0; i < SVD_PW; ++i) order[i] = i;
+  std::stable_sort(order, order + SVD_PW, [&](int x, int y) { return g[(size_t)x * SVD_PW + x] > g[(size_t)y * SVD_PW + y]; });
+  V.assign((size_t)k * n, 0.f);
+  std::vector<double> row((size_t)n);
+  for (int c = 0; c < k; ++c) {
+    const int col = order[c];
+    double norm2 = 0.0;
+    for (int64_t r = 0; r < n; ++r) {
+      double s = 0.0;
+      for (int i = 0; i < SVD_PW; ++i) s += (double)z[(size_t)r * SVD_PW + i] * u[(size_t)i * SVD_PW + col];
+      row[(size_t)r] = s;
+      norm2 += s * s;
+    }
+    if (!(norm2 > 0.0) || !std::isfinite(norm2)) return false;
+    const double inv = 1.0 / std::sqrt(norm2);
+    for (int64_t r = 0; r < n; ++r) V[(size_t)c * n + r] = (float)(row[(size_t)r] * inv);
+    sigma[c] = std::sqrt(std::max(g[(size_t)col * SVD_PW + col], 0.0));
+  }
+  return true;
+}
+
+const char* const kSvdBreakdown = ": breakdown - a panel of 32 columns became numerically dependent (a Cholesky pivot at or below 2^-40 of the "
+                                  "largest diagonal entry of its Gram matrix): the matrix has numerical rank below 32, or holds values that are not finite";
+
+// the fit's status word as it stands once `st` has drained; a raised one is cleared for the next call
+int svd_breakdown(sdrm_engine* e, const char* who, hipStream_t st, unsigned flag) {
+  if (!(flag & SVD_BREAKDOWN)) return SDRM_OK;
+  HIP_TRY(e, hipMemsetAsync(e->svd_flag, 0, sizeof(unsigned), st));
+  return fail(e, SDRM_ERR_ARG, std::string(who) + kSvdBreakdown);
+}
+
+}  // namespace
+
+// The host side that needs no device: the envelope of sdrm_svd_fit.
+int sdrm_debug_svd_args(int64_t m, int64_t n, int64_t nnz, int k, int n_iter) {
+  if (k < 1 || k + 10 > SVD_PW || std::min(m, n) < SVD_PW || m > SVD_MAX_DIM || n > SVD_MAX_DIM || nnz < 0 || nnz >= ((int64_t)1 << 40) ||
+      n_iter < 0 || n_iter > 10000)
+    return SDRM_ERR_SHAPE;
+  return SDRM_OK;
+}
+
+int sdrm_svd_fit(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, const int64_t* colptr, const int32_t* rowidx,
+                 const float* cdata, int64_t m, int64_t n, int64_t nnz, int k, int n_iter, uint64_t seed, uint32_t draw, const float* q0,
+                 float* components, double* singular_values_host, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!indptr || !indices || !colptr || !rowidx || !components || !singular_values_host) return fail(e, SDRM_ERR_ARG, "sdrm_svd_fit: null pointer");
+  if ((data == nullptr) != (cdata == nullptr)) return fail(e, SDRM_ERR_ARG, "sdrm_svd_fit: the values of the CSR and of the CSC form go together");
+  if (int rc = sdrm_debug_svd_args(m, n, nnz, k, n_iter)) return fail(e, rc, std::string("sdrm_svd_fit") + kSvdEnvelope);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = svd_scratch(e)) return rc;
+  if (int rc = grow(e, &e->svd_panel, &e->svd_panel_cap, (size_t)(m + n) * SVD_PW)) return rc;
+  float* Q = e->svd_panel;
+  float* Y = Q + (size_t)n * SVD_PW;
+  const CsrBatch by_rows{indptr, indices, data, nullptr, 0, m, (int)m, (int)n, e->feed_flag};
+  const CsrBatch by_cols{colptr, rowidx, cdata, nullptr, 0, n, (int)n, (int)m, e->feed_flag};
+  HIP_TRY(e, hipMemsetAsync(e->svd_flag, 0, sizeof(unsigned), st));
+  if (q0) {
+    HIP_TRY(e, hipMemcpyAsync(Q, q0, (size_t)n * SVD_PW * sizeof(float), hipMemcpyDeviceToDevice, st));
+  } else {
+    HIP_TRY(e, profiled(e, PC_SVD_EXPAND, 0.0, st, [&] {
+      SDRM_LAUNCH(e, k_svd_start, dim3((unsigned)std::min<int64_t>(4096, (n * 8 + 255) / 256)), dim3(256), 0, st, Q, (int)n, (uint32_t)seed,
+                  (uint32_t)(seed >> 32), draw);
+      return hipGetLastError();
+    }));
+  }
+  for (int it = 0; it <= n_iter; ++it) {
+    HIP_TRY(e, svd_spmm(e, by_rows, nnz, Q, Y, st));
+    HIP_TRY(e, svd_orth(e, Y, (int)m, st));
+    HIP_TRY(e, svd_spmm(e, by_cols, nnz, Y, Q, st));   // the last one stays as it is: Z = A^T Y
+    if (it < n_iter) HIP_TRY(e, svd_orth(e, Q, (int)n, st));
+  }
+  std::vector<float> z((size_t)n * SVD_PW), V;
+  unsigned flag = 0;
+  HIP_TRY(e, hipMemcpyAsync(z.data(), Q, z.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&flag, e->svd_flag, sizeof(flag), hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipStreamSynchronize(st));
+  if (int rc = svd_breakdown(e, "sdrm_svd_fit", st, flag)) return rc;
+  if (!svd_close(z, n, k, V, singular_values_host)) return fail(e, SDRM_ERR_ARG, std::string("sdrm_svd_fit") + kSvdBreakdown);
+  HIP_TRY(e, hipMemcpyAsync(components, V.data(), V.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipStreamSynchronize(st));   // V is this call's own
+  return SDRM_OK;
+}
+
+int sdrm_svd_scores(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, int64_t nnz,
+                    const int64_t* rows, int64_t row0, int b, int n_items, const float* components, int k, float* scores, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!components || !scores) return fail(e, SDRM_ERR_ARG, "sdrm_svd_scores: null pointer");
+  CsrBatch c;
+  if (int rc = csr_batch(e, "sdrm_svd_scores", indptr, indices, data, n_rows, rows, row0, b, n_items, &c)) return rc;
+  if (k < 1 || k > SVD_KMAX || n_items > SVD_MAX_DIM || b > SVD_MAX_DIM || nnz < 0 || nnz >= ((int64_t)1 << 40) ||
+      (int64_t)b * n_items >= ((int64_t)1 << 40))
+    return fail(e, SDRM_ERR_SHAPE, "sdrm_svd_scores: k outside 1 .. 22, b or n_items above 2^22, nnz outside 0 .. 2^40 - 1 or b x n_items at or above 2^40");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = grow(e, &e->svd_vt, &e->svd_vt_cap, ((size_t)n_items + (size_t)b) * SVD_PW)) return rc;
+  float* Vt = e->svd_vt;
+  float* T = Vt + (size_t)n_items * SVD_PW;
+  HIP_TRY(e, profiled(e, PC_SVD_EXPAND, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_svd_vt, dim3((unsigned)std::min<int64_t>(4096, ((int64_t)n_items * SVD_PW + 255) / 256)), dim3(256), 0, st, components, k, n_items, Vt);
+    return hipGetLastError();
+  }));
+  HIP_TRY(e, svd_spmm(e, c, nnz, Vt, T, st));
+  const SvdExpandArgs a{T, components, k, n_items, b, scores};
+  HIP_TRY(e, profiled(e, PC_SVD_EXPAND, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_svd_expand, dim3((unsigned)((n_items + 255) / 256), (unsigned)std::min(4096, (b + SVD_ROW_TILE - 1) / SVD_ROW_TILE)), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }));
+  return SDRM_OK;
+}
+
+// One product and one orthonormalisation on the caller's panels (include/sdrm_hip_debug.h).
+int sdrm_debug_svd_stage(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, int64_t n_cols,
+                         int64_t nnz, const float* q, float* y_prod, float* y_orth, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!indptr || !indices || !q || !y_prod || !y_orth) return fail(e, SDRM_ERR_ARG, "sdrm_debug_svd_stage: null pointer");
+  if (((uintptr_t)q | (uintptr_t)y_prod | (uintptr_t)y_orth) & 15u) return fail(e, SDRM_ERR_ARG, "sdrm_debug_svd_stage: the panels must be 16-byte aligned");
+  if (n_rows < 1 || n_rows > SVD_MAX_DIM || n_cols < 1 || n_cols > SVD_MAX_DIM || nnz < 0 || nnz >= ((int64_t)1 << 40))
+    return fail(e, SDRM_ERR_SHAPE, "sdrm_debug_svd_stage: n_rows or n_cols outside 1 .. 2^22 or nnz outside 0 .. 2^40 - 1");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = svd_scratch(e)) return rc;
+  const CsrBatch c{indptr, indices, data, nullptr, 0, n_rows, (int)n_rows, (int)n_cols, e->feed_flag};
+  HIP_TRY(e, hipMemsetAsync(e->svd_flag, 0, sizeof(unsigned), st));
+  HIP_TRY(e, svd_spmm(e, c, nnz, q, y_prod, st));
+  HIP_TRY(e, hipMemcpyAsync(y_orth, y_prod, (size_t)n_rows * SVD_PW * sizeof(float), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(e, svd_orth(e, y_orth, (int)n_rows, st));
+  unsigned flag = 0;
+  HIP_TRY(e, hipMemcpyAsync(&flag, e->svd_flag, sizeof(flag), hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipStreamSynchronize(st));
+  return svd_breakdown(e, "sdrm_debug_svd_stage", st, flag);
 }
 
 // ---------------------------------------------------------------------------------------------

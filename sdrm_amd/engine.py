@@ -993,6 +993,86 @@ class Engine:
         self._keepalive = (scores, hp, hi, tr)
         return recall, ndcg
 
+    # ------------------------------------------------------------------ truncated-SVD evaluator (csrc/svd_eval.h)
+    SVD_PANEL = 32   # columns of the fit's panel: n_components + the reference's 10 oversampling columns must fit
+
+    def _sparse_dev(self, who, name, sp_dev):
+        """(indptr, indices, data, n_rows, n_cols, nnz) of a `csr_to_device` / `csc_to_device` tuple, checked; an empty index array is
+        replaced by one element (torch gives an empty tensor no address, and the C ABI takes no null array)."""
+        indptr, indices, data, (n_rows, n_cols) = sp_dev
+        n_rows, n_cols, nnz = int(n_rows), int(n_cols), int(indices.numel())
+        major = n_cols if name == "csc" else n_rows
+        indptr = self._index(who, f"{name} indptr", indptr, torch.int64, major + 1)
+        indices = self._index(who, f"{name} indices", indices, torch.int32, nnz)
+        if data is not None:
+            data = self._f32(who, f"{name} data", data, (nnz,))
+        if nnz == 0:
+            indices = indices.new_zeros(1)
+        return indptr, indices, data, n_rows, n_cols, nnz
+
+    def svd_fit(self, csr_dev, csc_dev, n_components=20, n_iter=100, seed=0, draw=0, q0=None):
+        """`TruncatedSVD(n_components, n_iter=n_iter).fit` (svd_benchmark.py:47-48) on the device, sdrm_svd_fit: the subspace iteration of
+        sklearn's randomized SVD on a panel of 32 columns, from the `csr_to_device` and `csc_to_device` tuples of ONE matrix [m, n].
+        Returns (components [n_components, n] float32 device tensor, singular_values [n_components] float64 numpy array, descending).
+        The start panel is drawn on the device from Philox keys of (seed, draw), or is `q0` [n, 32] (float32, host or device).  The
+        sign of a component is the iteration's own.  Refused with SDRM_ERR_SHAPE before anything is launched: n_components < 1,
+        n_components + 10 > 32, min(m, n) < 32.  A matrix of numerical rank below 32 breaks the panel's factorisation down: the call
+        raises (SDRM_ERR_ARG), and the next fit on this engine works.  The call synchronises (one read-back) and asks `feed_status()`."""
+        who = "svd_fit"
+        k, n_iter = int(n_components), int(n_iter)
+        indptr, indices, data, m, n, nnz = self._sparse_dev(who, "csr", csr_dev)
+        colptr, rowidx, cdata, m2, n2, nnz2 = self._sparse_dev(who, "csc", csc_dev)
+        if (m2, n2, nnz2) != (m, n, nnz) or (data is None) != (cdata is None):
+            raise SdrmError(f"{who}: SDRM_ERR_ARG: the CSR form is {(m, n)} with {nnz} entries, the CSC form {(m2, n2)} with {nnz2}: not one matrix")
+        if k < 1 or k + 10 > self.SVD_PANEL or min(m, n) < self.SVD_PANEL or n_iter < 0:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: n_components = {k} outside 1 .. {self.SVD_PANEL - 10}, min(m, n) = {min(m, n)} < {self.SVD_PANEL} "
+                            f"or n_iter = {n_iter} < 0")
+        if q0 is not None:
+            q0 = self._f32(who, "q0", self._dev(q0, torch.float32), (n, self.SVD_PANEL))
+        components = torch.empty(k, n, dtype=torch.float32, device=self.device)
+        sigma = np.zeros(k, dtype=np.float64)
+        self._check(self.lib.sdrm_svd_fit(self._h, _ptr(indptr), _ptr(indices), _ptr(data), _ptr(colptr), _ptr(rowidx), _ptr(cdata), m, n, nnz, k,
+                                          n_iter, int(seed) & (2 ** 64 - 1), int(draw) & 0xFFFFFFFF, _ptr(q0), _ptr(components),
+                                          sigma.ctypes.data_as(C.c_void_p), _stream()), "sdrm_svd_fit")
+        self.feed_status()
+        return components, sigma
+
+    def svd_scores(self, csr_dev, components, rows=None, row0=0, b=None, check=True):
+        """`svd.inverse_transform(svd.transform(X))` (svd_benchmark.py:48-49) for a batch of rows of a `csr_to_device` matrix, sdrm_svd_scores:
+        the dense float32 [b, n_items] device tensor (X_rows V^T) V that `rank_metrics` takes, V = `components` [k, n_items] as `svd_fit`
+        returns them.  `rows` (int64) or row0 .. row0+b-1.  Seen items are not masked here.  Range checks and `check` as in
+        `csr_rows_to_dense`: a row or entry that fails contributes zeros."""
+        who = "svd_scores"
+        n_rows, n_items, b, batch = self._csr_batch(who, csr_dev, rows, row0, b)
+        if not isinstance(components, torch.Tensor) or components.dim() != 2:
+            raise SdrmError(f"{who}: components must be a 2-D float32 tensor [k, n_items]")
+        k = int(components.shape[0])
+        components = self._f32(who, "components", components, (k, n_items))
+        if not 1 <= k <= self.SVD_PANEL - 10:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {k} components outside 1 .. {self.SVD_PANEL - 10}")
+        indptr, indices, data, n_rows_, row_ids, row0_, b_ = batch
+        nnz = int(csr_dev[1].numel())
+        out = torch.empty(b, n_items, dtype=torch.float32, device=self.device)
+        self._check(self.lib.sdrm_svd_scores(self._h, indptr, indices, data, n_rows_, nnz, row_ids, row0_, b_, n_items, _ptr(components), k,
+                                             _ptr(out), _stream()), "sdrm_svd_scores")
+        if check:
+            self.feed_status()
+        return out
+
+    def debug_svd_stage(self, sp_dev, q, transposed=False):
+        """One product and one orthonormalisation of the fit on a caller's panel (sdrm_debug_svd_stage): (A q, orth(A q)) as float32 device
+        tensors [rows, 32] for a `csr_to_device` tuple, or (A^T q, orth(A^T q)) for a `csc_to_device` tuple with `transposed=True`."""
+        who = "debug_svd_stage"
+        indptr, indices, data, m, n, nnz = self._sparse_dev(who, "csc" if transposed else "csr", sp_dev)
+        rows, cols = (n, m) if transposed else (m, n)
+        q = self._f32(who, "q", self._dev(q, torch.float32), (cols, self.SVD_PANEL))
+        y = torch.empty(rows, self.SVD_PANEL, dtype=torch.float32, device=self.device)
+        y_orth = torch.empty_like(y)
+        self._check(self.lib.sdrm_debug_svd_stage(self._h, _ptr(indptr), _ptr(indices), _ptr(data), rows, cols, nnz, _ptr(q), _ptr(y), _ptr(y_orth),
+                                                  _stream()), "sdrm_debug_svd_stage")
+        self.feed_status()
+        return y, y_orth
+
     # ------------------------------------------------------------------ evaluation half of the VAE pre-stage (csrc/eval_half.h)
     def vae_eval_holdout(self, w1, b1, w2, b2, w3, b3, w4, b4, train_csr_dev, held_csr_dev, k, metric, batch=500, out=None, logits=None,
                          check=False):

@@ -7,6 +7,7 @@ the GPU box, where the reference itself cannot travel.  SURVEY.md §8f ("next" r
     equal_sparsity                  main.py:177-185        (threshold at the data's sparsity quantile)
     equal_sparsity_csr              main.py:177-180, :259-270  (the same as a csr_matrix made on the device, either side)
     compute_mf_results              svd_benchmark.py:17-70 (TruncatedSVD(20, n_iter=100) reconstruction, masked, Recall/NDCG@k)
+    compute_mf_results_device       the same evaluator with fit, reconstruction and ranking on the device (opt-in)
     run_experiment                  main.py:143-200        (train -> multi-res + full-res sampling -> evaluate)
 """
 from __future__ import annotations
@@ -139,6 +140,37 @@ def compute_mf_results(training_dataset, testing_dataset, synthetic_data, only_s
     return np.array(rec), np.array(ndcg)
 
 
+def mf_per_user_device(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0):
+    """The device evaluator up to the per-user figures: (recall [6, users], ndcg [6, users]) float64 numpy arrays for `K_LIST`, nan for
+    a user with nothing held out - what `compute_mf_results_device` averages."""
+    test_data, valid_data = metrics.split_train_test_proportion_from_csr_matrix(testing_dataset, batch_size=1000, random_seed=123)
+    synthetic = synthetic_data.tocsr() if issparse(synthetic_data) else csr_matrix(np.asarray(synthetic_data))
+    head = synthetic if only_synthetic else training_dataset.tocsr()
+    parts = [head.astype(np.float64), test_data.astype(np.float64)] + ([] if only_synthetic else [synthetic.astype(np.float64)])
+    combined = vstack(parts).tocsr()
+    combined.eliminate_zeros()   # (`mask_training_examples` masks the NONZERO entries of the stacked rows)
+    lo, users = head.shape[0], valid_data.shape[0]
+    csr_dev, csc_dev = engine.csr_to_device(combined), engine.csc_to_device(combined)
+    components, _ = engine.svd_fit(csr_dev, csc_dev, n_components=20, n_iter=100, seed=seed)
+    scores = engine.svd_scores(csr_dev, components, row0=lo, b=users)
+    # the validation users' stacked training rows as a CSR of their own: indptr holds absolute offsets, so a row range is a slice of it
+    seen_dev = (csr_dev[0][lo:lo + users + 1], csr_dev[1], None, (users, combined.shape[1]))
+    rec, ndcg = engine.rank_metrics(scores, engine.csr_to_device(valid_data), seen_dev, ks=K_LIST)
+    return rec.cpu().numpy(), ndcg.cpu().numpy()
+
+
+def compute_mf_results_device(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0):
+    """`compute_mf_results` with the fit, the reconstruction and the ranking on the device (opt-in: `hp["device_svd"]`).  The same
+    split and the same rows in the same order, stacked as scipy sparse - no dense matrix exists on the host.  The stacked matrix is
+    uploaded once in its CSR and CSC forms; `Engine.svd_fit` runs the rank-20, 100-iteration subspace iteration (csrc/svd_eval.h) from
+    a Philox start panel keyed by `seed`, `Engine.svd_scores` reconstructs the validation users' rows only, and `Engine.rank_metrics`
+    masks them with their stacked training rows and ranks.  Returns the same `(recall[6], ndcg[6])`, nanmean over the users, rounded
+    to 4 places.  `synthetic_data` may be dense 0/1 (`equal_sparsity`) or sparse (`equal_sparsity_csr`)."""
+    rec, ndcg = mf_per_user_device(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=only_synthetic, seed=seed)
+    return (np.array([np.round(np.nanmean(rec[q]), 4) for q in range(len(K_LIST))]),
+            np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
+
+
 # the pre-stage's opt-in flags that `hp` may carry, under `train_SDRM`'s keyword names
 VAE_FLAGS = ("vae_device_feed", "vae_device_holdout", "vae_sparse_input", "vae_device_latent", "vae_device_decoder", "vae_device_optimizer",
              "vae_device_eval")
@@ -147,7 +179,8 @@ VAE_FLAGS = ("vae_device_feed", "vae_device_holdout", "vae_sparse_input", "vae_d
 def run_experiment(split, hp, seed, vae_dir, verbose=False):
     """One run of main.py's loop body with the MI355X engine; returns {"M": (recall, ndcg), "F": ..., "V": ...}.  `hp` may carry the
     seven flags of the VAE pre-stage under the keys `VAE_FLAGS` (each False when absent): those that are set are handed to `train_SDRM`
-    under the same names, and an `hp` without them makes the call it always made."""
+    under the same names, and an `hp` without them makes the call it always made.  `hp["device_svd"]` (False when absent) sends the
+    three evaluations to `compute_mf_results_device` instead of `compute_mf_results`; nothing of it reaches `train_SDRM`."""
     from . import train_SDRM as ts
     train, train_partial, valid = split
     n_users, n_items = train.shape
@@ -168,5 +201,8 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
     V = vae.sample(n_users)
     binarise = equal_sparsity_csr if hp.get("sparse_synthetic", False) else equal_sparsity   # opt-in: CSR made on the device
     for tag, raw in (("M", M), ("F", F), ("V", V)):
-        out[tag] = compute_mf_results(train, valid, binarise(raw, sparsity, net.engine()), only_synthetic=True)
+        if hp.get("device_svd", False):   # opt-in: the downstream evaluator on the device (csrc/svd_eval.h)
+            out[tag] = compute_mf_results_device(train, valid, binarise(raw, sparsity, net.engine()), net.engine(), only_synthetic=True, seed=seed)
+        else:
+            out[tag] = compute_mf_results(train, valid, binarise(raw, sparsity, net.engine()), only_synthetic=True)
     return out
