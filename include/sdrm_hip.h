@@ -591,6 +591,44 @@ int sdrm_svd_fit(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, 
 int sdrm_svd_scores(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, int64_t nnz,
                     const int64_t* rows, int64_t row0, int b, int n_items, const float* components, int k, float* scores, void* stream);
 
+/* The NeuMF evaluator's forward on the device, EVAL MODE only (reference: neural_cf_benchmark_pt.py:125-144, `NCF.forward` of the
+ * 'NeuMF-end' model with dropout off; csrc/neumf.h).  For a user u and an item i, factor F, three MLP layers:
+ *   g = Pg[u] * Qg[i];  h1 = relu(W1 [Pm[u]; Qm[i]] + b1);  h2 = relu(W2 h1 + b2);  h3 = relu(W3 h2 + b3);  y = wp [g; h3] + bp
+ * The struct holds DEVICE pointers to the twelve tensors of the live module as PyTorch stores them (float32, contiguous; a Linear's
+ * weight is [out, in] row-major); they are read by the call, nothing is copied or re-packed on the host, and they are free again once
+ * the call is ordered on `stream`.  factor must be 8, 16 or 32 (SDRM_ERR_SHAPE before any launch otherwise).
+ * Arithmetic: fp32, every output element of every layer one fmaf chain in ascending k from its bias; layer 1 is split into a per-user and
+ * a per-item half (staged once per listed id: one launch) whose sum enters the relu.  A logit has the same bits from either entry point,
+ * at any position of a list and however a call is split.
+ * Ids are int32 and are range-checked on the device into the status word sdrm_feed_status reports: a user id outside [0, n_users)
+ * raises the row bit, an item id outside [0, n_items) the column bit; the offending row / column / logit is written as ZERO, adds
+ * nothing to the loss, and no load uses the id.  Scratch is library-owned and grow-only: a call whose
+ * scratch must grow - the first one, and each one with more listed ids or pairs than any before it on the handle - synchronises the
+ * DEVICE and frees the old buffer before it allocates (such a call cannot run under graph capture); a call that fits does not synchronise.
+ * sdrm_neumf_scores replaces :219-233 and :299-310 (the cartesian product of the validation users and the training items pushed through
+ *   the model in batches of 10000 and moved to a Python list): out [n_listed_users, n_listed_items] float32 row-major, the matrix
+ *   sdrm_rank_metrics takes, for users[0 .. n_listed_users) (any order, repeats allowed) and items[0 .. n_listed_items) - or, with items
+ *   null, the items 0 .. n_items - 1 (n_listed_items must then be n_items).  Two launches.
+ *   SDRM_ERR_SHAPE: no listed user or item, more than 2^20 - 16 listed users (16 per work-group on grid.y), more than 2^22 listed items, users x items at or above 2^40.
+ * sdrm_neumf_pair_loss replaces :209-210 (the validation triples through the model and BCEWithLogitsLoss): for the n pairs (users[j],
+ *   items[j]) logits [n] (may be null) and, with labels [n] float32, *loss_sum (a DEVICE double, may be null) = the sum over j of
+ *   max(x, 0) - x y + log1p(exp(-|x|)), the numerator of BCEWithLogitsLoss's mean: fp32 terms, per-work-group float64 partials and a fixed
+ *   final tree - no atomic, the same bits on every run.  Pairs are staged 65536 at a time: two launches per such chunk and one for the sum.
+ *   SDRM_ERR_ARG: loss_sum without labels, or neither output; SDRM_ERR_SHAPE: n outside 1 .. 2^31 - 1. */
+typedef struct sdrm_neumf {
+  const float* embed_user_gmf; const float* embed_item_gmf;   /* Pg [n_users, F], Qg [n_items, F] */
+  const float* embed_user_mlp; const float* embed_item_mlp;   /* Pm [n_users, 4F], Qm [n_items, 4F] */
+  const float* w1; const float* b1;                           /* MLP_layers.1: [4F, 8F], [4F] */
+  const float* w2; const float* b2;                           /* MLP_layers.4: [2F, 4F], [2F] */
+  const float* w3; const float* b3;                           /* MLP_layers.7: [F, 2F], [F] */
+  const float* wp; const float* bp;                           /* predict_layer: [1, 2F], [1] */
+  int n_users, n_items, factor;
+} sdrm_neumf;
+int sdrm_neumf_scores(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, int n_listed_users, const int32_t* items, int n_listed_items,
+                      float* out, void* stream);
+int sdrm_neumf_pair_loss(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, const int32_t* items, const float* labels, int64_t n,
+                         float* logits, double* loss_sum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,11 @@ int sdrm_debug_svd_args(int64_t m, int64_t n, int64_t nnz, int k, int n_iter);
 int sdrm_debug_svd_stage(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, int64_t n_cols,
                          int64_t nnz, const float* q, float* y_prod, float* y_orth, void* stream);
 
+/* The host side of sdrm_neumf_scores that needs no device: SDRM_OK, or SDRM_ERR_SHAPE for a call outside its envelope (factor outside
+ * {8, 16, 32}, a table without rows, no listed user or item, more than 2^20 - 16 listed users, more than 2^22 listed items, users x items at or
+ * above 2^40). */
+int sdrm_debug_neumf_args(int n_users, int n_items, int factor, int64_t listed_users, int64_t listed_items);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@
 #include "holdout.h"
 #include "input_layer.h"
 #include "latent.h"
+#include "neumf.h"
 #include "nll.h"
 #include "rank.h"
 #include "rowchain.h"
@@ -260,6 +261,12 @@ struct sdrm_engine {
   size_t svd_panel_cap = 0, svd_vt_cap = 0;
   double* svd_part = nullptr;
   unsigned* svd_flag = nullptr;
+  // sdrm_neumf_scores / sdrm_neumf_pair_loss (csrc/neumf.h), grow-only: W2t | W3t | the staged user and item sides; the validity words of
+  // both sides; the pair kernel's per-block loss partials
+  float* neumf_ws = nullptr;
+  int* neumf_valid = nullptr;
+  double* neumf_part = nullptr;
+  size_t neumf_ws_cap = 0, neumf_valid_cap = 0, neumf_part_cap = 0;
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
   Exchange xch;                      // RCCL communicator of the user-sharded step (sdrm_comm_init_rank / sdrm_allreduce_init)
   mutable int64_t n_launches = 0;    // kernel launches issued through this handle since sdrm_create
@@ -291,7 +298,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -317,7 +324,10 @@ static const char* kProfNames[PC_COUNT] = {
     "svd evaluator: k_svd_gram float64 partials of the panel's Gram matrix",
     "svd evaluator: k_svd_chol partials summed, 32 x 32 Cholesky factor and its inverse in float64 (one work-group)",
     "svd evaluator: k_svd_apply panel times R^-1, row by row",
-    "svd evaluator: k_svd_start / k_svd_vt / k_svd_expand start panel, V^T staging and the rank-k expansion into dense scores"};
+    "svd evaluator: k_svd_start / k_svd_vt / k_svd_expand start panel, V^T staging and the rank-k expansion into dense scores",
+    "neumf evaluator: k_neumf_stage layer 1 split per listed user / item, the GMF rows, W2 and W3 transposed",
+    "neumf evaluator: k_neumf_scores eval-mode forward of all listed users x listed items (fp32 vector FMAs, scalar weight operands)",
+    "neumf evaluator: k_neumf_pairs / k_neumf_loss_sum eval-mode forward of listed pairs and the BCE-with-logits numerator (float64 partials, fixed order)"};
 
 namespace {
 
@@ -1635,6 +1645,8 @@ int sdrm_destroy(sdrm_engine* e) {
     if (b) (void)hipFree(b);
   if (e->hold_cnt) (void)hipFree(e->hold_cnt);
   for (void* b : {(void*)e->svd_panel, (void*)e->svd_vt, (void*)e->svd_part, (void*)e->svd_flag})
+    if (b) (void)hipFree(b);
+  for (void* b : {(void*)e->neumf_ws, (void*)e->neumf_valid, (void*)e->neumf_part})
     if (b) (void)hipFree(b);
   if (e->csr_ws) (void)hipFree(e->csr_ws);
   if (e->csr_nnz_host) (void)hipHostFree(e->csr_nnz_host);
@@ -4015,6 +4027,139 @@ int sdrm_debug_svd_stage(sdrm_engine* e, const int64_t* indptr, const int32_t* i
   HIP_TRY(e, hipMemcpyAsync(&flag, e->svd_flag, sizeof(flag), hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipStreamSynchronize(st));
   return svd_breakdown(e, "sdrm_debug_svd_stage", st, flag);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The NeuMF evaluator's eval-mode forward (neural_cf_benchmark_pt.py:125-144 as :203-246 and :294-332 call it), csrc/neumf.h: layer 1
+// staged per listed id, then all listed users x listed items, or listed pairs with the BCE-with-logits numerator.
+namespace {
+
+constexpr int64_t NEUMF_MAX_USERS = ((int64_t)1 << 20) - 16;   // listed users of one sdrm_neumf_scores call: 16 per work-group on grid.y, 65535 at most
+constexpr int64_t NEUMF_MAX_ITEMS = (int64_t)1 << 22;   // listed items of one call
+const char* const kNeumfEnvelope = ": factor outside {8, 16, 32}, a table without rows, no listed user or item, more than 2^20 - 16 listed users, more "
+                                   "than 2^22 listed items, or users x items at or above 2^40";
+
+bool neumf_complete(const sdrm_neumf* w) {
+  return w && w->embed_user_gmf && w->embed_item_gmf && w->embed_user_mlp && w->embed_item_mlp && w->w1 && w->b1 && w->w2 && w->b2 && w->w3 &&
+         w->b3 && w->wp && w->bp;
+}
+
+struct NeumfStaged { const float *w2t, *w3t, *ua, *ibt; const int *uvalid, *ivalid; int64_t ld; };
+
+extern "C++" {   // (the ABI's extern "C" block is open: templates need C++ linkage)
+
+// One staging launch for nu listed users and ni listed items; pairs: the user side in the transposed form as well (nu == ni then).
+template <int F>
+int neumf_stage(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, int nu, bool pairs, const int32_t* items, int ni, hipStream_t st,
+                NeumfStaged* out) {
+  constexpr int ROW = NeumfShape<F>::ROW;
+  const int64_t ldu = ((int64_t)nu + 63) / 64 * 64, ldi = ((int64_t)ni + 63) / 64 * 64;
+  const size_t n_w2 = (size_t)8 * F * F, n_w3 = (size_t)2 * F * F;
+  const size_t n_u = pairs ? (size_t)ROW * ldu : (size_t)nu * ROW;
+  if (int rc = grow(e, &e->neumf_ws, &e->neumf_ws_cap, n_w2 + n_w3 + n_u + (size_t)ROW * ldi)) return rc;
+  if (int rc = grow(e, &e->neumf_valid, &e->neumf_valid_cap, (size_t)nu + ni)) return rc;
+  float* w2t = e->neumf_ws;
+  float* w3t = w2t + n_w2;
+  float* ua = w3t + n_w3;
+  float* ibt = ua + n_u;
+  NeumfStageArgs a;
+  a.side[0] = NeumfStageSide{w->embed_user_mlp, w->embed_user_gmf, users, nu, w->n_users, ua, e->neumf_valid, ldu, pairs ? 1 : 0, 0, FEED_BAD_ROW};
+  a.side[1] = NeumfStageSide{w->embed_item_mlp, w->embed_item_gmf, items, ni, w->n_items, ibt, e->neumf_valid + nu, ldi, 1, 4 * F, FEED_BAD_COL};
+  a.w1 = w->w1; a.b1 = w->b1; a.w2 = w->w2; a.w3 = w->w3;
+  a.w2t = w2t; a.w3t = w3t;
+  a.flag = e->feed_flag;
+  a.blocks[0] = (int)(((int64_t)nu * ROW + 255) / 256);
+  a.blocks[1] = (int)(((int64_t)ni * ROW + 255) / 256);
+  const unsigned grid = (unsigned)a.blocks[0] + (unsigned)a.blocks[1] + (unsigned)((10 * F * F + 255) / 256);
+  HIP_TRY(e, profiled(e, PC_NEUMF_STAGE, 2.0 * 16 * F * F * ((double)nu + ni), st, [&] {
+    SDRM_LAUNCH(e, k_neumf_stage<F>, dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }));
+  *out = NeumfStaged{w2t, w3t, ua, ibt, e->neumf_valid, e->neumf_valid + nu, ldi};
+  return SDRM_OK;
+}
+
+template <int F>
+int neumf_scores(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, int nu, const int32_t* items, int ni, float* out, hipStream_t st) {
+  NeumfStaged s;
+  if (int rc = neumf_stage<F>(e, w, users, nu, false, items, ni, st, &s)) return rc;
+  const dim3 grid((unsigned)((ni + NEUMF_ITEM_TILE - 1) / NEUMF_ITEM_TILE), (unsigned)((nu + NEUMF_USER_TILE - 1) / NEUMF_USER_TILE));
+  HIP_TRY(e, profiled(e, PC_NEUMF_SCORES, 2.0 * (10.0 * F * F + 2.0 * F) * nu * ni, st, [&] {
+    SDRM_LAUNCH(e, k_neumf_scores<F>, grid, dim3(256), 0, st, s.ua, s.uvalid, s.ibt, s.ivalid, s.ld, s.w2t, w->b2, s.w3t, w->b3, w->wp, w->bp, nu, ni,
+                out);
+    return hipGetLastError();
+  }));
+  return SDRM_OK;
+}
+
+template <int F>
+int neumf_pairs(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, const int32_t* items, const float* labels, int64_t n, float* logits,
+                double* loss_sum, hipStream_t st) {
+  const int64_t n_part = (n + 255) / 256;
+  if (loss_sum)
+    if (int rc = grow(e, &e->neumf_part, &e->neumf_part_cap, (size_t)n_part)) return rc;
+  for (int64_t off = 0; off < n; off += NEUMF_PAIR_CHUNK) {
+    const int m = (int)std::min<int64_t>(NEUMF_PAIR_CHUNK, n - off);
+    NeumfStaged s;
+    if (int rc = neumf_stage<F>(e, w, users + off, m, true, items + off, m, st, &s)) return rc;
+    const float* lab = labels ? labels + off : nullptr;
+    float* lg = logits ? logits + off : nullptr;
+    double* part = loss_sum ? e->neumf_part + off / 256 : nullptr;
+    HIP_TRY(e, profiled(e, PC_NEUMF_PAIRS, 2.0 * (10.0 * F * F + 2.0 * F) * m, st, [&] {
+      SDRM_LAUNCH(e, k_neumf_pairs<F>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, s.ua, s.uvalid, s.ibt, s.ivalid, s.ld, s.w2t, w->b2, s.w3t,
+                  w->b3, w->wp, w->bp, lab, m, lg, part);
+      return hipGetLastError();
+    }));
+  }
+  if (loss_sum)
+    HIP_TRY(e, profiled(e, PC_NEUMF_PAIRS, 0.0, st, [&] {
+      SDRM_LAUNCH(e, k_neumf_loss_sum, dim3(1), dim3(256), 0, st, (const double*)e->neumf_part, (int)n_part, loss_sum);
+      return hipGetLastError();
+    }));
+  return SDRM_OK;
+}
+
+}  // extern "C++"
+
+}  // namespace
+
+// The host side that needs no device: the envelope of sdrm_neumf_scores (listed users x listed items; a pair call hands in n and 1).
+int sdrm_debug_neumf_args(int n_users, int n_items, int factor, int64_t listed_users, int64_t listed_items) {
+  if (factor != 8 && factor != 16 && factor != 32) return SDRM_ERR_SHAPE;
+  if (n_users < 1 || n_items < 1 || listed_users < 1 || listed_items < 1) return SDRM_ERR_SHAPE;
+  if (listed_users > NEUMF_MAX_USERS || listed_items > NEUMF_MAX_ITEMS || listed_users * listed_items >= ((int64_t)1 << 40)) return SDRM_ERR_SHAPE;
+  return SDRM_OK;
+}
+
+int sdrm_neumf_scores(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, int n_listed_users, const int32_t* items, int n_listed_items,
+                      float* out, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!neumf_complete(w) || !users || !out) return fail(e, SDRM_ERR_ARG, "sdrm_neumf_scores: null pointer");
+  if (int rc = sdrm_debug_neumf_args(w->n_users, w->n_items, w->factor, n_listed_users, n_listed_items))
+    return fail(e, rc, std::string("sdrm_neumf_scores") + kNeumfEnvelope);
+  if (!items && n_listed_items != w->n_items) return fail(e, SDRM_ERR_SHAPE, "sdrm_neumf_scores: without an item list the columns are all n_items items");
+  hipStream_t st = (hipStream_t)stream;
+  switch (w->factor) {
+    case 8: return neumf_scores<8>(e, w, users, n_listed_users, items, n_listed_items, out, st);
+    case 16: return neumf_scores<16>(e, w, users, n_listed_users, items, n_listed_items, out, st);
+    default: return neumf_scores<32>(e, w, users, n_listed_users, items, n_listed_items, out, st);
+  }
+}
+
+int sdrm_neumf_pair_loss(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, const int32_t* items, const float* labels, int64_t n,
+                         float* logits, double* loss_sum, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!neumf_complete(w) || !users || !items) return fail(e, SDRM_ERR_ARG, "sdrm_neumf_pair_loss: null pointer");
+  if (!logits && !loss_sum) return fail(e, SDRM_ERR_ARG, "sdrm_neumf_pair_loss: neither logits nor loss_sum is asked for");
+  if (loss_sum && !labels) return fail(e, SDRM_ERR_ARG, "sdrm_neumf_pair_loss: the loss needs labels");
+  if (n < 1 || n > (int64_t)0x7fffffff || sdrm_debug_neumf_args(w->n_users, w->n_items, w->factor, 1, 1) != SDRM_OK)
+    return fail(e, SDRM_ERR_SHAPE, "sdrm_neumf_pair_loss: factor outside {8, 16, 32}, a table without rows, or n outside 1 .. 2^31 - 1");
+  hipStream_t st = (hipStream_t)stream;
+  switch (w->factor) {
+    case 8: return neumf_pairs<8>(e, w, users, items, labels, n, logits, loss_sum, st);
+    case 16: return neumf_pairs<16>(e, w, users, items, labels, n, logits, loss_sum, st);
+    default: return neumf_pairs<32>(e, w, users, items, labels, n, logits, loss_sum, st);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------

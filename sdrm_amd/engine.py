@@ -1073,6 +1073,84 @@ class Engine:
         self.feed_status()
         return y, y_orth
 
+    # ------------------------------------------------------------------ NeuMF evaluator's forward (csrc/neumf.h)
+    NEUMF_FACTORS = (8, 16, 32)
+    NEUMF_TENSORS = ("embed_user_GMF.weight", "embed_item_GMF.weight", "embed_user_MLP.weight", "embed_item_MLP.weight", "MLP_layers.1.weight",
+                     "MLP_layers.1.bias", "MLP_layers.4.weight", "MLP_layers.4.bias", "MLP_layers.7.weight", "MLP_layers.7.bias",
+                     "predict_layer.weight", "predict_layer.bias")
+
+    def _neumf(self, who, weights):
+        """The twelve tensors of a live NeuMF-end module with three MLP layers, in `NEUMF_TENSORS` (= `state_dict`) order, checked on the host
+        and handed on as they are: (sdrm_neumf struct, n_users, n_items, factor).  Refused: anything but twelve tensors (a tower of another
+        depth), a factor outside `NEUMF_FACTORS`, a tensor of another dtype / device / shape, tables whose row counts disagree."""
+        weights = list(weights.values()) if isinstance(weights, dict) else list(weights)
+        if len(weights) != len(self.NEUMF_TENSORS):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {len(weights)} tensors; NeuMF-end with THREE MLP layers has twelve ({', '.join(self.NEUMF_TENSORS)})")
+        pg = weights[0]
+        if not isinstance(pg, torch.Tensor) or pg.dim() != 2:
+            raise SdrmError(f"{who}: {self.NEUMF_TENSORS[0]} must be a 2-D float32 tensor [n_users, factor]")
+        n_users, F = int(pg.shape[0]), int(pg.shape[1])
+        if F not in self.NEUMF_FACTORS:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: factor {F} outside {self.NEUMF_FACTORS}")
+        n_items = int(weights[1].shape[0]) if isinstance(weights[1], torch.Tensor) and weights[1].dim() == 2 else -1
+        if n_users < 1 or n_items < 1:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: a table without rows")
+        shapes = ((n_users, F), (n_items, F), (n_users, 4 * F), (n_items, 4 * F), (4 * F, 8 * F), (4 * F,), (2 * F, 4 * F), (2 * F,), (F, 2 * F), (F,),
+                  (1, 2 * F), (1,))
+        ts = [self._f32(who, name, t.detach() if isinstance(t, torch.Tensor) else t, shape) for name, t, shape in zip(self.NEUMF_TENSORS, weights, shapes)]
+        return _lib.Neumf(*[t.data_ptr() for t in ts], n_users, n_items, F), ts, n_users, n_items
+
+    def _ids(self, who, name, ids):
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or ids.device != self.device or not ids.is_contiguous():
+            raise SdrmError(f"{who}: {name} must be a contiguous 1-D int32 tensor on the engine's device")
+        if ids.numel() < 1:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {name} is empty")
+        return ids
+
+    def neumf_scores(self, weights, users, items=None, out=None, check=True):
+        """neural_cf_benchmark_pt.py:219-233 / :299-310 on the device (sdrm_neumf_scores): the eval-mode logits of every listed user against
+        every listed item, dense float32 [len(users), len(items)] as `rank_metrics` takes it.  `weights`: the live module's twelve float32
+        tensors (`NEUMF_TENSORS` order, e.g. `list(model.state_dict().values())`), read in place.  `users`: int32 device tensor, any order,
+        repeats allowed; `items`: the same, or None for 0 .. n_items - 1.  Ids are range-checked on the device (an offending row / column is
+        zero); `check` as in `csr_rows_to_dense`."""
+        who = "neumf_scores"
+        w, keep, n_users, n_items = self._neumf(who, weights)
+        users = self._ids(who, "users", users)
+        if items is not None:
+            items = self._ids(who, "items", items)
+        nu, ni = users.numel(), n_items if items is None else items.numel()
+        if nu > 2 ** 20 - 16 or ni > 2 ** 22 or nu * ni >= 2 ** 40:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {nu} users x {ni} items: more than 2^20 - 16 users, 2^22 items or 2^40 - 1 pairs")
+        if out is None:
+            out = torch.empty(nu, ni, dtype=torch.float32, device=self.device)
+        out = self._f32(who, "out", out, (nu, ni))
+        self._check(self.lib.sdrm_neumf_scores(self._h, C.byref(w), _ptr(users), nu, _ptr(items), ni, _ptr(out), _stream()), "sdrm_neumf_scores")
+        if check:
+            self.feed_status()
+        return out
+
+    def neumf_pair_logits(self, weights, users, items, labels=None, check=True):
+        """neural_cf_benchmark_pt.py:209-210 on the device (sdrm_neumf_pair_loss): (logits [n] float32, loss_sum) for the listed pairs
+        (users[j], items[j]), int32 device tensors of one length.  With `labels` (float32 device tensor [n]) loss_sum is a device float64
+        scalar tensor, the sum of BCEWithLogitsLoss's terms in a fixed order (divide by n for the loss); without, None.  A pair with an id
+        outside its table has logit 0 and adds nothing to the sum."""
+        who = "neumf_pair_logits"
+        w, keep, n_users, n_items = self._neumf(who, weights)
+        users, items = self._ids(who, "users", users), self._ids(who, "items", items)
+        n = users.numel()
+        if items.numel() != n:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {n} users against {items.numel()} items")
+        loss_sum = None
+        if labels is not None:
+            labels = self._f32(who, "labels", labels, (n,))
+            loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
+        logits = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._check(self.lib.sdrm_neumf_pair_loss(self._h, C.byref(w), _ptr(users), _ptr(items), _ptr(labels), n, _ptr(logits), _ptr(loss_sum),
+                                                  _stream()), "sdrm_neumf_pair_loss")
+        if check:
+            self.feed_status()
+        return logits, loss_sum
+
     # ------------------------------------------------------------------ evaluation half of the VAE pre-stage (csrc/eval_half.h)
     def vae_eval_holdout(self, w1, b1, w2, b2, w3, b3, w4, b4, train_csr_dev, held_csr_dev, k, metric, batch=500, out=None, logits=None,
                          check=False):

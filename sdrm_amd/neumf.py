@@ -1,0 +1,274 @@
+"""The NeuMF downstream evaluator (reference: neural_cf_benchmark_pt.py): the module, its all-items ranking and the driver.
+
+The reference trains NeuMF-end on (user, item, label) triples and, after every epoch and once at the end, pushes the cartesian product
+of the validation users and the training items through the model in batches of 10000, merges the logits twice in pandas, rebuilds two
+CSR matrices through Python dicts, densifies them and ranks.  Here that evaluation half has a device form: `Engine.neumf_scores`
+(csrc/neumf.h) gives the dense logit matrix, `Engine.rank_metrics` masks and ranks it, `Engine.neumf_pair_logits` gives the per-epoch
+validation loss; the train loop stays PyTorch.  With `engine=None` the same functions run torch and numpy on the host - the checker.
+
+Triples are a numpy int array [n, 3] (user, item, label); a (user, item) pair occurs at most once per array.  Labels are taken as
+binary (> 0), which is what the reference feeds its evaluators.  No pandas, no sklearn."""
+from __future__ import annotations
+
+import copy
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+from scipy.sparse import csr_matrix
+
+K_LIST = (1, 3, 5, 10, 20, 50)
+LR, BATCH, NUM_NEG, EARLY_STOP = 1e-3, 256, 1, 10            # :28-36, :255
+EVAL_BATCH = 10000                                            # :224, :301 (host path)
+
+
+class NCF(nn.Module):
+    """NeuMF-end (:43-144 with model='NeuMF-end'): a GMF branch (elementwise product of two `factor`-wide embeddings) beside an MLP
+    branch (two embeddings of factor * 2^(layers-1), concatenated, then `layers` times Dropout, Linear halving the width, ReLU), both
+    concatenated into one Linear that gives the logit.  Parameter names, shapes and order are the reference's, so its checkpoints
+    load; so is the initialisation (:84-100): N(0, 0.01) embeddings, Xavier-uniform tower, Kaiming-uniform (a=1, sigmoid gain) predict
+    layer, zero biases."""
+
+    def __init__(self, n_users, n_items, factor=8, layers=3, dropout=0.5):
+        super().__init__()
+        self.factor, self.layers = int(factor), int(layers)
+        wide = self.factor * 2 ** (self.layers - 1)
+        self.embed_user_GMF = nn.Embedding(n_users, self.factor)
+        self.embed_item_GMF = nn.Embedding(n_items, self.factor)
+        self.embed_user_MLP = nn.Embedding(n_users, wide)
+        self.embed_item_MLP = nn.Embedding(n_items, wide)
+        tower, width = [], 2 * wide
+        for _ in range(self.layers):
+            tower += [nn.Dropout(p=dropout), nn.Linear(width, width // 2), nn.ReLU()]
+            width //= 2
+        self.MLP_layers = nn.Sequential(*tower)
+        self.predict_layer = nn.Linear(2 * self.factor, 1)
+        for table in (self.embed_user_GMF, self.embed_user_MLP, self.embed_item_GMF, self.embed_item_MLP):
+            nn.init.normal_(table.weight, std=0.01)
+        for m in self.MLP_layers:
+            if isinstance(m, nn.Linear):
+                nn.init.xavier_uniform_(m.weight)
+        nn.init.kaiming_uniform_(self.predict_layer.weight, a=1, nonlinearity="sigmoid")
+        for m in self.modules():
+            if isinstance(m, nn.Linear):
+                nn.init.zeros_(m.bias)
+
+    def forward(self, user, item):
+        gmf = self.embed_user_GMF(user) * self.embed_item_GMF(item)
+        mlp = self.MLP_layers(torch.cat((self.embed_user_MLP(user), self.embed_item_MLP(item)), -1))
+        return self.predict_layer(torch.cat((gmf, mlp), -1)).view(-1)
+
+    def engine_weights(self, device=None):
+        """The twelve tensors as `Engine.neumf_scores` takes them (`Engine.NEUMF_TENSORS` order): the live parameters themselves when
+        they sit on `device` already, copies on it otherwise."""
+        ts = [t.detach() for t in self.state_dict().values()]
+        return ts if device is None else [t.to(device) for t in ts]
+
+
+def _as_triples(a, name):
+    a = np.asarray(a)
+    if a.ndim != 2 or a.shape[1] != 3 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name}: an integer array [n, 3] of (user, item, label) triples is expected, got {a.dtype} {a.shape}")
+    return a.astype(np.int64, copy=False)
+
+
+def ranking_problem(training, heldout, users):
+    """What the reference's testing block (:294-326) ranks, as index arrays: (users ascending and unique, columns = the item ids that occur
+    in `training` ascending, relevant CSR [U, C] of the held-out triples with label > 0 whose item is a column, seen CSR [U, C] of every
+    (user, item) pair of `training` whatever its label)."""
+    training, heldout = _as_triples(training, "training"), _as_triples(heldout, "heldout")
+    users = np.unique(np.asarray(users, dtype=np.int64))
+    cols = np.unique(training[:, 1])
+
+    def compact(t):
+        keep = np.isin(t[:, 0], users) & np.isin(t[:, 1], cols)
+        r, c = np.searchsorted(users, t[keep, 0]), np.searchsorted(cols, t[keep, 1])
+        m = csr_matrix((np.ones(r.shape[0], dtype=np.float32), (r, c)), shape=(users.shape[0], cols.shape[0]))
+        m.sum_duplicates()
+        m.data[:] = 1.0
+        m.sort_indices()
+        return m
+    return users, cols, compact(heldout[heldout[:, 2] > 0]), compact(training)
+
+
+def _idcg_table():
+    tp = 1.0 / np.log2(np.arange(2, max(K_LIST) + 2))
+    return tp, np.asarray([tp[:m].sum() for m in range(max(K_LIST) + 1)])
+
+
+def host_metrics(scores, relevant):
+    """Per-user (recall [6, U], ndcg [6, U]) of masked scores [U, C] (float, -inf where seen) against the boolean `relevant` [U, C], the way
+    utilities.recall_at_k_batch / NDCG_binary_at_k_batch come out on the CSR matrices the reference builds: its held-out matrix stores an
+    explicit entry for EVERY pair of the cartesian product, so `getnnz` is the column count and the ideal DCG is sum(tp[:min(C, k)]) for
+    every user; a user without a relevant item has recall nan (0 / 0) and NDCG 0."""
+    U, C = scores.shape
+    if C <= max(K_LIST):
+        raise ValueError(f"ranking needs more than {max(K_LIST)} columns, got {C}")
+    tp, idcg = _idcg_table()
+    rows = np.arange(U)[:, None]
+    n_true = relevant.sum(axis=1)
+    recall, ndcg = np.empty((len(K_LIST), U)), np.empty((len(K_LIST), U))
+    for q, k in enumerate(K_LIST):
+        part = np.argpartition(-scores, k, axis=1)[:, :k]
+        topk = part[rows, np.argsort(-scores[rows, part], axis=1)]
+        hits = relevant[rows, part].sum(axis=1).astype(np.float32)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            recall[q] = hits / np.minimum(k, n_true)
+        ndcg[q] = (relevant[rows, topk] * tp[:k]).sum(axis=1) / idcg[min(C, k)]
+    return recall, ndcg
+
+
+@torch.no_grad()
+def host_scores(model, users, items):
+    """The logits of every listed user against every listed item from the torch module in eval mode, in the reference's batches of 10000
+    pairs (:219-233): float32 numpy [U, C]."""
+    device = next(model.parameters()).device
+    was_training = model.training
+    model.eval()
+    pairs = torch.cartesian_prod(torch.as_tensor(users, dtype=torch.int32, device=device), torch.as_tensor(items, dtype=torch.int32, device=device))
+    out = [model(pairs[s:s + EVAL_BATCH, 0], pairs[s:s + EVAL_BATCH, 1]) for s in range(0, pairs.shape[0], EVAL_BATCH)]
+    model.train(was_training)
+    return torch.cat(out).reshape(len(users), len(items)).cpu().numpy()
+
+
+def rank_all_items(model, training, heldout, users, engine=None):
+    """The reference's testing block (:294-332; the per-epoch one :215-246 is the same) for `model`: per-user (recall [6, U], ndcg [6, U])
+    float64 numpy arrays for `K_LIST`, row q of either for the q-th smallest id in `users`.  As the reference behaves:
+      * the columns are the item ids that occur in `training`; a held-out item that never occurs there is dropped;
+      * every (user, item) pair present in `training`, with any label, 0 included, is masked to -inf;
+      * only held-out triples with label > 0 are relevant;
+      * the ideal DCG counts min(columns, k) items for every user (see `host_metrics`); a user without a relevant item: recall nan, NDCG 0.
+    With an engine the two CSR matrices are compacted here with numpy and uploaded, the logits are ONE `neumf_scores` call, masking and
+    ranking are the existing `rank_metrics`; its NDCG (ideal DCG of min(relevant, k) items, nan without one) is put on the reference's
+    footing from the per-user counts on the host.  `feed_status()` is asked once.  Without one, torch and numpy do all of it."""
+    users, cols, relevant, seen = ranking_problem(training, heldout, users)
+    if cols.shape[0] <= max(K_LIST):
+        raise ValueError(f"ranking needs more than {max(K_LIST)} training items, got {cols.shape[0]}")
+    if engine is None:
+        scores = host_scores(model, users, cols).astype(np.float32)
+        scores[seen.nonzero()] = -np.inf
+        return host_metrics(scores, relevant.toarray() > 0)
+    weights = model.engine_weights(engine.device)
+    scores = engine.neumf_scores(weights, torch.from_numpy(users.astype(np.int32)).to(engine.device),
+                                 torch.from_numpy(cols.astype(np.int32)).to(engine.device), check=False)
+    rec, ndcg = engine.rank_metrics(scores, engine.csr_to_device(relevant), engine.csr_to_device(seen), ks=K_LIST)
+    rec, ndcg = rec.cpu().numpy(), ndcg.cpu().numpy()
+    engine.feed_status()
+    _, idcg = _idcg_table()
+    n_true = np.diff(relevant.indptr)
+    for q, k in enumerate(K_LIST):
+        ndcg[q] = np.where(n_true > 0, ndcg[q] * idcg[np.minimum(n_true, k)] / idcg[min(cols.shape[0], k)], 0.0)
+    return rec, ndcg
+
+
+def _bce_with_logits(logits, labels):
+    return nn.functional.binary_cross_entropy_with_logits(logits, labels)
+
+
+def validation_loss(model, triples, engine=None):
+    """`BCEWithLogitsLoss` of the model in eval mode on (user, item, label) triples (:203-211) as a Python float: `neumf_pair_logits`'s
+    loss sum over n with an engine, torch's own on the model's device without."""
+    triples = _as_triples(triples, "triples")
+    if engine is not None:
+        dev = engine.device
+        _, loss_sum = engine.neumf_pair_logits(model.engine_weights(dev), torch.from_numpy(triples[:, 0].astype(np.int32)).to(dev),
+                                               torch.from_numpy(triples[:, 1].astype(np.int32)).to(dev),
+                                               torch.from_numpy(triples[:, 2].astype(np.float32)).to(dev), check=False)
+        return float(loss_sum.item()) / triples.shape[0]
+    device = next(model.parameters()).device
+    was_training = model.training
+    model.eval()
+    with torch.no_grad():
+        x = torch.as_tensor(triples, dtype=torch.int32, device=device)
+        loss = _bce_with_logits(model(x[:, 0], x[:, 1]), x[:, 2].float()).item()
+    model.train(was_training)
+    return loss
+
+
+def compute_neuralcf_results(training, validation, n_users, n_items, engine=None, seed=0, epochs=20, eval_recall=True, device=None,
+                             history=None):
+    """The reference's driver (:154-334) over int triples [n, 3]: (recall [6], ndcg [6]) for `K_LIST`, nanmean over the validation users
+    rounded to 4 places.  As the reference: NCF(factor 8, three layers, dropout 0.5), Adam(1e-3), BCEWithLogitsLoss, batches of 256; per
+    epoch a fresh 80/20 split of `training`, as many label-0 rows of the 80 % drawn again WITH replacement as it has label-1 rows
+    (num_neg = 1), everything shuffled; after the epoch the loss on the 20 % and, with `eval_recall`, Recall@10 of the 20 %'s users
+    against `validation`.  Which weights rank at the end is the reference's too: without `eval_recall` those of the epoch with the lowest
+    validation loss; with it those of EPOCH 0 (the reference saves every epoch that improves Recall@10 but loads `best_epoch`, which
+    that branch never sets).  Where epoch 0's Recall@10 was 0 or nan the reference has no file of this run to load - it fails, or loads a
+    stale file of an earlier run; THIS driver's own choice there, not the reference's, is to rank with the last epoch's weights, and
+    `history` says so ('best_epoch' is then that last epoch and 'reference_has_no_checkpoint' is True).
+    The early-stop counter runs as the reference's does (with `eval_recall` it is never reset) and stops the loop at 10.  Weights are
+    kept in memory, not in a directory.
+    The reference's shuffles are unseeded; here every draw comes from `numpy.random.default_rng(seed)` (split permutation, negative
+    draw, shuffle, in that order per epoch), the module's initialisation and its dropout from torch's GLOBAL generator, seeded with
+    `seed` on entry (`torch.manual_seed`): numpy's global generator is not touched, torch's is left wherever training took it.
+    The train loop is torch in both modes and runs on `device` (default: the engine's device, the CPU without one).  With an engine the
+    per-epoch validation loss is `neumf_pair_logits`, both rankings are `rank_all_items(..., engine)`, and `feed_status()` is asked once
+    per evaluation; weights that live elsewhere than on the engine's device are copied there per evaluation.
+    `history`: a dict that receives 'valid_loss' (per epoch), 'recall10' (per epoch, with eval_recall), 'best_epoch' (the epoch whose
+    weights ranked), 'reference_has_no_checkpoint', 'best_recall_epoch', 'epochs_run', 'per_user' (the final per-user recall / ndcg)
+    and 'model' (the module that ranked)."""
+    training, validation = _as_triples(training, "training"), _as_triples(validation, "validation")
+    device = torch.device(device) if device is not None else (engine.device if engine is not None else torch.device("cpu"))
+    rng = np.random.default_rng(seed)
+    torch.manual_seed(seed)
+    model = NCF(n_users, n_items, factor=8, layers=3, dropout=0.5).to(device)
+    optimizer = torch.optim.Adam(model.parameters(), lr=LR)
+    best_loss, best_epoch, best_recall, best_recall_epoch, early_stop = math.inf, 0, 0.0, None, 0
+    kept = {0: None}
+    valid_losses, recalls, epochs_run = [], [], 0
+    n_hold = int(math.ceil(0.2 * training.shape[0]))          # sklearn's train_test_split(test_size=0.2): ceil for the test part
+    for epoch in range(epochs):
+        epochs_run += 1
+        model.train()
+        perm = rng.permutation(training.shape[0])
+        hold, part = training[perm[:n_hold]], training[perm[n_hold:]]
+        negatives = part[part[:, 2] == 0]
+        n_pos = int((part[:, 2] == 1).sum())
+        if n_pos and negatives.shape[0]:
+            part = np.concatenate([part, negatives[rng.integers(0, negatives.shape[0], size=n_pos * NUM_NEG)]])
+        part = part[rng.permutation(part.shape[0])]
+        for s in range(0, part.shape[0], BATCH):
+            x = torch.as_tensor(part[s:s + BATCH], dtype=torch.int32, device=device)
+            model.zero_grad()
+            loss = _bce_with_logits(model(x[:, 0], x[:, 1]), x[:, 2].float())
+            loss.backward()
+            optimizer.step()
+        model.eval()
+        valid_loss = validation_loss(model, hold, engine)
+        valid_losses.append(valid_loss)
+        if eval_recall:
+            rec, _ = rank_all_items(model, training, validation, hold[:, 0], engine)
+            with np.errstate(invalid="ignore"):
+                recall10 = float(np.nanmean(rec[K_LIST.index(10)])) if rec.shape[1] else float("nan")
+            recalls.append(recall10)
+            if recall10 > best_recall:
+                # The reference notes this epoch in `best_recall_epoch` and saves its weights, but loads `best_epoch` at the end, which
+                # this branch never sets: what it loads is epoch 0's file.  So only epoch 0's weights are ever needed here.
+                best_recall, best_recall_epoch, best_loss = recall10, epoch, valid_loss
+                if epoch == 0:
+                    kept = {0: copy.deepcopy(model.state_dict())}
+            else:
+                early_stop += 1
+        else:
+            if engine is not None:
+                engine.feed_status()          # (with eval_recall the ranking above has asked)
+            if best_loss > valid_loss:
+                best_loss, best_epoch, early_stop = valid_loss, epoch, 0
+                kept = {epoch: copy.deepcopy(model.state_dict())}
+            else:
+                early_stop += 1
+        if early_stop == EARLY_STOP:
+            break
+    no_checkpoint = kept.get(best_epoch) is None
+    if no_checkpoint:
+        best_epoch = epochs_run - 1       # nothing of this run to load: the live weights rank, and the history names their epoch
+    else:
+        model.load_state_dict(kept[best_epoch])
+    model.eval()
+    rec, ndcg = rank_all_items(model, training, validation, validation[:, 0], engine)
+    if history is not None:
+        history.update(valid_loss=valid_losses, recall10=recalls, best_epoch=best_epoch, reference_has_no_checkpoint=no_checkpoint, best_recall_epoch=best_recall_epoch, epochs_run=epochs_run, per_user=(rec, ndcg), model=model)
+    with np.errstate(invalid="ignore"):
+        return (np.array([np.round(np.nanmean(rec[q]), 4) for q in range(len(K_LIST))]),
+                np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
