@@ -285,6 +285,44 @@ int sdrm_equal_sparsity_csr_begin(sdrm_engine* e, const float* x, int64_t n_rows
                                   int64_t* indptr, float* threshold, int64_t* nnz_host, void* stream);
 int sdrm_equal_sparsity_csr_end(sdrm_engine* e, int32_t* indices, int64_t capacity, void* stream);
 
+/* A device-resident CSR matrix [n_rows, n_cols] to its CSC form, the CSR of the transpose (csrc/csr_transpose.h).  The input's
+ * contract is sdrm_csr_rows_to_dense's: device arrays, data null for all ones.  `capacity` is the number of elements of indices (and
+ * of data, rowidx and cdata).  indptr holds absolute offsets and need not start at 0: a row range of a larger matrix is a pointer
+ * offset.  Columns within a row must be distinct; they need not be sorted.
+ *   colptr [n_cols + 1] (device int64) starts at 0; rowidx (device int32) ascends within every column and cdata[q] is the value of the
+ *   entry rowidx[q] names; cdata is null exactly when data is.  For a canonical input this is what scipy's tocsc() + sort_indices()
+ *   gives, byte for byte.  Elements at and behind colptr[n_cols] are unspecified.
+ * The result is the same from call to call and does not depend on what earlier calls left in scratch (a bit table of
+ * ceil(n_rows / 64) x n_cols 64-bit words and as many 4-byte offsets, library-owned, grow-only, cleared on the stream by every call).
+ * Integer atomics only.  Nothing is read back and nothing synchronises, except the device synchronise when the scratch must grow.
+ * Range checks, into the status word sdrm_feed_status reports: an indptr pair that is negative, out of order or reaches behind
+ * `capacity` makes its row contribute nothing; a column outside [0, n_cols) is skipped; a row that holds a column twice raises a
+ * bit of its own - the output is then not the transpose.  No load or store uses an unchecked index, no store lands outside
+ * [0, capacity) of rowidx / cdata or [0, n_cols] of colptr for any input.
+ * Refused before any launch: SDRM_ERR_ARG for a null handle or required pointer, or values on one side only; SDRM_ERR_SHAPE for
+ * n_rows or n_cols outside 1 .. 2^22, capacity outside 0 .. 2^40 - 1, or ceil(n_rows / 64) x n_cols above 2^26. */
+int sdrm_csr_transpose(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, int64_t n_cols,
+                       int64_t capacity, int64_t* colptr, int32_t* rowidx, float* cdata, void* stream);
+
+/* Up to 8 device-resident CSR matrices of n_cols columns, one under the other (csrc/csr_transpose.h).  A part's indptr
+ * [n_rows + 1] holds absolute offsets; its true entry count lives on the device (indptr[n_rows] - indptr[0]) and `capacity` is only
+ * the size of its indices (and data) array - the convention of sdrm_holdout_split's outputs, which stack as they are.
+ *   indptr_out [sum n_rows + 1] (device int64) starts at 0; the rows appear in part order with their entries in their own order.
+ *   data_out is null when every part's data is null; otherwise it is required and an all-ones part contributes 1.0f.
+ * Rows are checked the way sdrm_holdout_split checks them (the output may feed sdrm_rank_metrics): a row whose indptr pair is
+ * negative, out of order, reaches behind its part's capacity or spans more than n_cols entries, and a row with a column outside
+ * [0, n_cols), is EMPTY in the output and recorded in the status word sdrm_feed_status reports.  The parts' running bases are scanned
+ * on the device: nothing is read back, nothing synchronises (except when the grow-only scratch of 12 bytes per row must grow).
+ * No store lands outside [0, capacity_out).
+ * SDRM_ERR_SHAPE: n_parts outside 1 .. 8, n_cols outside 1 .. 2^22, total rows outside 1 .. 2^22, capacity_out below the sum of the
+ * parts' capacities (the host cannot know less); SDRM_ERR_ARG: a null pointer, or data_out not as described. */
+typedef struct sdrm_csr_part {
+  const int64_t* indptr; const int32_t* indices; const float* data;
+  int64_t n_rows; int64_t capacity;
+} sdrm_csr_part;
+int sdrm_csr_vstack(sdrm_engine* e, const sdrm_csr_part* parts, int n_parts, int n_cols, int64_t* indptr_out, int32_t* indices_out,
+                    float* data_out, int64_t capacity_out, void* stream);
+
 /* The VAE decode hook on the device (reference: train_SDRM.py:212-214 `decoder = Linear(latent, hidden) -> Tanh ->
  * Linear(hidden, N_ITEMS)`, :252-254 `VAE.decode`, called by sample_ddpm at :49 / :61 on the sampled latents): two launches of
  * the engine's fp32 MFMA GEMM with the bias + tanh / bias epilogues.  The struct holds DEVICE pointers to the four nn.Linear

@@ -209,6 +209,12 @@ int sdrm_debug_gemm_time(int variant, int cfg, int M, int N, int K, int reps, fl
 /* The host side of sdrm_svd_fit that needs no device: SDRM_OK, or SDRM_ERR_SHAPE for a call outside its envelope (k < 1, k + 10 > 32,
  * min of m and n below 32, m or n above 2^22, nnz outside 0 .. 2^40 - 1, n_iter outside 0 .. 10000). */
 int sdrm_debug_svd_args(int64_t m, int64_t n, int64_t nnz, int k, int n_iter);
+/* The same of sdrm_csr_transpose: SDRM_ERR_SHAPE for m or n outside 1 .. 2^22, capacity outside 0 .. 2^40 - 1, or a bit table of
+ * ceil(m / 64) x n words above 2^26. */
+int sdrm_debug_csr_transpose_args(int64_t m, int64_t n, int64_t capacity);
+/* The mark pass of the CSR transpose, csrc/csr_transpose.h: 0 (default) by the matrix's width - column tiles in LDS up to 9 tiles of
+ * 4096 columns, 64-bit global atomics beyond -, 1 always global atomics, 2 always LDS tiles.  The result is the same bytes. */
+int sdrm_debug_set_csrt_mark(sdrm_engine* e, int mode);
 /* One stage of the fit on the caller's panels (csrc/svd_eval.h), for the stage tests: y_prod [n_rows, 32] = A q for the CSR matrix
  * A [n_rows, n_cols] (data null: all ones; hand in the CSC arrays with n_rows and n_cols swapped for the product with the transpose) and
  * q [n_cols, 32]; y_orth [n_rows, 32] = y_prod orthonormalised (CholeskyQR twice).  All three panels float32 on the device, 16-byte

@@ -32,6 +32,10 @@ class VaeEncoder(C.Structure):
                 ("latent", c_int)]
 
 
+class CsrPart(C.Structure):
+    _fields_ = [("indptr", c_void_p), ("indices", c_void_p), ("data", c_void_p), ("n_rows", c_int64), ("capacity", c_int64)]
+
+
 class Neumf(C.Structure):
     _fields_ = [(name, c_void_p) for name in ("embed_user_gmf", "embed_item_gmf", "embed_user_mlp", "embed_item_mlp", "w1", "b1", "w2", "b2",
                                               "w3", "b3", "wp", "bp")] + [("n_users", c_int), ("n_items", c_int), ("factor", c_int)]
@@ -124,6 +128,8 @@ SIGNATURES = {
     "sdrm_equal_sparsity_csr_begin": (c_int, [c_void_p, c_void_p, c_int64, c_int64, C.c_double, c_int, c_void_p, c_void_p,
                                               C.POINTER(c_int64), c_void_p]),
     "sdrm_equal_sparsity_csr_end": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "sdrm_csr_transpose": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdrm_csr_vstack": (c_int, [c_void_p, C.POINTER(CsrPart), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sdrm_rank_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_svd_fit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_uint64,
@@ -143,6 +149,8 @@ SIGNATURES = {
                                          C.POINTER(c_int64)]),
     "sdrm_debug_vae_eval_args": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int, c_int]),
     "sdrm_debug_svd_args": (c_int, [c_int64, c_int64, c_int64, c_int, c_int]),
+    "sdrm_debug_csr_transpose_args": (c_int, [c_int64, c_int64, c_int64]),
+    "sdrm_debug_set_csrt_mark": (c_int, [c_void_p, c_int]),
     "sdrm_debug_svd_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_debug_neumf_args": (c_int, [c_int, c_int, c_int, c_int64, c_int64]),
     "sdrm_debug_holdout_args": (c_int, [c_int, c_int64, c_int64, C.c_double, c_int64, C.POINTER(c_int64)]),

@@ -17,7 +17,8 @@ struct CsrBatch {
 };
 
 // The bits of the feed status word, and what sdrm_feed_status says for each.
-enum { FEED_BAD_ROW = 1u, FEED_BAD_COL = 2u, FEED_BAD_PTR = 4u, FEED_HOLD_PTR = 8u, FEED_HOLD_COL = 16u };
+enum { FEED_BAD_ROW = 1u, FEED_BAD_COL = 2u, FEED_BAD_PTR = 4u, FEED_HOLD_PTR = 8u, FEED_HOLD_COL = 16u, FEED_T_DUP = 32u, FEED_STACK_PTR = 64u,
+       FEED_STACK_COL = 128u };
 struct FeedStatusText { unsigned bit; const char* text; };
 constexpr FeedStatusText FEED_STATUS_TEXT[] = {
     {FEED_BAD_ROW, " a row id outside [0, n_rows) (its output row is zero);"},
@@ -25,6 +26,9 @@ constexpr FeedStatusText FEED_STATUS_TEXT[] = {
     {FEED_BAD_COL, " a column index outside [0, n_items) (that entry was skipped);"},
     {FEED_HOLD_PTR, " sdrm_holdout_split: an indptr pair that is out of order, reaches outside [0, nnz] or spans more than n_items entries (the row is empty in both outputs);"},
     {FEED_HOLD_COL, " sdrm_holdout_split: a column index outside [0, n_items) (the row is empty in both outputs);"},
+    {FEED_T_DUP, " sdrm_csr_transpose: a row that holds a column more than once (the output is not the transpose);"},
+    {FEED_STACK_PTR, " sdrm_csr_vstack: an indptr pair that is out of order, reaches outside its part's arrays or spans more than n_cols entries (the row is empty in the output);"},
+    {FEED_STACK_COL, " sdrm_csr_vstack: a column index outside [0, n_cols) (the row is empty in the output);"},
 };
 
 // Feed row `src` and CSR stretch [p0, p1) of batch row r, range-checked: a row id outside the matrix or an indptr pair out of order

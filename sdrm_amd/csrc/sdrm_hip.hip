@@ -17,6 +17,7 @@
 #include "../../include/sdrm_hip.h"
 #include "../../include/sdrm_hip_debug.h"
 #include "compact.h"
+#include "csr_transpose.h"
 #include "decode.h"
 #include "decoder_train.h"
 #include "elementwise.h"
@@ -150,7 +151,7 @@ struct ChainSched {
   bool hold_marked = false;    // ev_hold is recorded behind its weight gradients
 };
 
-constexpr int PROF_SLOTS = 32;   // room for the profile classes (ProfClass below holds PC_COUNT to it)
+constexpr int PROF_SLOTS = 40;   // room for the profile classes (ProfClass below holds PC_COUNT to it)
 
 struct sdrm_engine {
   int L, W, T, H, max_rows, device;
@@ -267,6 +268,11 @@ struct sdrm_engine {
   int* neumf_valid = nullptr;
   double* neumf_part = nullptr;
   size_t neumf_ws_cap = 0, neumf_valid_cap = 0, neumf_part_cap = 0;
+  // sdrm_csr_transpose / sdrm_csr_vstack (csrc/csr_transpose.h), grow-only, in 8-byte words: [checked | total | bit table | colptr int64 |
+  // offsets uint32 | column counts uint32] and [total | indptr int64 | row lengths uint32]
+  uint64_t *csrt_ws = nullptr, *stack_ws = nullptr;
+  size_t csrt_ws_cap = 0, stack_ws_cap = 0;
+  int csrt_mark_mode = 0;            // sdrm_debug_set_csrt_mark: 0 by the matrix's width, 1 global atomics, 2 LDS tiles
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
   Exchange xch;                      // RCCL communicator of the user-sharded step (sdrm_comm_init_rank / sdrm_allreduce_init)
   mutable int64_t n_launches = 0;    // kernel launches issued through this handle since sdrm_create
@@ -298,7 +304,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -327,7 +333,12 @@ static const char* kProfNames[PC_COUNT] = {
     "svd evaluator: k_svd_start / k_svd_vt / k_svd_expand start panel, V^T staging and the rank-k expansion into dense scores",
     "neumf evaluator: k_neumf_stage layer 1 split per listed user / item, the GMF rows, W2 and W3 transposed",
     "neumf evaluator: k_neumf_scores eval-mode forward of all listed users x listed items (fp32 vector FMAs, scalar weight operands)",
-    "neumf evaluator: k_neumf_pairs / k_neumf_loss_sum eval-mode forward of listed pairs and the BCE-with-logits numerator (float64 partials, fixed order)"};
+    "neumf evaluator: k_neumf_pairs / k_neumf_loss_sum eval-mode forward of listed pairs and the BCE-with-logits numerator (float64 partials, fixed order)",
+    "csr transpose: k_csrt_mark_lds / k_csrt_mark one pass over the entries, a row's bit into the row-blocked bit table (LDS column tiles, or 64-bit global atomics into a table cleared first), the count of checked entries",
+    "csr transpose: k_csrt_colscan a thread per column, running popcounts over the row blocks and the column counts",
+    "csr transpose: k_csr_scan column counts -> colptr (one work-group)",
+    "csr transpose: k_csrt_fill one pass over the entries, row index and value to the place the bit table gives",
+    "csr vstack: k_stack_counts / k_csr_scan / k_stack_copy checked row lengths, indptr, and the copy of up to 8 CSR parts one under the other"};
 
 namespace {
 
@@ -1360,6 +1371,12 @@ int sdrm_debug_set_skinny(sdrm_engine* e, int on) {
   return SDRM_OK;
 }
 
+int sdrm_debug_set_csrt_mark(sdrm_engine* e, int mode) {
+  if (!e) return SDRM_ERR_ARG;
+  e->csrt_mark_mode = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
+  return SDRM_OK;
+}
+
 int sdrm_debug_plan_wgrad(int rows, int n_out, int k_in, int* slices, int* rows_per_slice) {
   if (!slices || !rows_per_slice || rows < 1 || n_out < 1 || k_in < 1) return SDRM_ERR_ARG;
   pick_splits(Tuning{}, rows, wgrad_tiles(Tuning{}, n_out, k_in), *slices, *rows_per_slice);
@@ -1649,6 +1666,8 @@ int sdrm_destroy(sdrm_engine* e) {
   for (void* b : {(void*)e->neumf_ws, (void*)e->neumf_valid, (void*)e->neumf_part})
     if (b) (void)hipFree(b);
   if (e->csr_ws) (void)hipFree(e->csr_ws);
+  if (e->csrt_ws) (void)hipFree(e->csrt_ws);
+  if (e->stack_ws) (void)hipFree(e->stack_ws);
   if (e->csr_nnz_host) (void)hipHostFree(e->csr_nnz_host);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_hold) (void)hipEventDestroy(e->ev_hold);
@@ -3765,6 +3784,113 @@ int sdrm_equal_sparsity_csr_end(sdrm_engine* e, int32_t* indices, int64_t capaci
   }
   e->csr.active = false;
   return SDRM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// A device CSR to its CSC form, and CSR parts one under the other (csrc/csr_transpose.h).
+
+// The host side that needs no device: the envelope of sdrm_csr_transpose.
+int sdrm_debug_csr_transpose_args(int64_t m, int64_t n, int64_t capacity) {
+  if (m < 1 || m > CSRT_MAX_DIM || n < 1 || n > CSRT_MAX_DIM || capacity < 0 || capacity >= ((int64_t)1 << 40)) return SDRM_ERR_SHAPE;
+  if (((m + 63) / 64) * n > CSRT_MAX_WORDS) return SDRM_ERR_SHAPE;
+  return SDRM_OK;
+}
+
+int sdrm_csr_transpose(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, int64_t n_cols,
+                       int64_t capacity, int64_t* colptr, int32_t* rowidx, float* cdata, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!indptr || !indices || !colptr || !rowidx) return fail(e, SDRM_ERR_ARG, "sdrm_csr_transpose: null pointer");
+  if ((data == nullptr) != (cdata == nullptr)) return fail(e, SDRM_ERR_ARG, "sdrm_csr_transpose: the values of the input and of the output go together");
+  if (int rc = sdrm_debug_csr_transpose_args(n_rows, n_cols, capacity))
+    return fail(e, rc, "sdrm_csr_transpose: n_rows or n_cols outside 1 .. 2^22, capacity outside 0 .. 2^40 - 1, or ceil(n_rows / 64) x n_cols above 2^26 "
+                       "(the bit table's envelope: Engine.csc_to_device takes such a matrix on the host)");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t blocks = (size_t)((n_rows + 63) / 64), words = blocks * (size_t)n_cols;
+  const size_t off_table = 2, off_ptr = off_table + words, off_off = off_ptr + (size_t)n_cols + 1, off_cnt = off_off + (words + 1) / 2;
+  if (int rc = grow(e, &e->csrt_ws, &e->csrt_ws_cap, off_cnt + ((size_t)n_cols + 1) / 2)) return rc;
+  int64_t* own = reinterpret_cast<int64_t*>(e->csrt_ws + off_ptr);
+  CsrTransposeArgs a{};
+  a.csr = CsrBatch{indptr, indices, data, nullptr, 0, n_rows, (int)n_rows, (int)n_cols, e->feed_flag};
+  a.capacity = capacity;
+  a.checked = reinterpret_cast<unsigned long long*>(e->csrt_ws);
+  a.total = reinterpret_cast<const int64_t*>(e->csrt_ws + 1);
+  a.table = e->csrt_ws + off_table;
+  a.off = reinterpret_cast<uint32_t*>(e->csrt_ws + off_off);
+  a.counts = reinterpret_cast<uint32_t*>(e->csrt_ws + off_cnt);
+  a.colptr = own;
+  a.blocks = (int)blocks;
+  a.rowidx = rowidx; a.cdata = cdata;
+  // The count of checked entries, the total and the bit table are this call's own, made anew on the stream every time: the LDS-tile
+  // form of the mark pass stores every word of the table, the global-atomic form ORs into a cleared one.
+  const int64_t tiles = (n_cols + CSRT_TILE - 1) / CSRT_TILE;
+  const bool lds = e->csrt_mark_mode == 2 || (e->csrt_mark_mode == 0 && tiles <= CSRT_LDS_MAX_TILES);
+  HIP_TRY(e, hipMemsetAsync(e->csrt_ws, 0, off_table * sizeof(uint64_t), st));
+  const unsigned waves = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 1 << 16);   // the row kernels stride over the rows behind their grids
+  HIP_TRY(e, profiled(e, PC_CSRT_MARK, 0.0, st, [&] {   // (the clearing is the global form's cost: inside its interval)
+    if (lds) {
+      SDRM_LAUNCH(e, k_csrt_mark_lds, dim3((unsigned)blocks, (unsigned)tiles), dim3(256), 0, st, a);
+    } else {
+      const hipError_t rc = hipMemsetAsync(a.table, 0, words * sizeof(uint64_t), st);
+      if (rc != hipSuccess) return rc;
+      SDRM_LAUNCH(e, k_csrt_mark, dim3(waves), dim3(256), 0, st, a);
+    }
+    return hipGetLastError();
+  }));
+  HIP_TRY(e, profiled(e, PC_CSRT_COLSCAN, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_csrt_colscan, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }));
+  HIP_TRY(e, profiled(e, PC_CSRT_SCAN, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)a.counts, n_cols, own, colptr, reinterpret_cast<int64_t*>(e->csrt_ws + 1));
+    return hipGetLastError();
+  }));
+  HIP_TRY(e, profiled(e, PC_CSRT_FILL, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_csrt_fill, dim3(waves), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }));
+  return SDRM_OK;
+}
+
+int sdrm_csr_vstack(sdrm_engine* e, const sdrm_csr_part* parts, int n_parts, int n_cols, int64_t* indptr_out, int32_t* indices_out,
+                    float* data_out, int64_t capacity_out, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!parts || !indptr_out || !indices_out) return fail(e, SDRM_ERR_ARG, "sdrm_csr_vstack: null pointer");
+  if (n_parts < 1 || n_parts > CSR_STACK_MAX) return fail(e, SDRM_ERR_SHAPE, "sdrm_csr_vstack: n_parts outside 1 .. 8");
+  if (n_cols < 1 || n_cols > CSRT_MAX_DIM) return fail(e, SDRM_ERR_SHAPE, "sdrm_csr_vstack: n_cols outside 1 .. 2^22");
+  CsrStackArgs a{};
+  int64_t rows = 0, cap = 0;
+  bool values = false;
+  for (int k = 0; k < n_parts; ++k) {
+    const sdrm_csr_part& p = parts[k];
+    if (!p.indptr || !p.indices) return fail(e, SDRM_ERR_ARG, "sdrm_csr_vstack: null pointer in a part");
+    if (p.n_rows < 0 || p.n_rows > CSRT_MAX_DIM || p.capacity < 0 || p.capacity >= ((int64_t)1 << 40))
+      return fail(e, SDRM_ERR_SHAPE, "sdrm_csr_vstack: a part's n_rows outside 0 .. 2^22 or its capacity outside 0 .. 2^40 - 1");
+    a.part[k] = CsrStackPart{p.indptr, p.indices, p.data, p.capacity};
+    a.first[k] = rows;
+    rows += p.n_rows; cap += p.capacity;
+    values |= p.data != nullptr;
+  }
+  for (int k = n_parts; k <= CSR_STACK_MAX; ++k) a.first[k] = rows;
+  if (rows < 1 || rows > CSRT_MAX_DIM) return fail(e, SDRM_ERR_SHAPE, "sdrm_csr_vstack: total rows outside 1 .. 2^22");
+  if (capacity_out < cap) return fail(e, SDRM_ERR_SHAPE, "sdrm_csr_vstack: capacity_out below the sum of the parts' capacities");
+  if (values != (data_out != nullptr))
+    return fail(e, SDRM_ERR_ARG, "sdrm_csr_vstack: data_out is required when a part has values, and null when none has");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t off_ptr = 1, off_cnt = off_ptr + (size_t)rows + 1;
+  if (int rc = grow(e, &e->stack_ws, &e->stack_ws_cap, off_cnt + ((size_t)rows + 1) / 2)) return rc;
+  int64_t* own = reinterpret_cast<int64_t*>(e->stack_ws + off_ptr);
+  a.n_parts = n_parts; a.n_cols = n_cols;
+  a.cnt = reinterpret_cast<uint32_t*>(e->stack_ws + off_cnt);
+  a.rowptr = own;
+  a.indices_out = indices_out; a.data_out = data_out; a.capacity_out = capacity_out;
+  a.flag = e->feed_flag;
+  const unsigned waves = (unsigned)std::min<int64_t>((rows + 3) / 4, 1 << 16);
+  return hip_rc(e, "k_stack_copy", profiled(e, PC_CSR_VSTACK, 0.0, st, [&] {
+    SDRM_LAUNCH(e, k_stack_counts, dim3(waves), dim3(256), 0, st, a);
+    SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)a.cnt, rows, own, indptr_out, reinterpret_cast<int64_t*>(e->stack_ws));
+    SDRM_LAUNCH(e, k_stack_copy, dim3(waves), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }));
 }
 
 // ---------------------------------------------------------------------------------------------

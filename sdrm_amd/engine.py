@@ -126,11 +126,14 @@ class Engine:
         return int(n_rows), int(n_items), int(b), (_ptr(indptr), _ptr(indices), _ptr(data), int(n_rows), _ptr(rows), int(row0), int(b))
 
     def debug_set(self, tile=None, skinny=None, fused_reverse=None, chains=None, nt32_rows=None, nt32_rows_train=None,
-                  gradient_buckets=None, rowchain=None, wgrad_strips=None, dgrad_rows=None, rows48=None, rows48_split=None, sample_persist=None, rows48_share=None):
+                  gradient_buckets=None, rowchain=None, wgrad_strips=None, dgrad_rows=None, rows48=None, rows48_split=None, sample_persist=None, rows48_share=None,
+                  csrt_mark=None):
         """Test / tuning hooks of THIS engine (include/sdrm_hip_debug.h): force a GEMM tile shape (-1 = automatic),
         switch the narrow-net kernels, the fused reverse update, the sampler row chains, the 32x32-tile row thresholds,
         the number of gradient all-reduces of the sharded step (1 or 2), the row-owned train forward (0 never, 1 by
         size, 2 whenever the net allows), the strip-owned weight gradients and the row-owned input gradients behind it."""
+        if csrt_mark is not None:   # the mark pass of csr_transpose (csrc/csr_transpose.h): 0 by width, 1 global atomics, 2 LDS tiles
+            self._check(self.lib.sdrm_debug_set_csrt_mark(self._h, int(csrt_mark)), "sdrm_debug_set_csrt_mark")
         if rowchain is not None:
             self._check(self.lib.sdrm_debug_set_rowchain(self._h, int(rowchain)), "sdrm_debug_set_rowchain")
         if rows48_share is not None:   # the shared-tile form of the 48-row kernels (1 on, 0 the plain form)
@@ -872,6 +875,90 @@ class Engine:
         data = None if np.all(m.data == 1) else torch.from_numpy(m.data.astype(np.float32)).to(self.device)
         return (torch.from_numpy(m.indptr.astype(np.int64)).to(self.device),
                 torch.from_numpy(m.indices.astype(np.int32)).to(self.device), data, m.shape)
+
+    CSR_STACK_MAX = 8          # parts of one csr_vstack
+    CSR_TRANSPOSE_WORDS = 2 ** 26   # most words of csr_transpose's bit table, ceil(n_rows / 64) x n_cols
+
+    def _csr_arrays(self, who, name, csr_dev):
+        """(indptr, indices, data | None, n_rows, n_cols, capacity) of a device CSR tuple, checked on the host: the 4-tuple of
+        `csr_to_device` / `holdout_split` or the 3-tuple (indptr, indices, shape) of `equal_sparsity_csr`.  `capacity` is the size of
+        the index array; the entry count lives in indptr."""
+        if not isinstance(csr_dev, tuple) or len(csr_dev) not in (3, 4):
+            raise SdrmError(f"{who}: {name} must be a device CSR tuple (indptr, indices, data | None, shape) or (indptr, indices, shape)")
+        indptr, indices, data, shape = csr_dev if len(csr_dev) == 4 else (csr_dev[0], csr_dev[1], None, csr_dev[2])
+        n_rows, n_cols = int(shape[0]), int(shape[1])
+        indptr = self._index(who, f"{name} indptr", indptr, torch.int64, n_rows + 1)
+        if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32 or indices.device != self.device or not indices.is_contiguous():
+            raise SdrmError(f"{who}: {name} indices must be a contiguous int32 tensor on the engine's device")
+        capacity = int(indices.numel())
+        if data is not None:
+            data = self._f32(who, f"{name} data", data, (capacity,))
+        return indptr, indices, data, n_rows, n_cols, capacity
+
+    def csr_transpose(self, csr_dev, check=True, out=None):
+        """The CSC form of a device CSR matrix (sdrm_csr_transpose, csrc/csr_transpose.h), shaped like `csc_to_device`'s result:
+        (colptr int64 [n_cols + 1], rowidx int32, data float32 | None, shape).  Row indices ascend within a column; for a canonical
+        input these are the bytes `csc_to_device` ships.  The columns of a row must be distinct and need not be sorted; indptr may
+        hold absolute offsets into longer arrays (a row range of a larger matrix: slice its indptr and say the rows in the shape).
+        `rowidx` and `data` have the input's capacity and are filled up to colptr[-1].  Nothing is read back; range checks and
+        `check` as in `csr_rows_to_dense`, and a row that holds a column twice is reported there too.  `out`: (colptr, rowidx,
+        data | None) device tensors to fill.  Refused (SDRM_ERR_SHAPE) beyond 2^22 rows or columns or a bit table of
+        ceil(n_rows / 64) x n_cols > 2^26 words: `csc_to_device` takes such a matrix on the host."""
+        who = "csr_transpose"
+        indptr, indices, data, n_rows, n_cols, capacity = self._csr_arrays(who, "csr", csr_dev)
+        if not (1 <= n_rows <= 2 ** 22 and 1 <= n_cols <= 2 ** 22) or -(-n_rows // 64) * n_cols > self.CSR_TRANSPOSE_WORDS:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {n_rows} x {n_cols} is outside 1 .. 2^22 rows and columns or needs a bit table above 2^26 words")
+        if out is None:
+            out = (torch.empty(n_cols + 1, dtype=torch.int64, device=self.device), torch.empty(capacity, dtype=torch.int32, device=self.device),
+                   None if data is None else torch.empty(capacity, dtype=torch.float32, device=self.device))
+        colptr = self._index(who, "out colptr", out[0], torch.int64, n_cols + 1)
+        rowidx = self._index(who, "out rowidx", out[1], torch.int32, capacity)
+        if (data is None) != (out[2] is None):
+            raise SdrmError(f"{who}: SDRM_ERR_ARG: out carries values exactly when the input does")
+        cdata = None if data is None else self._f32(who, "out data", out[2], (capacity,))
+        # a matrix without an entry: torch gives an empty tensor no address, and the C ABI takes no null array
+        spare = (indices, rowidx, data, cdata) if capacity else (indices.new_zeros(1), indices.new_zeros(1)) + ((None, None) if data is None else (
+            torch.zeros(1, dtype=torch.float32, device=self.device), torch.zeros(1, dtype=torch.float32, device=self.device)))
+        self._check(self.lib.sdrm_csr_transpose(self._h, _ptr(indptr), _ptr(spare[0]), _ptr(spare[2]), n_rows, n_cols, capacity, _ptr(colptr),
+                                                _ptr(spare[1]), _ptr(spare[3]), _stream()), "sdrm_csr_transpose")
+        self._feed_keep = spare
+        if check:
+            self.feed_status()
+        return colptr, rowidx, cdata, (n_rows, n_cols)
+
+    def csr_vstack(self, parts, check=True):
+        """`scipy.sparse.vstack` of up to 8 device CSR matrices of one width (sdrm_csr_vstack, csrc/csr_transpose.h): a list of
+        `csr_to_device`-shaped tuples - `holdout_split`'s outputs as they are, whose arrays are longer than their entry counts - or
+        3-tuples of `equal_sparsity_csr`.  Returns a `csr_to_device`-shaped tuple: indptr from 0, the rows in part order with their
+        entries in their own order, `data` None when no part has values (else float32, an all-ones part contributing 1.0).  The index
+        array has the sum of the parts' capacities and is filled up to indptr[-1]; nothing is read back.  A row with a bad indptr pair
+        or a column outside the width is EMPTY in the output and raises the feed status word (`check` as in `csr_rows_to_dense`)."""
+        who = "csr_vstack"
+        parts = list(parts)
+        if not 1 <= len(parts) <= self.CSR_STACK_MAX:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {len(parts)} parts, outside 1 .. {self.CSR_STACK_MAX}")
+        arrays = [self._csr_arrays(who, f"part {i}", p) for i, p in enumerate(parts)]
+        n_cols = arrays[0][4]
+        if any(a[4] != n_cols for a in arrays):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: the parts have {[a[4] for a in arrays]} columns, not one width")
+        rows, capacity = sum(a[3] for a in arrays), sum(a[5] for a in arrays)
+        if not (1 <= rows <= 2 ** 22 and 1 <= n_cols <= 2 ** 22):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {rows} rows x {n_cols} columns, outside 1 .. 2^22")
+        values = any(a[2] is not None and a[5] > 0 for a in arrays)   # (an empty array has no address: such a part has no values to give)
+        indptr = torch.empty(rows + 1, dtype=torch.int64, device=self.device)
+        indices = torch.empty(capacity, dtype=torch.int32, device=self.device)
+        data = torch.empty(capacity, dtype=torch.float32, device=self.device) if values else None
+        spare = indices.new_zeros(1)   # a part without an entry: torch gives an empty tensor no address, and the C ABI takes no null array
+        desc = (_lib.CsrPart * len(arrays))()
+        for d, (ip, ix, dv, n_rows, _, cap) in zip(desc, arrays):
+            d.indptr, d.indices, d.data = ip.data_ptr(), (ix if cap else spare).data_ptr(), dv.data_ptr() if dv is not None and cap else None
+            d.n_rows, d.capacity = n_rows, cap
+        self._check(self.lib.sdrm_csr_vstack(self._h, desc, len(arrays), n_cols, _ptr(indptr), _ptr(indices if capacity else spare), _ptr(data), capacity,
+                                             _stream()), "sdrm_csr_vstack")
+        self._feed_keep = (spare, arrays)
+        if check:
+            self.feed_status()
+        return indptr, indices, data, (rows, n_cols)
 
     def csr_rows_to_dense(self, csr_dev, rows=None, row0=0, b=None, check=True):
         """dataloaders.py:46-79 + `.to_dense()` (train_SDRM.py:323) on the device: dense float32 [b, n_items] of the rows

@@ -8,6 +8,7 @@ the GPU box, where the reference itself cannot travel.  SURVEY.md §8f ("next" r
     equal_sparsity_csr              main.py:177-180, :259-270  (the same as a csr_matrix made on the device, either side)
     compute_mf_results              svd_benchmark.py:17-70 (TruncatedSVD(20, n_iter=100) reconstruction, masked, Recall/NDCG@k)
     compute_mf_results_device       the same evaluator with fit, reconstruction and ranking on the device (opt-in)
+    compute_mf_results_resident     ... from a CSR that is already on the device, stacked and transposed there (opt-in)
     run_experiment                  main.py:143-200        (train -> multi-res + full-res sampling -> evaluate)
 """
 from __future__ import annotations
@@ -171,6 +172,38 @@ def compute_mf_results_device(training_dataset, testing_dataset, synthetic_data,
             np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
 
 
+def mf_per_user_resident(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0):
+    """`mf_per_user_device` for synthetic data that is already on the device: `synthetic_data` is a device CSR tuple (what
+    `Engine.equal_sparsity_csr` returns, or a `csr_to_device` tuple).  The hold-out split of the validation users stays the host's
+    (the reference's draw, a few hundred users) and its two small results are uploaded; the stack [head | test | synthetic?] is made
+    by `Engine.csr_vstack` and its CSC form by `Engine.csr_transpose` - the synthetic matrix never visits the host.  The fit, the
+    scores and the ranking are `mf_per_user_device`'s calls."""
+    test_data, valid_data = metrics.split_train_test_proportion_from_csr_matrix(testing_dataset, batch_size=1000, random_seed=123)
+
+    def upload(m):
+        m = m.tocsr().astype(np.float64)
+        m.eliminate_zeros()   # (`mask_training_examples` masks the NONZERO entries of the stacked rows)
+        return engine.csr_to_device(m)
+    head = synthetic_data if only_synthetic else upload(training_dataset)
+    parts = [head, upload(test_data)] + ([] if only_synthetic else [synthetic_data])
+    csr_dev = engine.csr_vstack(parts, check=False)       # (no synchronise of their own: `svd_fit` below reads the status word that
+    csc_dev = engine.csr_transpose(csr_dev, check=False)  #  both calls' range checks raise, and raises for them)
+    lo, users = int(head[-1][0]), valid_data.shape[0]
+    components, _ = engine.svd_fit(csr_dev, csc_dev, n_components=20, n_iter=100, seed=seed)
+    scores = engine.svd_scores(csr_dev, components, row0=lo, b=users)
+    seen_dev = (csr_dev[0][lo:lo + users + 1], csr_dev[1], None, (users, csr_dev[3][1]))
+    rec, ndcg = engine.rank_metrics(scores, engine.csr_to_device(valid_data), seen_dev, ks=K_LIST)
+    return rec.cpu().numpy(), ndcg.cpu().numpy()
+
+
+def compute_mf_results_resident(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0):
+    """`compute_mf_results_device` from a device CSR tuple (opt-in: `hp["resident_svd"]`): the same `(recall[6], ndcg[6])`, with the
+    stacking and the CSR -> CSC conversion on the device (`mf_per_user_resident`)."""
+    rec, ndcg = mf_per_user_resident(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=only_synthetic, seed=seed)
+    return (np.array([np.round(np.nanmean(rec[q]), 4) for q in range(len(K_LIST))]),
+            np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
+
+
 # the pre-stage's opt-in flags that `hp` may carry, under `train_SDRM`'s keyword names
 VAE_FLAGS = ("vae_device_feed", "vae_device_holdout", "vae_sparse_input", "vae_device_latent", "vae_device_decoder", "vae_device_optimizer",
              "vae_device_eval")
@@ -180,7 +213,8 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
     """One run of main.py's loop body with the MI355X engine; returns {"M": (recall, ndcg), "F": ..., "V": ...}.  `hp` may carry the
     seven flags of the VAE pre-stage under the keys `VAE_FLAGS` (each False when absent): those that are set are handed to `train_SDRM`
     under the same names, and an `hp` without them makes the call it always made.  `hp["device_svd"]` (False when absent) sends the
-    three evaluations to `compute_mf_results_device` instead of `compute_mf_results`; nothing of it reaches `train_SDRM`."""
+    three evaluations to `compute_mf_results_device` instead of `compute_mf_results`; nothing of it reaches `train_SDRM`.  `hp["resident_svd"]` (False when absent) binarises with
+    `Engine.equal_sparsity_csr` and hands the device tuple to `compute_mf_results_resident`: no host copy of the synthetic matrix."""
     from . import train_SDRM as ts
     train, train_partial, valid = split
     n_users, n_items = train.shape
@@ -201,7 +235,9 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
     V = vae.sample(n_users)
     binarise = equal_sparsity_csr if hp.get("sparse_synthetic", False) else equal_sparsity   # opt-in: CSR made on the device
     for tag, raw in (("M", M), ("F", F), ("V", V)):
-        if hp.get("device_svd", False):   # opt-in: the downstream evaluator on the device (csrc/svd_eval.h)
+        if hp.get("resident_svd", False):   # opt-in: the CSR made on the device stays there, stacked and transposed on the device (csrc/csr_transpose.h)
+            out[tag] = compute_mf_results_resident(train, valid, net.engine().equal_sparsity_csr(raw, sparsity), net.engine(), only_synthetic=True, seed=seed)
+        elif hp.get("device_svd", False):   # opt-in: the downstream evaluator on the device (csrc/svd_eval.h)
             out[tag] = compute_mf_results_device(train, valid, binarise(raw, sparsity, net.engine()), net.engine(), only_synthetic=True, seed=seed)
         else:
             out[tag] = compute_mf_results(train, valid, binarise(raw, sparsity, net.engine()), only_synthetic=True)
