@@ -23,9 +23,6 @@
 
 namespace sdrm {
 
-// the staged weights and the batch's hand-overs, sdrm_engine::ev_buf (grow-only; nothing of enc_buf, lat_buf, dh_buf, dec_buf or il_buf)
-enum EvalBuf { EV_W1T = 0, EV_B1, EV_W2, EV_B2, EV_W3, EV_B3, EV_W4, EV_B4, EV_H1, EV_Z, EV_H3, EV_LOGITS, EV_BUFS };
-
 // Launch 1: k_encode_csr's body (csrc/encode.h) with the upper end of every train indptr pair held against a.nnz as well, so that the
 // gather loads no index behind the caller's array.  A pair that fails is the empty row here and in launch 5 alike: the user's logits are
 // those of a user without train entries, nothing of that user is masked, and FEED_BAD_PTR is raised.

@@ -153,6 +153,44 @@ struct ChainSched {
 
 constexpr int PROF_SLOTS = 40;   // room for the profile classes (ProfClass below holds PC_COUNT to it)
 
+// The library-owned device scratch of the utility entry points (sdrm_engine::scratch, reached through scratch<T>() only): one slot per
+// buffer, every slot grow-only and owned by ONE family of entry points, so nothing a family leaves behind is touched by another.  Two
+// promises of include/sdrm_hip.h rest on that: the encoder staged by sdrm_vae_encoder_load (ENC_W1T .. ENC_B2) survives every other
+// call, and the workspace of a pending sdrm_equal_sparsity_csr_begin (CSR_WS) survives until its _end.
+enum Scratch {
+  // sdrm_vae_decode: padded latents, weights, hidden activations
+  SCR_DEC_Z = 0, SCR_DEC_W1, SCR_DEC_B1, SCR_DEC_HID, SCR_DEC_W2, SCR_DEC_B2,
+  // the frozen VAE encoder staged by sdrm_vae_encoder_load (csrc/encode.h): W1^T [items][Hq] | tiled W1, b1, W2, b2; and the encode calls'
+  // normalised rows, hidden activations, [n][2 latent], densified rows, partial sums of the kl (k_encode_kl_rows, [KL_PARTS] float64)
+  SCR_ENC_W1T, SCR_ENC_W1, SCR_ENC_B1, SCR_ENC_W2, SCR_ENC_B2, SCR_ENC_XN, SCR_ENC_HID, SCR_ENC_OUT2, SCR_ENC_DENSE, SCR_ENC_PART,
+  // the train-mode input layer (csrc/input_layer.h): this call's W1^T [items][Hq] | dpre padded to [b][Hq] (hidden off the 16-byte grid only)
+  SCR_IL_W1T, SCR_IL_DPRE,
+  // the train-mode latent head (csrc/latent.h), this call's operands (h1, out2, eps are the caller's): h1 [MP][Hp] | W2 [L2r][Hp], b2 [L2r] |
+  // W2^T [Hr][L2p] | dout2 [MP][L2p] | weight-gradient slabs [S][L2p][Hp], bias sums [S][L2p] | partial sums of its kl (k_latent_reparam)
+  SCR_LAT_H, SCR_LAT_W2, SCR_LAT_B2, SCR_LAT_W2T, SCR_LAT_DOUT2, SCR_LAT_SLAB, SCR_LAT_DBIAS, SCR_LAT_PART,
+  // the train-mode decoder and loss head (csrc/decoder_train.h), every one written by the call that reads it (h3, logits, lse are the
+  // caller's): z [MP][Lp], W3 [Hr][Lp], b3 [Hr], h3 [MP][Hp], W4 [Ir][Hp], b4 [Ir] | W4^T [Hr][Ip], W3^T [Lr][Hp], zero bias [Lr], g [MP][Ip],
+  // dpre3 [MP][Hp], slabs [S][Ip][Hp] + bias sums [S][Ip] of dW4, slabs [S][Hp][Lp] + bias sums [S][Hp] of dW3
+  SCR_DH_Z, SCR_DH_W3, SCR_DH_B3, SCR_DH_H3, SCR_DH_W4, SCR_DH_B4, SCR_DH_W4T, SCR_DH_W3T, SCR_DH_ZB, SCR_DH_G, SCR_DH_DP3, SCR_DH_SLAB4,
+  SCR_DH_DB4, SCR_DH_SLAB3, SCR_DH_DB3,
+  // sdrm_vae_eval_holdout (csrc/eval_half.h), the live weights staged by that call and its batches' hand-overs: W1^T [items][Hq], b1 [Hr],
+  // W2[:L] [Lr][Hp], b2[:L] [Lr], W3 [Hr][Lp], b3 [Hr], W4 [Ir][Hp], b4 [Ir] | h1 [MP][Hp], z [MP][Lp], h3 [MP][Hp], logits [batch][items]
+  // (when the caller gives none)
+  SCR_EV_W1T, SCR_EV_B1, SCR_EV_W2, SCR_EV_B2, SCR_EV_W3, SCR_EV_B3, SCR_EV_W4, SCR_EV_B4, SCR_EV_H1, SCR_EV_Z, SCR_EV_H3, SCR_EV_LOGITS,
+  SCR_HOLD_CNT,      // sdrm_holdout_split (csrc/holdout.h): uint32 [2][rows] entries n_u and held entries m_u of every row
+  // sdrm_svd_fit / sdrm_svd_scores (csrc/svd_eval.h): the fit's panels Q [n][32] | Y [m][32]; the scores' V^T [n][32] | T [b][32]; the Gram
+  // partials [SVD_GRAM_PARTS][32][32] with R^-1 [32][32] behind them (float64); the fit's status word (bit 0: breakdown)
+  SCR_SVD_PANEL, SCR_SVD_VT, SCR_SVD_PART, SCR_SVD_FLAG,
+  // sdrm_neumf_scores / sdrm_neumf_pair_loss (csrc/neumf.h): W2t | W3t | the staged user and item sides; the validity words of both sides
+  // (int); the pair kernel's per-block loss partials (float64)
+  SCR_NEUMF_WS, SCR_NEUMF_VALID, SCR_NEUMF_PART,
+  SCR_CSR_WS,        // sdrm_equal_sparsity_csr_begin / _end (csrc/compact.h), 8-byte words: [mask words | row offsets int64 | row counts uint32]
+  // sdrm_csr_transpose / sdrm_csr_vstack (csrc/csr_transpose.h), 8-byte words: [checked | total | bit table | colptr int64 | offsets uint32 |
+  // column counts uint32] and [total | indptr int64 | row lengths uint32]
+  SCR_CSRT_WS, SCR_STACK_WS,
+  SCR_COUNT
+};
+
 struct sdrm_engine {
   int L, W, T, H, max_rows, device;
   Tuning tune;
@@ -204,10 +242,7 @@ struct sdrm_engine {
   const float* grad_src = nullptr;   // where the last backward wrote the flat gradient (internal g or the caller's buffer)
   float *rev_dev = nullptr;          // [3][T+1] reverse-step coefficients c1, sqrt(alpha), sqrt(beta)
   SelectState* sel = nullptr;        // radix-select workspace of sdrm_equal_sparsity
-  // sdrm_equal_sparsity_csr_begin / _end (csrc/compact.h): grow-only workspace [mask words | row offsets int64 | row counts uint32]
-  // and the call pending between the two
-  uint64_t* csr_ws = nullptr;
-  size_t csr_ws_cap = 0;             // in 8-byte words
+  // sdrm_equal_sparsity_csr_begin / _end (csrc/compact.h): the call pending between the two (its workspace: SCR_CSR_WS)
   int64_t *csr_nnz_host = nullptr, *csr_nnz_dev = nullptr;   // nnz of the scan, in host memory the device writes (and its device alias)
   struct CsrPending { bool active = false; int64_t n_rows = 0, nnz = 0; int wpr = 0; size_t off_ptr = 0; } csr;
   float* one_dev = nullptr;          // 1.0f (identity PReLU slope for layer 0 inside the batched weight-gradient launch)
@@ -223,55 +258,9 @@ struct sdrm_engine {
   int bwd_S0 = 1, bwd_SH = 1, bwd_SO = 1, bwd_kc0 = 0, bwd_kcH = 0, bwd_kcO = 0, bwd_dgrad_blocks = 0;
   int bwd_hidden_apps = 0;           // slab sets of the shared hidden layer's weight gradient per K-slice: H (one per application), or 1 (already summed)
   int bwd_cfg_w = 0;                 // tile of the split-K launches, fixed by backward_chain for the whole backward
-  // grow-only scratch of sdrm_vae_decode (padded latents / weights / hidden activations)
-  float* dec_buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t dec_cap[6] = {0, 0, 0, 0, 0, 0};
-  // the frozen VAE encoder staged by sdrm_vae_encoder_load (csrc/encode.h) and the grow-only scratch of the encode calls
-  enum { ENC_W1T = 0, ENC_W1, ENC_B1, ENC_W2, ENC_B2, ENC_XN, ENC_HID, ENC_OUT2, ENC_DENSE, ENC_BUFS };
-  float* enc_buf[ENC_BUFS] = {};     // W1^T [items][Hq] | tiled W1, b1, W2, b2 | normalised rows, hidden activations, [n][2 latent], densified rows
-  size_t enc_cap[ENC_BUFS] = {};
-  double* enc_part = nullptr;        // partial sums of the kl (k_encode_kl_rows)
+  struct { void* p = nullptr; size_t cap = 0; } scratch[SCR_COUNT];   // the pool (enum Scratch); cap in elements of the slot's one type
   bool enc_loaded = false;
   double* nll_part = nullptr;        // partial sums of the multinomial loss (k_nll_rows), [NLL_PARTS]
-  // grow-only scratch of the train-mode input layer (csrc/input_layer.h); nothing of the loaded encoder above is touched by it
-  enum { IL_W1T = 0, IL_DPRE, IL_BUFS };
-  float* il_buf[IL_BUFS] = {};       // this call's W1^T [items][Hq] | dpre padded to [b][Hq] (hidden off the 16-byte grid only)
-  size_t il_cap[IL_BUFS] = {};
-  // grow-only scratch of the train-mode latent head (csrc/latent.h): this call's operands, nothing of a loaded encoder or of a forward
-  // that still waits for its backward (h1, out2, eps are the caller's)
-  enum { LAT_H = 0, LAT_W2, LAT_B2, LAT_W2T, LAT_DOUT2, LAT_SLAB, LAT_DBIAS, LAT_BUFS };
-  float* lat_buf[LAT_BUFS] = {};     // h1 [MP][Hp] | W2 [L2r][Hp], b2 [L2r] | W2^T [Hr][L2p] | dout2 [MP][L2p] | weight-gradient slabs [S][L2p][Hp], bias sums [S][L2p]
-  size_t lat_cap[LAT_BUFS] = {};
-  double* lat_part = nullptr;        // partial sums of its kl (k_latent_reparam), [ENC_KL_PARTS]
-  // grow-only scratch of the train-mode decoder and loss head (csrc/decoder_train.h): this call's operands, every one written by the
-  // call that reads it; nothing of sdrm_vae_decode's dec_buf or of a forward that still waits for its backward (h3, logits, lse are the caller's)
-  enum { DH_Z = 0, DH_W3, DH_B3, DH_H3, DH_W4, DH_B4, DH_W4T, DH_W3T, DH_ZB, DH_G, DH_DP3, DH_SLAB4, DH_DB4, DH_SLAB3, DH_DB3, DH_BUFS };
-  float* dh_buf[DH_BUFS] = {};       // z [MP][Lp], W3 [Hr][Lp], b3 [Hr], h3 [MP][Hp], W4 [Ir][Hp], b4 [Ir] | W4^T [Hr][Ip], W3^T [Lr][Hp], zero bias [Lr],
-                                     // g [MP][Ip], dpre3 [MP][Hp], slabs [S][Ip][Hp] + bias sums [S][Ip] of dW4, slabs [S][Hp][Lp] + bias sums [S][Hp] of dW3
-  size_t dh_cap[DH_BUFS] = {};
-  // sdrm_vae_eval_holdout (csrc/eval_half.h: EvalBuf): the live weights staged by that call and its batches' hand-overs, grow-only;
-  // nothing of the loaded encoder (enc_buf) or of the train-mode entry points' scratch (il_buf, lat_buf, dh_buf) is touched by it
-  float* ev_buf[EV_BUFS] = {};       // W1^T [items][Hq], b1 [Hr], W2[:L] [Lr][Hp], b2[:L] [Lr], W3 [Hr][Lp], b3 [Hr], W4 [Ir][Hp], b4 [Ir] |
-                                     // h1 [MP][Hp], z [MP][Lp], h3 [MP][Hp], logits [batch][items] (when the caller gives none)
-  size_t ev_cap[EV_BUFS] = {};
-  uint32_t* hold_cnt = nullptr;      // grow-only scratch of sdrm_holdout_split (csrc/holdout.h): [2][rows] entries n_u and held entries m_u of every row
-  size_t hold_cap = 0;               // in elements
-  // sdrm_svd_fit / sdrm_svd_scores (csrc/svd_eval.h), grow-only: the fit's panels Q [n][32] | Y [m][32]; the scores' V^T [n][32] | T [b][32];
-  // the Gram partials [SVD_GRAM_PARTS][32][32] with R^-1 [32][32] behind them (float64), and the fit's status word (bit 0: breakdown)
-  float *svd_panel = nullptr, *svd_vt = nullptr;
-  size_t svd_panel_cap = 0, svd_vt_cap = 0;
-  double* svd_part = nullptr;
-  unsigned* svd_flag = nullptr;
-  // sdrm_neumf_scores / sdrm_neumf_pair_loss (csrc/neumf.h), grow-only: W2t | W3t | the staged user and item sides; the validity words of
-  // both sides; the pair kernel's per-block loss partials
-  float* neumf_ws = nullptr;
-  int* neumf_valid = nullptr;
-  double* neumf_part = nullptr;
-  size_t neumf_ws_cap = 0, neumf_valid_cap = 0, neumf_part_cap = 0;
-  // sdrm_csr_transpose / sdrm_csr_vstack (csrc/csr_transpose.h), grow-only, in 8-byte words: [checked | total | bit table | colptr int64 |
-  // offsets uint32 | column counts uint32] and [total | indptr int64 | row lengths uint32]
-  uint64_t *csrt_ws = nullptr, *stack_ws = nullptr;
-  size_t csrt_ws_cap = 0, stack_ws_cap = 0;
   int csrt_mark_mode = 0;            // sdrm_debug_set_csrt_mark: 0 by the matrix's width, 1 global atomics, 2 LDS tiles
   int enc_items = 0, enc_hidden = 0, enc_latent = 0;
   Exchange xch;                      // RCCL communicator of the user-sharded step (sdrm_comm_init_rank / sdrm_allreduce_init)
@@ -397,16 +386,22 @@ hipError_t dalloc(Tp** p, size_t n) {
   return hipMemset(*p, 0, (n + SLACK) * sizeof(Tp));
 }
 
-// Grow-only device scratch: *p holds n elements afterwards.  A buffer that is too small is freed behind a device synchronise (a
-// launch may still read it) and its contents are not kept.
+// One buffer of the scratch pool (enum Scratch), as elements of Tp: *out holds n of them afterwards (and SLACK zeroed ones behind).
+// Grow-only: a buffer that is too small is freed behind a device synchronise (a launch may still read it) and its contents are not
+// kept.  scratch_at: the buffer as it stands (null before its first scratch()).
 template <typename Tp>
-int grow(sdrm_engine* e, Tp** p, size_t* cap, size_t n) {
-  if (n <= *cap) return SDRM_OK;
-  if (*p) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(*p)); *p = nullptr; *cap = 0; }
-  HIP_TRY(e, dalloc(p, n));
-  *cap = n;
+int scratch(sdrm_engine* e, Scratch slot, size_t n, Tp** out) {
+  auto& s = e->scratch[slot];
+  if (n > s.cap) {
+    if (s.p) { HIP_TRY(e, hipDeviceSynchronize()); HIP_TRY(e, hipFree(s.p)); s.p = nullptr; s.cap = 0; }
+    HIP_TRY(e, dalloc((Tp**)&s.p, n));
+    s.cap = n;
+  }
+  *out = (Tp*)s.p;
   return SDRM_OK;
 }
+template <typename Tp = float>
+Tp* scratch_at(const sdrm_engine* e, Scratch slot) { return (Tp*)e->scratch[slot].p; }
 
 float* pre_buf(sdrm_engine* e, int k) { return e->pre + (size_t)k * e->MPmax * e->WP; }
 float* smp_buf(sdrm_engine* e, int k) { return e->smp_pre + (size_t)k * e->MPmax * e->WP; }   // the sampler's layer buffers
@@ -437,6 +432,17 @@ hipError_t profiled(sdrm_engine* e, int cls, double flops, hipStream_t st, Launc
 // ... for the launch helpers that return SDRM_* codes: the status of profiled(), with the kernel's name in the message
 int hip_rc(sdrm_engine* e, const char* kernel, hipError_t st) {
   return st == hipSuccess ? SDRM_OK : fail(e, SDRM_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(st));
+}
+// ONE kernel launch as its own interval of class `cls` (with its flops, if it counts any): counted like every launch, the kernel's name
+// in the message of a HIP error.  PC_NONE: a launch that no profile brackets - profiled() is not called at all (it records every class
+// while sdrm_profile_only is off).
+constexpr int PC_NONE = -1;
+struct LaunchClass { int cls; double flops; LaunchClass(int c, double f = 0.0) : cls(c), flops(f) {} };
+template <class... Params, class... Args>
+int launch_k(sdrm_engine* e, LaunchClass lc, const char* name, void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st,
+             const Args&... args) {
+  const auto go = [&] { SDRM_LAUNCH(e, kernel, grid, block, lds, st, args...); return hipGetLastError(); };
+  return hip_rc(e, name, lc.cls == PC_NONE ? go() : profiled(e, lc.cls, lc.flops, st, go));
 }
 
 // Runtime value -> template argument: f is a generic callable that takes the value as a std::integral_constant (VAL reads it back
@@ -512,17 +518,23 @@ int max_gemm_blocks(int M, int N) {
   return best;
 }
 
+// The tile loads address one tile x one K chunk with 32-bit offsets behind a 64-bit base (gemm.h: tile_resource): whether the spans of a
+// launch on a bm x bn tile stay below 2^32 bytes.  launch_gemm_cfg's test; the sdrm_debug_*_args envelopes ask it for every tile.
+bool gemm_span_ok(int bm, int bn, bool a_kcontig, bool b_kcontig, int lda, int ldb, int kchunk) {
+  const uint64_t kc = (uint64_t)std::max(kchunk, 1) + 64;
+  const uint64_t spanA = a_kcontig ? ((uint64_t)bm * lda + kc) : kc * lda;
+  const uint64_t spanB = b_kcontig ? ((uint64_t)bn * ldb + kc) : kc * ldb;
+  return spanA * 4 < (1ull << 32) && spanB * 4 < (1ull << 32);
+}
+bool gemm_span_ok(int cfg, bool kcontig, int lda, int ldb, int kchunk) {
+  return gemm_span_ok(kCfgBM[cfg], kCfgBN[cfg], kcontig, kcontig, lda, ldb, kchunk);
+}
+
 template <class Cfg, int LA, int LB, int XA, int XB, int EPI>
 hipError_t launch_gemm_cfg(GemmArgs& a, int M, int N, int splits, hipStream_t st, Prof pr) {
   const int tiles_m = (M + Cfg::BM - 1) / Cfg::BM, tiles_n = (N + Cfg::BN - 1) / Cfg::BN;
   if (!gemm_set_grid(a, tiles_m, tiles_n, splits)) return hipErrorInvalidValue;   // beyond the exact range of the magic divisions
-  // the tile loads address one tile x one K chunk with 32-bit offsets behind a 64-bit base (gemm.h: tile_resource)
-  {
-    const uint64_t kc = (uint64_t)std::max(a.kchunk, 1) + 64;
-    const uint64_t spanA = LA == LD_KCONTIG ? ((uint64_t)Cfg::BM * a.lda + kc) : kc * a.lda;
-    const uint64_t spanB = LB == LD_KCONTIG ? ((uint64_t)Cfg::BN * a.ldb + kc) : kc * a.ldb;
-    if (spanA * 4 >= (1ull << 32) || spanB * 4 >= (1ull << 32)) return hipErrorInvalidValue;
-  }
+  if (!gemm_span_ok(Cfg::BM, Cfg::BN, LA == LD_KCONTIG, LB == LD_KCONTIG, a.lda, a.ldb, a.kchunk)) return hipErrorInvalidValue;
   dim3 grid(EPI == EPI_SLAB ? (unsigned)(a.nblocks * splits) : (unsigned)a.nblocks, 1, 1);
   return profiled(pr.e, pr.cls, pr.flops, st, [&] {
 #ifdef SDRM_STAMPS
@@ -584,6 +596,62 @@ hipError_t gemm_wgrad(const float* dC, int lddc, int Nout, const float* Act, int
   a.dbias = dbias; a.dbias_stride = Nout;
   return launch_gemm<LD_MCONTIG, LD_MCONTIG, XF_NONE, XB, EPI_SLAB>(a, Nout, Kin, S, st, pr, cfg);
 }
+
+// gemm_set_grid keeps a launch's tile count inside the exact range of its magic divisions (nb < 2^31, nb x tiles_n < 2^32,
+// nb^2 x slices < 2^32).  A product of the VAE entry points' envelope can leave that range - 2^22 rows, or 2^20 output columns - so these
+// two give the most rows (NT launch, N columns) / output columns (split-K launch, Kin columns, S slices) of ONE launch on tile `cfg`, whole
+// tiles, and the helpers below send a larger product out in bands of that size.  0: not even one tile row fits.
+int gemm_nt_band_rows(int cfg, int N) {
+  const uint64_t tn = (uint64_t)((N + kCfgBN[cfg] - 1) / kCfgBN[cfg]);
+  const uint64_t t = std::min<uint64_t>(65535 / tn, ((1ull << 32) - 1) / (tn * tn));
+  return (int)t * kCfgBM[cfg];
+}
+int gemm_wgrad_band_cols(int cfg, int Kin, int S) {
+  const uint64_t tn = (uint64_t)((Kin + kCfgBN[cfg] - 1) / kCfgBN[cfg]);
+  uint64_t nb = (uint64_t)std::sqrt((double)((1ull << 32) - 1) / (double)S);   // the most tiles with nb^2 x S < 2^32
+  while (nb * nb * (uint64_t)S >= (1ull << 32)) --nb;
+  while ((nb + 1) * (nb + 1) * (uint64_t)S < (1ull << 32)) ++nb;
+  return (int)std::min<uint64_t>(nb / tn, 1u << 20) * kCfgBM[cfg];
+}
+
+// C[M, N] = epilogue(A[M, K] B[N, K]^T) in row bands; `a` carries B, C, K and the epilogue's operands, rows_valid counts from row 0
+template <int EPI>
+int gemm_nt_banded(sdrm_engine* e, const GemmArgs& a, const float* A, int lda, int M, int N, int rows_valid, hipStream_t st, Prof pr, int cfg) {
+  const int band = gemm_nt_band_rows(cfg, N);
+  if (band < 1) return fail(e, SDRM_ERR_SHAPE, "decoder head: no tile row of this product fits one launch");
+  for (int m0 = 0; m0 < M; m0 += band) {
+    GemmArgs x = a;
+    const int m = std::min(band, M - m0);
+    x.A = A + (size_t)m0 * lda; x.lda = lda; x.limA = m; x.limB = N;
+    x.C = a.C + (size_t)m0 * a.ldc;
+    if (a.aux) x.aux = a.aux + (size_t)m0 * a.ldaux;
+    x.kchunk = a.K;
+    x.rows_valid = std::max(0, std::min(rows_valid - m0, m));
+    HIP_TRY(e, (launch_gemm<LD_KCONTIG, LD_KCONTIG, XF_NONE, XF_NONE, EPI>(x, m, N, 1, st, pr, cfg)));
+  }
+  return SDRM_OK;
+}
+
+// gemm_wgrad in bands of output columns: slab [S][Nout][Kin] and dbias [S][Nout] keep their whole strides
+int gemm_wgrad_banded(sdrm_engine* e, const float* dC, int Nout, const float* Act, int Kin, int Mrows, int S, int kchunk, float* slab,
+                      float* dbias, hipStream_t st, Prof pr, int cfg) {
+  const int band = gemm_wgrad_band_cols(cfg, Kin, S);
+  if (band < 1) return fail(e, SDRM_ERR_SHAPE, "decoder head: no tile row of this weight gradient fits one launch");
+  for (int n0 = 0; n0 < Nout; n0 += band) {
+    GemmArgs a{};
+    a.A = dC + n0; a.lda = Nout; a.limA = std::min(band, Nout - n0);
+    a.B = Act; a.ldb = Kin; a.limB = Kin;
+    a.C = slab + (size_t)n0 * Kin; a.ldc = Kin;
+    a.K = Mrows; a.kchunk = kchunk;
+    a.slab_stride = (size_t)Nout * Kin;
+    a.dbias = dbias + n0; a.dbias_stride = Nout;
+    HIP_TRY(e, (launch_gemm<LD_MCONTIG, LD_MCONTIG, XF_NONE, XF_NONE, EPI_SLAB>(a, a.limA, Kin, S, st, pr, cfg)));
+  }
+  return SDRM_OK;
+}
+
+// work-groups of 256 threads for `items` work items: at least 1, at most 2048 (the kernels stride)
+unsigned blocks_for(int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (items + 255) / 256)); }
 
 // One weight gradient of a batched launch (gemm_batch_kernel): the arguments gemm_wgrad would pass, with the grid
 // bookkeeping launch_gemm_cfg does, for the default tile.  slopeB must be non-null: layer 0, whose operand is not a
@@ -1645,29 +1713,9 @@ int sdrm_destroy(sdrm_engine* e) {
   (void)hipDeviceSynchronize();
   if (e->xabort_host) (void)hipHostFree(e->xabort_host);
   (void)sdrm_comm_destroy(e);
-  for (float* b : e->dec_buf)
-    if (b) (void)hipFree(b);
-  for (float* b : e->enc_buf)
-    if (b) (void)hipFree(b);
-  if (e->enc_part) (void)hipFree(e->enc_part);
+  for (const auto& s : e->scratch)
+    if (s.p) (void)hipFree(s.p);
   if (e->nll_part) (void)hipFree(e->nll_part);
-  for (float* b : e->il_buf)
-    if (b) (void)hipFree(b);
-  for (float* b : e->lat_buf)
-    if (b) (void)hipFree(b);
-  if (e->lat_part) (void)hipFree(e->lat_part);
-  for (float* b : e->dh_buf)
-    if (b) (void)hipFree(b);
-  for (float* b : e->ev_buf)
-    if (b) (void)hipFree(b);
-  if (e->hold_cnt) (void)hipFree(e->hold_cnt);
-  for (void* b : {(void*)e->svd_panel, (void*)e->svd_vt, (void*)e->svd_part, (void*)e->svd_flag})
-    if (b) (void)hipFree(b);
-  for (void* b : {(void*)e->neumf_ws, (void*)e->neumf_valid, (void*)e->neumf_part})
-    if (b) (void)hipFree(b);
-  if (e->csr_ws) (void)hipFree(e->csr_ws);
-  if (e->csrt_ws) (void)hipFree(e->csrt_ws);
-  if (e->stack_ws) (void)hipFree(e->stack_ws);
   if (e->csr_nnz_host) (void)hipHostFree(e->csr_nnz_host);
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
   if (e->ev_hold) (void)hipEventDestroy(e->ev_hold);
@@ -2715,9 +2763,7 @@ int sdrm_csr_rows_to_dense(sdrm_engine* e, const int64_t* indptr, const int32_t*
   FeedArgs a{};
   if (int rc = csr_batch(e, "sdrm_csr_rows_to_dense", indptr, indices, data, n_rows, rows, row0, b, n_items, &a.csr)) return rc;
   a.out = out;
-  SDRM_LAUNCH(e, k_csr_rows_to_dense, dim3(b), dim3(256), 0, (hipStream_t)stream, a);
-  HIP_TRY(e, hipGetLastError());
-  return SDRM_OK;
+  return launch_k(e, PC_NONE, "k_csr_rows_to_dense", k_csr_rows_to_dense, dim3(b), dim3(256), 0, (hipStream_t)stream, a);
 }
 
 // what the feed launches since the last call found (synchronises `stream`), and clears it
@@ -2761,22 +2807,40 @@ void quantile_ranks(int64_t n, double q, int64_t& r0, int64_t& r1, float& gamma)
 int select_and_binarize(sdrm_engine* e, const float* x, int64_t n, float gamma, uint8_t* out, float* threshold, hipStream_t st) {
   const int blocks = (int)std::min<int64_t>(2048, (n / 4 + 255) / 256 + 1);
   for (int pass = 0; pass < SEL_PASSES; ++pass) {
-    if (pass == 0) SDRM_LAUNCH(e, (k_select_hist<4>), dim3(blocks), dim3(256), 0, st, x, n, e->sel, pass);
-    else SDRM_LAUNCH(e, (k_select_hist<1>), dim3(blocks), dim3(256), 0, st, x, n, e->sel, pass);
-    HIP_TRY(e, hipGetLastError());
-    SDRM_LAUNCH(e, k_select_pick, dim3(1), dim3(256), 0, st, e->sel, pass, gamma);
-    HIP_TRY(e, hipGetLastError());
+    if (int rc = launch_k(e, PC_NONE, "k_select_hist", pass == 0 ? k_select_hist<4> : k_select_hist<1>, dim3(blocks), dim3(256), 0, st, x, n, e->sel, pass))
+      return rc;
+    if (int rc = launch_k(e, PC_NONE, "k_select_pick", k_select_pick, dim3(1), dim3(256), 0, st, e->sel, pass, gamma)) return rc;
   }
   if (threshold) HIP_TRY(e, hipMemcpyAsync(threshold, &e->sel->threshold, 4, hipMemcpyDeviceToDevice, st));
-  if (out) {
-    SDRM_LAUNCH(e, k_binarize_ge, dim3(blocks), dim3(256), 0, st, x, n, (const float*)&e->sel->threshold, out);
-    HIP_TRY(e, hipGetLastError());
-  }
+  if (out) return launch_k(e, PC_NONE, "k_binarize_ge", k_binarize_ge, dim3(blocks), dim3(256), 0, st, x, n, &e->sel->threshold, out);
   return SDRM_OK;
 }
 
-int dec_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->dec_buf[slot], &e->dec_cap[slot], n); }
-int enc_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->enc_buf[slot], &e->enc_cap[slot], n); }
+// The VAE-shaped entry points' limits, the same for every one of them (ENC_GATHER_MAX_Q and EVAL_MAX_ITEMS below are limits of their own)
+constexpr int VAE_MAX_HIDDEN = 4096, VAE_MAX_LATENT = 4096;   // (hidden: ENC_GATHER_MAX_Q float4 slices in the gather kernels' registers)
+constexpr int MAX_ITEMS = 1 << 20, MAX_BATCH_ROWS = 1 << 22;
+
+// The padded extents of a VAE-shaped call, by three rules: K and N of the GEMMs go to 32 (Hp, Lp, L2p, Ip; Kb: the batch as the K of a
+// weight gradient); the rows of an operand go to the largest tile, 128 (Hr, Lr, L2r, Ir; MP: the batch where it is a buffer's rows); the
+// batch as a launch's M goes to the default tile, 64 (rows64).  Hq is `hidden` on the float4 grid of the gather kernels; L2 = 2 latent,
+// the encoder's mu | logvar.  An extent that a call does not have goes in as 0.
+struct VaeDims { int Hq, Hp, Hr, Lp, Lr, L2, L2p, L2r, Ip, Ir, MP, rows64, Kb; };
+VaeDims vae_dims(int n_items, int hidden, int latent, int b) {
+  VaeDims d;
+  d.Hq = round_up(hidden, 4); d.Hp = round_up(hidden, 32); d.Hr = round_up(d.Hp, 128);
+  d.Lp = round_up(latent, 32); d.Lr = round_up(d.Lp, 128);
+  d.L2 = 2 * latent; d.L2p = round_up(d.L2, 32); d.L2r = round_up(d.L2p, 128);
+  d.Ip = round_up(n_items, 32); d.Ir = round_up(d.Ip, 128);
+  d.MP = round_up(b, 128); d.rows64 = round_up(b, BM); d.Kb = round_up(b, 32);
+  return d;
+}
+
+// Split-K plan of a weight gradient over Kb batch rows, in slabs of at most `chunk` rows
+struct SplitK { int kchunk, S; };
+SplitK split_k(int Kb, int chunk) {
+  const int kc = std::min(Kb, chunk);
+  return SplitK{kc, (Kb + kc - 1) / kc};
+}
 
 // The segments of ONE k_pad2d launch: src [rows, cols] -> dst [rowsP, colsP], zero-padded
 struct PadList {
@@ -2788,48 +2852,48 @@ struct PadList {
     most = std::max<int64_t>(most, (int64_t)rowsP * (colsP / 4));
     ++k;
   }
-  int launch(sdrm_engine* e, hipStream_t st) const {
-    SDRM_LAUNCH(e, k_pad2d, dim3((unsigned)std::min<int64_t>(2048, (most + 255) / 256), (unsigned)k), dim3(256), 0, st, sg);
-    HIP_TRY(e, hipGetLastError());
-    return SDRM_OK;
+  int launch(sdrm_engine* e, LaunchClass lc, hipStream_t st) const {   // (no lower bound of 1 on the grid: a list is never empty)
+    return launch_k(e, lc, "k_pad2d", k_pad2d, dim3((unsigned)std::min<int64_t>(2048, (most + 255) / 256), (unsigned)k), dim3(256), 0, st, sg);
   }
 };
 
 // decoder(z) = Linear(hidden, items)(tanh(Linear(latent, hidden)(z)))   (train_SDRM.py:212-214, :252-254): one staging launch, two GEMMs
-int decode_launches(sdrm_engine* e, const sdrm_vae_decoder* d, const float* z, int n, float* out, hipStream_t st) {
-  const int Lp = round_up(d->latent, 32), Hp = round_up(d->hidden, 32), Ip = round_up(d->n_items, 32);
-  const int MP = round_up(n, 128), Hr = round_up(Hp, 128), Ir = round_up(Ip, 128);
-  enum { Z = 0, W1, B1, HID, W2, B2 };
+int decode_launches(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z, int n, float* out, hipStream_t st) {
+  const VaeDims d = vae_dims(dec->n_items, dec->hidden, dec->latent, n);
+  float *zp, *w1p, *b1p, *hid, *w2p, *b2p;
   int rc;
-  if ((rc = dec_grow(e, Z, (size_t)MP * Lp)) || (rc = dec_grow(e, W1, (size_t)Hr * Lp)) || (rc = dec_grow(e, B1, Hr)) ||
-      (rc = dec_grow(e, HID, (size_t)MP * Hp)) || (rc = dec_grow(e, W2, (size_t)Ir * Hp)) || (rc = dec_grow(e, B2, Ir)))
+  if ((rc = scratch(e, SCR_DEC_Z, (size_t)d.MP * d.Lp, &zp)) || (rc = scratch(e, SCR_DEC_W1, (size_t)d.Hr * d.Lp, &w1p)) ||
+      (rc = scratch(e, SCR_DEC_B1, d.Hr, &b1p)) || (rc = scratch(e, SCR_DEC_HID, (size_t)d.MP * d.Hp, &hid)) ||
+      (rc = scratch(e, SCR_DEC_W2, (size_t)d.Ir * d.Hp, &w2p)) || (rc = scratch(e, SCR_DEC_B2, d.Ir, &b2p)))
     return rc;
   PadList pad;
-  pad.add(z, n, d->latent, e->dec_buf[Z], MP, Lp);
-  pad.add(d->w1, d->hidden, d->latent, e->dec_buf[W1], Hr, Lp);
-  pad.add(d->b1, 1, d->hidden, e->dec_buf[B1], 1, Hr);
-  pad.add(d->w2, d->n_items, d->hidden, e->dec_buf[W2], Ir, Hp);
-  pad.add(d->b2, 1, d->n_items, e->dec_buf[B2], 1, Ir);
-  if ((rc = pad.launch(e, st))) return rc;
-  const int rows64 = round_up(n, BM);
-  const int cfg = choose_cfg(e->tune, rows64, e->tune.nt32_max_rows);
+  pad.add(z, n, dec->latent, zp, d.MP, d.Lp);
+  pad.add(dec->w1, dec->hidden, dec->latent, w1p, d.Hr, d.Lp);
+  pad.add(dec->b1, 1, dec->hidden, b1p, 1, d.Hr);
+  pad.add(dec->w2, dec->n_items, dec->hidden, w2p, d.Ir, d.Hp);
+  pad.add(dec->b2, 1, dec->n_items, b2p, 1, d.Ir);
+  if ((rc = pad.launch(e, PC_NONE, st))) return rc;
+  const int cfg = choose_cfg(e->tune, d.rows64, e->tune.nt32_max_rows);
   {
     GemmArgs a{};
-    a.C = e->dec_buf[HID]; a.ldc = Hp; a.bias = e->dec_buf[B1];
-    HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_TANH>(a, e->dec_buf[Z], Lp, e->dec_buf[W1], Lp, rows64, Hp, Lp, st,
-                                                     Prof{nullptr, 0, 0.0}, cfg)));
+    a.C = hid; a.ldc = d.Hp; a.bias = b1p;
+    HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_TANH>(a, zp, d.Lp, w1p, d.Lp, d.rows64, d.Hp, d.Lp, st, Prof{nullptr, 0, 0.0}, cfg)));
   }
   GemmArgs a{};
-  a.C = out; a.ldc = d->n_items; a.bias = e->dec_buf[B2];
-  a.rows_valid = n; a.cols_valid = d->n_items;
-  HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, e->dec_buf[HID], Hp, e->dec_buf[W2], Hp, rows64, Ip, Hp, st, Prof{nullptr, 0, 0.0}, cfg)));
+  a.C = out; a.ldc = dec->n_items; a.bias = b2p;
+  a.rows_valid = n; a.cols_valid = dec->n_items;
+  HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, hid, d.Hp, w2p, d.Hp, d.rows64, d.Ip, d.Hp, st, Prof{nullptr, 0, 0.0}, cfg)));
   return SDRM_OK;
 }
 
+// the four tensors of a decoder / an encoder are there (bwd: the backward reads no bias)
+bool dec_tensors(const sdrm_vae_decoder* d, bool biases = true) { return d && d->w1 && d->w2 && (!biases || (d->b1 && d->b2)); }
+bool enc_tensors(const sdrm_vae_encoder* d) { return d && d->w1 && d->b1 && d->w2 && d->b2; }
+
 int check_decoder(sdrm_engine* e, const sdrm_vae_decoder* d, const float* z, int n, const char* who) {
-  if (!e || !d || !z || !d->w1 || !d->b1 || !d->w2 || !d->b2) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
-  if (n < 1 || n > (1 << 22) || d->latent < 1 || d->latent > 4096 || d->hidden < 1 || d->hidden > 16384 || d->n_items < 1 ||
-      d->n_items > (1 << 20))
+  if (!e || !dec_tensors(d) || !z) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (n < 1 || n > MAX_BATCH_ROWS || d->latent < 1 || d->latent > VAE_MAX_LATENT || d->hidden < 1 || d->hidden > 16384 || d->n_items < 1 ||
+      d->n_items > MAX_ITEMS)
     return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": n, latent, hidden or n_items outside the supported envelope");
   return SDRM_OK;
 }
@@ -2847,68 +2911,54 @@ int sdrm_vae_decode(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z,
 // VAE encode hook, frozen and in eval mode (train_SDRM.py:241-250, called at :323), csrc/encode.h.
 namespace {
 
-constexpr int ENC_KL_PARTS = 512;    // work-groups of k_encode_kl_rows
+constexpr int KL_PARTS = 512;    // work-groups of k_encode_kl_rows / k_latent_reparam: the float64 partials k_encode_kl_sum adds
 constexpr int ENC_GATHER_MAX_Q = 1024;   // float4 slices of the hidden vector k_encode_csr holds in registers (256 threads x 4): hidden <= 4096
 
-
-struct EncDims { int Ip, Hq, Hp, Hr, L2p, L2r; };
-EncDims enc_dims(int n_items, int hidden, int latent) {
-  EncDims d;
-  d.Ip = round_up(n_items, 32); d.Hq = round_up(hidden, 4); d.Hp = round_up(hidden, 32); d.Hr = round_up(d.Hp, 128);
-  d.L2p = round_up(2 * latent, 32); d.L2r = round_up(d.L2p, 128);
-  return d;
-}
-
-// The second Linear on the hidden activations enc_buf[ENC_HID] [rows64][Hp], and the kl.  kl null: only the mu rows of W2, straight into z.
+// The second Linear on the hidden activations SCR_ENC_HID [rows64][Hp], and the kl.  kl null: only the mu rows of W2, straight into z.
 int encode_tail(sdrm_engine* e, int n, float* z, float* kl, hipStream_t st) {
-  const EncDims d = enc_dims(e->enc_items, e->enc_hidden, e->enc_latent);
+  const VaeDims d = vae_dims(e->enc_items, e->enc_hidden, e->enc_latent, n);
   const int L = e->enc_latent;
-  const int rows64 = round_up(n, BM);
-  const int cfg = choose_cfg(e->tune, rows64, e->tune.nt32_max_rows);
+  const int cfg = choose_cfg(e->tune, d.rows64, e->tune.nt32_max_rows);
+  const float *hid = scratch_at(e, SCR_ENC_HID), *w2 = scratch_at(e, SCR_ENC_W2);
   GemmArgs a{};
-  a.bias = e->enc_buf[sdrm_engine::ENC_B2];
+  a.bias = scratch_at(e, SCR_ENC_B2);
   a.rows_valid = n;
   if (!kl) {
     a.C = z; a.ldc = L; a.cols_valid = L;
-    HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, e->enc_buf[sdrm_engine::ENC_HID], d.Hp, e->enc_buf[sdrm_engine::ENC_W2], d.Hp, rows64,
-                                                   round_up(L, 32), d.Hp, st, Prof{nullptr, 0, 0.0}, cfg)));
+    HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, hid, d.Hp, w2, d.Hp, d.rows64, d.Lp, d.Hp, st, Prof{nullptr, 0, 0.0}, cfg)));
     return SDRM_OK;
   }
-  if (int rc = enc_grow(e, sdrm_engine::ENC_OUT2, (size_t)n * 2 * L)) return rc;
-  a.C = e->enc_buf[sdrm_engine::ENC_OUT2]; a.ldc = 2 * L; a.cols_valid = 2 * L;
-  HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, e->enc_buf[sdrm_engine::ENC_HID], d.Hp, e->enc_buf[sdrm_engine::ENC_W2], d.Hp, rows64, d.L2p,
-                                                 d.Hp, st, Prof{nullptr, 0, 0.0}, cfg)));
-  const int parts = std::min(n, ENC_KL_PARTS);
-  SDRM_LAUNCH(e, k_encode_kl_rows, dim3(parts), dim3(256), 0, st, (const float*)e->enc_buf[sdrm_engine::ENC_OUT2], n, L, z, e->enc_part);
-  HIP_TRY(e, hipGetLastError());
-  SDRM_LAUNCH(e, k_encode_kl_sum, dim3(1), dim3(256), 0, st, (const double*)e->enc_part, parts, n, kl);
-  HIP_TRY(e, hipGetLastError());
-  return SDRM_OK;
+  float* out2;
+  if (int rc = scratch(e, SCR_ENC_OUT2, (size_t)n * d.L2, &out2)) return rc;
+  a.C = out2; a.ldc = d.L2; a.cols_valid = d.L2;
+  HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, hid, d.Hp, w2, d.Hp, d.rows64, d.L2p, d.Hp, st, Prof{nullptr, 0, 0.0}, cfg)));
+  const int parts = std::min(n, KL_PARTS);
+  double* part = scratch_at<double>(e, SCR_ENC_PART);
+  if (int rc = launch_k(e, PC_NONE, "k_encode_kl_rows", k_encode_kl_rows, dim3(parts), dim3(256), 0, st, out2, n, L, z, part)) return rc;
+  return launch_k(e, PC_NONE, "k_encode_kl_sum", k_encode_kl_sum, dim3(1), dim3(256), 0, st, part, parts, n, kl);
 }
 
 // x [n, n_items] dense -> z (, kl): normalise + pad, Linear + tanh, tail
 int encode_dense_launches(sdrm_engine* e, const float* x, int n, float* z, float* kl, hipStream_t st) {
-  const EncDims d = enc_dims(e->enc_items, e->enc_hidden, e->enc_latent);
-  const int MP = round_up(n, 128), rows64 = round_up(n, BM);
+  const VaeDims d = vae_dims(e->enc_items, e->enc_hidden, e->enc_latent, n);
+  float *xn, *hid;
   int rc;
-  if ((rc = enc_grow(e, sdrm_engine::ENC_XN, (size_t)MP * d.Ip)) || (rc = enc_grow(e, sdrm_engine::ENC_HID, (size_t)MP * d.Hp))) return rc;
-  SDRM_LAUNCH(e, k_encode_norm_rows, dim3(n), dim3(256), 0, st, x, e->enc_items, e->enc_buf[sdrm_engine::ENC_XN], d.Ip);
-  HIP_TRY(e, hipGetLastError());
+  if ((rc = scratch(e, SCR_ENC_XN, (size_t)d.MP * d.Ip, &xn)) || (rc = scratch(e, SCR_ENC_HID, (size_t)d.MP * d.Hp, &hid))) return rc;
+  if ((rc = launch_k(e, PC_NONE, "k_encode_norm_rows", k_encode_norm_rows, dim3(n), dim3(256), 0, st, x, e->enc_items, xn, d.Ip))) return rc;
   GemmArgs a{};
-  a.C = e->enc_buf[sdrm_engine::ENC_HID]; a.ldc = d.Hp; a.bias = e->enc_buf[sdrm_engine::ENC_B1];
-  HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_TANH>(a, e->enc_buf[sdrm_engine::ENC_XN], d.Ip, e->enc_buf[sdrm_engine::ENC_W1], d.Ip, rows64, d.Hp,
-                                                   d.Ip, st, Prof{nullptr, 0, 0.0}, choose_cfg(e->tune, rows64, e->tune.nt32_max_rows))));
+  a.C = hid; a.ldc = d.Hp; a.bias = scratch_at(e, SCR_ENC_B1);
+  HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_TANH>(a, xn, d.Ip, scratch_at(e, SCR_ENC_W1), d.Ip, d.rows64, d.Hp, d.Ip, st, Prof{nullptr, 0, 0.0},
+                                                   choose_cfg(e->tune, d.rows64, e->tune.nt32_max_rows))));
   return encode_tail(e, n, z, kl, st);
 }
 
 // One launch of a row-owned gather kernel (csrc/csr_batch.h) over the rows of a batch.  The gather shape goes by the q float4 slices
 // of the hidden vector alone: TPR threads own a row, NV slices each, U entries in flight.  kernel_of(TPR, NV, U) names the kernel.
 extern "C++" template <class Args, class KernelOf>
-hipError_t launch_gather_rows(sdrm_engine* e, int q, const Args& a, hipStream_t st, KernelOf&& kernel_of) {
+int launch_gather_rows(sdrm_engine* e, LaunchClass lc, const char* name, int q, const Args& a, hipStream_t st, KernelOf&& kernel_of) {
   const auto go = [&](auto tpr, auto nv, auto u) {
     constexpr int rpw = 256 / VAL(tpr);
-    SDRM_LAUNCH(e, kernel_of(tpr, nv, u), dim3((unsigned)((a.csr.b + rpw - 1) / rpw)), dim3(256), 0, st, a);
-    return hipGetLastError();
+    return launch_k(e, lc, name, kernel_of(tpr, nv, u), dim3((unsigned)((a.csr.b + rpw - 1) / rpw)), dim3(256), 0, st, a);
   };
   using std::integral_constant;
   if (q <= 64) return go(integral_constant<int, 64>{}, integral_constant<int, 1>{}, integral_constant<int, 8>{});   // one wave per row, four rows per work-group (ADM: hidden 200)
@@ -2919,10 +2969,16 @@ hipError_t launch_gather_rows(sdrm_engine* e, int q, const Args& a, hipStream_t 
 
 int check_encoder(sdrm_engine* e, const sdrm_vae_encoder* d, const char* who) {
   if (!e) return SDRM_ERR_ARG;
-  if (!d || !d->w1 || !d->b1 || !d->w2 || !d->b2) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
-  if (d->latent < 1 || d->latent > 4096 || d->hidden < 1 || d->hidden > 16384 || d->n_items < 1 || d->n_items > (1 << 20))
+  if (!enc_tensors(d)) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (d->latent < 1 || d->latent > VAE_MAX_LATENT || d->hidden < 1 || d->hidden > 16384 || d->n_items < 1 || d->n_items > MAX_ITEMS)
     return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": latent, hidden or n_items outside the supported envelope");
   return SDRM_OK;
+}
+
+// W1 [hidden][items] -> W1^T [items][Hq], the gather kernels' operand
+int launch_w1t(sdrm_engine* e, LaunchClass lc, const float* w1, int hidden, int n_items, float* w1t, int Hq, hipStream_t st) {
+  return launch_k(e, lc, "k_encode_w1t", k_encode_w1t, dim3((unsigned)((n_items + 31) / 32), (unsigned)((Hq + 31) / 32)), dim3(256), 0, st, w1,
+                  hidden, n_items, w1t, Hq);
 }
 
 }  // namespace
@@ -2931,23 +2987,22 @@ int sdrm_vae_encoder_load(sdrm_engine* e, const sdrm_vae_encoder* enc, void* str
   if (int rc = check_encoder(e, enc, "sdrm_vae_encoder_load")) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (int jr = chains_join(e, st)) return jr;
-  const EncDims d = enc_dims(enc->n_items, enc->hidden, enc->latent);
+  const VaeDims d = vae_dims(enc->n_items, enc->hidden, enc->latent, 0);
   e->enc_loaded = false;
+  float *w1t, *w1p, *b1p, *w2p, *b2p;
+  double* part;
   int rc;
-  if ((rc = enc_grow(e, sdrm_engine::ENC_W1T, (size_t)enc->n_items * d.Hq)) || (rc = enc_grow(e, sdrm_engine::ENC_W1, (size_t)d.Hr * d.Ip)) ||
-      (rc = enc_grow(e, sdrm_engine::ENC_B1, d.Hr)) || (rc = enc_grow(e, sdrm_engine::ENC_W2, (size_t)d.L2r * d.Hp)) ||
-      (rc = enc_grow(e, sdrm_engine::ENC_B2, d.L2r)))
+  if ((rc = scratch(e, SCR_ENC_W1T, (size_t)enc->n_items * d.Hq, &w1t)) || (rc = scratch(e, SCR_ENC_W1, (size_t)d.Hr * d.Ip, &w1p)) ||
+      (rc = scratch(e, SCR_ENC_B1, d.Hr, &b1p)) || (rc = scratch(e, SCR_ENC_W2, (size_t)d.L2r * d.Hp, &w2p)) ||
+      (rc = scratch(e, SCR_ENC_B2, d.L2r, &b2p)) || (rc = scratch(e, SCR_ENC_PART, KL_PARTS, &part)))
     return rc;
-  if (!e->enc_part) HIP_TRY(e, dalloc(&e->enc_part, ENC_KL_PARTS));
   PadList pad;
-  pad.add(enc->w1, enc->hidden, enc->n_items, e->enc_buf[sdrm_engine::ENC_W1], d.Hr, d.Ip);
-  pad.add(enc->b1, 1, enc->hidden, e->enc_buf[sdrm_engine::ENC_B1], 1, d.Hr);
-  pad.add(enc->w2, 2 * enc->latent, enc->hidden, e->enc_buf[sdrm_engine::ENC_W2], d.L2r, d.Hp);
-  pad.add(enc->b2, 1, 2 * enc->latent, e->enc_buf[sdrm_engine::ENC_B2], 1, d.L2r);
-  if ((rc = pad.launch(e, st))) return rc;
-  SDRM_LAUNCH(e, k_encode_w1t, dim3((unsigned)((enc->n_items + 31) / 32), (unsigned)((d.Hq + 31) / 32)), dim3(256), 0, st, enc->w1, enc->hidden,
-              enc->n_items, e->enc_buf[sdrm_engine::ENC_W1T], d.Hq);
-  HIP_TRY(e, hipGetLastError());
+  pad.add(enc->w1, enc->hidden, enc->n_items, w1p, d.Hr, d.Ip);
+  pad.add(enc->b1, 1, enc->hidden, b1p, 1, d.Hr);
+  pad.add(enc->w2, d.L2, enc->hidden, w2p, d.L2r, d.Hp);
+  pad.add(enc->b2, 1, d.L2, b2p, 1, d.L2r);
+  if ((rc = pad.launch(e, PC_NONE, st))) return rc;
+  if ((rc = launch_w1t(e, PC_NONE, enc->w1, enc->hidden, enc->n_items, w1t, d.Hq, st))) return rc;
   e->enc_items = enc->n_items; e->enc_hidden = enc->hidden; e->enc_latent = enc->latent;
   e->enc_loaded = true;
   return SDRM_OK;
@@ -2957,7 +3012,7 @@ int sdrm_vae_encode(sdrm_engine* e, const float* x, int n, float* z, float* kl, 
   if (!e) return SDRM_ERR_ARG;
   if (!x || !z) return fail(e, SDRM_ERR_ARG, "sdrm_vae_encode: null pointer");
   if (!e->enc_loaded) return fail(e, SDRM_ERR_STATE, "sdrm_vae_encode: no encoder loaded (sdrm_vae_encoder_load)");
-  if (n < 1 || n > (1 << 22)) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode: n outside 1 .. 2^22");
+  if (n < 1 || n > MAX_BATCH_ROWS) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode: n outside 1 .. 2^22");
   if (int jr = chains_join(e, (hipStream_t)stream)) return jr;
   return encode_dense_launches(e, x, n, z, kl, (hipStream_t)stream);
 }
@@ -2969,51 +3024,37 @@ int sdrm_vae_encode_csr(sdrm_engine* e, const int64_t* indptr, const int32_t* in
   if (!e->enc_loaded) return fail(e, SDRM_ERR_STATE, "sdrm_vae_encode_csr: no encoder loaded (sdrm_vae_encoder_load)");
   EncodeCsrArgs a{};
   if (int rc = csr_batch(e, "sdrm_vae_encode_csr", indptr, indices, data, n_rows, rows, row0, b, e->enc_items, &a.csr)) return rc;
-  if (b > (1 << 22)) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode_csr: b outside 1 .. 2^22");
+  if (b > MAX_BATCH_ROWS) return fail(e, SDRM_ERR_SHAPE, "sdrm_vae_encode_csr: b outside 1 .. 2^22");
   hipStream_t st = (hipStream_t)stream;
   if (int jr = chains_join(e, st)) return jr;
-  const EncDims d = enc_dims(e->enc_items, e->enc_hidden, e->enc_latent);
+  const VaeDims d = vae_dims(e->enc_items, e->enc_hidden, e->enc_latent, b);
   const int q = d.Hq / 4;
   if (q > ENC_GATHER_MAX_Q) {   // a hidden vector wider than the gather kernel's registers: densify into scratch, then the dense form
-    if (int rc = enc_grow(e, sdrm_engine::ENC_DENSE, (size_t)b * e->enc_items)) return rc;
-    if (int rc = sdrm_csr_rows_to_dense(e, indptr, indices, data, n_rows, rows, row0, b, e->enc_items, e->enc_buf[sdrm_engine::ENC_DENSE], stream)) return rc;
-    return encode_dense_launches(e, e->enc_buf[sdrm_engine::ENC_DENSE], b, z, kl, st);
+    float* dense;
+    if (int rc = scratch(e, SCR_ENC_DENSE, (size_t)b * e->enc_items, &dense)) return rc;
+    if (int rc = sdrm_csr_rows_to_dense(e, indptr, indices, data, n_rows, rows, row0, b, e->enc_items, dense, stream)) return rc;
+    return encode_dense_launches(e, dense, b, z, kl, st);
   }
-  if (int rc = enc_grow(e, sdrm_engine::ENC_HID, (size_t)round_up(b, 128) * d.Hp)) return rc;
-  a.w1t = e->enc_buf[sdrm_engine::ENC_W1T]; a.b1 = e->enc_buf[sdrm_engine::ENC_B1]; a.Hq = d.Hq; a.Hp = d.Hp;
-  a.hid = e->enc_buf[sdrm_engine::ENC_HID];
-  HIP_TRY(e, launch_gather_rows(e, q, a, st, [](auto tpr, auto nv, auto u) { return k_encode_csr<VAL(tpr), VAL(nv), VAL(u)>; }));
+  if (int rc = scratch(e, SCR_ENC_HID, (size_t)d.MP * d.Hp, &a.hid)) return rc;
+  a.w1t = scratch_at(e, SCR_ENC_W1T); a.b1 = scratch_at(e, SCR_ENC_B1); a.Hq = d.Hq; a.Hp = d.Hp;
+  if (int rc = launch_gather_rows(e, PC_NONE, "k_encode_csr", q, a, st, [](auto tpr, auto nv, auto u) { return k_encode_csr<VAL(tpr), VAL(nv), VAL(u)>; }))
+    return rc;
   return encode_tail(e, b, z, kl, st);
 }
 
 // ---------------------------------------------------------------------------------------------
 // The VAE encoder behind its first pre-activation in TRAIN mode (train_SDRM.py:244-250 with is_training == 1: Tanh, the second Linear,
 // chunk, the KL, the reparameterisation; and their share of :148), csrc/latent.h.  The frozen encoder above is not touched.
-constexpr int LATENT_MAX_HIDDEN = 4096, LATENT_MAX_LATENT = 4096;
 constexpr int LATENT_WGRAD_KCHUNK = 8192;   // most batch rows of one weight-gradient slab (the pre-stage's batches are a few hundred: one slab)
 
 // The host side of both entry points that needs no device: the envelope (`contiguous` != 0: the feed rows are row0 .. row0 + b - 1).
 int sdrm_debug_latent_args(int hidden, int latent, int b, int64_t row0, int contiguous) {
-  if (hidden < 1 || hidden > LATENT_MAX_HIDDEN || latent < 1 || latent > LATENT_MAX_LATENT || b < 1 || b > (1 << 22)) return SDRM_ERR_SHAPE;
+  if (hidden < 1 || hidden > VAE_MAX_HIDDEN || latent < 1 || latent > VAE_MAX_LATENT || b < 1 || b > MAX_BATCH_ROWS) return SDRM_ERR_SHAPE;
   if (contiguous && (row0 < 0 || row0 + b > ((int64_t)1 << 31))) return SDRM_ERR_SHAPE;
   return SDRM_OK;
 }
 
 namespace {
-
-int lat_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->lat_buf[slot], &e->lat_cap[slot], n); }
-
-// padded extents: K and N of the GEMMs to 32, operand rows to the largest tile (128), the batch to 64 (the launches' M)
-struct LatDims { int Hp, Hr, L2, L2p, L2r, MP, rows64; };
-LatDims lat_dims(int hidden, int latent, int b) {
-  LatDims d;
-  d.Hp = round_up(hidden, 32); d.Hr = round_up(d.Hp, 128);
-  d.L2 = 2 * latent; d.L2p = round_up(d.L2, 32); d.L2r = round_up(d.L2p, 128);
-  d.MP = round_up(b, 128); d.rows64 = round_up(b, BM);
-  return d;
-}
-
-unsigned lat_blocks(int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, (items + 255) / 256)); }
 
 const char* const kLatentEnvelope = ": hidden outside 1 .. 4096, latent outside 1 .. 4096, b outside 1 .. 2^22, or feed rows row0 .. row0 + b - 1 "
                                     "outside [0, 2^31)";
@@ -3028,46 +3069,35 @@ int sdrm_vae_latent_fwd(sdrm_engine* e, const float* pre, const float* w2, const
   if (int rc = sdrm_debug_latent_args(hidden, latent, b, row0, rows == nullptr)) return fail(e, rc, std::string("sdrm_vae_latent_fwd") + kLatentEnvelope);
   hipStream_t st = (hipStream_t)stream;
   if (int jr = chains_join(e, st)) return jr;
-  const LatDims d = lat_dims(hidden, latent, b);
-  int rc;
-  if ((rc = lat_grow(e, sdrm_engine::LAT_H, (size_t)d.MP * d.Hp)) || (rc = lat_grow(e, sdrm_engine::LAT_W2, (size_t)d.L2r * d.Hp)) ||
-      (rc = lat_grow(e, sdrm_engine::LAT_B2, d.L2r)))
-    return rc;
-  if (!e->lat_part) HIP_TRY(e, dalloc(&e->lat_part, ENC_KL_PARTS));
-  // 1: h1 = tanh(pre) into the caller's buffer and the padded operand; W2 and b2 padded (they change with every optimiser step)
+  const VaeDims d = vae_dims(0, hidden, latent, b);
   LatentStageArgs sa{};
-  sa.pre = pre; sa.h1 = h1; sa.hp = e->lat_buf[sdrm_engine::LAT_H]; sa.b = b; sa.H = hidden; sa.MP = d.MP; sa.Hp = d.Hp;
-  sa.w2 = w2; sa.w2p = e->lat_buf[sdrm_engine::LAT_W2]; sa.L2 = d.L2; sa.L2r = d.L2r;
-  sa.b2 = b2; sa.b2p = e->lat_buf[sdrm_engine::LAT_B2];
-  if ((rc = hip_rc(e, "k_latent_stage", profiled(e, PC_LATENT, 0.0, st, [&] {
-         SDRM_LAUNCH(e, k_latent_stage, dim3(lat_blocks((int64_t)std::max(d.MP, d.L2r) * (d.Hp / 4)), 3), dim3(256), 0, st, sa);
-         return hipGetLastError();
-       }))))
+  LatentReparamArgs ra{};
+  int rc;
+  if ((rc = scratch(e, SCR_LAT_H, (size_t)d.MP * d.Hp, &sa.hp)) || (rc = scratch(e, SCR_LAT_W2, (size_t)d.L2r * d.Hp, &sa.w2p)) ||
+      (rc = scratch(e, SCR_LAT_B2, d.L2r, &sa.b2p)) || (rc = scratch(e, SCR_LAT_PART, KL_PARTS, &ra.part)))
+    return rc;
+  // 1: h1 = tanh(pre) into the caller's buffer and the padded operand; W2 and b2 padded (they change with every optimiser step)
+  sa.pre = pre; sa.h1 = h1; sa.b = b; sa.H = hidden; sa.MP = d.MP; sa.Hp = d.Hp;
+  sa.w2 = w2; sa.L2 = d.L2; sa.L2r = d.L2r;
+  sa.b2 = b2;
+  if ((rc = launch_k(e, PC_LATENT, "k_latent_stage", k_latent_stage, dim3(blocks_for((int64_t)std::max(d.MP, d.L2r) * (d.Hp / 4)), 3), dim3(256), 0,
+                     st, sa)))
     return rc;
   // 2: out2 = h1 W2^T + b2, bounds-checked into the caller's [b][2L]
   {
     GemmArgs a{};
-    a.C = out2; a.ldc = d.L2; a.bias = e->lat_buf[sdrm_engine::LAT_B2];
+    a.C = out2; a.ldc = d.L2; a.bias = sa.b2p;
     a.rows_valid = b; a.cols_valid = d.L2;
-    HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, e->lat_buf[sdrm_engine::LAT_H], d.Hp, e->lat_buf[sdrm_engine::LAT_W2], d.Hp, d.rows64, d.L2p,
-                                                   d.Hp, st, Prof{e, PC_LATENT, 2.0 * b * d.L2 * hidden},
+    HIP_TRY(e, (gemm_forward<XF_NONE, EPI_BIAS_G>(a, sa.hp, d.Hp, sa.w2p, d.Hp, d.rows64, d.L2p, d.Hp, st, Prof{e, PC_LATENT, 2.0 * b * d.L2 * hidden},
                                                    choose_cfg(e->tune, d.rows64, e->tune.nt32_max_rows))));
   }
   // 3: the draw, z and the KL partials; 4: their sum
-  const int parts = std::min(b, ENC_KL_PARTS);
-  LatentReparamArgs ra{};
+  const int parts = std::min(b, KL_PARTS);
   ra.out2 = out2; ra.rows = rows; ra.row0 = row0; ra.b = b; ra.L = latent;
   ra.k0 = (uint32_t)seed; ra.k1 = (uint32_t)(seed >> 32); ra.step = step; ra.draw = draw;
-  ra.eps = eps; ra.z = z; ra.part = e->lat_part; ra.flag = e->feed_flag;
-  if ((rc = hip_rc(e, "k_latent_reparam", profiled(e, PC_LATENT, 0.0, st, [&] {
-         SDRM_LAUNCH(e, k_latent_reparam, dim3((unsigned)parts), dim3(256), 0, st, ra);
-         return hipGetLastError();
-       }))))
-    return rc;
-  return hip_rc(e, "k_encode_kl_sum", profiled(e, PC_LATENT, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_encode_kl_sum, dim3(1), dim3(256), 0, st, (const double*)e->lat_part, parts, b, kl);
-    return hipGetLastError();
-  }));
+  ra.eps = eps; ra.z = z; ra.flag = e->feed_flag;
+  if ((rc = launch_k(e, PC_LATENT, "k_latent_reparam", k_latent_reparam, dim3((unsigned)parts), dim3(256), 0, st, ra))) return rc;
+  return launch_k(e, PC_LATENT, "k_encode_kl_sum", k_encode_kl_sum, dim3(1), dim3(256), 0, st, ra.part, parts, b, kl);
 }
 
 int sdrm_vae_latent_bwd(sdrm_engine* e, const float* h1, const float* out2, const float* eps, const float* w2, int hidden, int latent, int b,
@@ -3077,38 +3107,28 @@ int sdrm_vae_latent_bwd(sdrm_engine* e, const float* h1, const float* out2, cons
   if (int rc = sdrm_debug_latent_args(hidden, latent, b, 0, 0)) return fail(e, rc, std::string("sdrm_vae_latent_bwd") + kLatentEnvelope);
   hipStream_t st = (hipStream_t)stream;
   if (int jr = chains_join(e, st)) return jr;
-  const LatDims d = lat_dims(hidden, latent, b);
-  const int Kb = round_up(b, 32), kchunk = std::min(Kb, LATENT_WGRAD_KCHUNK), S = (Kb + kchunk - 1) / kchunk;
+  const VaeDims d = vae_dims(0, hidden, latent, b);
+  const SplitK sk = split_k(d.Kb, LATENT_WGRAD_KCHUNK);
+  float *hp, *w2t, *dp, *slab, *dbias;
   int rc;
-  if ((rc = lat_grow(e, sdrm_engine::LAT_H, (size_t)d.MP * d.Hp)) || (rc = lat_grow(e, sdrm_engine::LAT_W2T, (size_t)d.Hr * d.L2p)) ||
-      (rc = lat_grow(e, sdrm_engine::LAT_DOUT2, (size_t)d.MP * d.L2p)) || (rc = lat_grow(e, sdrm_engine::LAT_SLAB, (size_t)S * d.L2p * d.Hp)) ||
-      (rc = lat_grow(e, sdrm_engine::LAT_DBIAS, (size_t)S * d.L2p)))
+  if ((rc = scratch(e, SCR_LAT_H, (size_t)d.MP * d.Hp, &hp)) || (rc = scratch(e, SCR_LAT_W2T, (size_t)d.Hr * d.L2p, &w2t)) ||
+      (rc = scratch(e, SCR_LAT_DOUT2, (size_t)d.MP * d.L2p, &dp)) || (rc = scratch(e, SCR_LAT_SLAB, (size_t)sk.S * d.L2p * d.Hp, &slab)) ||
+      (rc = scratch(e, SCR_LAT_DBIAS, (size_t)sk.S * d.L2p, &dbias)))
     return rc;
-  float* hp = e->lat_buf[sdrm_engine::LAT_H];
-  float* w2t = e->lat_buf[sdrm_engine::LAT_W2T];
-  float* dp = e->lat_buf[sdrm_engine::LAT_DOUT2];
-  float* slab = e->lat_buf[sdrm_engine::LAT_SLAB];
-  float* dbias = e->lat_buf[sdrm_engine::LAT_DBIAS];
   // 1: W2^T (the NT dgrad's operand) and the padded h1 (the weight gradient's operand, the dgrad epilogue's aux)
   LatentStageBwdArgs sa{};
   sa.w2 = w2; sa.w2t = w2t; sa.L2 = d.L2; sa.H = hidden; sa.L2p = d.L2p; sa.Hr = d.Hr;
   sa.h1 = h1; sa.hp = hp; sa.b = b; sa.MP = d.MP; sa.Hp = d.Hp;
   sa.tiles_l = d.L2p / 32; sa.tiles = (d.Hr / 32) * sa.tiles_l;
-  if ((rc = hip_rc(e, "k_latent_stage_bwd", profiled(e, PC_LATENT, 0.0, st, [&] {
-         SDRM_LAUNCH(e, k_latent_stage_bwd, dim3((unsigned)sa.tiles + lat_blocks((int64_t)d.MP * (d.Hp / 4))), dim3(256), 0, st, sa);
-         return hipGetLastError();
-       }))))
+  if ((rc = launch_k(e, PC_LATENT, "k_latent_stage_bwd", k_latent_stage_bwd, dim3((unsigned)sa.tiles + blocks_for((int64_t)d.MP * (d.Hp / 4))),
+                     dim3(256), 0, st, sa)))
     return rc;
   // 2: dout2 = [dmu | dlv], padded
   LatentSeedArgs ga{};
   ga.out2 = out2; ga.eps = eps; ga.gz = gz; ga.gkl = gkl; ga.b = b; ga.L = latent; ga.MP = d.MP; ga.L2p = d.L2p; ga.dp = dp;
-  if ((rc = hip_rc(e, "k_latent_seed", profiled(e, PC_LATENT, 0.0, st, [&] {
-         SDRM_LAUNCH(e, k_latent_seed, dim3(lat_blocks((int64_t)d.MP * (d.L2p / 4))), dim3(256), 0, st, ga);
-         return hipGetLastError();
-       }))))
-    return rc;
+  if ((rc = launch_k(e, PC_LATENT, "k_latent_seed", k_latent_seed, dim3(blocks_for((int64_t)d.MP * (d.L2p / 4))), dim3(256), 0, st, ga))) return rc;
   // 3: dW2 = dout2^T h1 into slabs, db2 = column sums of dout2 (the reduction runs over the batch rows: M-contiguous operands)
-  HIP_TRY(e, (gemm_wgrad<XF_NONE>(dp, d.L2p, d.L2p, hp, d.Hp, d.Hp, nullptr, Kb, S, kchunk, slab, dbias, st,
+  HIP_TRY(e, (gemm_wgrad<XF_NONE>(dp, d.L2p, d.L2p, hp, d.Hp, d.Hp, nullptr, d.Kb, sk.S, sk.kchunk, slab, dbias, st,
                                   Prof{e, PC_LATENT, 2.0 * b * d.L2 * hidden}, pick_cfg(e->tune))));
   // 4: dpre = (dout2 W2) (1 - h1^2), bounds-checked into the caller's [b][hidden]
   {
@@ -3123,25 +3143,16 @@ int sdrm_vae_latent_bwd(sdrm_engine* e, const float* h1, const float* out2, cons
   }
   // 5: the slabs and bias sums into the caller's dw2 [2L][hidden] and db2 [2L]
   LatentUnpadArgs ua{};
-  ua.slab = slab; ua.dbias = dbias; ua.S = S; ua.L2 = d.L2; ua.H = hidden; ua.L2p = d.L2p; ua.Hp = d.Hp; ua.dw2 = dw2; ua.db2 = db2;
-  return hip_rc(e, "k_latent_unpad", profiled(e, PC_LATENT, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_latent_unpad, dim3(lat_blocks((int64_t)d.L2 * ((hidden + 3) / 4) + d.L2)), dim3(256), 0, st, ua);
-    return hipGetLastError();
-  }));
+  ua.slab = slab; ua.dbias = dbias; ua.S = sk.S; ua.L2 = d.L2; ua.H = hidden; ua.L2p = d.L2p; ua.Hp = d.Hp; ua.dw2 = dw2; ua.db2 = db2;
+  return launch_k(e, PC_LATENT, "k_latent_unpad", k_latent_unpad, dim3(blocks_for((int64_t)d.L2 * ((hidden + 3) / 4) + d.L2)), dim3(256), 0, st, ua);
 }
 
 // ---------------------------------------------------------------------------------------------
 // The VAE decoder and the multinomial loss head in TRAIN mode (train_SDRM.py:252-254 and :141-142, and their share of :148),
 // csrc/decoder_train.h.  The scratch of sdrm_vae_decode and a loaded frozen encoder are not touched.
-constexpr int DECHEAD_MAX_HIDDEN = 4096, DECHEAD_MAX_LATENT = 4096;
 constexpr int DECHEAD_WGRAD_KCHUNK = 8192;   // most batch rows of one weight-gradient slab (the pre-stage's batches are a few hundred: one slab)
 
 namespace {
-
-int dh_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->dh_buf[slot], &e->dh_cap[slot], n); }
-
-// padded extents: K and N of the GEMMs to 32, operand rows to the largest tile (128), the batch to 64 (the launches' M)
-struct DhDims { int Lp, Lr, Hp, Hr, Ip, Ir, MP, rows64, Kb, kc4, S4, kc3, S3; };
 
 // Batch rows of one slab of the dW4 weight gradient: launch_gemm_cfg refuses a launch whose K chunk (+ 64) times the operand's row
 // stride reaches 2^32 bytes, and g's stride is Ip - so the chunk follows from Ip (8192 up to Ip = 130048, 928 at Ip = 2^20).
@@ -3149,77 +3160,9 @@ int dh_kchunk4(int Ip) {
   const int64_t kc = (((int64_t)1 << 30) - 1) / Ip - 64;   // (kc + 64) * Ip * 4 < 2^32
   return (int)std::min<int64_t>(DECHEAD_WGRAD_KCHUNK, kc / 32 * 32);
 }
-
-DhDims dh_dims(int latent, int hidden, int n_items, int b) {
-  DhDims d;
-  d.Lp = round_up(latent, 32); d.Lr = round_up(d.Lp, 128);
-  d.Hp = round_up(hidden, 32); d.Hr = round_up(d.Hp, 128);
-  d.Ip = round_up(n_items, 32); d.Ir = round_up(d.Ip, 128);
-  d.MP = round_up(b, 128); d.rows64 = round_up(b, BM); d.Kb = round_up(b, 32);
-  d.kc4 = std::min(d.Kb, dh_kchunk4(d.Ip)); d.S4 = (d.Kb + d.kc4 - 1) / d.kc4;
-  d.kc3 = std::min(d.Kb, DECHEAD_WGRAD_KCHUNK); d.S3 = (d.Kb + d.kc3 - 1) / d.kc3;
-  return d;
-}
-
-// gemm_set_grid keeps a launch's tile count inside the exact range of its magic divisions (nb < 2^31, nb x tiles_n < 2^32,
-// nb^2 x slices < 2^32).  A product of the decoder's envelope can leave that range - 2^22 rows, or 2^20 output columns - so these two
-// give the most rows (NT launch, N columns) / output columns (split-K launch, Kin columns, S slices) of ONE launch on tile `cfg`, whole
-// tiles, and the helpers below send a larger product out in bands of that size.  0: not even one tile row fits.
-int dh_nt_band(int cfg, int N) {
-  const uint64_t tn = (uint64_t)((N + kCfgBN[cfg] - 1) / kCfgBN[cfg]);
-  const uint64_t t = std::min<uint64_t>(65535 / tn, ((1ull << 32) - 1) / (tn * tn));
-  return (int)t * kCfgBM[cfg];
-}
-int dh_wgrad_band(int cfg, int Kin, int S) {
-  const uint64_t tn = (uint64_t)((Kin + kCfgBN[cfg] - 1) / kCfgBN[cfg]);
-  uint64_t nb = (uint64_t)std::sqrt((double)((1ull << 32) - 1) / (double)S);   // the most tiles with nb^2 x S < 2^32
-  while (nb * nb * (uint64_t)S >= (1ull << 32)) --nb;
-  while ((nb + 1) * (nb + 1) * (uint64_t)S < (1ull << 32)) ++nb;
-  return (int)std::min<uint64_t>(nb / tn, 1u << 20) * kCfgBM[cfg];
-}
-// launch_gemm_cfg's own test of a tile x K-chunk span, for a launch on tile `cfg`
-bool dh_span_ok(int cfg, bool kcontig, int lda, int ldb, int kchunk) {
-  const uint64_t kc = (uint64_t)std::max(kchunk, 1) + 64;
-  const uint64_t spanA = kcontig ? ((uint64_t)kCfgBM[cfg] * lda + kc) : kc * lda;
-  const uint64_t spanB = kcontig ? ((uint64_t)kCfgBN[cfg] * ldb + kc) : kc * ldb;
-  return spanA * 4 < (1ull << 32) && spanB * 4 < (1ull << 32);
-}
-
-// C[M, N] = epilogue(A[M, K] B[N, K]^T) in row bands; `a` carries B, C, K and the epilogue's operands, rows_valid counts from row 0
-extern "C++" template <int EPI>
-int dh_nt(sdrm_engine* e, const GemmArgs& a, const float* A, int lda, int M, int N, int rows_valid, hipStream_t st, Prof pr, int cfg) {
-  const int band = dh_nt_band(cfg, N);
-  if (band < 1) return fail(e, SDRM_ERR_SHAPE, "decoder head: no tile row of this product fits one launch");
-  for (int m0 = 0; m0 < M; m0 += band) {
-    GemmArgs x = a;
-    const int m = std::min(band, M - m0);
-    x.A = A + (size_t)m0 * lda; x.lda = lda; x.limA = m; x.limB = N;
-    x.C = a.C + (size_t)m0 * a.ldc;
-    if (a.aux) x.aux = a.aux + (size_t)m0 * a.ldaux;
-    x.kchunk = a.K;
-    x.rows_valid = std::max(0, std::min(rows_valid - m0, m));
-    HIP_TRY(e, (launch_gemm<LD_KCONTIG, LD_KCONTIG, XF_NONE, XF_NONE, EPI>(x, m, N, 1, st, pr, cfg)));
-  }
-  return SDRM_OK;
-}
-
-// gemm_wgrad in bands of output columns: slab [S][Nout][Kin] and dbias [S][Nout] keep their whole strides
-int dh_wgrad(sdrm_engine* e, const float* dC, int Nout, const float* Act, int Kin, int Mrows, int S, int kchunk, float* slab, float* dbias,
-             hipStream_t st, Prof pr, int cfg) {
-  const int band = dh_wgrad_band(cfg, Kin, S);
-  if (band < 1) return fail(e, SDRM_ERR_SHAPE, "decoder head: no tile row of this weight gradient fits one launch");
-  for (int n0 = 0; n0 < Nout; n0 += band) {
-    GemmArgs a{};
-    a.A = dC + n0; a.lda = Nout; a.limA = std::min(band, Nout - n0);
-    a.B = Act; a.ldb = Kin; a.limB = Kin;
-    a.C = slab + (size_t)n0 * Kin; a.ldc = Kin;
-    a.K = Mrows; a.kchunk = kchunk;
-    a.slab_stride = (size_t)Nout * Kin;
-    a.dbias = dbias + n0; a.dbias_stride = Nout;
-    HIP_TRY(e, (launch_gemm<LD_MCONTIG, LD_MCONTIG, XF_NONE, XF_NONE, EPI_SLAB>(a, a.limA, Kin, S, st, pr, cfg)));
-  }
-  return SDRM_OK;
-}
+// the split-K plans of dW4 and dW3
+SplitK dh_split4(const VaeDims& d) { return split_k(d.Kb, dh_kchunk4(d.Ip)); }
+SplitK dh_split3(const VaeDims& d) { return split_k(d.Kb, DECHEAD_WGRAD_KCHUNK); }
 
 const char* const kDecheadEnvelope = ": latent outside 1 .. 4096, hidden outside 1 .. 4096, n_items outside 1 .. 2^20, b outside 1 .. 2^22, b x n_items >= 2^40, "
                                      "n_rows < 1, row0 < 0, or rows row0 .. row0 + b - 1 end behind the matrix";
@@ -3229,19 +3172,20 @@ const char* const kDecheadEnvelope = ": latent outside 1 .. 4096, hidden outside
 // The host side of both entry points that needs no device: the envelope, and every test a later launch would make on any tile
 // (`contiguous` != 0: the batch is the feed rows row0 .. row0 + b - 1).
 int sdrm_debug_decoder_nll_args(int latent, int hidden, int n_items, int b, int64_t row0, int64_t n_rows, int contiguous) {
-  if (latent < 1 || latent > DECHEAD_MAX_LATENT || hidden < 1 || hidden > DECHEAD_MAX_HIDDEN || n_items < 1 || n_items > (1 << 20) || b < 1 ||
-      b > (1 << 22) || (int64_t)b * n_items >= ((int64_t)1 << 40) || n_rows < 1 || row0 < 0)
+  if (latent < 1 || latent > VAE_MAX_LATENT || hidden < 1 || hidden > VAE_MAX_HIDDEN || n_items < 1 || n_items > MAX_ITEMS || b < 1 ||
+      b > MAX_BATCH_ROWS || (int64_t)b * n_items >= ((int64_t)1 << 40) || n_rows < 1 || row0 < 0)
     return SDRM_ERR_SHAPE;
   if (contiguous && row0 + b > n_rows) return SDRM_ERR_SHAPE;
-  const DhDims d = dh_dims(latent, hidden, n_items, b);
-  if (d.kc4 < 32) return SDRM_ERR_SHAPE;
+  const VaeDims d = vae_dims(n_items, hidden, latent, b);
+  const SplitK s4 = dh_split4(d), s3 = dh_split3(d);
+  if (s4.kchunk < 32) return SDRM_ERR_SHAPE;
   for (int cfg = 0; cfg < N_TILE_CFGS; ++cfg) {
     // forward: z W3^T, h3 W4^T; backward: g W4 (K = Ip), dpre3 W3 (K = Hp); the two weight gradients
-    if (dh_nt_band(cfg, d.Hp) < 1 || dh_nt_band(cfg, d.Ip) < 1 || dh_nt_band(cfg, d.Lp) < 1) return SDRM_ERR_SHAPE;
-    if (!dh_span_ok(cfg, true, d.Lp, d.Lp, d.Lp) || !dh_span_ok(cfg, true, d.Hp, d.Hp, d.Hp) || !dh_span_ok(cfg, true, d.Ip, d.Ip, d.Ip))
+    if (gemm_nt_band_rows(cfg, d.Hp) < 1 || gemm_nt_band_rows(cfg, d.Ip) < 1 || gemm_nt_band_rows(cfg, d.Lp) < 1) return SDRM_ERR_SHAPE;
+    if (!gemm_span_ok(cfg, true, d.Lp, d.Lp, d.Lp) || !gemm_span_ok(cfg, true, d.Hp, d.Hp, d.Hp) || !gemm_span_ok(cfg, true, d.Ip, d.Ip, d.Ip))
       return SDRM_ERR_SHAPE;
-    if (dh_wgrad_band(cfg, d.Hp, d.S4) < 1 || dh_wgrad_band(cfg, d.Lp, d.S3) < 1) return SDRM_ERR_SHAPE;
-    if (!dh_span_ok(cfg, false, d.Ip, d.Hp, d.kc4) || !dh_span_ok(cfg, false, d.Hp, d.Lp, d.kc3)) return SDRM_ERR_SHAPE;
+    if (gemm_wgrad_band_cols(cfg, d.Hp, s4.S) < 1 || gemm_wgrad_band_cols(cfg, d.Lp, s3.S) < 1) return SDRM_ERR_SHAPE;
+    if (!gemm_span_ok(cfg, false, d.Ip, d.Hp, s4.kchunk) || !gemm_span_ok(cfg, false, d.Hp, d.Lp, s3.kchunk)) return SDRM_ERR_SHAPE;
   }
   return SDRM_OK;
 }
@@ -3251,8 +3195,7 @@ int sdrm_vae_decoder_nll_fwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const 
                              float* lse, float* loss, void* stream) {
   const char* who = "sdrm_vae_decoder_nll_fwd";
   if (!e) return SDRM_ERR_ARG;
-  if (!dec || !dec->w1 || !dec->b1 || !dec->w2 || !dec->b2 || !z || !indptr || !indices || !h3 || !logits || !lse || !loss)
-    return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (!dec_tensors(dec) || !z || !indptr || !indices || !h3 || !logits || !lse || !loss) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
   if ((uintptr_t)logits & 15u) return fail(e, SDRM_ERR_ARG, std::string(who) + ": logits must be 16-byte aligned");
   const int L = dec->latent, H = dec->hidden, I = dec->n_items;
   if (int rc = sdrm_debug_decoder_nll_args(L, H, I, b, row0, n_rows, rows == nullptr)) return fail(e, rc, std::string(who) + kDecheadEnvelope);
@@ -3261,24 +3204,13 @@ int sdrm_vae_decoder_nll_fwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const 
   na.logits = logits;
   hipStream_t st = (hipStream_t)stream;
   if (int jr = chains_join(e, st)) return jr;
-  const DhDims d = dh_dims(L, H, I, b);
+  const VaeDims d = vae_dims(I, H, L, b);
+  float *zp, *w3p, *b3p, *h3p, *w4p, *b4p;
   int rc;
-  if ((rc = dh_grow(e, sdrm_engine::DH_Z, (size_t)d.MP * d.Lp)) || (rc = dh_grow(e, sdrm_engine::DH_W3, (size_t)d.Hr * d.Lp)) ||
-      (rc = dh_grow(e, sdrm_engine::DH_B3, d.Hr)) || (rc = dh_grow(e, sdrm_engine::DH_H3, (size_t)d.MP * d.Hp)) ||
-      (rc = dh_grow(e, sdrm_engine::DH_W4, (size_t)d.Ir * d.Hp)) || (rc = dh_grow(e, sdrm_engine::DH_B4, d.Ir)))
+  if ((rc = scratch(e, SCR_DH_Z, (size_t)d.MP * d.Lp, &zp)) || (rc = scratch(e, SCR_DH_W3, (size_t)d.Hr * d.Lp, &w3p)) ||
+      (rc = scratch(e, SCR_DH_B3, d.Hr, &b3p)) || (rc = scratch(e, SCR_DH_H3, (size_t)d.MP * d.Hp, &h3p)) ||
+      (rc = scratch(e, SCR_DH_W4, (size_t)d.Ir * d.Hp, &w4p)) || (rc = scratch(e, SCR_DH_B4, d.Ir, &b4p)))
     return rc;
-  float* zp = e->dh_buf[sdrm_engine::DH_Z];
-  float* w3p = e->dh_buf[sdrm_engine::DH_W3];
-  float* b3p = e->dh_buf[sdrm_engine::DH_B3];
-  float* h3p = e->dh_buf[sdrm_engine::DH_H3];
-  float* w4p = e->dh_buf[sdrm_engine::DH_W4];
-  float* b4p = e->dh_buf[sdrm_engine::DH_B4];
-  const auto pad_launch = [&](const PadList& pad) {
-    return hip_rc(e, "k_pad2d", profiled(e, PC_DECODER, 0.0, st, [&] {
-      SDRM_LAUNCH(e, k_pad2d, dim3((unsigned)std::min<int64_t>(2048, (pad.most + 255) / 256), (unsigned)pad.k), dim3(256), 0, st, pad.sg);
-      return hipGetLastError();
-    }));
-  };
   // 1: z and the four tensors padded (the weights change with every optimiser step)
   {
     PadList pad;
@@ -3287,7 +3219,7 @@ int sdrm_vae_decoder_nll_fwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const 
     pad.add(dec->b1, 1, H, b3p, 1, d.Hr);
     pad.add(dec->w2, I, H, w4p, d.Ir, d.Hp);
     pad.add(dec->b2, 1, I, b4p, 1, d.Ir);
-    if ((rc = pad_launch(pad))) return rc;
+    if ((rc = pad.launch(e, PC_DECODER, st))) return rc;
   }
   const int cfg = choose_cfg(e->tune, d.rows64, e->tune.nt32_max_rows);
   // 2: h3 = tanh(z W3^T + b3) into the padded [MP][Hp], the second GEMM's A operand (the launch decode_launches makes; columns behind
@@ -3295,34 +3227,23 @@ int sdrm_vae_decoder_nll_fwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const 
   {
     GemmArgs a{};
     a.B = w3p; a.ldb = d.Lp; a.C = h3p; a.ldc = d.Hp; a.K = d.Lp; a.bias = b3p;
-    if ((rc = dh_nt<EPI_BIAS_TANH>(e, a, zp, d.Lp, d.rows64, d.Hp, b, st, Prof{e, PC_DECODER, 2.0 * b * (double)H * L}, cfg))) return rc;
+    if ((rc = gemm_nt_banded<EPI_BIAS_TANH>(e, a, zp, d.Lp, d.rows64, d.Hp, b, st, Prof{e, PC_DECODER, 2.0 * b * (double)H * L}, cfg))) return rc;
   }
   // 3: its b rows and H columns into the caller's h3 [b][H]
   {
     const DecH3Args ha{h3p, h3, b, H, d.Hp};
-    if ((rc = hip_rc(e, "k_dechead_h3", profiled(e, PC_DECODER, 0.0, st, [&] {
-           SDRM_LAUNCH(e, k_dechead_h3, dim3(lat_blocks((int64_t)b * ((H + 3) / 4))), dim3(256), 0, st, ha);
-           return hipGetLastError();
-         }))))
-      return rc;
+    if ((rc = launch_k(e, PC_DECODER, "k_dechead_h3", k_dechead_h3, dim3(blocks_for((int64_t)b * ((H + 3) / 4))), dim3(256), 0, st, ha))) return rc;
   }
   // 4: logits = h3 W4^T + b4, bounds-checked into the caller's [b][I]
   {
     GemmArgs a{};
     a.B = w4p; a.ldb = d.Hp; a.C = logits; a.ldc = I; a.K = d.Hp; a.bias = b4p; a.cols_valid = I;
-    if ((rc = dh_nt<EPI_BIAS_G>(e, a, h3p, d.Hp, d.rows64, d.Ip, b, st, Prof{e, PC_DECODER, 2.0 * b * (double)I * H}, cfg))) return rc;
+    if ((rc = gemm_nt_banded<EPI_BIAS_G>(e, a, h3p, d.Hp, d.rows64, d.Ip, b, st, Prof{e, PC_DECODER, 2.0 * b * (double)I * H}, cfg))) return rc;
   }
   // 5: lse and the loss terms over exactly I columns of the caller's logits (csrc/nll.h); 6: their sum
   const int parts = std::min(b, NLL_PARTS);
-  if ((rc = hip_rc(e, "k_nll_rows", profiled(e, PC_DECODER, 0.0, st, [&] {
-         SDRM_LAUNCH(e, k_nll_rows, dim3((unsigned)parts), dim3(256), 0, st, na, lse, e->nll_part);
-         return hipGetLastError();
-       }))))
-    return rc;
-  return hip_rc(e, "k_nll_sum", profiled(e, PC_DECODER, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_nll_sum, dim3(1), dim3(256), 0, st, (const double*)e->nll_part, parts, b, loss);
-    return hipGetLastError();
-  }));
+  if ((rc = launch_k(e, PC_DECODER, "k_nll_rows", k_nll_rows, dim3((unsigned)parts), dim3(256), 0, st, na, lse, e->nll_part))) return rc;
+  return launch_k(e, PC_DECODER, "k_nll_sum", k_nll_sum, dim3(1), dim3(256), 0, st, e->nll_part, parts, b, loss);
 }
 
 int sdrm_vae_decoder_nll_bwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const float* z, const float* h3, const float* logits, const float* lse,
@@ -3330,7 +3251,7 @@ int sdrm_vae_decoder_nll_bwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const 
                              int64_t row0, int b, const float* scale, float* dz, float* dw3, float* db3, float* dw4, float* db4, void* stream) {
   const char* who = "sdrm_vae_decoder_nll_bwd";
   if (!e) return SDRM_ERR_ARG;
-  if (!dec || !dec->w1 || !dec->w2 || !z || !h3 || !logits || !lse || !indptr || !indices || !dw3 || !db3 || !dw4 || !db4)
+  if (!dec_tensors(dec, false) || !z || !h3 || !logits || !lse || !indptr || !indices || !dw3 || !db3 || !dw4 || !db4)
     return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
   if ((uintptr_t)logits & 15u) return fail(e, SDRM_ERR_ARG, std::string(who) + ": logits must be 16-byte aligned");
   const int L = dec->latent, H = dec->hidden, I = dec->n_items;
@@ -3339,26 +3260,17 @@ int sdrm_vae_decoder_nll_bwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const 
   if (int rc = csr_batch(e, who, indptr, indices, data, n_rows, rows, row0, b, I, &ga.csr)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (int jr = chains_join(e, st)) return jr;
-  const DhDims d = dh_dims(L, H, I, b);
+  const VaeDims d = vae_dims(I, H, L, b);
+  const SplitK s4 = dh_split4(d), s3 = dh_split3(d);
+  float *zp, *h3p, *w4t, *w3t, *zb, *g, *dp3, *slab4, *dbs4, *slab3, *dbs3;
   int rc;
-  if ((rc = dh_grow(e, sdrm_engine::DH_Z, (size_t)d.MP * d.Lp)) || (rc = dh_grow(e, sdrm_engine::DH_H3, (size_t)d.MP * d.Hp)) ||
-      (rc = dh_grow(e, sdrm_engine::DH_W4T, (size_t)d.Hr * d.Ip)) || (rc = dh_grow(e, sdrm_engine::DH_W3T, (size_t)d.Lr * d.Hp)) ||
-      (rc = dh_grow(e, sdrm_engine::DH_ZB, d.Lr)) || (rc = dh_grow(e, sdrm_engine::DH_G, (size_t)d.MP * d.Ip)) ||
-      (rc = dh_grow(e, sdrm_engine::DH_DP3, (size_t)d.MP * d.Hp)) || (rc = dh_grow(e, sdrm_engine::DH_SLAB4, (size_t)d.S4 * d.Ip * d.Hp)) ||
-      (rc = dh_grow(e, sdrm_engine::DH_DB4, (size_t)d.S4 * d.Ip)) || (rc = dh_grow(e, sdrm_engine::DH_SLAB3, (size_t)d.S3 * d.Hp * d.Lp)) ||
-      (rc = dh_grow(e, sdrm_engine::DH_DB3, (size_t)d.S3 * d.Hp)))
+  if ((rc = scratch(e, SCR_DH_Z, (size_t)d.MP * d.Lp, &zp)) || (rc = scratch(e, SCR_DH_H3, (size_t)d.MP * d.Hp, &h3p)) ||
+      (rc = scratch(e, SCR_DH_W4T, (size_t)d.Hr * d.Ip, &w4t)) || (rc = scratch(e, SCR_DH_W3T, (size_t)d.Lr * d.Hp, &w3t)) ||
+      (rc = scratch(e, SCR_DH_ZB, d.Lr, &zb)) || (rc = scratch(e, SCR_DH_G, (size_t)d.MP * d.Ip, &g)) ||
+      (rc = scratch(e, SCR_DH_DP3, (size_t)d.MP * d.Hp, &dp3)) || (rc = scratch(e, SCR_DH_SLAB4, (size_t)s4.S * d.Ip * d.Hp, &slab4)) ||
+      (rc = scratch(e, SCR_DH_DB4, (size_t)s4.S * d.Ip, &dbs4)) || (rc = scratch(e, SCR_DH_SLAB3, (size_t)s3.S * d.Hp * d.Lp, &slab3)) ||
+      (rc = scratch(e, SCR_DH_DB3, (size_t)s3.S * d.Hp, &dbs3)))
     return rc;
-  float* zp = e->dh_buf[sdrm_engine::DH_Z];
-  float* h3p = e->dh_buf[sdrm_engine::DH_H3];
-  float* w4t = e->dh_buf[sdrm_engine::DH_W4T];
-  float* w3t = e->dh_buf[sdrm_engine::DH_W3T];
-  float* zb = e->dh_buf[sdrm_engine::DH_ZB];
-  float* g = e->dh_buf[sdrm_engine::DH_G];
-  float* dp3 = e->dh_buf[sdrm_engine::DH_DP3];
-  float* slab4 = e->dh_buf[sdrm_engine::DH_SLAB4];
-  float* dbs4 = e->dh_buf[sdrm_engine::DH_DB4];
-  float* slab3 = e->dh_buf[sdrm_engine::DH_SLAB3];
-  float* dbs3 = e->dh_buf[sdrm_engine::DH_DB3];
   // 1: W4^T and W3^T (the NT dgrads' operands), h3 and z padded (the weight gradients' operands), the last dgrad's zero bias
   DecStageBwdArgs sa{};
   sa.t4 = DecTranspose{dec->w2, w4t, I, H, d.Ip, d.Ip / 32};
@@ -3367,44 +3279,37 @@ int sdrm_vae_decoder_nll_bwd(sdrm_engine* e, const sdrm_vae_decoder* dec, const 
   sa.h3 = h3; sa.h3p = h3p; sa.b = b; sa.H = H; sa.MP = d.MP; sa.Hp = d.Hp;
   sa.z = z; sa.zp = zp; sa.L = L; sa.Lp = d.Lp;
   sa.zb = zb; sa.Lr = d.Lr;
-  if ((rc = hip_rc(e, "k_dechead_stage_bwd", profiled(e, PC_DECODER, 0.0, st, [&] {
-         SDRM_LAUNCH(e, k_dechead_stage_bwd, dim3((unsigned)sa.tiles + lat_blocks((int64_t)d.MP * ((d.Hp + d.Lp) / 4) + d.Lr / 4)), dim3(256), 0, st, sa);
-         return hipGetLastError();
-       }))))
+  if ((rc = launch_k(e, PC_DECODER, "k_dechead_stage_bwd", k_dechead_stage_bwd,
+                     dim3((unsigned)sa.tiles + blocks_for((int64_t)d.MP * ((d.Hp + d.Lp) / 4) + d.Lr / 4)), dim3(256), 0, st, sa)))
     return rc;
   // 2: g = scale (softmax s_r - X) / b into [MP][Ip], zero behind b rows / I columns
   ga.logits = logits; ga.lse = lse; ga.scale = scale; ga.g = g; ga.MP = d.MP; ga.Ip = d.Ip;
-  if ((rc = hip_rc(e, "k_dechead_grad", profiled(e, PC_DECODER, 0.0, st, [&] {
-         SDRM_LAUNCH(e, k_dechead_grad, dim3((unsigned)std::min(d.MP, 1 << 16)), dim3(256), 0, st, ga);
-         return hipGetLastError();
-       }))))
-    return rc;
+  if ((rc = launch_k(e, PC_DECODER, "k_dechead_grad", k_dechead_grad, dim3((unsigned)std::min(d.MP, 1 << 16)), dim3(256), 0, st, ga))) return rc;
   const int cfg_w = pick_cfg(e->tune), cfg = choose_cfg(e->tune, d.rows64, e->tune.nt32_max_rows);
   // 3: dW4 = g^T h3 into slabs, db4 = column sums of g (the reduction runs over the batch rows: M-contiguous operands)
-  if ((rc = dh_wgrad(e, g, d.Ip, h3p, d.Hp, d.Kb, d.S4, d.kc4, slab4, dbs4, st, Prof{e, PC_DECODER, 2.0 * b * (double)I * H}, cfg_w))) return rc;
+  if ((rc = gemm_wgrad_banded(e, g, d.Ip, h3p, d.Hp, d.Kb, s4.S, s4.kchunk, slab4, dbs4, st, Prof{e, PC_DECODER, 2.0 * b * (double)I * H}, cfg_w)))
+    return rc;
   // 4: dpre3 = (g W4)(1 - h3^2) into [MP][Hp]: all rows64 rows and Hp columns are stored - behind b rows g is zero, behind H columns
   //    W4^T is: the products are zeros, written by this call
   {
     GemmArgs a{};
     a.B = w4t; a.ldb = d.Ip; a.C = dp3; a.ldc = d.Hp; a.K = d.Ip; a.aux = h3p; a.ldaux = d.Hp; a.cols_valid = d.Hp;
-    if ((rc = dh_nt<EPI_DTANH_G>(e, a, g, d.Ip, d.rows64, d.Hp, d.rows64, st, Prof{e, PC_DECODER, 2.0 * b * (double)I * H}, cfg))) return rc;
+    if ((rc = gemm_nt_banded<EPI_DTANH_G>(e, a, g, d.Ip, d.rows64, d.Hp, d.rows64, st, Prof{e, PC_DECODER, 2.0 * b * (double)I * H}, cfg))) return rc;
   }
   // 5: dW3 = dpre3^T z into slabs, db3 = column sums of dpre3
-  if ((rc = dh_wgrad(e, dp3, d.Hp, zp, d.Lp, d.Kb, d.S3, d.kc3, slab3, dbs3, st, Prof{e, PC_DECODER, 2.0 * b * (double)H * L}, cfg_w))) return rc;
+  if ((rc = gemm_wgrad_banded(e, dp3, d.Hp, zp, d.Lp, d.Kb, s3.S, s3.kchunk, slab3, dbs3, st, Prof{e, PC_DECODER, 2.0 * b * (double)H * L}, cfg_w)))
+    return rc;
   // 6: dz = dpre3 W3, bounds-checked into the caller's [b][L] (the bias epilogue on a bias of zeros)
   if (dz) {
     GemmArgs a{};
     a.B = w3t; a.ldb = d.Hp; a.C = dz; a.ldc = L; a.K = d.Hp; a.bias = zb; a.cols_valid = L;
-    if ((rc = dh_nt<EPI_BIAS_G>(e, a, dp3, d.Hp, d.rows64, d.Lp, b, st, Prof{e, PC_DECODER, 2.0 * b * (double)H * L}, cfg))) return rc;
+    if ((rc = gemm_nt_banded<EPI_BIAS_G>(e, a, dp3, d.Hp, d.rows64, d.Lp, b, st, Prof{e, PC_DECODER, 2.0 * b * (double)H * L}, cfg))) return rc;
   }
   // 7: the slabs and bias sums into the caller's dw4 [I][H], db4 [I], dw3 [H][L], db3 [H]
   DecUnpadArgs ua{};
-  ua.seg[0] = DecUnpadSeg{slab4, dbs4, d.S4, I, H, d.Ip, d.Hp, dw4, db4};
-  ua.seg[1] = DecUnpadSeg{slab3, dbs3, d.S3, H, L, d.Hp, d.Lp, dw3, db3};
-  return hip_rc(e, "k_dechead_unpad", profiled(e, PC_DECODER, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_dechead_unpad, dim3(lat_blocks((int64_t)I * ((H + 3) / 4) + I), 2), dim3(256), 0, st, ua);
-    return hipGetLastError();
-  }));
+  ua.seg[0] = DecUnpadSeg{slab4, dbs4, s4.S, I, H, d.Ip, d.Hp, dw4, db4};
+  ua.seg[1] = DecUnpadSeg{slab3, dbs3, s3.S, H, L, d.Hp, d.Lp, dw3, db3};
+  return launch_k(e, PC_DECODER, "k_dechead_unpad", k_dechead_unpad, dim3(blocks_for((int64_t)I * ((H + 3) / 4) + I), 2), dim3(256), 0, st, ua);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3482,11 +3387,7 @@ int sdrm_vae_adam_step(sdrm_engine* e, const sdrm_vae_adam_tensor* t, int n_tens
       c += (unsigned)((s.n + VADAM_CHUNK - 1) / VADAM_CHUNK);
     }
     a.chunk0 = chunk0;
-    if (int rc = hip_rc(e, "k_vae_adam", profiled(e, PC_VAE_ADAM, 0.0, st, [&] {
-          SDRM_LAUNCH(e, k_vae_adam, dim3(c), dim3(256), 0, st, tab, a);
-          return hipGetLastError();
-        })))
-      return rc;
+    if (int rc = launch_k(e, PC_VAE_ADAM, "k_vae_adam", k_vae_adam, dim3(c), dim3(256), 0, st, tab, a)) return rc;
     chunk0 += c;
   }
   return SDRM_OK;
@@ -3498,11 +3399,8 @@ int sdrm_vae_loss_slot(sdrm_engine* e, const float* neg_ll, const float* kl, flo
   if (!e) return SDRM_ERR_ARG;
   if (!neg_ll || !kl || !out) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
   if (l2_partials && n_partials < 1) return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": l2_partials given with n_partials < 1");
-  hipStream_t st = (hipStream_t)stream;
-  return hip_rc(e, "k_vae_loss_slot", profiled(e, PC_VAE_ADAM, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_vae_loss_slot, dim3(1), dim3(256), 0, st, neg_ll, kl, anneal, l2_partials, n_partials, weight_decay, out);
-    return hipGetLastError();
-  }));
+  return launch_k(e, PC_VAE_ADAM, "k_vae_loss_slot", k_vae_loss_slot, dim3(1), dim3(256), 0, (hipStream_t)stream, neg_ll, kl, anneal, l2_partials,
+                  n_partials, weight_decay, out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3518,7 +3416,7 @@ int nll_args(sdrm_engine* e, const char* who, const float* logits, const int64_t
   if (!logits) return fail(e, SDRM_ERR_ARG, w + ": null pointer");
   if ((uintptr_t)logits & 15u) return fail(e, SDRM_ERR_ARG, w + ": logits must be 16-byte aligned");
   if (int rc = csr_batch(e, who, indptr, indices, data, n_rows, rows, row0, b, n_items, &a->csr)) return rc;
-  if (n_items > (1 << 20) || (int64_t)b * n_items >= ((int64_t)1 << 40))
+  if (n_items > MAX_ITEMS || (int64_t)b * n_items >= ((int64_t)1 << 40))
     return fail(e, SDRM_ERR_SHAPE, w + ": n_items outside 1 .. 2^20 or b x n_items >= 2^40");
   a->logits = logits;
   return SDRM_OK;
@@ -3534,14 +3432,8 @@ int sdrm_multinomial_nll_csr(sdrm_engine* e, const float* logits, const int64_t*
   if (int rc = nll_args(e, "sdrm_multinomial_nll_csr", logits, indptr, indices, data, n_rows, rows, row0, b, n_items, &a)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int parts = std::min(b, NLL_PARTS);
-  if (int rc = hip_rc(e, "k_nll_rows", profiled(e, PC_NLL, 0.0, st, [&] {
-        SDRM_LAUNCH(e, k_nll_rows, dim3((unsigned)parts), dim3(256), 0, st, a, lse, e->nll_part);
-        return hipGetLastError();
-      })))
-    return rc;
-  SDRM_LAUNCH(e, k_nll_sum, dim3(1), dim3(256), 0, st, (const double*)e->nll_part, parts, b, loss);
-  HIP_TRY(e, hipGetLastError());
-  return SDRM_OK;
+  if (int rc = launch_k(e, PC_NLL, "k_nll_rows", k_nll_rows, dim3((unsigned)parts), dim3(256), 0, st, a, lse, e->nll_part)) return rc;
+  return launch_k(e, PC_NONE, "k_nll_sum", k_nll_sum, dim3(1), dim3(256), 0, st, e->nll_part, parts, b, loss);
 }
 
 int sdrm_multinomial_nll_csr_grad(sdrm_engine* e, const float* logits, const float* lse, const int64_t* indptr, const int32_t* indices,
@@ -3555,22 +3447,18 @@ int sdrm_multinomial_nll_csr_grad(sdrm_engine* e, const float* logits, const flo
   const uintptr_t lo = (uintptr_t)logits, go = (uintptr_t)grad, bytes = (uintptr_t)b * (uintptr_t)n_items * sizeof(float);
   if (lo != go && lo < go + bytes && go < lo + bytes)
     return fail(e, SDRM_ERR_ARG, "sdrm_multinomial_nll_csr_grad: grad overlaps logits (only grad == logits may alias)");
-  hipStream_t st = (hipStream_t)stream;
-  return hip_rc(e, "k_nll_grad", profiled(e, PC_NLL, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_nll_grad, dim3((unsigned)std::min(b, NLL_GRAD_BLOCKS)), dim3(256), 0, st, a, lse, scale, grad);
-    return hipGetLastError();
-  }));
+  return launch_k(e, PC_NLL, "k_nll_grad", k_nll_grad, dim3((unsigned)std::min(b, NLL_GRAD_BLOCKS)), dim3(256), 0, (hipStream_t)stream, a, lse, scale,
+                  grad);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Input layer of the VAE encoder in train mode (train_SDRM.py:242-244, first Linear; its weight's share of :148), csrc/input_layer.h.
-constexpr int IL_MAX_HIDDEN = 4096;
 
 // The host side of both entry points that needs no device: the envelope, and the dropout threshold and scale of a float p_drop.
 int sdrm_debug_input_layer_args(int n_items, int hidden, int64_t n_rows, int64_t first, int b, int contiguous, float p_drop,
                                 uint32_t* thr, float* scale) {
-  if (n_items < 1 || n_items > (1 << 20) || hidden < 1 || hidden > IL_MAX_HIDDEN || n_rows < 1 || n_rows > (int64_t)INT32_MAX ||
-      b < 1 || b > (1 << 22) || first < 0)
+  if (n_items < 1 || n_items > MAX_ITEMS || hidden < 1 || hidden > VAE_MAX_HIDDEN || n_rows < 1 || n_rows > (int64_t)INT32_MAX ||
+      b < 1 || b > MAX_BATCH_ROWS || first < 0)
     return SDRM_ERR_SHAPE;
   if (contiguous && first + b > n_rows) return SDRM_ERR_SHAPE;
   if (!(p_drop >= 0.f && p_drop < 1.f)) return SDRM_ERR_SHAPE;   // (a NaN fails both compares)
@@ -3582,19 +3470,16 @@ int sdrm_debug_input_layer_args(int n_items, int hidden, int64_t n_rows, int64_t
 
 namespace {
 
-int il_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->il_buf[slot], &e->il_cap[slot], n); }
-
 DropArgs drop_args(uint64_t seed, uint32_t step, uint32_t thr) {
   DropArgs d;
   d.k0 = (uint32_t)seed; d.k1 = (uint32_t)(seed >> 32); d.step = step; d.thr = thr;
   return d;
 }
 
-hipError_t launch_input_wgrad(sdrm_engine* e, void (*kernel)(const InputWgradArgs), dim3 grid, size_t lds, const InputWgradArgs& a, hipStream_t st) {
+int launch_input_wgrad(sdrm_engine* e, void (*kernel)(const InputWgradArgs), dim3 grid, size_t lds, const InputWgradArgs& a, hipStream_t st) {
   // the kernel's static LDS (the chunk, 2 KB) comes on top of the tile
-  if (const hipError_t rc = allow_full_lds(reinterpret_cast<const void*>(kernel), LDS_MAX_BYTES - 4096)) return rc;
-  SDRM_LAUNCH(e, kernel, grid, dim3(256), lds, st, a);
-  return hipGetLastError();
+  if (const hipError_t rc = allow_full_lds(reinterpret_cast<const void*>(kernel), LDS_MAX_BYTES - 4096)) return hip_rc(e, "k_input_wgrad", rc);
+  return launch_k(e, PC_INPUT_LAYER, "k_input_wgrad", kernel, grid, dim3(256), lds, st, a);
 }
 
 }  // namespace
@@ -3613,17 +3498,14 @@ int sdrm_vae_input_layer_fwd(sdrm_engine* e, const float* w1, const float* b1, i
                        "1 .. 2^22, row0 < 0, rows row0 .. row0 + b - 1 end behind the matrix, or p_drop outside [0, 1)");
   hipStream_t st = (hipStream_t)stream;
   if (int jr = chains_join(e, st)) return jr;
-  const int Hq = round_up(hidden, 4), q = Hq / 4;
-  if (int rc = il_grow(e, sdrm_engine::IL_W1T, (size_t)n_items * Hq)) return rc;
+  const int Hq = vae_dims(n_items, hidden, 0, b).Hq;
+  float* w1t;
+  if (int rc = scratch(e, SCR_IL_W1T, (size_t)n_items * Hq, &w1t)) return rc;
   // W1 changes with every optimiser step: the transposed copy is this call's
-  SDRM_LAUNCH(e, k_encode_w1t, dim3((unsigned)((n_items + 31) / 32), (unsigned)((Hq + 31) / 32)), dim3(256), 0, st, w1, hidden, n_items,
-              e->il_buf[sdrm_engine::IL_W1T], Hq);
-  HIP_TRY(e, hipGetLastError());
-  a.w1t = e->il_buf[sdrm_engine::IL_W1T]; a.b1 = b1; a.hidden = hidden; a.Hq = Hq;
+  if (int rc = launch_w1t(e, PC_NONE, w1, hidden, n_items, w1t, Hq, st)) return rc;
+  a.w1t = w1t; a.b1 = b1; a.hidden = hidden; a.Hq = Hq;
   a.drop = drop_args(seed, step, thr); a.scale = scale; a.pre = pre; a.rowscale = rowscale;
-  return hip_rc(e, "k_input_fwd", profiled(e, PC_INPUT_LAYER, 0.0, st, [&] {
-    return launch_gather_rows(e, q, a, st, [](auto tpr, auto nv, auto u) { return k_input_fwd<VAL(tpr), VAL(nv), VAL(u)>; });
-  }));
+  return launch_gather_rows(e, PC_INPUT_LAYER, "k_input_fwd", Hq / 4, a, st, [](auto tpr, auto nv, auto u) { return k_input_fwd<VAL(tpr), VAL(nv), VAL(u)>; });
 }
 
 int sdrm_vae_input_layer_wgrad(sdrm_engine* e, const float* dpre, const float* rowscale, int hidden, const int64_t* colptr,
@@ -3638,26 +3520,25 @@ int sdrm_vae_input_layer_wgrad(sdrm_engine* e, const float* dpre, const float* r
                        "1 .. 2^22, lo < 0, places lo .. lo + b - 1 end behind the feed, or p_drop outside [0, 1)");
   hipStream_t st = (hipStream_t)stream;
   if (int jr = chains_join(e, st)) return jr;
-  const int Hq = round_up(hidden, 4), q = Hq / 4;
+  const int Hq = vae_dims(n_items, hidden, 0, b).Hq, q = Hq / 4;
   InputWgradArgs a{};
   a.dpre = dpre; a.ldd = hidden;
   if ((hidden & 3) || ((uintptr_t)dpre & 15u)) {   // rows off the 16-byte grid: a padded copy [b][Hq]
-    if (int rc = il_grow(e, sdrm_engine::IL_DPRE, (size_t)b * Hq)) return rc;
+    float* dp;
+    if (int rc = scratch(e, SCR_IL_DPRE, (size_t)b * Hq, &dp)) return rc;
     PadList pad;
-    pad.add(dpre, b, hidden, e->il_buf[sdrm_engine::IL_DPRE], b, Hq);
-    if (int rc = pad.launch(e, st)) return rc;
-    a.dpre = e->il_buf[sdrm_engine::IL_DPRE]; a.ldd = Hq;
+    pad.add(dpre, b, hidden, dp, b, Hq);
+    if (int rc = pad.launch(e, PC_NONE, st)) return rc;
+    a.dpre = dp; a.ldd = Hq;
   }
   a.rowscale = rowscale; a.colptr = colptr; a.rowidx = rowidx; a.data = data; a.pos = pos; a.lo = lo; a.n_rows = n_rows; a.b = b;
   a.n_items = n_items; a.hidden = hidden; a.Hq = Hq; a.flag = e->feed_flag; a.drop = drop_args(seed, step, thr); a.dw1 = dw1;
   const unsigned tiles = (unsigned)((n_items + IL_CT - 1) / IL_CT);
   // the LDS tile [16][ld]: ld = the pass's share of Hq + 4 floats (<= 131 KB at 2048 of them)
   const auto lds = [&](int span) { return (size_t)IL_CT * (size_t)(std::min(Hq, span) + 4) * sizeof(float); };
-  return hip_rc(e, "k_input_wgrad", profiled(e, PC_INPUT_LAYER, 0.0, st, [&] {
-    if (q <= 64) return launch_input_wgrad(e, k_input_wgrad<64, 1, 4>, dim3(tiles, 1), lds(256), a, st);      // one wave per column
-    if (q <= 256) return launch_input_wgrad(e, k_input_wgrad<256, 1, 4>, dim3(tiles, 1), lds(1024), a, st);   // the work-group per column
-    return launch_input_wgrad(e, k_input_wgrad<256, 2, 2>, dim3(tiles, (unsigned)((Hq + 2047) / 2048)), lds(2048), a, st);
-  }));
+  if (q <= 64) return launch_input_wgrad(e, k_input_wgrad<64, 1, 4>, dim3(tiles, 1), lds(256), a, st);      // one wave per column
+  if (q <= 256) return launch_input_wgrad(e, k_input_wgrad<256, 1, 4>, dim3(tiles, 1), lds(1024), a, st);   // the work-group per column
+  return launch_input_wgrad(e, k_input_wgrad<256, 2, 2>, dim3(tiles, (unsigned)((Hq + 2047) / 2048)), lds(2048), a, st);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3665,7 +3546,7 @@ int sdrm_vae_input_layer_wgrad(sdrm_engine* e, const float* dpre, const float* r
 
 // The host side that needs no device: the envelope, and m_u of a row of n_u entries.
 int sdrm_debug_holdout_args(int n_items, int64_t n_rows, int64_t nnz, double test_prop, int64_t n_u, int64_t* m_out) {
-  if (n_items < 1 || n_items > (1 << 20) || n_rows < 1 || n_rows > (int64_t)INT32_MAX || nnz < 0 || nnz >= ((int64_t)1 << 40))
+  if (n_items < 1 || n_items > MAX_ITEMS || n_rows < 1 || n_rows > (int64_t)INT32_MAX || nnz < 0 || nnz >= ((int64_t)1 << 40))
     return SDRM_ERR_SHAPE;
   if (!(test_prop > 0.0 && test_prop < 1.0)) return SDRM_ERR_SHAPE;   // (a NaN fails both compares)
   if (m_out) *m_out = holdout_m(test_prop, n_u);
@@ -3681,10 +3562,10 @@ int sdrm_holdout_split(sdrm_engine* e, const int64_t* indptr, const int32_t* ind
   if (int rc = sdrm_debug_holdout_args(n_items, n_rows, nnz, test_prop, 0, nullptr))
     return fail(e, rc, "sdrm_holdout_split: n_items outside 1 .. 2^20, n_rows outside 1 .. 2^31 - 1, nnz outside 0 .. 2^40 - 1 or test_prop outside (0, 1)");
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = grow(e, &e->hold_cnt, &e->hold_cap, 2 * (size_t)n_rows)) return rc;
   HoldoutArgs a{};
+  if (int rc = scratch(e, SCR_HOLD_CNT, 2 * (size_t)n_rows, &a.cnt)) return rc;
   a.indptr = indptr; a.indices = indices; a.n_rows = n_rows; a.nnz = nnz; a.n_items = n_items; a.test_prop = test_prop;
-  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.draw = draw; a.cnt = e->hold_cnt;
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.draw = draw;
   a.train_indptr = train_indptr; a.train_indices = train_indices; a.held_indptr = held_indptr; a.held_indices = held_indices;
   a.flag = e->feed_flag;
   const unsigned waves = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 1 << 20);   // the kernels stride over the rows behind their grids
@@ -3708,8 +3589,7 @@ int sdrm_equal_sparsity(sdrm_engine* e, const float* x, int64_t n, double q, uin
   int64_t r0, r1;
   float gamma;
   quantile_ranks(n, q, r0, r1, gamma);
-  SDRM_LAUNCH(e, k_select_init, dim3(8), dim3(256), 0, st, e->sel, r0, r1);
-  HIP_TRY(e, hipGetLastError());
+  if (int rc = launch_k(e, PC_NONE, "k_select_init", k_select_init, dim3(8), dim3(256), 0, st, e->sel, r0, r1)) return rc;
   return select_and_binarize(e, x, n, gamma, out, threshold, st);
 }
 
@@ -3732,7 +3612,8 @@ int sdrm_equal_sparsity_csr_begin(sdrm_engine* e, const float* x, int64_t n_rows
   e->csr.active = false;   // a second begin replaces a pending one
   const size_t words = (size_t)(n_rows * wpr), off_ptr = words, off_cnt = off_ptr + (size_t)n_rows + 1;
   const size_t need = off_cnt + ((size_t)n_rows + 1) / 2;
-  if (int rc = grow(e, &e->csr_ws, &e->csr_ws_cap, need)) return rc;
+  uint64_t* ws;
+  if (int rc = scratch(e, SCR_CSR_WS, need, &ws)) return rc;
   if (!e->csr_nnz_host) {
     HIP_TRY(e, hipHostMalloc((void**)&e->csr_nnz_host, sizeof(int64_t), hipHostMallocMapped));
     HIP_TRY(e, hipHostGetDevicePointer((void**)&e->csr_nnz_dev, e->csr_nnz_host, 0));
@@ -3741,19 +3622,17 @@ int sdrm_equal_sparsity_csr_begin(sdrm_engine* e, const float* x, int64_t n_rows
   int64_t r0, r1;
   float gamma;
   quantile_ranks(n, q, r0, r1, gamma);
-  SDRM_LAUNCH(e, k_select_init, dim3(8), dim3(256), 0, st, e->sel, r0, r1);
-  HIP_TRY(e, hipGetLastError());
+  if (int rc = launch_k(e, PC_NONE, "k_select_init", k_select_init, dim3(8), dim3(256), 0, st, e->sel, r0, r1)) return rc;
   if (int rc = select_and_binarize(e, x, n, gamma, nullptr, threshold, st)) return rc;
-  uint32_t* counts = reinterpret_cast<uint32_t*>(e->csr_ws + off_cnt);
-  int64_t* own = reinterpret_cast<int64_t*>(e->csr_ws + off_ptr);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + off_cnt);
+  int64_t* own = reinterpret_cast<int64_t*>(ws + off_ptr);
   HIP_TRY(e, hipMemsetAsync(counts, 0, (size_t)n_rows * sizeof(uint32_t), st));
   const dim3 grid((unsigned)((words + 4 * CSR_MASK_WORDS - 1) / (4 * CSR_MASK_WORDS)));   // four waves per work-group
-  if (side == 0) SDRM_LAUNCH(e, (k_csr_mask<0>), grid, dim3(256), 0, st, x, (int)n_cols, (int)wpr, (uint32_t)words, (const float*)&e->sel->threshold, e->csr_ws, counts);
-  else SDRM_LAUNCH(e, (k_csr_mask<1>), grid, dim3(256), 0, st, x, (int)n_cols, (int)wpr, (uint32_t)words, (const float*)&e->sel->threshold, e->csr_ws, counts);
-  HIP_TRY(e, hipGetLastError());
+  if (int rc = launch_k(e, PC_NONE, "k_csr_mask", side == 0 ? k_csr_mask<0> : k_csr_mask<1>, grid, dim3(256), 0, st, x, (int)n_cols, (int)wpr,
+                        (uint32_t)words, &e->sel->threshold, ws, counts))
+    return rc;
   *e->csr_nnz_host = -1;
-  SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)counts, n_rows, own, indptr, e->csr_nnz_dev);
-  HIP_TRY(e, hipGetLastError());
+  if (int rc = launch_k(e, PC_NONE, "k_csr_scan", k_csr_scan, dim3(1), dim3(256), 0, st, counts, n_rows, own, indptr, e->csr_nnz_dev)) return rc;
   HIP_TRY(e, hipStreamSynchronize(st));
   const int64_t nnz = *(volatile int64_t*)e->csr_nnz_host;
   if (nnz < 0 || nnz > n) return fail(e, SDRM_ERR_STATE, "sdrm_equal_sparsity_csr_begin: the row counts do not add up");
@@ -3770,17 +3649,15 @@ int sdrm_equal_sparsity_csr_end(sdrm_engine* e, int32_t* indices, int64_t capaci
   if (!indices && e->csr.nnz > 0) return fail(e, SDRM_ERR_ARG, "sdrm_equal_sparsity_csr_end: null pointer");
   const auto& c = e->csr;
   if (c.nnz > 0) {
-    const int64_t* own = reinterpret_cast<const int64_t*>(e->csr_ws + c.off_ptr);
+    const uint64_t* ws = scratch_at<uint64_t>(e, SCR_CSR_WS);
+    const int64_t* own = reinterpret_cast<const int64_t*>(ws + c.off_ptr);
     // rows per work-group: 4 (a wave per row) for the wide matrices (3125 columns: 49 words, 8582: 135), 16 for rows of at most 32 words
     // (843 x 1008: 16 words), where a wave per row would leave three lanes in four without a word
-    if (c.wpr > 32) {
-      const unsigned blocks = (unsigned)std::min<int64_t>((c.n_rows + 3) / 4, 65536);
-      SDRM_LAUNCH(e, (k_csr_fill<64>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint64_t*)e->csr_ws, own, c.n_rows, c.wpr, indices, c.nnz);
-    } else {
-      const unsigned blocks = (unsigned)std::min<int64_t>((c.n_rows + 15) / 16, 65536);
-      SDRM_LAUNCH(e, (k_csr_fill<16>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint64_t*)e->csr_ws, own, c.n_rows, c.wpr, indices, c.nnz);
-    }
-    HIP_TRY(e, hipGetLastError());
+    const int rpw = c.wpr > 32 ? 4 : 16;
+    const unsigned blocks = (unsigned)std::min<int64_t>((c.n_rows + rpw - 1) / rpw, 65536);
+    if (int rc = launch_k(e, PC_NONE, "k_csr_fill", c.wpr > 32 ? k_csr_fill<64> : k_csr_fill<16>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ws,
+                          own, c.n_rows, c.wpr, indices, c.nnz))
+      return rc;
   }
   e->csr.active = false;
   return SDRM_OK;
@@ -3807,16 +3684,17 @@ int sdrm_csr_transpose(sdrm_engine* e, const int64_t* indptr, const int32_t* ind
   hipStream_t st = (hipStream_t)stream;
   const size_t blocks = (size_t)((n_rows + 63) / 64), words = blocks * (size_t)n_cols;
   const size_t off_table = 2, off_ptr = off_table + words, off_off = off_ptr + (size_t)n_cols + 1, off_cnt = off_off + (words + 1) / 2;
-  if (int rc = grow(e, &e->csrt_ws, &e->csrt_ws_cap, off_cnt + ((size_t)n_cols + 1) / 2)) return rc;
-  int64_t* own = reinterpret_cast<int64_t*>(e->csrt_ws + off_ptr);
+  uint64_t* ws;
+  if (int rc = scratch(e, SCR_CSRT_WS, off_cnt + ((size_t)n_cols + 1) / 2, &ws)) return rc;
+  int64_t* own = reinterpret_cast<int64_t*>(ws + off_ptr);
   CsrTransposeArgs a{};
   a.csr = CsrBatch{indptr, indices, data, nullptr, 0, n_rows, (int)n_rows, (int)n_cols, e->feed_flag};
   a.capacity = capacity;
-  a.checked = reinterpret_cast<unsigned long long*>(e->csrt_ws);
-  a.total = reinterpret_cast<const int64_t*>(e->csrt_ws + 1);
-  a.table = e->csrt_ws + off_table;
-  a.off = reinterpret_cast<uint32_t*>(e->csrt_ws + off_off);
-  a.counts = reinterpret_cast<uint32_t*>(e->csrt_ws + off_cnt);
+  a.checked = reinterpret_cast<unsigned long long*>(ws);
+  a.total = reinterpret_cast<const int64_t*>(ws + 1);
+  a.table = ws + off_table;
+  a.off = reinterpret_cast<uint32_t*>(ws + off_off);
+  a.counts = reinterpret_cast<uint32_t*>(ws + off_cnt);
   a.colptr = own;
   a.blocks = (int)blocks;
   a.rowidx = rowidx; a.cdata = cdata;
@@ -3824,7 +3702,7 @@ int sdrm_csr_transpose(sdrm_engine* e, const int64_t* indptr, const int32_t* ind
   // form of the mark pass stores every word of the table, the global-atomic form ORs into a cleared one.
   const int64_t tiles = (n_cols + CSRT_TILE - 1) / CSRT_TILE;
   const bool lds = e->csrt_mark_mode == 2 || (e->csrt_mark_mode == 0 && tiles <= CSRT_LDS_MAX_TILES);
-  HIP_TRY(e, hipMemsetAsync(e->csrt_ws, 0, off_table * sizeof(uint64_t), st));
+  HIP_TRY(e, hipMemsetAsync(ws, 0, off_table * sizeof(uint64_t), st));
   const unsigned waves = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 1 << 16);   // the row kernels stride over the rows behind their grids
   HIP_TRY(e, profiled(e, PC_CSRT_MARK, 0.0, st, [&] {   // (the clearing is the global form's cost: inside its interval)
     if (lds) {
@@ -3836,19 +3714,11 @@ int sdrm_csr_transpose(sdrm_engine* e, const int64_t* indptr, const int32_t* ind
     }
     return hipGetLastError();
   }));
-  HIP_TRY(e, profiled(e, PC_CSRT_COLSCAN, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_csrt_colscan, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, a);
-    return hipGetLastError();
-  }));
-  HIP_TRY(e, profiled(e, PC_CSRT_SCAN, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)a.counts, n_cols, own, colptr, reinterpret_cast<int64_t*>(e->csrt_ws + 1));
-    return hipGetLastError();
-  }));
-  HIP_TRY(e, profiled(e, PC_CSRT_FILL, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_csrt_fill, dim3(waves), dim3(256), 0, st, a);
-    return hipGetLastError();
-  }));
-  return SDRM_OK;
+  if (int rc = launch_k(e, PC_CSRT_COLSCAN, "k_csrt_colscan", k_csrt_colscan, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, a)) return rc;
+  if (int rc = launch_k(e, PC_CSRT_SCAN, "k_csr_scan", k_csr_scan, dim3(1), dim3(256), 0, st, a.counts, n_cols, own, colptr,
+                        reinterpret_cast<int64_t*>(ws + 1)))
+    return rc;
+  return launch_k(e, PC_CSRT_FILL, "k_csrt_fill", k_csrt_fill, dim3(waves), dim3(256), 0, st, a);
 }
 
 int sdrm_csr_vstack(sdrm_engine* e, const sdrm_csr_part* parts, int n_parts, int n_cols, int64_t* indptr_out, int32_t* indices_out,
@@ -3877,17 +3747,18 @@ int sdrm_csr_vstack(sdrm_engine* e, const sdrm_csr_part* parts, int n_parts, int
     return fail(e, SDRM_ERR_ARG, "sdrm_csr_vstack: data_out is required when a part has values, and null when none has");
   hipStream_t st = (hipStream_t)stream;
   const size_t off_ptr = 1, off_cnt = off_ptr + (size_t)rows + 1;
-  if (int rc = grow(e, &e->stack_ws, &e->stack_ws_cap, off_cnt + ((size_t)rows + 1) / 2)) return rc;
-  int64_t* own = reinterpret_cast<int64_t*>(e->stack_ws + off_ptr);
+  uint64_t* ws;
+  if (int rc = scratch(e, SCR_STACK_WS, off_cnt + ((size_t)rows + 1) / 2, &ws)) return rc;
+  int64_t* own = reinterpret_cast<int64_t*>(ws + off_ptr);
   a.n_parts = n_parts; a.n_cols = n_cols;
-  a.cnt = reinterpret_cast<uint32_t*>(e->stack_ws + off_cnt);
+  a.cnt = reinterpret_cast<uint32_t*>(ws + off_cnt);
   a.rowptr = own;
   a.indices_out = indices_out; a.data_out = data_out; a.capacity_out = capacity_out;
   a.flag = e->feed_flag;
   const unsigned waves = (unsigned)std::min<int64_t>((rows + 3) / 4, 1 << 16);
   return hip_rc(e, "k_stack_copy", profiled(e, PC_CSR_VSTACK, 0.0, st, [&] {
     SDRM_LAUNCH(e, k_stack_counts, dim3(waves), dim3(256), 0, st, a);
-    SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)a.cnt, rows, own, indptr_out, reinterpret_cast<int64_t*>(e->stack_ws));
+    SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)a.cnt, rows, own, indptr_out, reinterpret_cast<int64_t*>(ws));
     SDRM_LAUNCH(e, k_stack_copy, dim3(waves), dim3(256), 0, st, a);
     return hipGetLastError();
   }));
@@ -3920,9 +3791,7 @@ int sdrm_rank_metrics(sdrm_engine* e, const float* scores, int U, int I, const i
   const size_t lds = (size_t)I * sizeof(float);
   if (lds > 48 * 1024)
     HIP_TRY(e, hipFuncSetAttribute((const void*)k_rank_metrics, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  SDRM_LAUNCH(e, k_rank_metrics, dim3(U), dim3(256), lds, (hipStream_t)stream, a);
-  HIP_TRY(e, hipGetLastError());
-  return SDRM_OK;
+  return launch_k(e, PC_NONE, "k_rank_metrics", k_rank_metrics, dim3(U), dim3(256), lds, (hipStream_t)stream, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3933,43 +3802,31 @@ constexpr int64_t SVD_MAX_DIM = (int64_t)1 << 22;
 const char* const kSvdEnvelope = ": k outside 1 .. 22 (k + 10 columns must fit the panel of 32), min(m, n) < 32, m or n above 2^22, nnz outside 0 .. 2^40 - 1 "
                                  "or n_iter outside 0 .. 10000";
 
-int svd_scratch(sdrm_engine* e) {
-  if (!e->svd_part) HIP_TRY(e, dalloc(&e->svd_part, (size_t)(SVD_GRAM_PARTS + 1) * SVD_PW * SVD_PW));
-  if (!e->svd_flag) HIP_TRY(e, dalloc(&e->svd_flag, 4));
-  return SDRM_OK;
+// the Gram partials with R^-1 behind them, and the status word: made once, at their fixed sizes
+int svd_scratch(sdrm_engine* e, unsigned** flag) {
+  double* part;
+  if (int rc = scratch(e, SCR_SVD_PART, (size_t)(SVD_GRAM_PARTS + 1) * SVD_PW * SVD_PW, &part)) return rc;
+  return scratch(e, SCR_SVD_FLAG, 4, flag);
 }
 
 // y [c.b][32] = (the rows of c) q
-hipError_t svd_spmm(sdrm_engine* e, const CsrBatch& c, int64_t nnz, const float* q, float* y, hipStream_t st) {
+int svd_spmm(sdrm_engine* e, const CsrBatch& c, int64_t nnz, const float* q, float* y, hipStream_t st) {
   const SvdSpmmArgs a{c, nnz, q, y};
-  return profiled(e, PC_SVD_SPMM, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_svd_spmm, dim3((unsigned)((c.b + 31) / 32)), dim3(256), 0, st, a);
-    return hipGetLastError();
-  });
+  return launch_k(e, PC_SVD_SPMM, "k_svd_spmm", k_svd_spmm, dim3((unsigned)((c.b + 31) / 32)), dim3(256), 0, st, a);
 }
 
 // y [rows][32] <- orth(y): CholeskyQR twice, three launches each
-hipError_t svd_orth(sdrm_engine* e, float* y, int rows, hipStream_t st) {
+int svd_orth(sdrm_engine* e, float* y, int rows, hipStream_t st) {
   const int parts = std::min(SVD_GRAM_PARTS, (rows + SVD_GRAM_ROWS - 1) / SVD_GRAM_ROWS);
-  double* rinv = e->svd_part + (size_t)SVD_GRAM_PARTS * SVD_PW * SVD_PW;
-  hipError_t rc = hipSuccess;
-  for (int pass = 0; pass < 2 && rc == hipSuccess; ++pass) {
-    rc = profiled(e, PC_SVD_GRAM, 0.0, st, [&] {
-      SDRM_LAUNCH(e, k_svd_gram, dim3((unsigned)parts), dim3(256), 0, st, (const float*)y, rows, e->svd_part);
-      return hipGetLastError();
-    });
-    if (rc == hipSuccess)
-      rc = profiled(e, PC_SVD_CHOL, 0.0, st, [&] {
-        SDRM_LAUNCH(e, k_svd_chol, dim3(1), dim3(256), 0, st, (const double*)e->svd_part, parts, rinv, e->svd_flag);
-        return hipGetLastError();
-      });
-    if (rc == hipSuccess)
-      rc = profiled(e, PC_SVD_APPLY, 0.0, st, [&] {
-        SDRM_LAUNCH(e, k_svd_apply, dim3((unsigned)((rows + 31) / 32)), dim3(256), 0, st, y, rows, (const double*)rinv);
-        return hipGetLastError();
-      });
+  double* part = scratch_at<double>(e, SCR_SVD_PART);
+  double* rinv = part + (size_t)SVD_GRAM_PARTS * SVD_PW * SVD_PW;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (int rc = launch_k(e, PC_SVD_GRAM, "k_svd_gram", k_svd_gram, dim3((unsigned)parts), dim3(256), 0, st, y, rows, part)) return rc;
+    if (int rc = launch_k(e, PC_SVD_CHOL, "k_svd_chol", k_svd_chol, dim3(1), dim3(256), 0, st, part, parts, rinv, scratch_at<unsigned>(e, SCR_SVD_FLAG)))
+      return rc;
+    if (int rc = launch_k(e, PC_SVD_APPLY, "k_svd_apply", k_svd_apply, dim3((unsigned)((rows + 31) / 32)), dim3(256), 0, st, y, rows, rinv)) return rc;
   }
-  return rc;
+  return SDRM_OK;
 }
 
 // Eigen-decomposition of the symmetric a [n][n] by cyclic Jacobi rotations (float64): the eigenvalues end on a's diagonal, column j of v
@@ -4052,7 +3909,7 @@ const char* const kSvdBreakdown = ": breakdown - a panel of 32 columns became nu
 // the fit's status word as it stands once `st` has drained; a raised one is cleared for the next call
 int svd_breakdown(sdrm_engine* e, const char* who, hipStream_t st, unsigned flag) {
   if (!(flag & SVD_BREAKDOWN)) return SDRM_OK;
-  HIP_TRY(e, hipMemsetAsync(e->svd_flag, 0, sizeof(unsigned), st));
+  HIP_TRY(e, hipMemsetAsync(scratch_at<unsigned>(e, SCR_SVD_FLAG), 0, sizeof(unsigned), st));
   return fail(e, SDRM_ERR_ARG, std::string(who) + kSvdBreakdown);
 }
 
@@ -4074,32 +3931,30 @@ int sdrm_svd_fit(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, 
   if ((data == nullptr) != (cdata == nullptr)) return fail(e, SDRM_ERR_ARG, "sdrm_svd_fit: the values of the CSR and of the CSC form go together");
   if (int rc = sdrm_debug_svd_args(m, n, nnz, k, n_iter)) return fail(e, rc, std::string("sdrm_svd_fit") + kSvdEnvelope);
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = svd_scratch(e)) return rc;
-  if (int rc = grow(e, &e->svd_panel, &e->svd_panel_cap, (size_t)(m + n) * SVD_PW)) return rc;
-  float* Q = e->svd_panel;
+  unsigned* dflag;
+  float* Q;
+  int rc;
+  if ((rc = svd_scratch(e, &dflag)) || (rc = scratch(e, SCR_SVD_PANEL, (size_t)(m + n) * SVD_PW, &Q))) return rc;
   float* Y = Q + (size_t)n * SVD_PW;
   const CsrBatch by_rows{indptr, indices, data, nullptr, 0, m, (int)m, (int)n, e->feed_flag};
   const CsrBatch by_cols{colptr, rowidx, cdata, nullptr, 0, n, (int)n, (int)m, e->feed_flag};
-  HIP_TRY(e, hipMemsetAsync(e->svd_flag, 0, sizeof(unsigned), st));
+  HIP_TRY(e, hipMemsetAsync(dflag, 0, sizeof(unsigned), st));
   if (q0) {
     HIP_TRY(e, hipMemcpyAsync(Q, q0, (size_t)n * SVD_PW * sizeof(float), hipMemcpyDeviceToDevice, st));
-  } else {
-    HIP_TRY(e, profiled(e, PC_SVD_EXPAND, 0.0, st, [&] {
-      SDRM_LAUNCH(e, k_svd_start, dim3((unsigned)std::min<int64_t>(4096, (n * 8 + 255) / 256)), dim3(256), 0, st, Q, (int)n, (uint32_t)seed,
-                  (uint32_t)(seed >> 32), draw);
-      return hipGetLastError();
-    }));
+  } else if ((rc = launch_k(e, PC_SVD_EXPAND, "k_svd_start", k_svd_start, dim3((unsigned)std::min<int64_t>(4096, (n * 8 + 255) / 256)), dim3(256), 0, st,
+                            Q, (int)n, (uint32_t)seed, (uint32_t)(seed >> 32), draw))) {
+    return rc;
   }
   for (int it = 0; it <= n_iter; ++it) {
-    HIP_TRY(e, svd_spmm(e, by_rows, nnz, Q, Y, st));
-    HIP_TRY(e, svd_orth(e, Y, (int)m, st));
-    HIP_TRY(e, svd_spmm(e, by_cols, nnz, Y, Q, st));   // the last one stays as it is: Z = A^T Y
-    if (it < n_iter) HIP_TRY(e, svd_orth(e, Q, (int)n, st));
+    if ((rc = svd_spmm(e, by_rows, nnz, Q, Y, st)) || (rc = svd_orth(e, Y, (int)m, st)) ||
+        (rc = svd_spmm(e, by_cols, nnz, Y, Q, st)) ||   // the last one stays as it is: Z = A^T Y
+        (it < n_iter && (rc = svd_orth(e, Q, (int)n, st))))
+      return rc;
   }
   std::vector<float> z((size_t)n * SVD_PW), V;
   unsigned flag = 0;
   HIP_TRY(e, hipMemcpyAsync(z.data(), Q, z.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_TRY(e, hipMemcpyAsync(&flag, e->svd_flag, sizeof(flag), hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&flag, dflag, sizeof(flag), hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipStreamSynchronize(st));
   if (int rc = svd_breakdown(e, "sdrm_svd_fit", st, flag)) return rc;
   if (!svd_close(z, n, k, V, singular_values_host)) return fail(e, SDRM_ERR_ARG, std::string("sdrm_svd_fit") + kSvdBreakdown);
@@ -4118,20 +3973,16 @@ int sdrm_svd_scores(sdrm_engine* e, const int64_t* indptr, const int32_t* indice
       (int64_t)b * n_items >= ((int64_t)1 << 40))
     return fail(e, SDRM_ERR_SHAPE, "sdrm_svd_scores: k outside 1 .. 22, b or n_items above 2^22, nnz outside 0 .. 2^40 - 1 or b x n_items at or above 2^40");
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = grow(e, &e->svd_vt, &e->svd_vt_cap, ((size_t)n_items + (size_t)b) * SVD_PW)) return rc;
-  float* Vt = e->svd_vt;
+  float* Vt;
+  if (int rc = scratch(e, SCR_SVD_VT, ((size_t)n_items + (size_t)b) * SVD_PW, &Vt)) return rc;
   float* T = Vt + (size_t)n_items * SVD_PW;
-  HIP_TRY(e, profiled(e, PC_SVD_EXPAND, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_svd_vt, dim3((unsigned)std::min<int64_t>(4096, ((int64_t)n_items * SVD_PW + 255) / 256)), dim3(256), 0, st, components, k, n_items, Vt);
-    return hipGetLastError();
-  }));
-  HIP_TRY(e, svd_spmm(e, c, nnz, Vt, T, st));
+  if (int rc = launch_k(e, PC_SVD_EXPAND, "k_svd_vt", k_svd_vt, dim3((unsigned)std::min<int64_t>(4096, ((int64_t)n_items * SVD_PW + 255) / 256)), dim3(256),
+                        0, st, components, k, n_items, Vt))
+    return rc;
+  if (int rc = svd_spmm(e, c, nnz, Vt, T, st)) return rc;
   const SvdExpandArgs a{T, components, k, n_items, b, scores};
-  HIP_TRY(e, profiled(e, PC_SVD_EXPAND, 0.0, st, [&] {
-    SDRM_LAUNCH(e, k_svd_expand, dim3((unsigned)((n_items + 255) / 256), (unsigned)std::min(4096, (b + SVD_ROW_TILE - 1) / SVD_ROW_TILE)), dim3(256), 0, st, a);
-    return hipGetLastError();
-  }));
-  return SDRM_OK;
+  return launch_k(e, PC_SVD_EXPAND, "k_svd_expand", k_svd_expand,
+                  dim3((unsigned)((n_items + 255) / 256), (unsigned)std::min(4096, (b + SVD_ROW_TILE - 1) / SVD_ROW_TILE)), dim3(256), 0, st, a);
 }
 
 // One product and one orthonormalisation on the caller's panels (include/sdrm_hip_debug.h).
@@ -4143,14 +3994,15 @@ int sdrm_debug_svd_stage(sdrm_engine* e, const int64_t* indptr, const int32_t* i
   if (n_rows < 1 || n_rows > SVD_MAX_DIM || n_cols < 1 || n_cols > SVD_MAX_DIM || nnz < 0 || nnz >= ((int64_t)1 << 40))
     return fail(e, SDRM_ERR_SHAPE, "sdrm_debug_svd_stage: n_rows or n_cols outside 1 .. 2^22 or nnz outside 0 .. 2^40 - 1");
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = svd_scratch(e)) return rc;
+  unsigned* dflag;
+  if (int rc = svd_scratch(e, &dflag)) return rc;
   const CsrBatch c{indptr, indices, data, nullptr, 0, n_rows, (int)n_rows, (int)n_cols, e->feed_flag};
-  HIP_TRY(e, hipMemsetAsync(e->svd_flag, 0, sizeof(unsigned), st));
-  HIP_TRY(e, svd_spmm(e, c, nnz, q, y_prod, st));
+  HIP_TRY(e, hipMemsetAsync(dflag, 0, sizeof(unsigned), st));
+  if (int rc = svd_spmm(e, c, nnz, q, y_prod, st)) return rc;
   HIP_TRY(e, hipMemcpyAsync(y_orth, y_prod, (size_t)n_rows * SVD_PW * sizeof(float), hipMemcpyDeviceToDevice, st));
-  HIP_TRY(e, svd_orth(e, y_orth, (int)n_rows, st));
+  if (int rc = svd_orth(e, y_orth, (int)n_rows, st)) return rc;
   unsigned flag = 0;
-  HIP_TRY(e, hipMemcpyAsync(&flag, e->svd_flag, sizeof(flag), hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&flag, dflag, sizeof(flag), hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipStreamSynchronize(st));
   return svd_breakdown(e, "sdrm_debug_svd_stage", st, flag);
 }
@@ -4182,27 +4034,24 @@ int neumf_stage(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, int n
   const int64_t ldu = ((int64_t)nu + 63) / 64 * 64, ldi = ((int64_t)ni + 63) / 64 * 64;
   const size_t n_w2 = (size_t)8 * F * F, n_w3 = (size_t)2 * F * F;
   const size_t n_u = pairs ? (size_t)ROW * ldu : (size_t)nu * ROW;
-  if (int rc = grow(e, &e->neumf_ws, &e->neumf_ws_cap, n_w2 + n_w3 + n_u + (size_t)ROW * ldi)) return rc;
-  if (int rc = grow(e, &e->neumf_valid, &e->neumf_valid_cap, (size_t)nu + ni)) return rc;
-  float* w2t = e->neumf_ws;
+  float* w2t;
+  int* valid;
+  if (int rc = scratch(e, SCR_NEUMF_WS, n_w2 + n_w3 + n_u + (size_t)ROW * ldi, &w2t)) return rc;
+  if (int rc = scratch(e, SCR_NEUMF_VALID, (size_t)nu + ni, &valid)) return rc;
   float* w3t = w2t + n_w2;
   float* ua = w3t + n_w3;
   float* ibt = ua + n_u;
   NeumfStageArgs a;
-  a.side[0] = NeumfStageSide{w->embed_user_mlp, w->embed_user_gmf, users, nu, w->n_users, ua, e->neumf_valid, ldu, pairs ? 1 : 0, 0, FEED_BAD_ROW};
-  a.side[1] = NeumfStageSide{w->embed_item_mlp, w->embed_item_gmf, items, ni, w->n_items, ibt, e->neumf_valid + nu, ldi, 1, 4 * F, FEED_BAD_COL};
+  a.side[0] = NeumfStageSide{w->embed_user_mlp, w->embed_user_gmf, users, nu, w->n_users, ua, valid, ldu, pairs ? 1 : 0, 0, FEED_BAD_ROW};
+  a.side[1] = NeumfStageSide{w->embed_item_mlp, w->embed_item_gmf, items, ni, w->n_items, ibt, valid + nu, ldi, 1, 4 * F, FEED_BAD_COL};
   a.w1 = w->w1; a.b1 = w->b1; a.w2 = w->w2; a.w3 = w->w3;
   a.w2t = w2t; a.w3t = w3t;
   a.flag = e->feed_flag;
   a.blocks[0] = (int)(((int64_t)nu * ROW + 255) / 256);
   a.blocks[1] = (int)(((int64_t)ni * ROW + 255) / 256);
   const unsigned grid = (unsigned)a.blocks[0] + (unsigned)a.blocks[1] + (unsigned)((10 * F * F + 255) / 256);
-  HIP_TRY(e, profiled(e, PC_NEUMF_STAGE, 2.0 * 16 * F * F * ((double)nu + ni), st, [&] {
-    SDRM_LAUNCH(e, k_neumf_stage<F>, dim3(grid), dim3(256), 0, st, a);
-    return hipGetLastError();
-  }));
-  *out = NeumfStaged{w2t, w3t, ua, ibt, e->neumf_valid, e->neumf_valid + nu, ldi};
-  return SDRM_OK;
+  *out = NeumfStaged{w2t, w3t, ua, ibt, valid, valid + nu, ldi};
+  return launch_k(e, {PC_NEUMF_STAGE, 2.0 * 16 * F * F * ((double)nu + ni)}, "k_neumf_stage", k_neumf_stage<F>, dim3(grid), dim3(256), 0, st, a);
 }
 
 template <int F>
@@ -4210,38 +4059,29 @@ int neumf_scores(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, int 
   NeumfStaged s;
   if (int rc = neumf_stage<F>(e, w, users, nu, false, items, ni, st, &s)) return rc;
   const dim3 grid((unsigned)((ni + NEUMF_ITEM_TILE - 1) / NEUMF_ITEM_TILE), (unsigned)((nu + NEUMF_USER_TILE - 1) / NEUMF_USER_TILE));
-  HIP_TRY(e, profiled(e, PC_NEUMF_SCORES, 2.0 * (10.0 * F * F + 2.0 * F) * nu * ni, st, [&] {
-    SDRM_LAUNCH(e, k_neumf_scores<F>, grid, dim3(256), 0, st, s.ua, s.uvalid, s.ibt, s.ivalid, s.ld, s.w2t, w->b2, s.w3t, w->b3, w->wp, w->bp, nu, ni,
-                out);
-    return hipGetLastError();
-  }));
-  return SDRM_OK;
+  return launch_k(e, {PC_NEUMF_SCORES, 2.0 * (10.0 * F * F + 2.0 * F) * nu * ni}, "k_neumf_scores", k_neumf_scores<F>, grid, dim3(256), 0, st, s.ua,
+                  s.uvalid, s.ibt, s.ivalid, s.ld, s.w2t, w->b2, s.w3t, w->b3, w->wp, w->bp, nu, ni, out);
 }
 
 template <int F>
 int neumf_pairs(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, const int32_t* items, const float* labels, int64_t n, float* logits,
                 double* loss_sum, hipStream_t st) {
   const int64_t n_part = (n + 255) / 256;
+  double* parts = nullptr;
   if (loss_sum)
-    if (int rc = grow(e, &e->neumf_part, &e->neumf_part_cap, (size_t)n_part)) return rc;
+    if (int rc = scratch(e, SCR_NEUMF_PART, (size_t)n_part, &parts)) return rc;
   for (int64_t off = 0; off < n; off += NEUMF_PAIR_CHUNK) {
     const int m = (int)std::min<int64_t>(NEUMF_PAIR_CHUNK, n - off);
     NeumfStaged s;
     if (int rc = neumf_stage<F>(e, w, users + off, m, true, items + off, m, st, &s)) return rc;
     const float* lab = labels ? labels + off : nullptr;
     float* lg = logits ? logits + off : nullptr;
-    double* part = loss_sum ? e->neumf_part + off / 256 : nullptr;
-    HIP_TRY(e, profiled(e, PC_NEUMF_PAIRS, 2.0 * (10.0 * F * F + 2.0 * F) * m, st, [&] {
-      SDRM_LAUNCH(e, k_neumf_pairs<F>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, s.ua, s.uvalid, s.ibt, s.ivalid, s.ld, s.w2t, w->b2, s.w3t,
-                  w->b3, w->wp, w->bp, lab, m, lg, part);
-      return hipGetLastError();
-    }));
+    double* part = loss_sum ? parts + off / 256 : nullptr;
+    if (int rc = launch_k(e, {PC_NEUMF_PAIRS, 2.0 * (10.0 * F * F + 2.0 * F) * m}, "k_neumf_pairs", k_neumf_pairs<F>, dim3((unsigned)((m + 255) / 256)),
+                          dim3(256), 0, st, s.ua, s.uvalid, s.ibt, s.ivalid, s.ld, s.w2t, w->b2, s.w3t, w->b3, w->wp, w->bp, lab, m, lg, part))
+      return rc;
   }
-  if (loss_sum)
-    HIP_TRY(e, profiled(e, PC_NEUMF_PAIRS, 0.0, st, [&] {
-      SDRM_LAUNCH(e, k_neumf_loss_sum, dim3(1), dim3(256), 0, st, (const double*)e->neumf_part, (int)n_part, loss_sum);
-      return hipGetLastError();
-    }));
+  if (loss_sum) return launch_k(e, PC_NEUMF_PAIRS, "k_neumf_loss_sum", k_neumf_loss_sum, dim3(1), dim3(256), 0, st, parts, (int)n_part, loss_sum);
   return SDRM_OK;
 }
 
@@ -4294,20 +4134,6 @@ int sdrm_neumf_pair_loss(sdrm_engine* e, const sdrm_neumf* w, const int32_t* use
 namespace {
 
 constexpr int EVAL_MAX_ITEMS = 36864;   // k_rank_metrics' LDS row
-constexpr int EVAL_MAX_HIDDEN = 4096, EVAL_MAX_LATENT = 4096;   // (hidden: ENC_GATHER_MAX_Q float4 slices in k_encode_csr's registers)
-
-int ev_grow(sdrm_engine* e, int slot, size_t n) { return grow(e, &e->ev_buf[slot], &e->ev_cap[slot], n); }
-
-// padded extents: K and N of the GEMMs to 32, operand rows to the largest tile (128), the batch to 64 (the launches' M)
-struct EvDims { int Hq, Hp, Hr, Lp, Lr, Ip, Ir, MP, rows64; };
-EvDims ev_dims(int n_items, int hidden, int latent, int batch) {
-  EvDims d;
-  d.Hq = round_up(hidden, 4); d.Hp = round_up(hidden, 32); d.Hr = round_up(d.Hp, 128);
-  d.Lp = round_up(latent, 32); d.Lr = round_up(d.Lp, 128);
-  d.Ip = round_up(n_items, 32); d.Ir = round_up(d.Ip, 128);
-  d.MP = round_up(batch, 128); d.rows64 = round_up(batch, BM);
-  return d;
-}
 
 const char* const kEvalEnvelope = ": n_items outside 1 .. 36864, hidden or latent outside 1 .. 4096, n_rows outside 1 .. 2^31 - 1, batch outside 1 .. 2^22, "
                                   "k outside 1 .. min(128, n_items), metric not 0 (recall) or 1 (ndcg), a negative nnz, or the encoder's and the decoder's sizes differ";
@@ -4317,14 +4143,14 @@ const char* const kEvalEnvelope = ": n_items outside 1 .. 36864, hidden or laten
 // The host side that needs no device: the envelope, and the tests that the three GEMM launches of sdrm_vae_eval_holdout make on any
 // tile (A's stride equal to K, as those launches have it; a launch of another form added to the call needs its own line here).
 int sdrm_debug_vae_eval_args(int n_items, int hidden, int latent, int64_t n_rows, int batch, int k, int metric) {
-  if (n_items < 1 || n_items > EVAL_MAX_ITEMS || hidden < 1 || hidden > EVAL_MAX_HIDDEN || latent < 1 || latent > EVAL_MAX_LATENT || n_rows < 1 ||
-      n_rows > (int64_t)INT32_MAX || batch < 1 || batch > (1 << 22) || k < 1 || k > RANK_MAX_K || k > n_items || (metric != 0 && metric != 1))
+  if (n_items < 1 || n_items > EVAL_MAX_ITEMS || hidden < 1 || hidden > VAE_MAX_HIDDEN || latent < 1 || latent > VAE_MAX_LATENT || n_rows < 1 ||
+      n_rows > (int64_t)INT32_MAX || batch < 1 || batch > MAX_BATCH_ROWS || k < 1 || k > RANK_MAX_K || k > n_items || (metric != 0 && metric != 1))
     return SDRM_ERR_SHAPE;
-  const EvDims d = ev_dims(n_items, hidden, latent, batch);
+  const VaeDims d = vae_dims(n_items, hidden, latent, batch);
   for (int cfg = 0; cfg < N_TILE_CFGS; ++cfg) {
     // h1 W2[:L]^T (K = Hp), z W3^T (K = Lp), h3 W4^T (K = Hp): a row band of each fits a launch, and a tile x K span stays below 2^32 bytes
-    if (dh_nt_band(cfg, d.Lp) < 1 || dh_nt_band(cfg, d.Hp) < 1 || dh_nt_band(cfg, d.Ip) < 1) return SDRM_ERR_SHAPE;
-    if (!dh_span_ok(cfg, true, d.Hp, d.Hp, d.Hp) || !dh_span_ok(cfg, true, d.Lp, d.Lp, d.Lp)) return SDRM_ERR_SHAPE;
+    if (gemm_nt_band_rows(cfg, d.Lp) < 1 || gemm_nt_band_rows(cfg, d.Hp) < 1 || gemm_nt_band_rows(cfg, d.Ip) < 1) return SDRM_ERR_SHAPE;
+    if (!gemm_span_ok(cfg, true, d.Hp, d.Hp, d.Hp) || !gemm_span_ok(cfg, true, d.Lp, d.Lp, d.Lp)) return SDRM_ERR_SHAPE;
   }
   return SDRM_OK;
 }
@@ -4335,8 +4161,7 @@ int sdrm_vae_eval_holdout(sdrm_engine* e, const sdrm_vae_encoder* enc, const sdr
                           float* logits, void* stream) {
   const char* who = "sdrm_vae_eval_holdout";
   if (!e) return SDRM_ERR_ARG;
-  if (!enc || !dec || !enc->w1 || !enc->b1 || !enc->w2 || !enc->b2 || !dec->w1 || !dec->b1 || !dec->w2 || !dec->b2 || !train_indptr ||
-      !train_indices || !held_indptr || !held_indices || !tp || !idcg || !scores)
+  if (!enc_tensors(enc) || !dec_tensors(dec) || !train_indptr || !train_indices || !held_indptr || !held_indices || !tp || !idcg || !scores)
     return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
   const int I = enc->n_items, H = enc->hidden, L = enc->latent;
   if (dec->n_items != I || dec->hidden != H || dec->latent != L || train_nnz < 0 || held_nnz < 0)
@@ -4345,37 +4170,30 @@ int sdrm_vae_eval_holdout(sdrm_engine* e, const sdrm_vae_encoder* enc, const sdr
   hipStream_t st = (hipStream_t)stream;
   if (int jr = chains_join(e, st)) return jr;
   const int bmax = (int)std::min<int64_t>(batch, n_rows);
-  const EvDims d = ev_dims(I, H, L, bmax);
+  const VaeDims d = vae_dims(I, H, L, bmax);
+  float *w1t, *b1p, *w2p, *b2p, *w3p, *b3p, *w4p, *b4p, *h1, *zp, *h3, *own_logits = nullptr;
   int rc;
-  if ((rc = ev_grow(e, EV_W1T, (size_t)I * d.Hq)) || (rc = ev_grow(e, EV_B1, d.Hr)) || (rc = ev_grow(e, EV_W2, (size_t)d.Lr * d.Hp)) ||
-      (rc = ev_grow(e, EV_B2, d.Lr)) || (rc = ev_grow(e, EV_W3, (size_t)d.Hr * d.Lp)) || (rc = ev_grow(e, EV_B3, d.Hr)) ||
-      (rc = ev_grow(e, EV_W4, (size_t)d.Ir * d.Hp)) || (rc = ev_grow(e, EV_B4, d.Ir)) || (rc = ev_grow(e, EV_H1, (size_t)d.MP * d.Hp)) ||
-      (rc = ev_grow(e, EV_Z, (size_t)d.MP * d.Lp)) || (rc = ev_grow(e, EV_H3, (size_t)d.MP * d.Hp)))
+  if ((rc = scratch(e, SCR_EV_W1T, (size_t)I * d.Hq, &w1t)) || (rc = scratch(e, SCR_EV_B1, d.Hr, &b1p)) ||
+      (rc = scratch(e, SCR_EV_W2, (size_t)d.Lr * d.Hp, &w2p)) || (rc = scratch(e, SCR_EV_B2, d.Lr, &b2p)) ||
+      (rc = scratch(e, SCR_EV_W3, (size_t)d.Hr * d.Lp, &w3p)) || (rc = scratch(e, SCR_EV_B3, d.Hr, &b3p)) ||
+      (rc = scratch(e, SCR_EV_W4, (size_t)d.Ir * d.Hp, &w4p)) || (rc = scratch(e, SCR_EV_B4, d.Ir, &b4p)) ||
+      (rc = scratch(e, SCR_EV_H1, (size_t)d.MP * d.Hp, &h1)) || (rc = scratch(e, SCR_EV_Z, (size_t)d.MP * d.Lp, &zp)) ||
+      (rc = scratch(e, SCR_EV_H3, (size_t)d.MP * d.Hp, &h3)))
     return rc;
-  if (!logits && (rc = ev_grow(e, EV_LOGITS, (size_t)bmax * I))) return rc;
-  float* const* ev = e->ev_buf;
+  if (!logits && (rc = scratch(e, SCR_EV_LOGITS, (size_t)bmax * I, &own_logits))) return rc;
   const size_t lds = (size_t)I * sizeof(float);
   if (lds > 48 * 1024) HIP_TRY(e, allow_full_lds((const void*)k_rank_metrics_checked, EVAL_MAX_ITEMS * (int)sizeof(float)));
   // staging, once per call (the weights change with every optimiser step): seven tensors padded in one launch, W1 transposed in a second
   {
     PadList pad;
-    pad.add(enc->b1, 1, H, ev[EV_B1], 1, d.Hr);
-    pad.add(enc->w2, L, H, ev[EV_W2], d.Lr, d.Hp);   // the mu rows: the first L of [2 L][H]
-    pad.add(enc->b2, 1, L, ev[EV_B2], 1, d.Lr);
-    pad.add(dec->w1, H, L, ev[EV_W3], d.Hr, d.Lp);
-    pad.add(dec->b1, 1, H, ev[EV_B3], 1, d.Hr);
-    pad.add(dec->w2, I, H, ev[EV_W4], d.Ir, d.Hp);
-    pad.add(dec->b2, 1, I, ev[EV_B4], 1, d.Ir);
-    if ((rc = hip_rc(e, "k_pad2d", profiled(e, PC_EVAL_HALF, 0.0, st, [&] {
-           SDRM_LAUNCH(e, k_pad2d, dim3((unsigned)std::min<int64_t>(2048, (pad.most + 255) / 256), (unsigned)pad.k), dim3(256), 0, st, pad.sg);
-           return hipGetLastError();
-         }))))
-      return rc;
-    if ((rc = hip_rc(e, "k_encode_w1t", profiled(e, PC_EVAL_HALF, 0.0, st, [&] {
-           SDRM_LAUNCH(e, k_encode_w1t, dim3((unsigned)((I + 31) / 32), (unsigned)((d.Hq + 31) / 32)), dim3(256), 0, st, enc->w1, H, I, ev[EV_W1T], d.Hq);
-           return hipGetLastError();
-         }))))
-      return rc;
+    pad.add(enc->b1, 1, H, b1p, 1, d.Hr);
+    pad.add(enc->w2, L, H, w2p, d.Lr, d.Hp);   // the mu rows: the first L of [2 L][H]
+    pad.add(enc->b2, 1, L, b2p, 1, d.Lr);
+    pad.add(dec->w1, H, L, w3p, d.Hr, d.Lp);
+    pad.add(dec->b1, 1, H, b3p, 1, d.Hr);
+    pad.add(dec->w2, I, H, w4p, d.Ir, d.Hp);
+    pad.add(dec->b2, 1, I, b4p, 1, d.Ir);
+    if ((rc = pad.launch(e, PC_EVAL_HALF, st)) || (rc = launch_w1t(e, PC_EVAL_HALF, enc->w1, H, I, w1t, d.Hq, st))) return rc;
   }
   for (int64_t row0 = 0; row0 < n_rows; row0 += batch) {
     const int b = (int)std::min<int64_t>(batch, n_rows - row0);
@@ -4385,30 +4203,29 @@ int sdrm_vae_eval_holdout(sdrm_engine* e, const sdrm_vae_encoder* enc, const sdr
     {
       EncodeCsrArgs a{};
       a.csr = CsrBatch{train_indptr, train_indices, nullptr, nullptr, row0, n_rows, b, I, e->feed_flag};
-      a.w1t = ev[EV_W1T]; a.b1 = ev[EV_B1]; a.Hq = d.Hq; a.Hp = d.Hp; a.hid = ev[EV_H1]; a.nnz = train_nnz;
-      if ((rc = hip_rc(e, "k_encode_csr_checked", profiled(e, PC_EVAL_HALF, 0.0, st, [&] {
-             return launch_gather_rows(e, d.Hq / 4, a, st, [](auto tpr, auto nv, auto u) { return k_encode_csr_checked<VAL(tpr), VAL(nv), VAL(u)>; });
-           }))))
+      a.w1t = w1t; a.b1 = b1p; a.Hq = d.Hq; a.Hp = d.Hp; a.hid = h1; a.nnz = train_nnz;
+      if ((rc = launch_gather_rows(e, PC_EVAL_HALF, "k_encode_csr_checked", d.Hq / 4, a, st,
+                                   [](auto tpr, auto nv, auto u) { return k_encode_csr_checked<VAL(tpr), VAL(nv), VAL(u)>; })))
         return rc;
     }
     // 2: z = h1 W2[:L]^T + b2[:L] into the padded [MP][Lp] (W2's pad rows and b2's pad are zero: columns behind L are 0)
     {
       GemmArgs a{};
-      a.B = ev[EV_W2]; a.ldb = d.Hp; a.C = ev[EV_Z]; a.ldc = d.Lp; a.K = d.Hp; a.bias = ev[EV_B2];
-      if ((rc = dh_nt<EPI_BIAS>(e, a, ev[EV_H1], d.Hp, rows64, d.Lp, b, st, Prof{e, PC_EVAL_HALF, 2.0 * b * (double)L * H}, cfg))) return rc;
+      a.B = w2p; a.ldb = d.Hp; a.C = zp; a.ldc = d.Lp; a.K = d.Hp; a.bias = b2p;
+      if ((rc = gemm_nt_banded<EPI_BIAS>(e, a, h1, d.Hp, rows64, d.Lp, b, st, Prof{e, PC_EVAL_HALF, 2.0 * b * (double)L * H}, cfg))) return rc;
     }
     // 3: h3 = tanh(z W3^T + b3) into the padded [MP][Hp]
     {
       GemmArgs a{};
-      a.B = ev[EV_W3]; a.ldb = d.Lp; a.C = ev[EV_H3]; a.ldc = d.Hp; a.K = d.Lp; a.bias = ev[EV_B3];
-      if ((rc = dh_nt<EPI_BIAS_TANH>(e, a, ev[EV_Z], d.Lp, rows64, d.Hp, b, st, Prof{e, PC_EVAL_HALF, 2.0 * b * (double)H * L}, cfg))) return rc;
+      a.B = w3p; a.ldb = d.Lp; a.C = h3; a.ldc = d.Hp; a.K = d.Lp; a.bias = b3p;
+      if ((rc = gemm_nt_banded<EPI_BIAS_TANH>(e, a, zp, d.Lp, rows64, d.Hp, b, st, Prof{e, PC_EVAL_HALF, 2.0 * b * (double)H * L}, cfg))) return rc;
     }
     // 4: s = h3 W4^T + b4, bounds-checked into the batch's [b][I]: the scratch, or the caller's rows row0 ..
-    float* s_out = logits ? logits + (size_t)row0 * I : ev[EV_LOGITS];
+    float* s_out = logits ? logits + (size_t)row0 * I : own_logits;
     {
       GemmArgs a{};
-      a.B = ev[EV_W4]; a.ldb = d.Hp; a.C = s_out; a.ldc = I; a.K = d.Hp; a.bias = ev[EV_B4]; a.cols_valid = I;
-      if ((rc = dh_nt<EPI_BIAS_G>(e, a, ev[EV_H3], d.Hp, rows64, d.Ip, b, st, Prof{e, PC_EVAL_HALF, 2.0 * b * (double)I * H}, cfg))) return rc;
+      a.B = w4p; a.ldb = d.Hp; a.C = s_out; a.ldc = I; a.K = d.Hp; a.bias = b4p; a.cols_valid = I;
+      if ((rc = gemm_nt_banded<EPI_BIAS_G>(e, a, h3, d.Hp, rows64, d.Ip, b, st, Prof{e, PC_EVAL_HALF, 2.0 * b * (double)I * H}, cfg))) return rc;
     }
     // 5: the chosen metric of the batch's users into scores[row0 ..] (the indptr arrays hold absolute offsets: a row range is a pointer offset)
     {
@@ -4421,11 +4238,7 @@ int sdrm_vae_eval_holdout(sdrm_engine* e, const sdrm_vae_encoder* enc, const sdr
       a.recall = metric == 0 ? scores + row0 : nullptr;
       a.ndcg = metric == 1 ? scores + row0 : nullptr;
       const RankCheck ck{held_nnz, train_nnz, e->feed_flag};
-      if ((rc = hip_rc(e, "k_rank_metrics_checked", profiled(e, PC_EVAL_HALF, 0.0, st, [&] {
-             SDRM_LAUNCH(e, k_rank_metrics_checked, dim3((unsigned)b), dim3(256), lds, st, a, ck);
-             return hipGetLastError();
-           }))))
-        return rc;
+      if ((rc = launch_k(e, PC_EVAL_HALF, "k_rank_metrics_checked", k_rank_metrics_checked, dim3((unsigned)b), dim3(256), lds, st, a, ck))) return rc;
     }
   }
   return SDRM_OK;
