@@ -667,6 +667,40 @@ int sdrm_neumf_scores(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users,
 int sdrm_neumf_pair_loss(sdrm_engine* e, const sdrm_neumf* w, const int32_t* users, const int32_t* items, const float* labels, int64_t n,
                          float* logits, double* loss_sum, void* stream);
 
+/* The NeuMF evaluator's TRAIN steps on the device (reference: neural_cf_benchmark_pt.py:186-200, the batch loop of an epoch - `model.zero_grad()`,
+ * `model(X[:, 0], X[:, 1])` in TRAIN mode :125-144, `BCEWithLogitsLoss` :197, `loss.backward()` :199 and `optimizer.step()` :200 of the
+ * `optim.Adam` of :169; csrc/neumf_train.h).  With s = 1 / (1 - p_drop) and k0, k1, k2 the keep decisions of the three Dropout modules:
+ *   a0 = k0 s [Pm[u]; Qm[i]];  a1 = k1 s relu(W1 a0 + b1);  a2 = k2 s relu(W2 a1 + b2);  h3 = relu(W3 a2 + b3);  g = Pg[u] * Qg[i]
+ *   y = wp [g; h3] + bp;  loss = mean_j(max(y, 0) - y l + log1p(exp(-|y|)));  dy_j = (sigmoid(y_j) - l_j) / b
+ * followed by the gradients of all twelve tensors and torch.optim.Adam's default DENSE update of all twelve (a table row outside the batch
+ * still moves while its moments are non-zero), Adam's step count for step t of the call being step0 + t + 1.
+ * The struct holds DEVICE pointers to the twelve LIVE tensors p (updated in place) and to their moments m = exp_avg, v = exp_avg_sq (the
+ * same shapes, updated in place), in the order of sdrm_neumf's fields (= `state_dict()`): float32, contiguous, no two of them sharing a
+ * byte (SDRM_ERR_ARG).  factor is 8 or 16; factor 32 is NOT built for training and is SDRM_ERR_SHAPE.
+ * sdrm_neumf_train_steps replaces :186-200 for a whole pass over triples [n][3] int32 (user, item, label 0 / 1) on the device: ceil(n / batch)
+ *   consecutive steps over the array in order, the last one partial, 1 <= batch <= 1024, 1 <= n <= 2^31 - 1.  Four launches per step, all
+ *   enqueued on `stream`; nothing is read back and no step waits for the host.  Scratch is library-owned and grow-only: a call whose scratch
+ *   must grow - the first one, and each one with larger tables than any before it on the handle - synchronises the DEVICE and frees the old
+ *   buffer before it allocates (such a call cannot run under graph capture); a call that fits does not synchronise.
+ *   Arithmetic is fp32; every sum (a weight gradient over the batch, the gradient of a table row that several pairs share, in ascending
+ *   pair order, the loss: fp32 terms, float64 sum by a fixed tree) has a fixed order and there is no floating-point atomic: the same
+ *   bits on every run, and a call over the whole array gives the bits of one call per batch.
+ *   Ids are range-checked on the device: a pair with a user outside [0, n_users) or an item outside [0, n_items) raises the feed status word
+ *   (sdrm_feed_status: "row" for a user, "column" for an item), contributes nothing to the loss or to any gradient and still counts in the
+ *   divisor b; no load or store uses the id.
+ *   Dropout: mode SDRM_RNG_EXPLICIT reads keep [n][14 factor] uint8 (per pair: 8 factor bytes of k0, 4 factor of k1, 2 factor of k2; non-zero
+ *   = kept); SDRM_RNG_PHILOX ignores keep: column c of the pair at position j of `triples` is kept iff word c & 3 of Philox4x32-10 with
+ *   counter (j, c >> 2, 10, call_id) and key seed is >= floor(p_drop 2^32), 0 <= p_drop < 1 - so a call is a function of (seed, call_id)
+ *   and of nothing the host drew.
+ *   losses: DEVICE double [ceil(n / batch)] that receives each step's loss, or null.  grads: HOST array of twelve DEVICE pointers that
+ *   receive the dense gradients of the LAST step of the call (each the size of its tensor), or null.
+ *   SDRM_ERR_ARG: a null pointer, EXPLICIT without keep, an unknown mode, step0 < 0, p_drop outside [0, 1), overlapping tensors;
+ *   SDRM_ERR_SHAPE: factor outside {8, 16}, a table without rows, n or batch outside their ranges.  Refused calls launch nothing. */
+typedef struct sdrm_neumf_train { float* p[12]; float* m[12]; float* v[12]; int n_users, n_items, factor; } sdrm_neumf_train;
+int sdrm_neumf_train_steps(sdrm_engine* e, const sdrm_neumf_train* s, const int32_t* triples, int64_t n, int batch, int64_t step0, float lr,
+                           float beta1, float beta2, float eps, float p_drop, int mode, const uint8_t* keep, uint64_t seed, uint32_t call_id,
+                           double* losses, float* const* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -227,6 +227,11 @@ int sdrm_debug_svd_stage(sdrm_engine* e, const int64_t* indptr, const int32_t* i
  * above 2^40). */
 int sdrm_debug_neumf_args(int n_users, int n_items, int factor, int64_t listed_users, int64_t listed_items);
 
+/* The host side of sdrm_neumf_train_steps that needs no device: SDRM_OK, SDRM_ERR_SHAPE for a call outside its envelope (factor outside
+ * {8, 16} - 32 is not built for training -, a table without rows, n outside 1 .. 2^31 - 1, batch outside 1 .. 1024), or SDRM_ERR_ARG
+ * (step0 < 0, p_drop outside [0, 1) or not a number). */
+int sdrm_debug_neumf_train_args(int n_users, int n_items, int factor, int64_t n, int batch, int64_t step0, float p_drop);
+
 #ifdef __cplusplus
 }
 #endif

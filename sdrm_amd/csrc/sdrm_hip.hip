@@ -30,6 +30,7 @@
 #include "input_layer.h"
 #include "latent.h"
 #include "neumf.h"
+#include "neumf_train.h"
 #include "nll.h"
 #include "rank.h"
 #include "rowchain.h"
@@ -184,6 +185,10 @@ enum Scratch {
   // sdrm_neumf_scores / sdrm_neumf_pair_loss (csrc/neumf.h): W2t | W3t | the staged user and item sides; the validity words of both sides
   // (int); the pair kernel's per-block loss partials (float64)
   SCR_NEUMF_WS, SCR_NEUMF_VALID, SCR_NEUMF_PART,
+  // sdrm_neumf_train_steps (csrc/neumf_train.h): the step's column-major workspace [NtCols::COUNT][NT_LD] with the dense gradients of the
+  // eight tower tensors behind it | the dense gradients of the four embedding tables, ALL ZERO between two calls (a step writes the rows
+  // its pairs name and zeroes them again): nothing else may ever be carved out of that slot
+  SCR_NEUMF_TRAIN_WS, SCR_NEUMF_TRAIN_TAB,
   SCR_CSR_WS,        // sdrm_equal_sparsity_csr_begin / _end (csrc/compact.h), 8-byte words: [mask words | row offsets int64 | row counts uint32]
   // sdrm_csr_transpose / sdrm_csr_vstack (csrc/csr_transpose.h), 8-byte words: [checked | total | bit table | colptr int64 | offsets uint32 |
   // column counts uint32] and [total | indptr int64 | row lengths uint32]
@@ -293,7 +298,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -323,6 +328,10 @@ static const char* kProfNames[PC_COUNT] = {
     "neumf evaluator: k_neumf_stage layer 1 split per listed user / item, the GMF rows, W2 and W3 transposed",
     "neumf evaluator: k_neumf_scores eval-mode forward of all listed users x listed items (fp32 vector FMAs, scalar weight operands)",
     "neumf evaluator: k_neumf_pairs / k_neumf_loss_sum eval-mode forward of listed pairs and the BCE-with-logits numerator (float64 partials, fixed order)",
+    "neumf train step: k_nt_pairs train-mode forward with dropout, loss terms and the backward down to the embedding rows, a lane per pair (fp32 vector FMAs, scalar weight operands)",
+    "neumf train step: k_nt_grads weight and bias gradients of the tower (fixed pair order), the dense table-gradient rows of the batch, the loss (float64, fixed tree)",
+    "neumf train step: k_vae_adam dense Adam over the twelve tensors in one launch",
+    "neumf train step: k_nt_clear the batch's rows of the dense table gradients zeroed again",
     "csr transpose: k_csrt_mark_lds / k_csrt_mark one pass over the entries, a row's bit into the row-blocked bit table (LDS column tiles, or 64-bit global atomics into a table cleared first), the count of checked entries",
     "csr transpose: k_csrt_colscan a thread per column, running popcounts over the row blocks and the column counts",
     "csr transpose: k_csr_scan column counts -> colptr (one work-group)",
@@ -4126,6 +4135,143 @@ int sdrm_neumf_pair_loss(sdrm_engine* e, const sdrm_neumf* w, const int32_t* use
     case 16: return neumf_pairs<16>(e, w, users, items, labels, n, logits, loss_sum, st);
     default: return neumf_pairs<32>(e, w, users, items, labels, n, logits, loss_sum, st);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The NeuMF evaluator's train steps (neural_cf_benchmark_pt.py:186-200: the batch loop with zero_grad, the train-mode forward, BCEWithLogitsLoss,
+// backward and optimizer.step()), csrc/neumf_train.h: per step k_nt_pairs, k_nt_grads, k_vae_adam, k_nt_clear; a whole call is enqueued
+// without a host synchronisation.
+namespace {
+
+constexpr int NT_TENSORS = 12;
+
+extern "C++" {
+
+template <int F>
+int neumf_train_steps(sdrm_engine* e, const sdrm_neumf_train* s, const int32_t* triples, int64_t n, int batch, int64_t step0, float lr, float beta1,
+                      float beta2, float eps, float p_drop, const uint8_t* keep, uint64_t seed, uint32_t call_id, double* losses,
+                      float* const* grads, hipStream_t st) {
+  using Cols = NtCols<F>;
+  const int64_t nu = s->n_users, ni = s->n_items;
+  const int64_t count[NT_TENSORS] = {nu * F, ni * F, nu * 4 * F, ni * 4 * F, 32 * F * F, 4 * F, 8 * F * F, 2 * F, 2 * F * F, F, 2 * F, 1};
+  // dense gradients: the four tables in their own slot (all zero between calls), the eight tower tensors behind the step's workspace;
+  // every one starts on a 16-byte boundary (k_vae_adam's 16-byte accesses)
+  size_t off[NT_TENSORS], tab = 0, tower = (size_t)Cols::COUNT * NT_LD;
+  for (int i = 0; i < NT_TENSORS; ++i) {
+    size_t& at = i < 4 ? tab : tower;
+    off[i] = at;
+    at += ((size_t)count[i] + 3) / 4 * 4;
+  }
+  float *ws, *gt;
+  if (int rc = scratch(e, SCR_NEUMF_TRAIN_WS, tower, &ws)) return rc;
+  if (int rc = scratch(e, SCR_NEUMF_TRAIN_TAB, tab, &gt)) return rc;
+  float* g[NT_TENSORS];
+  for (int i = 0; i < NT_TENSORS; ++i) g[i] = (i < 4 ? gt : ws) + off[i];
+  // Adam's table, the same for every step of the call; its refusals (a range of p, m, v or g sharing a byte with another) before any launch
+  {
+    uint64_t addr[4 * NT_TENSORS];
+    float coef[NT_TENSORS] = {0};
+    for (int i = 0; i < NT_TENSORS; ++i) {
+      addr[4 * i] = (uint64_t)(uintptr_t)s->p[i]; addr[4 * i + 1] = (uint64_t)(uintptr_t)g[i];
+      addr[4 * i + 2] = (uint64_t)(uintptr_t)s->m[i]; addr[4 * i + 3] = (uint64_t)(uintptr_t)s->v[i];
+    }
+    if (int rc = sdrm_debug_vae_adam_args(addr, count, coef, NT_TENSORS, step0 + 1, 0, 0, nullptr))
+      return fail(e, rc, "sdrm_neumf_train_steps: two of the parameter / moment tensors share a byte, or a table of more than 2^40 elements");
+  }
+  VAdamTable tabl{};
+  tabl.n = NT_TENSORS;
+  unsigned chunks = 0;
+  for (int i = 0; i < NT_TENSORS; ++i) {
+    VAdamTensor& d = tabl.t[i];
+    d.p = s->p[i]; d.g = g[i]; d.m = s->m[i]; d.v = s->v[i]; d.n = count[i];
+    d.wd2 = 0.f;
+    d.first_chunk = chunks;
+    d.vector_ok = (((uintptr_t)d.p | (uintptr_t)d.g | (uintptr_t)d.m | (uintptr_t)d.v) & 15u) == 0;
+    chunks += (unsigned)((count[i] + VADAM_CHUNK - 1) / VADAM_CHUNK);
+  }
+  const double p = (double)p_drop;
+  NtPairArgs pa{};
+  pa.ws = ws; pa.flag = e->feed_flag; pa.n_users = s->n_users; pa.n_items = s->n_items;
+  pa.k0 = (uint32_t)seed; pa.k1 = (uint32_t)(seed >> 32); pa.call_id = call_id;
+  pa.thr = (uint32_t)std::floor(p * 4294967296.0);
+  pa.s = (float)(1.0 / (1.0 - p));
+  NtGradArgs ga{};
+  const int in[4] = {8 * F, 4 * F, 2 * F, 2 * F}, out[4] = {4 * F, 2 * F, F, 1};
+  const int colA[4] = {Cols::A0, Cols::A1, Cols::A2, Cols::AP}, colD[4] = {Cols::DZ1, Cols::DZ2, Cols::DZ3, Cols::DY};
+  int wb = 0;
+  for (int l = 0; l < 4; ++l) {
+    ga.layer[l] = NtLayerJob{ws + (size_t)colA[l] * NT_LD, ws + (size_t)colD[l] * NT_LD, g[4 + 2 * l], g[5 + 2 * l], in[l], out[l], wb};
+    wb += (out[l] * (in[l] + 1) + 255) / 256;
+  }
+  ga.w_blocks = wb;
+  const int* uid = reinterpret_cast<const int*>(ws + (size_t)Cols::UID * NT_LD);
+  const int* iid = reinterpret_cast<const int*>(ws + (size_t)Cols::IID * NT_LD);
+  ga.ids[0] = uid; ga.ids[1] = iid;
+  ga.D[0] = ws + (size_t)Cols::DU * NT_LD; ga.D[1] = ws + (size_t)Cols::DI * NT_LD;
+  ga.g_mlp[0] = g[2]; ga.g_mlp[1] = g[3]; ga.g_gmf[0] = g[0]; ga.g_gmf[1] = g[1];
+  ga.lt = ws + (size_t)Cols::LT * NT_LD;
+  const int64_t steps = (n + batch - 1) / batch;
+  for (int64_t t = 0; t < steps; ++t) {
+    const int64_t j0 = t * batch;
+    const int b = (int)std::min<int64_t>(batch, n - j0);
+    pa.triples = triples + 3 * j0;
+    pa.keep = keep ? keep + (size_t)j0 * 14 * F : nullptr;
+    pa.b = b; pa.j0 = (uint32_t)j0;
+    const double fl_pair = 2.0 * (2.0 * 42.0 * F * F + 4.0 * F);
+    if (int rc = launch_k(e, {PC_NEUMF_TRAIN_PAIRS, fl_pair * b}, "k_nt_pairs", k_nt_pairs<F>, dim3((unsigned)((b + NT_PAIR_BLOCK - 1) / NT_PAIR_BLOCK)),
+                          dim3(NT_PAIR_BLOCK), 0, st, (const float*)s->p[0], (const float*)s->p[1], (const float*)s->p[2], (const float*)s->p[3],
+                          (const float*)s->p[4], (const float*)s->p[5], (const float*)s->p[6], (const float*)s->p[7], (const float*)s->p[8],
+                          (const float*)s->p[9], (const float*)s->p[10], (const float*)s->p[11], pa))
+      return rc;
+    ga.b = b;
+    ga.row_blocks = (b * 5 * F + 255) / 256;
+    ga.loss = losses ? losses + t : nullptr;
+    const unsigned gblocks = (unsigned)(wb + 2 * ga.row_blocks + (losses ? 1 : 0));
+    if (int rc = launch_k(e, {PC_NEUMF_TRAIN_GRADS, 2.0 * (42.0 * F * F + 2.0 * F) * b}, "k_nt_grads", k_nt_grads<F>, dim3(gblocks), dim3(256), 0, st, ga))
+      return rc;
+    if (grads && t == steps - 1)
+      for (int i = 0; i < NT_TENSORS; ++i) HIP_TRY(e, hipMemcpyAsync(grads[i], g[i], (size_t)count[i] * sizeof(float), hipMemcpyDeviceToDevice, st));
+    VAdamArgs aa{};
+    adam_scalars(step0 + t + 1, lr, (double)beta1, (double)beta2, aa.step_size, aa.bc2_sqrt);
+    aa.b1 = beta1; aa.b2 = beta2; aa.eps = eps;
+    if (int rc = launch_k(e, PC_NEUMF_TRAIN_ADAM, "k_vae_adam", k_vae_adam, dim3(chunks), dim3(256), 0, st, tabl, aa)) return rc;
+    if (int rc = launch_k(e, PC_NEUMF_TRAIN_CLEAR, "k_nt_clear", k_nt_clear<F>, dim3((unsigned)((2 * b * 5 * F + 255) / 256)), dim3(256), 0, st, uid, iid,
+                          g[2], g[0], g[3], g[1], b))
+      return rc;
+  }
+  return SDRM_OK;
+}
+
+}  // extern "C++"
+
+}  // namespace
+
+// The host side that needs no device: the envelope of sdrm_neumf_train_steps.
+int sdrm_debug_neumf_train_args(int n_users, int n_items, int factor, int64_t n, int batch, int64_t step0, float p_drop) {
+  if (factor != 8 && factor != 16) return SDRM_ERR_SHAPE;   // (32 as well: csrc/neumf_train.h)
+  if (n_users < 1 || n_items < 1 || n < 1 || n > (int64_t)0x7fffffff || batch < 1 || batch > NT_LD) return SDRM_ERR_SHAPE;
+  if (step0 < 0 || step0 > ((int64_t)1 << 52)) return SDRM_ERR_ARG;
+  if (!(p_drop >= 0.f && p_drop < 1.f)) return SDRM_ERR_ARG;   // (a NaN fails both compares)
+  return SDRM_OK;
+}
+
+int sdrm_neumf_train_steps(sdrm_engine* e, const sdrm_neumf_train* s, const int32_t* triples, int64_t n, int batch, int64_t step0, float lr, float beta1,
+                           float beta2, float eps, float p_drop, int mode, const uint8_t* keep, uint64_t seed, uint32_t call_id, double* losses,
+                           float* const* grads, void* stream) {
+  const char* who = "sdrm_neumf_train_steps";
+  if (!e) return SDRM_ERR_ARG;
+  if (!s || !triples) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  for (int i = 0; i < NT_TENSORS; ++i)
+    if (!s->p[i] || !s->m[i] || !s->v[i] || (grads && !grads[i])) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null tensor pointer");
+  if (mode != SDRM_RNG_EXPLICIT && mode != SDRM_RNG_PHILOX) return fail(e, SDRM_ERR_ARG, std::string(who) + ": mode is neither SDRM_RNG_EXPLICIT nor SDRM_RNG_PHILOX");
+  if (mode == SDRM_RNG_EXPLICIT && !keep) return fail(e, SDRM_ERR_ARG, std::string(who) + ": SDRM_RNG_EXPLICIT needs keep [n][14 factor]");
+  if (int rc = sdrm_debug_neumf_train_args(s->n_users, s->n_items, s->factor, n, batch, step0, p_drop))
+    return fail(e, rc, std::string(who) + ": factor outside {8, 16} (32 is not built: csrc/neumf_train.h), a table without rows, n outside 1 .. 2^31 - 1 or "
+                                          "batch outside 1 .. 1024 (SDRM_ERR_SHAPE); step0 < 0 or p_drop outside [0, 1) (SDRM_ERR_ARG)");
+  const uint8_t* k = mode == SDRM_RNG_EXPLICIT ? keep : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  if (s->factor == 8) return neumf_train_steps<8>(e, s, triples, n, batch, step0, lr, beta1, beta2, eps, p_drop, k, seed, call_id, losses, grads, st);
+  return neumf_train_steps<16>(e, s, triples, n, batch, step0, lr, beta1, beta2, eps, p_drop, k, seed, call_id, losses, grads, st);
 }
 
 // ---------------------------------------------------------------------------------------------

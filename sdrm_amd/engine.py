@@ -1238,6 +1238,66 @@ class Engine:
             self.feed_status()
         return logits, loss_sum
 
+    # ------------------------------------------------------------------ NeuMF evaluator's train steps (csrc/neumf_train.h)
+    NEUMF_TRAIN_FACTORS = (8, 16)
+    NEUMF_TRAIN_MAX_BATCH = 1024
+
+    def neumf_train_steps(self, weights, exp_avg, exp_avg_sq, triples, batch, step0, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, p_drop=0.5, seed=0,
+                          call_id=0, keep=None, grads=None, check=True):
+        """neural_cf_benchmark_pt.py:186-200 on the device (sdrm_neumf_train_steps): ceil(n / batch) consecutive train steps of NeuMF-end
+        over `triples` (int32 device tensor [n, 3]: user, item, label) in order, the last batch partial - train-mode forward with the
+        three dropouts, BCEWithLogitsLoss, the gradients of all twelve tensors and `torch.optim.Adam`'s dense update, all enqueued by this
+        one call with no host synchronisation between steps.  `weights`: the live module's twelve float32 tensors (`NEUMF_TENSORS` order),
+        UPDATED IN PLACE; `exp_avg`, `exp_avg_sq`: twelve tensors of the same shapes, Adam's moments, updated in place.  Adam's step count
+        for step t of the call is `step0 + t + 1` - the caller's number, the engine keeps nothing of the optimizer.
+        Dropout: with `keep` (uint8 device tensor [n, 14 factor]; per pair 8 factor bytes for the input of layer 1, 4 factor for layer 2,
+        2 factor for layer 3, non-zero = kept) the masks are the caller's; without, they are Philox4x32-10's of (seed, call_id, the pair's
+        place in `triples`, column) - never torch's generator.  `grads`: twelve float32 tensors of the weights' shapes that receive the
+        dense gradients of the LAST step.  Ids are range-checked on the device (such a pair adds nothing, the divisor still counts it);
+        `check` as in `csr_rows_to_dense`.  Returns the per-step losses, a float64 device tensor [ceil(n / batch)]."""
+        who = "neumf_train_steps"
+        w, ts, n_users, n_items = self._neumf(who, weights)
+        F = int(ts[0].shape[1])
+        if F not in self.NEUMF_TRAIN_FACTORS:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: factor {F} outside {self.NEUMF_TRAIN_FACTORS} (the train step is not built for 32)")
+        lists = {"exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
+        if grads is not None:
+            lists["grads"] = grads
+        checked = {}
+        for lname, lst in lists.items():
+            lst = list(lst.values()) if isinstance(lst, dict) else list(lst)
+            if len(lst) != len(ts):
+                raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {lname} has {len(lst)} tensors, the weights have {len(ts)}")
+            checked[lname] = [self._f32(who, f"{lname}[{name}]", t, p.shape) for name, t, p in zip(self.NEUMF_TENSORS, lst, ts)]
+        if (not isinstance(triples, torch.Tensor) or triples.dtype != torch.int32 or triples.device != self.device or not triples.is_contiguous()
+                or triples.dim() != 2 or triples.shape[1] != 3):
+            raise SdrmError(f"{who}: triples must be a contiguous int32 tensor [n, 3] on the engine's device")
+        n, batch, step0 = int(triples.shape[0]), int(batch), int(step0)
+        if n < 1 or n > 2 ** 31 - 1 or batch < 1 or batch > self.NEUMF_TRAIN_MAX_BATCH:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: n = {n} outside 1 .. 2^31 - 1 or batch = {batch} outside 1 .. {self.NEUMF_TRAIN_MAX_BATCH}")
+        if step0 < 0 or not (0.0 <= float(p_drop) < 1.0):
+            raise SdrmError(f"{who}: SDRM_ERR_ARG: step0 = {step0} < 0 or p_drop = {p_drop} outside [0, 1)")
+        mode = 1
+        if keep is not None:
+            if (not isinstance(keep, torch.Tensor) or keep.dtype != torch.uint8 or keep.device != self.device or not keep.is_contiguous()
+                    or tuple(keep.shape) != (n, 14 * F)):
+                raise SdrmError(f"{who}: keep must be a contiguous uint8 tensor [{n}, {14 * F}] on the engine's device")
+            mode = 0
+        rec = _lib.NeumfTrain()
+        for i in range(len(ts)):
+            rec.p[i], rec.m[i], rec.v[i] = ts[i].data_ptr(), checked["exp_avg"][i].data_ptr(), checked["exp_avg_sq"][i].data_ptr()
+        rec.n_users, rec.n_items, rec.factor = n_users, n_items, F
+        gptr = None
+        if grads is not None:
+            gptr = (C.c_void_p * len(ts))(*[t.data_ptr() for t in checked["grads"]])
+        losses = torch.empty(-(-n // batch), dtype=torch.float64, device=self.device)
+        self._check(self.lib.sdrm_neumf_train_steps(self._h, C.byref(rec), _ptr(triples), n, batch, step0, float(lr), float(betas[0]), float(betas[1]),
+                                                    float(eps), float(p_drop), mode, _ptr(keep), int(seed) & (2 ** 64 - 1), int(call_id) & 0xFFFFFFFF,
+                                                    _ptr(losses), gptr, _stream()), "sdrm_neumf_train_steps")
+        if check:
+            self.feed_status()
+        return losses
+
     # ------------------------------------------------------------------ evaluation half of the VAE pre-stage (csrc/eval_half.h)
     def vae_eval_holdout(self, w1, b1, w2, b2, w3, b3, w4, b4, train_csr_dev, held_csr_dev, k, metric, batch=500, out=None, logits=None,
                          check=False):

@@ -4,7 +4,8 @@ The reference trains NeuMF-end on (user, item, label) triples and, after every e
 of the validation users and the training items through the model in batches of 10000, merges the logits twice in pandas, rebuilds two
 CSR matrices through Python dicts, densifies them and ranks.  Here that evaluation half has a device form: `Engine.neumf_scores`
 (csrc/neumf.h) gives the dense logit matrix, `Engine.rank_metrics` masks and ranks it, `Engine.neumf_pair_logits` gives the per-epoch
-validation loss; the train loop stays PyTorch.  With `engine=None` the same functions run torch and numpy on the host - the checker.
+validation loss.  The train loop is PyTorch by default; with `device_train=True` an epoch's batch loop is ONE `Engine.neumf_train_steps`
+call (csrc/neumf_train.h: forward with dropout, loss, backward and Adam on the device).  With `engine=None` the same functions run torch and numpy on the host - the checker.
 
 Triples are a numpy int array [n, 3] (user, item, label); a (user, item) pair occurs at most once per array.  Labels are taken as
 binary (> 0), which is what the reference feeds its evaluators.  No pandas, no sklearn."""
@@ -187,7 +188,7 @@ def validation_loss(model, triples, engine=None):
 
 
 def compute_neuralcf_results(training, validation, n_users, n_items, engine=None, seed=0, epochs=20, eval_recall=True, device=None,
-                             history=None):
+                             history=None, device_train=False):
     """The reference's driver (:154-334) over int triples [n, 3]: (recall [6], ndcg [6]) for `K_LIST`, nanmean over the validation users
     rounded to 4 places.  As the reference: NCF(factor 8, three layers, dropout 0.5), Adam(1e-3), BCEWithLogitsLoss, batches of 256; per
     epoch a fresh 80/20 split of `training`, as many label-0 rows of the 80 % drawn again WITH replacement as it has label-1 rows
@@ -205,15 +206,31 @@ def compute_neuralcf_results(training, validation, n_users, n_items, engine=None
     The train loop is torch in both modes and runs on `device` (default: the engine's device, the CPU without one).  With an engine the
     per-epoch validation loss is `neumf_pair_logits`, both rankings are `rank_all_items(..., engine)`, and `feed_status()` is asked once
     per evaluation; weights that live elsewhere than on the engine's device are copied there per evaluation.
+    `device_train=True` (needs an engine; the model then lives on the engine's device) replaces the batch loop :186-200 of every epoch by
+    ONE `Engine.neumf_train_steps` call: the shuffled triples are uploaded as int32 once per epoch, Adam's moments are twelve zero tensors
+    made once and its step count runs on across the epochs, no torch optimizer exists and no autograd runs.  The split, the negatives, the
+    shuffle, the early stop and which weights rank are untouched - but the DROPOUT draws are then the engine's Philox4x32-10 of
+    (seed, epoch, the triple's place in the epoch's array, column), not torch's generator, so the trained weights differ from the torch
+    loop's as two seeds of it differ.  `history` then also receives 'train_loss': every step's loss, read back once per epoch.
     `history`: a dict that receives 'valid_loss' (per epoch), 'recall10' (per epoch, with eval_recall), 'best_epoch' (the epoch whose
     weights ranked), 'reference_has_no_checkpoint', 'best_recall_epoch', 'epochs_run', 'per_user' (the final per-user recall / ndcg)
     and 'model' (the module that ranked)."""
     training, validation = _as_triples(training, "training"), _as_triples(validation, "validation")
     device = torch.device(device) if device is not None else (engine.device if engine is not None else torch.device("cpu"))
+    if device_train:
+        if engine is None:
+            raise ValueError("compute_neuralcf_results: device_train=True needs an engine (the train step runs on the device; there is no host form)")
+        if device != engine.device:
+            raise ValueError(f"compute_neuralcf_results: device_train=True trains on the engine's device {engine.device}, not on {device}")
     rng = np.random.default_rng(seed)
     torch.manual_seed(seed)
     model = NCF(n_users, n_items, factor=8, layers=3, dropout=0.5).to(device)
-    optimizer = torch.optim.Adam(model.parameters(), lr=LR)
+    train_losses, steps_done = [], 0
+    if device_train:
+        live = model.engine_weights()                        # the parameters themselves: the engine updates them in place
+        exp_avg, exp_avg_sq = [torch.zeros_like(t) for t in live], [torch.zeros_like(t) for t in live]
+    else:
+        optimizer = torch.optim.Adam(model.parameters(), lr=LR)
     best_loss, best_epoch, best_recall, best_recall_epoch, early_stop = math.inf, 0, 0.0, None, 0
     kept = {0: None}
     valid_losses, recalls, epochs_run = [], [], 0
@@ -228,7 +245,13 @@ def compute_neuralcf_results(training, validation, n_users, n_items, engine=None
         if n_pos and negatives.shape[0]:
             part = np.concatenate([part, negatives[rng.integers(0, negatives.shape[0], size=n_pos * NUM_NEG)]])
         part = part[rng.permutation(part.shape[0])]
-        for s in range(0, part.shape[0], BATCH):
+        if device_train:
+            triples_dev = torch.from_numpy(np.ascontiguousarray(part, dtype=np.int32)).to(device)
+            losses = engine.neumf_train_steps(live, exp_avg, exp_avg_sq, triples_dev, BATCH, steps_done, lr=LR, p_drop=0.5, seed=seed, call_id=epoch,
+                                              check=False)     # (the evaluation below asks feed_status)
+            steps_done += int(losses.numel())
+            train_losses.extend(losses.cpu().tolist())
+        for s in () if device_train else range(0, part.shape[0], BATCH):
             x = torch.as_tensor(part[s:s + BATCH], dtype=torch.int32, device=device)
             model.zero_grad()
             loss = _bce_with_logits(model(x[:, 0], x[:, 1]), x[:, 2].float())
@@ -269,6 +292,8 @@ def compute_neuralcf_results(training, validation, n_users, n_items, engine=None
     rec, ndcg = rank_all_items(model, training, validation, validation[:, 0], engine)
     if history is not None:
         history.update(valid_loss=valid_losses, recall10=recalls, best_epoch=best_epoch, reference_has_no_checkpoint=no_checkpoint, best_recall_epoch=best_recall_epoch, epochs_run=epochs_run, per_user=(rec, ndcg), model=model)
+        if device_train:
+            history["train_loss"] = train_losses
     with np.errstate(invalid="ignore"):
         return (np.array([np.round(np.nanmean(rec[q]), 4) for q in range(len(K_LIST))]),
                 np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
