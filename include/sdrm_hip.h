@@ -629,6 +629,46 @@ int sdrm_svd_fit(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, 
 int sdrm_svd_scores(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n_rows, int64_t nnz,
                     const int64_t* rows, int64_t row0, int b, int n_items, const float* components, int k, float* scores, void* stream);
 
+/* Non-negative matrix factorisation of a sparse matrix on the device, and the scores of its reconstruction (reference:
+ * svd_benchmark.py:49-54 with nnmf=True, `NMF(n_components=15, max_iter=50)` fitted on the stacked matrix, `inverse_transform(fit_transform(.))`
+ * as the score matrix; sklearn's defaults: the `cd` solver, no regularisation, no shuffle, tol = 1e-4, init = NNDSVDa).  csrc/nmf.h.
+ * Everything is float64.  A factor is stored row-major with a row stride of 16 doubles, 16-byte aligned: W [m][16], Ht = H^T [n][16]; the
+ * columns k .. 15 are zero on entry and on exit and are never read into a result.  The matrix X [m, n] is device-resident under the contract
+ * of sdrm_svd_fit: CSR (indptr [m + 1] int64, indices [nnz] int32, data [nnz] float32 or null for all ones) and, for the fit, CSC as well.
+ * sdrm_nmf_fit: W and Ht are the start on entry (sklearn's init='custom') and the result on exit.  Iteration i = 1 .. max_iter updates W, then
+ *   H, by one cyclic sweep of coordinate descent each (`_update_coordinate_descent`: the product X Ht gathered in CSR order, the Gram matrix
+ *   Ht^T Ht from per-work-group partials added in block order, then per row, t ascending: grad = -XHt[t] + sum_r HHt[t][r] W[r]; the
+ *   projected gradient pg = grad, or min(0, grad) where W[t] == 0, adds |pg| to the violation; W[t] = max(W[t] - grad / HHt[t][t], 0) unless
+ *   HHt[t][t] == 0).  Every sum is one fused chain in a fixed order, nothing is atomic: the same bits on every call.  After iteration i the
+ *   device forms v_i = violation of both halves, stores it in violations_dev[i - 1], and stops when v_1 == 0 or v_i / v_1 <= tol: *n_iter_dev
+ *   = i, the factors are those of iteration i, the launches behind it return at once and violations_dev[i ..] stay 0.  Without a stop
+ *   *n_iter_dev = max_iter.  n_iter_dev: a device int32; violations_dev: device float64 [max_iter].  Five launches per iteration, all
+ *   queued by the one call: NO synchronisation and no read-back.
+ *   SDRM_ERR_SHAPE, before any launch: k outside 1 .. 16, max_iter outside 1 .. 10000, tol < 0 (or NaN), m or n outside 1 .. 2^22, nnz
+ *   outside 0 .. 2^40 - 1.  A null pointer, data without cdata or a factor off the 16-byte grid is SDRM_ERR_ARG.
+ * sdrm_nmf_init: W0 [m][16], Ht0 [n][16] = `_initialize_nmf(X, k, init='nndsvda')` with the truncated SVD that sdrm_svd_fit leaves -
+ *   components [k, n] float32 on the device, singular_values_host [k] on the HOST - in the place of sklearn's randomized one: U = X V^T /
+ *   sigma by the fit's product kernel in float64; component 0 is sqrt(sigma_0) |u_0|, sqrt(sigma_0) |v_0|; component j >= 1 the positive or
+ *   the negative parts of (u_j, v_j), whichever pair has the larger product of norms (the negative pair on a tie), normalised and scaled by
+ *   sqrt(sigma_j x that product); an entry below 1e-6 becomes 0 and every zero becomes X.mean() - (entries) / (m n) for all-ones data, else
+ *   the sum of the values in a fixed order over m n.  The sign of a component does not matter.  Six launches, no synchronisation.
+ *   SDRM_ERR_SHAPE as above; a singular value that is not positive and finite is SDRM_ERR_ARG.
+ * sdrm_nmf_scores: scores [b, n_items] float32 contiguous, scores[r][j] = sum_{c < k} W[row_r][c] Ht[j][c], c ascending, added in float64
+ *   and rounded once, for the rows rows[0..b) of W [n_rows][16] (or row0 .. row0+b-1 when rows is null).  One launch, every element written
+ *   exactly once, no synchronisation.  Seen items are NOT masked: sdrm_rank_metrics does that.
+ *   SDRM_ERR_SHAPE: k outside 1 .. 16, b, n_items or n_rows outside 1 .. 2^22, b x n_items at or above 2^40, a contiguous range that ends
+ *   behind n_rows.
+ * Range checks of all three, into the status word sdrm_feed_status reports: row ids, indptr / colptr pairs (negative, out of order or reaching
+ * behind nnz: the row is empty), column / row indices outside the matrix (the entry is skipped); a listed row of sdrm_nmf_scores outside
+ * [0, n_rows) is a zero row.  No load or store uses an unchecked index.  Scratch is library-owned and grow-only. */
+int sdrm_nmf_fit(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, const int64_t* colptr, const int32_t* rowidx,
+                 const float* cdata, int64_t m, int64_t n, int64_t nnz, int k, int max_iter, double tol, double* W, double* Ht, int32_t* n_iter_dev,
+                 double* violations_dev, void* stream);
+int sdrm_nmf_init(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t m, int64_t n, int64_t nnz, int k,
+                  const float* components, const double* singular_values_host, double* W0, double* Ht0, void* stream);
+int sdrm_nmf_scores(sdrm_engine* e, const double* W, const double* Ht, int64_t n_rows, int k, const int64_t* rows, int64_t row0, int b, int n_items,
+                    float* scores, void* stream);
+
 /* The NeuMF evaluator's forward on the device, EVAL MODE only (reference: neural_cf_benchmark_pt.py:125-144, `NCF.forward` of the
  * 'NeuMF-end' model with dropout off; csrc/neumf.h).  For a user u and an item i, factor F, three MLP layers:
  *   g = Pg[u] * Qg[i];  h1 = relu(W1 [Pm[u]; Qm[i]] + b1);  h2 = relu(W2 h1 + b2);  h3 = relu(W3 h2 + b3);  y = wp [g; h3] + bp

@@ -140,6 +140,10 @@ SIGNATURES = {
                              C.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_svd_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p,
                                 c_void_p]),
+    "sdrm_nmf_fit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, C.c_double,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdrm_nmf_init": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdrm_nmf_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "sdrm_neumf_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sdrm_neumf_pair_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sdrm_neumf_train_steps": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_int,

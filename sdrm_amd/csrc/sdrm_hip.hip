@@ -32,6 +32,7 @@
 #include "neumf.h"
 #include "neumf_train.h"
 #include "nll.h"
+#include "nmf.h"
 #include "rank.h"
 #include "rowchain.h"
 #include "rows48.h"
@@ -193,6 +194,10 @@ enum Scratch {
   // sdrm_csr_transpose / sdrm_csr_vstack (csrc/csr_transpose.h), 8-byte words: [checked | total | bit table | colptr int64 | offsets uint32 |
   // column counts uint32] and [total | indptr int64 | row lengths uint32]
   SCR_CSRT_WS, SCR_STACK_WS,
+  // sdrm_nmf_fit (csrc/nmf.h), float64: [the fit's state (2) | Gram partials [NMF_PARTS][16][16] | the product [max(m, n)][16] | violation
+  // partials of the W half, of the H half]; sdrm_nmf_init, float64: [mean, sigma [16] (32) | norm partials of U, of V [NMF_PARTS][2][16] each
+  // | V^T [n][16] | X V^T [m][16]]
+  SCR_NMF_FIT, SCR_NMF_INIT,
   SCR_COUNT
 };
 
@@ -298,7 +303,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -336,7 +341,10 @@ static const char* kProfNames[PC_COUNT] = {
     "csr transpose: k_csrt_colscan a thread per column, running popcounts over the row blocks and the column counts",
     "csr transpose: k_csr_scan column counts -> colptr (one work-group)",
     "csr transpose: k_csrt_fill one pass over the entries, row index and value to the place the bit table gives",
-    "csr vstack: k_stack_counts / k_csr_scan / k_stack_copy checked row lengths, indptr, and the copy of up to 8 CSR parts one under the other"};
+    "csr vstack: k_stack_counts / k_csr_scan / k_stack_copy checked row lengths, indptr, and the copy of up to 8 CSR parts one under the other",
+    "nmf evaluator: k_nmf_prod / k_nmf_sweep / k_nmf_stop sparse x [., 16] float64 product with the Gram partials, the coordinate-descent sweep (a lane per row) and the stop rule",
+    "nmf evaluator: k_nmf_vt / k_nmf_mean / k_nmf_norms / k_nmf_init the NNDSVDa start from the truncated SVD's factors",
+    "nmf evaluator: k_nmf_expand the rank-k expansion W H into dense float32 scores (float64 sums, rounded once)"};
 
 namespace {
 
@@ -4014,6 +4022,121 @@ int sdrm_debug_svd_stage(sdrm_engine* e, const int64_t* indptr, const int32_t* i
   HIP_TRY(e, hipMemcpyAsync(&flag, dflag, sizeof(flag), hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipStreamSynchronize(st));
   return svd_breakdown(e, "sdrm_debug_svd_stage", st, flag);
+}
+
+// ---------------------------------------------------------------------------------------------
+// NMF of a sparse matrix by coordinate descent from an NNDSVDa start, and the scores of its reconstruction (svd_benchmark.py:49-54 with
+// nnmf=True), csrc/nmf.h.
+namespace {
+
+constexpr int64_t NMF_MAX_DIM = (int64_t)1 << 22;
+const char* const kNmfEnvelope = ": k outside 1 .. 16, m or n outside 1 .. 2^22 or nnz outside 0 .. 2^40 - 1";
+
+int nmf_parts(int64_t rows) { return (int)std::min<int64_t>(NMF_PARTS, (rows + NMF_GRAM_ROWS - 1) / NMF_GRAM_ROWS); }
+
+int nmf_dims(int64_t m, int64_t n, int64_t nnz, int k) {
+  return (k < 1 || k > NMF_LD || m < 1 || n < 1 || m > NMF_MAX_DIM || n > NMF_MAX_DIM || nnz < 0 || nnz >= ((int64_t)1 << 40)) ? SDRM_ERR_SHAPE : SDRM_OK;
+}
+
+// out [c.b][16] = (the rows of c) f, and with `gram` the partials of f^T f behind it in the same launch
+int nmf_prod(sdrm_engine* e, const CsrBatch& c, int64_t nnz, const double* f, double* out, double* gram, const NmfState* state, hipStream_t st) {
+  const int pb = (c.b + 31) / 32, gb = gram ? nmf_parts(c.n_items) : 0;
+  const NmfProdArgs a{c, nnz, f, out, pb, gram, state};
+  return launch_k(e, PC_NMF_STEP, "k_nmf_prod", k_nmf_prod, dim3((unsigned)(pb + gb)), dim3(256), 0, st, a);
+}
+
+// `_update_coordinate_descent` of the factor w [c.b][16] against f [c.n_items][16]: two launches
+int nmf_half(sdrm_engine* e, const CsrBatch& c, int64_t nnz, const double* f, double* w, int k, double* xh, double* gram, double* viol,
+             const NmfState* state, hipStream_t st) {
+  if (int rc = nmf_prod(e, c, nnz, f, xh, gram, state, st)) return rc;
+  const NmfSweepArgs a{w, xh, gram, nmf_parts(c.n_items), c.b, k, viol, state};
+  return launch_k(e, PC_NMF_STEP, "k_nmf_sweep", k_nmf_sweep, dim3((unsigned)((c.b + 255) / 256)), dim3(256), 0, st, a);
+}
+
+}  // namespace
+
+int sdrm_nmf_fit(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, const int64_t* colptr, const int32_t* rowidx,
+                 const float* cdata, int64_t m, int64_t n, int64_t nnz, int k, int max_iter, double tol, double* W, double* Ht, int32_t* n_iter_dev,
+                 double* violations_dev, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!indptr || !indices || !colptr || !rowidx || !W || !Ht || !n_iter_dev || !violations_dev) return fail(e, SDRM_ERR_ARG, "sdrm_nmf_fit: null pointer");
+  if ((data == nullptr) != (cdata == nullptr)) return fail(e, SDRM_ERR_ARG, "sdrm_nmf_fit: the values of the CSR and of the CSC form go together");
+  if (((uintptr_t)W | (uintptr_t)Ht) & 15u) return fail(e, SDRM_ERR_ARG, "sdrm_nmf_fit: the factors must be 16-byte aligned");
+  if (nmf_dims(m, n, nnz, k) || max_iter < 1 || max_iter > 10000 || !(tol >= 0.0))
+    return fail(e, SDRM_ERR_SHAPE, std::string("sdrm_nmf_fit") + kNmfEnvelope + ", max_iter outside 1 .. 10000 or tol < 0");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t wide = std::max(m, n);
+  const size_t bw = (size_t)((m + 255) / 256), bh = (size_t)((n + 255) / 256);
+  double* ws;
+  if (int rc = scratch(e, SCR_NMF_FIT, 2 + (size_t)NMF_PARTS * NMF_LD * NMF_LD + (size_t)wide * NMF_LD + bw + bh, &ws)) return rc;
+  NmfState* state = reinterpret_cast<NmfState*>(ws);
+  double* gram = ws + 2;
+  double* xh = gram + (size_t)NMF_PARTS * NMF_LD * NMF_LD;
+  double* viol_w = xh + (size_t)wide * NMF_LD;
+  double* viol_h = viol_w + bw;
+  const CsrBatch by_rows{indptr, indices, data, nullptr, 0, m, (int)m, (int)n, e->feed_flag};
+  const CsrBatch by_cols{colptr, rowidx, cdata, nullptr, 0, n, (int)n, (int)m, e->feed_flag};
+  HIP_TRY(e, hipMemsetAsync(state, 0, sizeof(NmfState), st));
+  HIP_TRY(e, hipMemsetAsync(violations_dev, 0, (size_t)max_iter * sizeof(double), st));
+  HIP_TRY(e, hipMemsetAsync(n_iter_dev, 0, sizeof(int32_t), st));
+  for (int it = 1; it <= max_iter; ++it) {
+    int rc;
+    if ((rc = nmf_half(e, by_rows, nnz, Ht, W, k, xh, gram, viol_w, state, st)) ||
+        (rc = nmf_half(e, by_cols, nnz, W, Ht, k, xh, gram, viol_h, state, st)) ||
+        (rc = launch_k(e, PC_NMF_STEP, "k_nmf_stop", k_nmf_stop, dim3(1), dim3(256), 0, st, (const double*)viol_w, (int)bw, (const double*)viol_h, (int)bh, it,
+                       max_iter, tol, state, (int*)n_iter_dev, violations_dev)))
+      return rc;
+  }
+  return SDRM_OK;
+}
+
+int sdrm_nmf_init(sdrm_engine* e, const int64_t* indptr, const int32_t* indices, const float* data, int64_t m, int64_t n, int64_t nnz, int k,
+                  const float* components, const double* singular_values_host, double* W0, double* Ht0, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!indptr || !indices || !components || !singular_values_host || !W0 || !Ht0) return fail(e, SDRM_ERR_ARG, "sdrm_nmf_init: null pointer");
+  if (((uintptr_t)W0 | (uintptr_t)Ht0) & 15u) return fail(e, SDRM_ERR_ARG, "sdrm_nmf_init: the factors must be 16-byte aligned");
+  if (nmf_dims(m, n, nnz, k)) return fail(e, SDRM_ERR_SHAPE, std::string("sdrm_nmf_init") + kNmfEnvelope);
+  NmfSigma sigma, ones;
+  for (int c = 0; c < NMF_LD; ++c) {
+    ones.s[c] = 1.0;
+    sigma.s[c] = c < k ? singular_values_host[c] : 1.0;
+    if (!(sigma.s[c] > 0.0) || !std::isfinite(sigma.s[c])) return fail(e, SDRM_ERR_ARG, "sdrm_nmf_init: a singular value that is not positive and finite");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int pu = nmf_parts(m), pv = nmf_parts(n);
+  double* ws;
+  if (int rc = scratch(e, SCR_NMF_INIT, 32 + 2 * (size_t)NMF_PARTS * 32 + (size_t)(m + n) * NMF_LD, &ws)) return rc;
+  double* mean = ws;
+  double* part_u = ws + 32;
+  double* part_v = part_u + (size_t)NMF_PARTS * 32;
+  double* vt = part_v + (size_t)NMF_PARTS * 32;
+  double* u = vt + (size_t)n * NMF_LD;
+  const CsrBatch by_rows{indptr, indices, data, nullptr, 0, m, (int)m, (int)n, e->feed_flag};
+  int rc;
+  if ((rc = launch_k(e, PC_NMF_INIT, "k_nmf_vt", k_nmf_vt, dim3((unsigned)std::min<int64_t>(4096, (n * NMF_LD + 255) / 256)), dim3(256), 0, st, components, k,
+                     (int)n, vt)) ||
+      (rc = nmf_prod(e, by_rows, nnz, vt, u, nullptr, nullptr, st)) ||
+      (rc = launch_k(e, PC_NMF_INIT, "k_nmf_mean", k_nmf_mean, dim3(1), dim3(256), 0, st, indptr, data, m, n, nnz, mean)) ||
+      (rc = launch_k(e, PC_NMF_INIT, "k_nmf_norms", k_nmf_norms, dim3((unsigned)pu), dim3(256), 0, st, (const double*)u, (int)m, k, sigma, part_u)) ||
+      (rc = launch_k(e, PC_NMF_INIT, "k_nmf_norms", k_nmf_norms, dim3((unsigned)pv), dim3(256), 0, st, (const double*)vt, (int)n, k, ones, part_v)))
+    return rc;
+  const int blocks_w = (int)((m + 255) / 256);
+  const NmfInitArgs a{u, vt, sigma, part_u, part_v, mean, (int)m, (int)n, k, pu, pv, blocks_w, W0, Ht0};
+  return launch_k(e, PC_NMF_INIT, "k_nmf_init", k_nmf_init, dim3((unsigned)(blocks_w + (n + 255) / 256)), dim3(256), 0, st, a);
+}
+
+int sdrm_nmf_scores(sdrm_engine* e, const double* W, const double* Ht, int64_t n_rows, int k, const int64_t* rows, int64_t row0, int b, int n_items,
+                    float* scores, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!W || !Ht || !scores) return fail(e, SDRM_ERR_ARG, "sdrm_nmf_scores: null pointer");
+  if (((uintptr_t)W | (uintptr_t)Ht) & 15u) return fail(e, SDRM_ERR_ARG, "sdrm_nmf_scores: the factors must be 16-byte aligned");
+  if (k < 1 || k > NMF_LD || b < 1 || n_items < 1 || n_rows < 1 || row0 < 0 || n_items > NMF_MAX_DIM || b > NMF_MAX_DIM || n_rows > NMF_MAX_DIM ||
+      (int64_t)b * n_items >= ((int64_t)1 << 40))
+    return fail(e, SDRM_ERR_SHAPE, "sdrm_nmf_scores: k outside 1 .. 16, b, n_items or n_rows outside 1 .. 2^22, row0 < 0 or b x n_items at or above 2^40");
+  if (!rows && row0 + b > n_rows) return fail(e, SDRM_ERR_SHAPE, "sdrm_nmf_scores: rows row0 .. row0 + b - 1 end behind the factor");
+  const NmfExpandArgs a{W, Ht, rows, row0, n_rows, k, n_items, b, scores, e->feed_flag};
+  return launch_k(e, PC_NMF_EXPAND, "k_nmf_expand", k_nmf_expand,
+                  dim3((unsigned)((n_items + 255) / 256), (unsigned)std::min(4096, (b + NMF_ROW_TILE - 1) / NMF_ROW_TILE)), dim3(256), 0, (hipStream_t)stream, a);
 }
 
 // ---------------------------------------------------------------------------------------------

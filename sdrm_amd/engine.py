@@ -1160,6 +1160,103 @@ class Engine:
         self.feed_status()
         return y, y_orth
 
+    # ------------------------------------------------------------------ NMF evaluator (csrc/nmf.h)
+    NMF_LD = 16      # row stride of a factor in the C ABI, and the most components
+
+    def _nmf_factor(self, who, name, a, rows, k):
+        """A factor [rows, k] (host or device) as the C ABI stores it: float64 [rows, 16] on the device, columns k .. 15 zero."""
+        t = self._dev(a, torch.float64)
+        if tuple(t.shape) != (rows, k):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {name} must be {[rows, k]}, got {list(t.shape)}")
+        out = torch.zeros(rows, self.NMF_LD, dtype=torch.float64, device=self.device)
+        out[:, :k] = t
+        return out
+
+    def _nmf_init(self, who, csr, m, n, nnz, k, csr_dev, csc_dev, seed, draw, svd_iter):
+        """(W0 [m, 16], Ht0 [n, 16]) as sdrm_nmf_init leaves them, from svd_fit's factors."""
+        if svd_iter is None:
+            svd_iter = 7 if k < 0.1 * min(m, n) else 4     # sklearn's n_iter='auto'
+        components, sigma = self.svd_fit(csr_dev, csc_dev, n_components=k, n_iter=int(svd_iter), seed=seed, draw=draw)
+        w0 = torch.zeros(m, self.NMF_LD, dtype=torch.float64, device=self.device)
+        ht0 = torch.zeros(n, self.NMF_LD, dtype=torch.float64, device=self.device)
+        indptr, indices, data = csr
+        self._check(self.lib.sdrm_nmf_init(self._h, _ptr(indptr), _ptr(indices), _ptr(data), m, n, nnz, k, _ptr(components),
+                                           sigma.ctypes.data_as(C.c_void_p), _ptr(w0), _ptr(ht0), _stream()), "sdrm_nmf_init")
+        return w0, ht0
+
+    def nmf_init(self, csr_dev, csc_dev, n_components=15, seed=0, draw=0, svd_iter=None):
+        """sklearn's `_initialize_nmf(X, n_components, init='nndsvda')` - NMF's default start - on the device, sdrm_nmf_init, with
+        `svd_fit(csr_dev, csc_dev, n_components, n_iter=svd_iter, seed, draw)` in the place of sklearn's randomized SVD (`svd_iter=None`
+        follows its 'auto' rule: 7 iterations when n_components < 0.1 min(m, n), else 4).  Returns (W0 [m, k], H0 [k, n]) float64 device
+        tensors, every entry positive.  It inherits `svd_fit`'s refusals: n_components + 10 > 32, min(m, n) < 32, a matrix of numerical
+        rank below 32.  The call synchronises (svd_fit's read-back) and asks `feed_status()`."""
+        who = "nmf_init"
+        k = int(n_components)
+        indptr, indices, data, m, n, nnz = self._sparse_dev(who, "csr", csr_dev)
+        if not 1 <= k <= self.NMF_LD:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: n_components = {k} outside 1 .. {self.NMF_LD}")
+        w0, ht0 = self._nmf_init(who, (indptr, indices, data), m, n, nnz, k, csr_dev, csc_dev, seed, draw, svd_iter)
+        self.feed_status()
+        return w0[:, :k].contiguous(), ht0[:, :k].t().contiguous()
+
+    def nmf_fit(self, csr_dev, csc_dev, n_components=15, max_iter=50, tol=1e-4, init=None, seed=0, check=True):
+        """`NMF(n_components, max_iter=max_iter, tol=tol).fit` (svd_benchmark.py:50-53; sklearn's `cd` solver without regularisation or
+        shuffle) on the device, sdrm_nmf_fit, from the `csr_to_device` and `csc_to_device` tuples of ONE matrix [m, n].  `init=(W0
+        [m, k], H0 [k, n])` (host or device) is sklearn's init='custom'; otherwise the start is `nmf_init(..., seed=seed)`.  Returns
+        (W [m, k], H [k, n] float64 device tensors, n_iter, violations float64 numpy array [n_iter]): the iterations run, and the
+        violation v_i of each (the fit stops when v_i / v_1 <= tol).  The whole fit is queued without a host round trip; the call then
+        reads n_iter and the violations back in one copy and, with `check`, asks `feed_status()`.  The same bits on every call."""
+        who = "nmf_fit"
+        k, max_iter, tol = int(n_components), int(max_iter), float(tol)
+        indptr, indices, data, m, n, nnz = self._sparse_dev(who, "csr", csr_dev)
+        colptr, rowidx, cdata, m2, n2, nnz2 = self._sparse_dev(who, "csc", csc_dev)
+        if (m2, n2, nnz2) != (m, n, nnz) or (data is None) != (cdata is None):
+            raise SdrmError(f"{who}: SDRM_ERR_ARG: the CSR form is {(m, n)} with {nnz} entries, the CSC form {(m2, n2)} with {nnz2}: not one matrix")
+        if not 1 <= k <= self.NMF_LD or not 1 <= max_iter <= 10000 or not tol >= 0:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: n_components = {k} outside 1 .. {self.NMF_LD}, max_iter = {max_iter} outside 1 .. 10000 or tol = {tol} < 0")
+        if init is None:
+            w, ht = self._nmf_init(who, (indptr, indices, data), m, n, nnz, k, csr_dev, csc_dev, seed, 0, None)
+        else:
+            w = self._nmf_factor(who, "W0", init[0], m, k)
+            ht = self._nmf_factor(who, "H0^T", self._dev(init[1], torch.float64).t(), n, k)
+        tail = torch.zeros(max_iter + 1, dtype=torch.float64, device=self.device)   # violations [max_iter] | n_iter (int32) in the last slot
+        n_iter_ptr = C.c_void_p(tail.data_ptr() + 8 * max_iter)
+        self._check(self.lib.sdrm_nmf_fit(self._h, _ptr(indptr), _ptr(indices), _ptr(data), _ptr(colptr), _ptr(rowidx), _ptr(cdata), m, n, nnz, k,
+                                          max_iter, tol, _ptr(w), _ptr(ht), n_iter_ptr, _ptr(tail), _stream()), "sdrm_nmf_fit")
+        host = tail.cpu().numpy()
+        n_iter = int(host[max_iter:].view(np.int32)[0])
+        if check:
+            self.feed_status()
+        return w[:, :k].contiguous(), ht[:, :k].t().contiguous(), n_iter, host[:n_iter].copy()
+
+    def nmf_scores(self, W, H, rows=None, row0=0, b=None, check=True):
+        """`nmf.inverse_transform(W)` (svd_benchmark.py:54) for a batch of rows of W, sdrm_nmf_scores: the dense float32 [b, n_items]
+        device tensor W[rows] H that `rank_metrics` takes, every element added in float64 and rounded once.  W [m, k], H [k, n_items]
+        as `nmf_fit` returns them (host or device); `rows` (int64) or row0 .. row0+b-1 (all rows when neither is given).  Seen items
+        are not masked here.  A row id outside W gives a zero row and raises the feed status word (`check` as in `csr_rows_to_dense`)."""
+        who = "nmf_scores"
+        if W.ndim != 2 or H.ndim != 2 or W.shape[1] != H.shape[0]:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: W must be [m, k] and H [k, n_items]")
+        m, k, n_items = int(W.shape[0]), int(W.shape[1]), int(H.shape[1])
+        if not 1 <= k <= self.NMF_LD:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {k} components outside 1 .. {self.NMF_LD}")
+        w = self._nmf_factor(who, "W", W, m, k)
+        ht = self._nmf_factor(who, "H^T", self._dev(H, torch.float64).t(), n_items, k)
+        if rows is not None:
+            rows = self._dev(rows, torch.int64)
+            b = rows.numel()
+        elif b is None:
+            row0, b = 0, m
+        row0, b = int(row0), int(b)
+        if b < 1 or row0 < 0 or (rows is None and row0 + b > m):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: rows {row0} .. {row0 + b - 1} end behind W's {m} rows, or there is none")
+        out = torch.empty(b, n_items, dtype=torch.float32, device=self.device)
+        self._check(self.lib.sdrm_nmf_scores(self._h, _ptr(w), _ptr(ht), m, k, _ptr(rows), row0, b, n_items, _ptr(out), _stream()), "sdrm_nmf_scores")
+        self._feed_keep = (rows, w, ht)
+        if check:
+            self.feed_status()
+        return out
+
     # ------------------------------------------------------------------ NeuMF evaluator's forward (csrc/neumf.h)
     NEUMF_FACTORS = (8, 16, 32)
     NEUMF_TENSORS = ("embed_user_GMF.weight", "embed_item_GMF.weight", "embed_user_MLP.weight", "embed_item_MLP.weight", "MLP_layers.1.weight",

@@ -9,6 +9,7 @@ the GPU box, where the reference itself cannot travel.  SURVEY.md §8f ("next" r
     compute_mf_results              svd_benchmark.py:17-70 (TruncatedSVD(20, n_iter=100) reconstruction, masked, Recall/NDCG@k)
     compute_mf_results_device       the same evaluator with fit, reconstruction and ranking on the device (opt-in)
     compute_mf_results_resident     ... from a CSR that is already on the device, stacked and transposed there (opt-in)
+                                    (all three with `nnmf=True`: svd_benchmark.py:49-50, NMF(15, max_iter=50) in the SVD's place)
     run_experiment                  main.py:143-200        (train -> multi-res + full-res sampling -> evaluate)
 """
 from __future__ import annotations
@@ -119,11 +120,12 @@ def equal_sparsity_csr(raw, sparsity: float, engine, side=">=") -> csr_matrix:
     return m
 
 
-def compute_mf_results(training_dataset, testing_dataset, synthetic_data, only_synthetic=True):
+def compute_mf_results(training_dataset, testing_dataset, synthetic_data, only_synthetic=True, nnmf=False):
     """Recall@k and NDCG@k (k = 1,3,5,10,20,50) of a rank-20 truncated SVD fitted on
     [synthetic | 80 % of each test user's items] and scored on the held-out 20 %.  `synthetic_data` may be a scipy sparse
-    matrix (`equal_sparsity_csr`): it is densified here, the fit itself is the dense one either way."""
-    from sklearn.decomposition import TruncatedSVD
+    matrix (`equal_sparsity_csr`): it is densified here, the fit itself is the dense one either way.  `nnmf=True` fits the
+    reference's other factorisation in its place, `NMF(n_components=15, max_iter=50)` (svd_benchmark.py:49-50)."""
+    from sklearn import decomposition
     test_data, valid_data = metrics.split_train_test_proportion_from_csr_matrix(testing_dataset, batch_size=1000, random_seed=123)
     if issparse(synthetic_data):
         synthetic_data = synthetic_data.toarray()
@@ -131,8 +133,16 @@ def compute_mf_results(training_dataset, testing_dataset, synthetic_data, only_s
     head = synthetic if only_synthetic else training_dataset.toarray()
     training = np.concatenate([head, test_data.toarray()], axis=0)
     combined = training if only_synthetic else np.concatenate([training, synthetic], axis=0)
-    svd = TruncatedSVD(n_components=20, n_iter=100)
-    recon = svd.inverse_transform(svd.fit_transform(combined))
+    if nnmf:
+        import warnings
+        from sklearn.exceptions import ConvergenceWarning
+        mf = decomposition.NMF(n_components=15, max_iter=50)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", category=ConvergenceWarning)   # (svd_benchmark.py:14; 50 iterations do not reach tol)
+            recon = mf.inverse_transform(mf.fit_transform(combined))
+    else:
+        svd = decomposition.TruncatedSVD(n_components=20, n_iter=100)
+        recon = svd.inverse_transform(svd.fit_transform(combined))
     masked = metrics.mask_training_examples(sparse_training_set=training, dense_matrix=recon[:training.shape[0]].copy())
     lo = head.shape[0]
     scored = masked[lo:lo + valid_data.shape[0]]
@@ -141,9 +151,19 @@ def compute_mf_results(training_dataset, testing_dataset, synthetic_data, only_s
     return np.array(rec), np.array(ndcg)
 
 
-def mf_per_user_device(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0):
+def _device_scores(engine, csr_dev, csc_dev, lo, users, seed, nnmf):
+    """The validation users' rows of the reconstruction, float32 [users, n_items] on the device: the rank-20 truncated SVD's, or with
+    `nnmf` those of the NMF of 15 components and 50 iterations from its NNDSVDa start (csrc/nmf.h)."""
+    if nnmf:
+        w, h, _, _ = engine.nmf_fit(csr_dev, csc_dev, n_components=15, max_iter=50, seed=seed)
+        return engine.nmf_scores(w, h, row0=lo, b=users)
+    components, _ = engine.svd_fit(csr_dev, csc_dev, n_components=20, n_iter=100, seed=seed)
+    return engine.svd_scores(csr_dev, components, row0=lo, b=users)
+
+
+def mf_per_user_device(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0, nnmf=False):
     """The device evaluator up to the per-user figures: (recall [6, users], ndcg [6, users]) float64 numpy arrays for `K_LIST`, nan for
-    a user with nothing held out - what `compute_mf_results_device` averages."""
+    a user with nothing held out - what `compute_mf_results_device` averages.  `nnmf=True`: the NMF evaluator in the SVD's place."""
     test_data, valid_data = metrics.split_train_test_proportion_from_csr_matrix(testing_dataset, batch_size=1000, random_seed=123)
     synthetic = synthetic_data.tocsr() if issparse(synthetic_data) else csr_matrix(np.asarray(synthetic_data))
     head = synthetic if only_synthetic else training_dataset.tocsr()
@@ -152,27 +172,27 @@ def mf_per_user_device(training_dataset, testing_dataset, synthetic_data, engine
     combined.eliminate_zeros()   # (`mask_training_examples` masks the NONZERO entries of the stacked rows)
     lo, users = head.shape[0], valid_data.shape[0]
     csr_dev, csc_dev = engine.csr_to_device(combined), engine.csc_to_device(combined)
-    components, _ = engine.svd_fit(csr_dev, csc_dev, n_components=20, n_iter=100, seed=seed)
-    scores = engine.svd_scores(csr_dev, components, row0=lo, b=users)
+    scores = _device_scores(engine, csr_dev, csc_dev, lo, users, seed, nnmf)
     # the validation users' stacked training rows as a CSR of their own: indptr holds absolute offsets, so a row range is a slice of it
     seen_dev = (csr_dev[0][lo:lo + users + 1], csr_dev[1], None, (users, combined.shape[1]))
     rec, ndcg = engine.rank_metrics(scores, engine.csr_to_device(valid_data), seen_dev, ks=K_LIST)
     return rec.cpu().numpy(), ndcg.cpu().numpy()
 
 
-def compute_mf_results_device(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0):
+def compute_mf_results_device(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0, nnmf=False):
     """`compute_mf_results` with the fit, the reconstruction and the ranking on the device (opt-in: `hp["device_svd"]`).  The same
     split and the same rows in the same order, stacked as scipy sparse - no dense matrix exists on the host.  The stacked matrix is
     uploaded once in its CSR and CSC forms; `Engine.svd_fit` runs the rank-20, 100-iteration subspace iteration (csrc/svd_eval.h) from
     a Philox start panel keyed by `seed`, `Engine.svd_scores` reconstructs the validation users' rows only, and `Engine.rank_metrics`
     masks them with their stacked training rows and ranks.  Returns the same `(recall[6], ndcg[6])`, nanmean over the users, rounded
-    to 4 places.  `synthetic_data` may be dense 0/1 (`equal_sparsity`) or sparse (`equal_sparsity_csr`)."""
-    rec, ndcg = mf_per_user_device(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=only_synthetic, seed=seed)
+    to 4 places.  `synthetic_data` may be dense 0/1 (`equal_sparsity`) or sparse (`equal_sparsity_csr`).  `nnmf=True` is the
+    reference's `nnmf=True` (opt-in: `hp["nmf"]`): `Engine.nmf_fit` and `Engine.nmf_scores` in the place of the SVD's two calls."""
+    rec, ndcg = mf_per_user_device(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=only_synthetic, seed=seed, nnmf=nnmf)
     return (np.array([np.round(np.nanmean(rec[q]), 4) for q in range(len(K_LIST))]),
             np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
 
 
-def mf_per_user_resident(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0):
+def mf_per_user_resident(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0, nnmf=False):
     """`mf_per_user_device` for synthetic data that is already on the device: `synthetic_data` is a device CSR tuple (what
     `Engine.equal_sparsity_csr` returns, or a `csr_to_device` tuple).  The hold-out split of the validation users stays the host's
     (the reference's draw, a few hundred users) and its two small results are uploaded; the stack [head | test | synthetic?] is made
@@ -189,17 +209,16 @@ def mf_per_user_resident(training_dataset, testing_dataset, synthetic_data, engi
     csr_dev = engine.csr_vstack(parts, check=False)       # (no synchronise of their own: `svd_fit` below reads the status word that
     csc_dev = engine.csr_transpose(csr_dev, check=False)  #  both calls' range checks raise, and raises for them)
     lo, users = int(head[-1][0]), valid_data.shape[0]
-    components, _ = engine.svd_fit(csr_dev, csc_dev, n_components=20, n_iter=100, seed=seed)
-    scores = engine.svd_scores(csr_dev, components, row0=lo, b=users)
+    scores = _device_scores(engine, csr_dev, csc_dev, lo, users, seed, nnmf)
     seen_dev = (csr_dev[0][lo:lo + users + 1], csr_dev[1], None, (users, csr_dev[3][1]))
     rec, ndcg = engine.rank_metrics(scores, engine.csr_to_device(valid_data), seen_dev, ks=K_LIST)
     return rec.cpu().numpy(), ndcg.cpu().numpy()
 
 
-def compute_mf_results_resident(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0):
+def compute_mf_results_resident(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=True, seed=0, nnmf=False):
     """`compute_mf_results_device` from a device CSR tuple (opt-in: `hp["resident_svd"]`): the same `(recall[6], ndcg[6])`, with the
     stacking and the CSR -> CSC conversion on the device (`mf_per_user_resident`)."""
-    rec, ndcg = mf_per_user_resident(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=only_synthetic, seed=seed)
+    rec, ndcg = mf_per_user_resident(training_dataset, testing_dataset, synthetic_data, engine, only_synthetic=only_synthetic, seed=seed, nnmf=nnmf)
     return (np.array([np.round(np.nanmean(rec[q]), 4) for q in range(len(K_LIST))]),
             np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
 
@@ -214,7 +233,8 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
     seven flags of the VAE pre-stage under the keys `VAE_FLAGS` (each False when absent): those that are set are handed to `train_SDRM`
     under the same names, and an `hp` without them makes the call it always made.  `hp["device_svd"]` (False when absent) sends the
     three evaluations to `compute_mf_results_device` instead of `compute_mf_results`; nothing of it reaches `train_SDRM`.  `hp["resident_svd"]` (False when absent) binarises with
-    `Engine.equal_sparsity_csr` and hands the device tuple to `compute_mf_results_resident`: no host copy of the synthetic matrix."""
+    `Engine.equal_sparsity_csr` and hands the device tuple to `compute_mf_results_resident`: no host copy of the synthetic matrix.
+    `hp["nmf"]` (False when absent) makes those two device routes evaluate with `nnmf=True`, the reference's NMF of 15 components."""
     from . import train_SDRM as ts
     train, train_partial, valid = split
     n_users, n_items = train.shape
@@ -234,11 +254,12 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
     F = ts.sample_ddpm(n_users, net, vae, hp["latent"], hp["nd"], n_timesteps=hp["T"]).detach()
     V = vae.sample(n_users)
     binarise = equal_sparsity_csr if hp.get("sparse_synthetic", False) else equal_sparsity   # opt-in: CSR made on the device
+    nmf = {"nnmf": True} if hp.get("nmf", False) else {}   # opt-in, the two device routes only: the NMF evaluator in the SVD's place (csrc/nmf.h)
     for tag, raw in (("M", M), ("F", F), ("V", V)):
         if hp.get("resident_svd", False):   # opt-in: the CSR made on the device stays there, stacked and transposed on the device (csrc/csr_transpose.h)
-            out[tag] = compute_mf_results_resident(train, valid, net.engine().equal_sparsity_csr(raw, sparsity), net.engine(), only_synthetic=True, seed=seed)
+            out[tag] = compute_mf_results_resident(train, valid, net.engine().equal_sparsity_csr(raw, sparsity), net.engine(), only_synthetic=True, seed=seed, **nmf)
         elif hp.get("device_svd", False):   # opt-in: the downstream evaluator on the device (csrc/svd_eval.h)
-            out[tag] = compute_mf_results_device(train, valid, binarise(raw, sparsity, net.engine()), net.engine(), only_synthetic=True, seed=seed)
+            out[tag] = compute_mf_results_device(train, valid, binarise(raw, sparsity, net.engine()), net.engine(), only_synthetic=True, seed=seed, **nmf)
         else:
             out[tag] = compute_mf_results(train, valid, binarise(raw, sparsity, net.engine()), only_synthetic=True)
     return out
