@@ -741,6 +741,40 @@ int sdrm_neumf_train_steps(sdrm_engine* e, const sdrm_neumf_train* s, const int3
                            float beta1, float beta2, float eps, float p_drop, int mode, const uint8_t* keep, uint64_t seed, uint32_t call_id,
                            double* losses, float* const* grads, void* stream);
 
+/* The MLP evaluator's TRAIN steps on the device (reference: mlp_benchmark.py:37-62 the model, :85-110 `model.fit` with Keras's Adam and
+ * `binary_crossentropy`; restated, with the Keras facts it rests on, in sdrm_amd/mlp_eval.py; csrc/mlp_train.h).  The input rows are 0 / 1,
+ * given as the PATTERN of a device CSR matrix [n_rows, n_items] (an entry means 1).  With s = 1 / (1 - p_drop) and k1, k2, k3 the keep
+ * decisions of the three Dropout layers:
+ *   a0[r, 8j + f] = E[x_rj][f];  a1 = k1 s relu(a0 W1 + b1);  a2 = k2 s relu(a1 W2 + b2);  a3 = k3 s relu(a2 W3 + b3);  y = a3 W4 + b4
+ *   loss = sum(max(y, 0) - y x + log1p(exp(-|y|))) / (b n_items);  dy = (sigmoid(y) - x) / (b n_items)
+ * followed by the gradients of all nine tensors and Keras's Adam: alpha = lr sqrt(1 - beta2^t) / (1 - beta1^t), m += (g - m)(1 - beta1),
+ * v += (g^2 - v)(1 - beta2), p -= alpha m / (sqrt(v) + eps), t = step0 + 1 for the first step of the call.  Of E only rows 0 and 1 are read
+ * and updated (Keras's sparse embedding update).
+ * The struct holds DEVICE pointers to the nine LIVE tensors p (updated in place) and to their moments m, v (the same shapes, updated in
+ * place) in Keras's `get_weights()` order and layout, kernels [in][out]: E [n_users][8], W1 [8 n_items][512], b1 [512], W2 [512][256],
+ * b2 [256], W3 [256][256], b3 [256], W4 [256][n_items], b4 [n_items]: float32, contiguous, every base on the 16-byte grid, no two of
+ * them sharing a byte.
+ * sdrm_mlp_train_steps runs ceil(n / batch) consecutive steps over rows [n] (int64 row ids of the CSR matrix, DEVICE) in order, the last
+ *   one partial, all enqueued on `stream`; nothing is read back and no step waits for the host.  Neither the dense input [b][8 n_items]
+ *   nor the gradient of W1 exists in memory (but in grads_out): a step is ONE read-modify-write pass over W1 and its moments.  Scratch
+ *   is library-owned and grow-only, as for sdrm_neumf_train_steps.  Values are fp32, every sum is accumulated in float64 in a fixed
+ *   order and rounded once, there is no floating-point atomic: the same bits on every run, and a call over n rows gives the bits of
+ *   one call per batch.
+ *   A row id outside [0, n_rows), an indptr pair out of order (such a row adds nothing to the loss or to any gradient) and a column
+ *   outside [0, n_items) (skipped) raise the feed status word (sdrm_feed_status); the divisor b n_items still counts them.
+ *   Dropout: mode SDRM_RNG_EXPLICIT reads keep [n][1024] uint8 (per row 512 bytes of k1, 256 of k2, 256 of k3; non-zero = kept);
+ *   SDRM_RNG_PHILOX ignores keep: column c of the row at place j of `rows` is kept iff word c & 3 of Philox4x32-10 with counter
+ *   (j, c >> 2, 11, call_id) and key seed is >= floor(p_drop 2^32).
+ *   losses: DEVICE double [ceil(n / batch)], each step's loss.  grads_out: null, or a HOST array of nine DEVICE pointers (the tensors'
+ *   shapes, the same alignment and no shared byte) that receive the gradients the update used - allowed for a call of ONE step only.
+ *   SDRM_ERR_SHAPE: n_items outside 1 .. 36864, n_users < 2, batch outside 1 .. 16, n outside 1 .. 2^31 - 1, step0 < 0, p_drop outside
+ *   [0, 1), n_rows < 1; SDRM_ERR_ARG: a null pointer, EXPLICIT without keep, an unknown mode, grads_out with more than one step, a tensor
+ *   off the 16-byte grid, two tensors that share a byte.  Refused calls launch nothing. */
+typedef struct sdrm_mlp_train { float* p[9]; float* m[9]; float* v[9]; int n_users, n_items; } sdrm_mlp_train;
+int sdrm_mlp_train_steps(sdrm_engine* e, const sdrm_mlp_train* s, const int64_t* indptr, const int32_t* indices, int64_t n_rows, const int64_t* rows,
+                         int64_t n, int batch, int64_t step0, float lr, float beta1, float beta2, float eps, float p_drop, int mode,
+                         const uint8_t* keep, uint64_t seed, uint32_t call_id, double* losses, float* const* grads_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

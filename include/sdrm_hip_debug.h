@@ -232,6 +232,14 @@ int sdrm_debug_neumf_args(int n_users, int n_items, int factor, int64_t listed_u
  * (step0 < 0, p_drop outside [0, 1) or not a number). */
 int sdrm_debug_neumf_train_args(int n_users, int n_items, int factor, int64_t n, int batch, int64_t step0, float p_drop);
 
+/* The host side of sdrm_mlp_train_steps that needs no device: SDRM_OK, SDRM_ERR_SHAPE for a call outside its envelope (n_items outside
+ * 1 .. 36864, n_users < 2, batch outside 1 .. 16, n outside 1 .. 2^31 - 1, step0 < 0, p_drop outside [0, 1) or not a number), or
+ * SDRM_ERR_ARG: with_grads for more than one step (n > batch) and, when `addr` is given - the base addresses of p[9], m[9], v[9] and, with
+ * with_grads, of the nine gradient tensors, n_addr = 27 or 36 of them - a null address, one off the 16-byte grid, two tensors that share a
+ * byte, or another n_addr. */
+int sdrm_debug_mlp_train_args(int n_users, int n_items, int64_t n, int batch, int64_t step0, float p_drop, int with_grads, const uint64_t* addr,
+                              int n_addr);
+
 #ifdef __cplusplus
 }
 #endif

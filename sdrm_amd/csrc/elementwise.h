@@ -544,6 +544,18 @@ __device__ __forceinline__ float adam_math(float w, float g, float& m, float& v,
   return w - step_size * (mm * __builtin_amdgcn_rcpf(denom));
 }
 
+// Keras's Adam for one element (keras/src/optimizers/adam.py, update_step): m += (g - m)(1 - beta1), v += (g^2 - v)(1 - beta2),
+// p -= alpha m / (sqrt(v) + eps) with alpha = lr sqrt(1 - beta2^t) / (1 - beta1^t) - eps is added to sqrt(v) itself, not to
+// sqrt(v) / sqrt(1 - beta2^t) as torch does above, so the two differ wherever sqrt(v) is not large against eps.  omb1 = 1 - beta1,
+// omb2 = 1 - beta2 and alpha are the host's.
+__device__ __forceinline__ float adam_math_keras(float w, float g, float& m, float& v, float alpha, float omb1, float omb2, float eps) {
+#pragma clang fp contract(off)
+  const float mm = m + (g - m) * omb1;
+  const float vv = v + (g * g - v) * omb2;
+  m = mm; v = vv;
+  return w - (alpha * mm) * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(vv) + eps);
+}
+
 __device__ __forceinline__ float adam_element(const AdamArgs& a, int64_t fi) {
   float w = a.p[fi];
   if (a.update) {

@@ -18,7 +18,8 @@ enum : uint32_t {
   PURPOSE_VAE_DROP = 7,    // input dropout of the VAE encoder in train mode (csrc/input_layer.h): word c & 3 of (feed row, column quad)
   PURPOSE_HOLDOUT = 8,     // sort key of the per-user hold-out split (csrc/holdout.h): word p & 3 of (feed row, quad of the place p in the row)
   PURPOSE_VAE_EPS = 9,     // reparameterisation draw of the VAE encoder in train mode (csrc/latent.h): normal j & 3 of (feed row, column quad j >> 2)
-  PURPOSE_NEUMF_DROP = 10  // the three dropouts of a NeuMF train step (csrc/neumf_train.h): word c & 3 of (pair's place in the call, quad of the column c of its 14F)
+  PURPOSE_NEUMF_DROP = 10, // the three dropouts of a NeuMF train step (csrc/neumf_train.h): word c & 3 of (pair's place in the call, quad of the column c of its 14F)
+  PURPOSE_MLP_DROP = 11     // the three dropouts of an MLP-evaluator train step (csrc/mlp_train.h): word c & 3 of (row's place in the call, quad of the column c of its 1024)
 };
 
 struct U4 { uint32_t x, y, z, w; };

@@ -30,6 +30,7 @@
 #include "input_layer.h"
 #include "latent.h"
 #include "neumf.h"
+#include "mlp_train.h"
 #include "neumf_train.h"
 #include "nll.h"
 #include "nmf.h"
@@ -153,7 +154,7 @@ struct ChainSched {
   bool hold_marked = false;    // ev_hold is recorded behind its weight gradients
 };
 
-constexpr int PROF_SLOTS = 40;   // room for the profile classes (ProfClass below holds PC_COUNT to it)
+constexpr int PROF_SLOTS = 48;   // room for the profile classes (ProfClass below holds PC_COUNT to it)
 
 // The library-owned device scratch of the utility entry points (sdrm_engine::scratch, reached through scratch<T>() only): one slot per
 // buffer, every slot grow-only and owned by ONE family of entry points, so nothing a family leaves behind is touched by another.  Two
@@ -190,6 +191,9 @@ enum Scratch {
   // eight tower tensors behind it | the dense gradients of the four embedding tables, ALL ZERO between two calls (a step writes the rows
   // its pairs name and zeroes them again): nothing else may ever be carved out of that slot
   SCR_NEUMF_TRAIN_WS, SCR_NEUMF_TRAIN_TAB,
+  // sdrm_mlp_train_steps (csrc/mlp_train.h), 8-byte words: [B_f of the weights, two copies | the W1 pass's partial B_f and dE[1] | the gather's
+  // partial sums | loss partials | a1, a2, a3, dz1, dz2, dz3, dy (float) | live words | item mask]
+  SCR_MLP_TRAIN_WS,
   SCR_CSR_WS,        // sdrm_equal_sparsity_csr_begin / _end (csrc/compact.h), 8-byte words: [mask words | row offsets int64 | row counts uint32]
   // sdrm_csr_transpose / sdrm_csr_vstack (csrc/csr_transpose.h), 8-byte words: [checked | total | bit table | colptr int64 | offsets uint32 |
   // column counts uint32] and [total | indptr int64 | row lengths uint32]
@@ -303,7 +307,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_MLP_FWD, PC_MLP_BWD, PC_MLP_W1, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -344,7 +348,10 @@ static const char* kProfNames[PC_COUNT] = {
     "csr vstack: k_stack_counts / k_csr_scan / k_stack_copy checked row lengths, indptr, and the copy of up to 8 CSR parts one under the other",
     "nmf evaluator: k_nmf_prod / k_nmf_sweep / k_nmf_stop sparse x [., 16] float64 product with the Gram partials, the coordinate-descent sweep (a lane per row) and the stop rule",
     "nmf evaluator: k_nmf_vt / k_nmf_mean / k_nmf_norms / k_nmf_init the NNDSVDa start from the truncated SVD's factors",
-    "nmf evaluator: k_nmf_expand the rank-k expansion W H into dense float32 scores (float64 sums, rounded once)"};
+    "nmf evaluator: k_nmf_expand the rank-k expansion W H into dense float32 scores (float64 sums, rounded once)",
+    "mlp train step: k_mlp_mask / k_mlp_gather / k_mlp_z1 / k_mlp_fwd train-mode forward from CSR rows with the three dropouts, the loss terms and dy",
+    "mlp train step: k_mlp_dgrad / k_mlp_adam / k_mlp_embed / k_mlp_bsum input gradients, Keras's Adam on W2 .. b4 and on E's two rows with the gradient made inside the pass, the loss, B_f",
+    "mlp train step: k_mlp_w1 the one read-modify-write pass over W1 and its moments (gradient per element from S and T_j, Keras's Adam, partial B_f and dE[1])"};
 
 namespace {
 
@@ -4395,6 +4402,161 @@ int sdrm_neumf_train_steps(sdrm_engine* e, const sdrm_neumf_train* s, const int3
   hipStream_t st = (hipStream_t)stream;
   if (s->factor == 8) return neumf_train_steps<8>(e, s, triples, n, batch, step0, lr, beta1, beta2, eps, p_drop, k, seed, call_id, losses, grads, st);
   return neumf_train_steps<16>(e, s, triples, n, batch, step0, lr, beta1, beta2, eps, p_drop, k, seed, call_id, losses, grads, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The MLP evaluator's train steps (mlp_benchmark.py:85-110: the batch loop of `model.fit`), csrc/mlp_train.h; a whole call is enqueued
+// without a host synchronisation.
+namespace {
+
+constexpr int MLP_TENSORS = 9;
+
+// elements of E, W1, b1, W2, b2, W3, b3, W4, b4
+void mlp_counts(int n_users, int n_items, int64_t (&count)[MLP_TENSORS]) {
+  const int64_t I = n_items;
+  const int64_t c[MLP_TENSORS] = {(int64_t)n_users * MLP_F, I * MLP_F * MLP_H1, MLP_H1, (int64_t)MLP_H1 * MLP_H2, MLP_H2, (int64_t)MLP_H2 * MLP_H3, MLP_H3,
+                                  (int64_t)MLP_H3 * I, I};
+  for (int i = 0; i < MLP_TENSORS; ++i) count[i] = c[i];
+}
+
+}  // namespace
+
+// The host side that needs no device: the envelope of sdrm_mlp_train_steps and, with `addr`, the checks of its tensors' addresses.
+int sdrm_debug_mlp_train_args(int n_users, int n_items, int64_t n, int batch, int64_t step0, float p_drop, int with_grads, const uint64_t* addr,
+                              int n_addr) {
+  if (n_items < 1 || n_items > MLP_MAX_ITEMS || n_users < 2 || batch < 1 || batch > MLP_MAX_BATCH || n < 1 || n > (int64_t)0x7fffffff)
+    return SDRM_ERR_SHAPE;
+  if (step0 < 0 || step0 > ((int64_t)1 << 52) || !(p_drop >= 0.f && p_drop < 1.f)) return SDRM_ERR_SHAPE;   // (a NaN fails both compares)
+  if (with_grads && n > batch) return SDRM_ERR_ARG;   // the gradients of ONE step
+  if (!addr) return SDRM_OK;
+  if (n_addr != (with_grads ? 4 : 3) * MLP_TENSORS) return SDRM_ERR_ARG;
+  int64_t count[MLP_TENSORS];
+  mlp_counts(n_users, n_items, count);
+  std::vector<std::pair<uint64_t, uint64_t>> span;
+  for (int i = 0; i < n_addr; ++i) {
+    if (!addr[i] || (addr[i] & 15u)) return SDRM_ERR_ARG;   // null, or off the 16-byte grid
+    span.emplace_back(addr[i], addr[i] + (uint64_t)count[i % MLP_TENSORS] * sizeof(float));
+  }
+  std::sort(span.begin(), span.end());
+  for (size_t i = 1; i < span.size(); ++i)
+    if (span[i].first < span[i - 1].second) return SDRM_ERR_ARG;   // two tensors share a byte
+  return SDRM_OK;
+}
+
+int sdrm_mlp_train_steps(sdrm_engine* e, const sdrm_mlp_train* s, const int64_t* indptr, const int32_t* indices, int64_t n_rows, const int64_t* rows,
+                         int64_t n, int batch, int64_t step0, float lr, float beta1, float beta2, float eps, float p_drop, int mode,
+                         const uint8_t* keep, uint64_t seed, uint32_t call_id, double* losses, float* const* grads_out, void* stream) {
+  const char* who = "sdrm_mlp_train_steps";
+  if (!e) return SDRM_ERR_ARG;
+  if (!s || !indptr || !indices || !rows || !losses) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (mode != SDRM_RNG_EXPLICIT && mode != SDRM_RNG_PHILOX) return fail(e, SDRM_ERR_ARG, std::string(who) + ": mode is neither SDRM_RNG_EXPLICIT nor SDRM_RNG_PHILOX");
+  if (mode == SDRM_RNG_EXPLICIT && !keep) return fail(e, SDRM_ERR_ARG, std::string(who) + ": SDRM_RNG_EXPLICIT needs keep [n][1024]");
+  if (n_rows < 1) return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": a CSR matrix without rows");
+  uint64_t addr[4 * MLP_TENSORS];
+  for (int i = 0; i < MLP_TENSORS; ++i) {
+    addr[i] = (uint64_t)(uintptr_t)s->p[i]; addr[MLP_TENSORS + i] = (uint64_t)(uintptr_t)s->m[i]; addr[2 * MLP_TENSORS + i] = (uint64_t)(uintptr_t)s->v[i];
+    addr[3 * MLP_TENSORS + i] = grads_out ? (uint64_t)(uintptr_t)grads_out[i] : 0;
+  }
+  if (int rc = sdrm_debug_mlp_train_args(s->n_users, s->n_items, n, batch, step0, p_drop, grads_out != nullptr, addr, (grads_out ? 4 : 3) * MLP_TENSORS))
+    return fail(e, rc, std::string(who) + ": n_items outside 1 .. 36864, n_users < 2, batch outside 1 .. 16, n outside 1 .. 2^31 - 1, step0 < 0 or p_drop "
+                                          "outside [0, 1) (SDRM_ERR_SHAPE); grads_out with more than one step, a null tensor, a tensor off the 16-byte grid "
+                                          "or two tensors that share a byte (SDRM_ERR_ARG)");
+  hipStream_t st = (hipStream_t)stream;
+  const int I = s->n_items;
+  int64_t count[MLP_TENSORS];
+  mlp_counts(s->n_users, I, count);
+  // the workspace: 8-byte words first
+  const int w1_blocks = (I + MLP_W1_ITEMS - 1) / MLP_W1_ITEMS, out_blocks = (I + 63) / 64;
+  const size_t BF = (size_t)MLP_F * MLP_H1;
+  size_t at = 0;
+  const auto take = [&](size_t words) { const size_t o = at; at += (words + 1) / 2 * 2; return o; };   // (every piece on the 16-byte grid)
+  const size_t o_bsum = take(2 * BF), o_bpart = take((size_t)w1_blocks * BF), o_e1 = take((size_t)w1_blocks * MLP_F),
+               o_zpart = take((size_t)MLP_MAX_BATCH * MLP_GCH * MLP_H1), o_loss = take((size_t)out_blocks);
+  const auto take_f = [&](size_t floats) { return take((floats + 1) / 2); };
+  const size_t o_a1 = take_f(MLP_MAX_BATCH * MLP_H1), o_a2 = take_f(MLP_MAX_BATCH * MLP_H2), o_a3 = take_f(MLP_MAX_BATCH * MLP_H3),
+               o_dz1 = take_f(MLP_MAX_BATCH * MLP_H1), o_dz2 = take_f(MLP_MAX_BATCH * MLP_H2), o_dz3 = take_f(MLP_MAX_BATCH * MLP_H3),
+               o_dy = take_f((size_t)MLP_MAX_BATCH * I), o_live = take_f(MLP_MAX_BATCH), o_mask = take_f((size_t)I);
+  double* ws;
+  if (int rc = scratch(e, SCR_MLP_TRAIN_WS, at, &ws)) return rc;
+  double *bsum = ws + o_bsum, *bpart = ws + o_bpart, *e1part = ws + o_e1, *zpart = ws + o_zpart, *losspart = ws + o_loss;
+  const auto fl = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
+  float *a1 = fl(o_a1), *a2 = fl(o_a2), *a3 = fl(o_a3), *dz1 = fl(o_dz1), *dz2 = fl(o_dz2), *dz3 = fl(o_dz3), *dy = fl(o_dy);
+  int* live = reinterpret_cast<int*>(ws + o_live);
+  unsigned* mask = reinterpret_cast<unsigned*>(ws + o_mask);
+  float* const* P = s->p; float* const* M = s->m; float* const* V = s->v;
+  float* G[MLP_TENSORS];
+  for (int i = 0; i < MLP_TENSORS; ++i) G[i] = grads_out ? grads_out[i] : nullptr;
+
+  const double p = (double)p_drop;
+  MlpDrop drop{};
+  drop.k0 = (uint32_t)seed; drop.k1 = (uint32_t)(seed >> 32); drop.call_id = call_id;
+  drop.thr = (uint32_t)std::floor(p * 4294967296.0);
+  drop.s = (float)(1.0 / (1.0 - p));
+  const LaunchClass pc(PC_MLP_FWD), pcb(PC_MLP_BWD), pcw(PC_MLP_W1);
+
+  // B_f of the weights as they stand: the W1 pass in its read-only form, then the sum of its partials
+  MlpW1Args wa{};
+  wa.W = P[1]; wa.mW = M[1]; wa.vW = V[1]; wa.gW = G[1]; wa.B = P[2]; wa.mB = M[2]; wa.vB = V[2]; wa.gB = G[2];
+  wa.E = P[0]; wa.dz1 = dz1; wa.mask = mask; wa.bpart = bpart; wa.e1part = e1part; wa.n_items = I;
+  if (int rc = launch_k(e, pcw, "k_mlp_w1<false>", k_mlp_w1<false>, dim3((unsigned)w1_blocks), dim3(128), 0, st, wa)) return rc;
+  if (int rc = launch_k(e, pcb, "k_mlp_bsum", k_mlp_bsum, dim3((unsigned)(BF / 16)), dim3(256), 0, st, (const double*)bpart, w1_blocks, bsum)) return rc;
+  if (G[0]) HIP_TRY(e, hipMemsetAsync(G[0], 0, (size_t)count[0] * sizeof(float), st));   // (rows 2 .. of dE: a 0 / 1 input names none of them)
+
+  const int64_t steps = (n + batch - 1) / batch;
+  for (int64_t t = 0; t < steps; ++t) {
+    const int64_t j0 = t * batch;
+    const int b = (int)std::min<int64_t>(batch, n - j0);
+    double* bcur = bsum + (size_t)(t & 1) * BF;
+    double* bnext = bsum + (size_t)((t + 1) & 1) * BF;
+    const CsrBatch cb{indptr, indices, nullptr, rows + j0, 0, n_rows, b, I, e->feed_flag};
+    drop.keep = mode == SDRM_RNG_EXPLICIT ? keep + (size_t)j0 * MLP_KEEP_COLS : nullptr;
+    drop.j0 = (uint32_t)j0;
+    MlpAdam ad{};
+    {
+      const double k = (double)(step0 + t + 1), b1d = (double)beta1, b2d = (double)beta2;
+      ad.alpha = (float)((double)lr * std::sqrt(1.0 - std::pow(b2d, k)) / (1.0 - std::pow(b1d, k)));
+      ad.omb1 = (float)(1.0 - b1d); ad.omb2 = (float)(1.0 - b2d); ad.eps = eps;
+    }
+    HIP_TRY(e, hipMemsetAsync(mask, 0, (size_t)I * sizeof(unsigned), st));
+    if (int rc = launch_k(e, pc, "k_mlp_mask", k_mlp_mask, dim3((unsigned)b), dim3(256), 0, st, cb, mask, live)) return rc;
+    if (int rc = launch_k(e, pc, "k_mlp_gather", k_mlp_gather, dim3(MLP_GCH, (unsigned)b), dim3(128), 0, st, cb, (const float*)P[0], (const float*)P[1], zpart))
+      return rc;
+    if (int rc = launch_k(e, pc, "k_mlp_z1", k_mlp_z1, dim3((unsigned)(b * MLP_H1 / 256)), dim3(256), 0, st, (const float*)P[0], (const float*)P[2],
+                          (const double*)bcur, (const double*)zpart, drop, a1))
+      return rc;
+    // layers 2, 3 and the output layer
+    MlpFwdArgs fa{};
+    fa.b = b; fa.d = drop; fa.mask = mask; fa.live = live; fa.losspart = losspart;
+    fa.A = a1; fa.W = P[3]; fa.bias = P[4]; fa.out = a2; fa.IN = MLP_H1; fa.OUT = MLP_H2; fa.drop0 = MLP_H1;
+    if (int rc = launch_k(e, pc, "k_mlp_fwd<false>", k_mlp_fwd<false>, dim3(MLP_H2 / 64), dim3(256), 0, st, fa)) return rc;
+    fa.A = a2; fa.W = P[5]; fa.bias = P[6]; fa.out = a3; fa.IN = MLP_H2; fa.OUT = MLP_H3; fa.drop0 = MLP_H1 + MLP_H2;
+    if (int rc = launch_k(e, pc, "k_mlp_fwd<false>", k_mlp_fwd<false>, dim3(MLP_H3 / 64), dim3(256), 0, st, fa)) return rc;
+    fa.A = a3; fa.W = P[7]; fa.bias = P[8]; fa.out = dy; fa.IN = MLP_H3; fa.OUT = I; fa.drop0 = 0;
+    if (int rc = launch_k(e, pc, "k_mlp_fwd<true>", k_mlp_fwd<true>, dim3((unsigned)out_blocks), dim3(256), 0, st, fa)) return rc;
+    // down the layers: the input gradient from the kernel before its update, then the kernel's Adam pass with its gradient inside
+    const float* Ain[3] = {a3, a2, a1};
+    const float* Dn[3] = {dy, dz3, dz2};
+    float* dzo[3] = {dz3, dz2, dz1};
+    const int in[3] = {MLP_H3, MLP_H2, MLP_H1}, out[3] = {I, MLP_H3, MLP_H2}, wi[3] = {7, 5, 3};
+    for (int l = 0; l < 3; ++l) {
+      const MlpDgradArgs da{Dn[l], P[wi[l]], Ain[l], dzo[l], b, in[l], out[l], drop.s};
+      if (int rc = launch_k(e, pcb, "k_mlp_dgrad", k_mlp_dgrad, dim3((unsigned)in[l]), dim3(256), 0, st, da)) return rc;
+      MlpAdamArgs aa{};
+      aa.A = Ain[l]; aa.DZ = Dn[l]; aa.b = b; aa.IN = in[l]; aa.OUT = out[l]; aa.adam = ad;
+      aa.W = P[wi[l]]; aa.mW = M[wi[l]]; aa.vW = V[wi[l]]; aa.gW = G[wi[l]];
+      aa.B = P[wi[l] + 1]; aa.mB = M[wi[l] + 1]; aa.vB = V[wi[l] + 1]; aa.gB = G[wi[l] + 1];
+      if (int rc = launch_k(e, pcb, "k_mlp_adam", k_mlp_adam, dim3((unsigned)((out[l] + 255) / 256), (unsigned)(in[l] / MLP_ADAM_ROWS)), dim3(256), 0, st, aa))
+        return rc;
+    }
+    wa.b = b; wa.adam = ad;
+    if (int rc = launch_k(e, pcw, "k_mlp_w1<true>", k_mlp_w1<true>, dim3((unsigned)w1_blocks), dim3(128), 0, st, wa)) return rc;
+    MlpEmbedArgs ea{};
+    ea.E = P[0]; ea.mE = M[0]; ea.vE = V[0]; ea.gE = G[0]; ea.e1part = e1part; ea.parts = w1_blocks; ea.bsum = bcur; ea.dz1 = dz1;
+    ea.losspart = losspart; ea.loss_parts = out_blocks; ea.loss = losses + t; ea.b = b; ea.n_items = I; ea.adam = ad;
+    if (int rc = launch_k(e, pcb, "k_mlp_embed", k_mlp_embed, dim3(1), dim3(256), 0, st, ea)) return rc;
+    if (int rc = launch_k(e, pcb, "k_mlp_bsum", k_mlp_bsum, dim3((unsigned)(BF / 16)), dim3(256), 0, st, (const double*)bpart, w1_blocks, bnext)) return rc;
+  }
+  return SDRM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1395,6 +1395,83 @@ class Engine:
             self.feed_status()
         return losses
 
+    # ------------------------------------------------------------------ MLP evaluator's train steps (csrc/mlp_train.h)
+    MLP_TENSORS = ("mf_embedding_user", "layer1/kernel", "layer1/bias", "layer2/kernel", "layer2/bias", "layer3/kernel", "layer3/bias",
+                   "prediction/kernel", "prediction/bias")
+    MLP_WIDTHS = (512, 256, 256)
+    MLP_FACTORS = 8
+    MLP_MAX_BATCH = 16
+    MLP_MAX_ITEMS = 36864
+
+    @classmethod
+    def mlp_shapes(cls, n_users, n_items):
+        """The nine shapes of the MLP evaluator's tensors in Keras's `get_weights()` order (`MLP_TENSORS`), kernels [in, out]."""
+        h1, h2, h3 = cls.MLP_WIDTHS
+        return ((n_users, cls.MLP_FACTORS), (cls.MLP_FACTORS * n_items, h1), (h1,), (h1, h2), (h2,), (h2, h3), (h3,), (h3, n_items), (n_items,))
+
+    def mlp_train_steps(self, weights, exp_avg, exp_avg_sq, csr_dev, rows, batch=16, step0=0, lr=1e-3, betas=(0.9, 0.999), eps=1e-7, p_drop=0.5,
+                        seed=0, call_id=0, keep=None, grads_out=None, check=True):
+        """The batch loop of the MLP evaluator's `model.fit` (mlp_benchmark.py:102-107) on the device (sdrm_mlp_train_steps): ceil(n / batch)
+        consecutive train steps over the rows `rows` (int64 device tensor [n]) of the 0 / 1 matrix `csr_dev` (a `csr_to_device` tuple; only
+        its pattern is read) in order, the last batch partial - train-mode forward with the three dropouts, binary cross-entropy from the
+        logits over all b n_items elements, the gradients of all nine tensors and Keras's Adam (eps beside sqrt(v)), all enqueued by this
+        one call with no host synchronisation.  `weights`: the nine live float32 tensors in `MLP_TENSORS` order and `mlp_shapes`' shapes
+        (`mlp_eval.MLP.engine_weights()`), UPDATED IN PLACE; `exp_avg`, `exp_avg_sq`: nine tensors of the same shapes, updated in place;
+        every one starts on a 16-byte boundary and no two share a byte.  Adam's step count for step t of the call is `step0 + t + 1`.
+        Dropout: with `keep` (uint8 device tensor [n, 1024]: 512 + 256 + 256 columns, non-zero = kept) the masks are the caller's; without,
+        they are Philox4x32-10's of (seed, call_id, the row's place in `rows`, column).  `grads_out`: nine float32 tensors of the weights'
+        shapes that receive the gradients the update used - for a call of ONE step only.  Row ids and column indices are range-checked on
+        the device (`check` as in `csr_rows_to_dense`).  Returns the per-step losses, a float64 device tensor [ceil(n / batch)]."""
+        who = "mlp_train_steps"
+        lists = {"weights": weights, "exp_avg": exp_avg, "exp_avg_sq": exp_avg_sq}
+        if grads_out is not None:
+            lists["grads_out"] = grads_out
+        for lname, lst in lists.items():
+            lst = list(lst.values()) if isinstance(lst, dict) else list(lst)
+            if len(lst) != len(self.MLP_TENSORS):
+                raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {lname} has {len(lst)} tensors; the model has nine ({', '.join(self.MLP_TENSORS)})")
+            lists[lname] = lst
+        e, w1 = lists["weights"][0], lists["weights"][1]
+        if not isinstance(e, torch.Tensor) or e.dim() != 2 or not isinstance(w1, torch.Tensor) or w1.dim() != 2 or w1.shape[0] % self.MLP_FACTORS:
+            raise SdrmError(f"{who}: {self.MLP_TENSORS[0]} must be a 2-D tensor [n_users, 8] and {self.MLP_TENSORS[1]} one [8 n_items, 512]")
+        n_users, n_items = int(e.shape[0]), int(w1.shape[0]) // self.MLP_FACTORS
+        shapes = self.mlp_shapes(n_users, n_items)
+        checked = {lname: [self._f32(who, f"{lname}[{name}]", t.detach() if isinstance(t, torch.Tensor) else t, shape)
+                           for name, t, shape in zip(self.MLP_TENSORS, lst, shapes)] for lname, lst in lists.items()}
+        indptr, indices, _, m_rows, m_cols, _ = self._sparse_dev(who, "csr", csr_dev)
+        if m_cols != n_items:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: the matrix has {m_cols} columns, the model {n_items} items")
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.device != self.device or not rows.is_contiguous() or rows.dim() != 1:
+            raise SdrmError(f"{who}: rows must be a contiguous 1-D int64 tensor on the engine's device")
+        n, batch, step0 = int(rows.numel()), int(batch), int(step0)
+        if (not 1 <= n_items <= self.MLP_MAX_ITEMS or n_users < 2 or m_rows < 1 or not 1 <= n <= 2 ** 31 - 1 or not 1 <= batch <= self.MLP_MAX_BATCH
+                or step0 < 0 or not (0.0 <= float(p_drop) < 1.0)):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: n_items = {n_items} outside 1 .. {self.MLP_MAX_ITEMS}, n_users = {n_users} < 2, no row, n = {n} "
+                            f"outside 1 .. 2^31 - 1, batch = {batch} outside 1 .. {self.MLP_MAX_BATCH}, step0 = {step0} < 0 or p_drop = {p_drop} "
+                            f"outside [0, 1)")
+        mode = 1
+        if keep is not None:
+            if (not isinstance(keep, torch.Tensor) or keep.dtype != torch.uint8 or keep.device != self.device or not keep.is_contiguous()
+                    or tuple(keep.shape) != (n, sum(self.MLP_WIDTHS))):
+                raise SdrmError(f"{who}: keep must be a contiguous uint8 tensor [{n}, {sum(self.MLP_WIDTHS)}] on the engine's device")
+            mode = 0
+        rec = _lib.MlpTrain()
+        for i in range(len(self.MLP_TENSORS)):
+            rec.p[i], rec.m[i], rec.v[i] = (checked[k][i].data_ptr() for k in ("weights", "exp_avg", "exp_avg_sq"))
+        rec.n_users, rec.n_items = n_users, n_items
+        gptr = None
+        if grads_out is not None:
+            gptr = (C.c_void_p * len(self.MLP_TENSORS))(*[t.data_ptr() for t in checked["grads_out"]])
+        losses = torch.empty(-(-n // batch), dtype=torch.float64, device=self.device)
+        self._check(self.lib.sdrm_mlp_train_steps(self._h, C.byref(rec), _ptr(indptr), _ptr(indices), m_rows, _ptr(rows), n, batch, step0, float(lr),
+                                                  float(betas[0]), float(betas[1]), float(eps), float(p_drop), mode, _ptr(keep),
+                                                  int(seed) & (2 ** 64 - 1), int(call_id) & 0xFFFFFFFF, _ptr(losses), gptr, _stream()),
+                    "sdrm_mlp_train_steps")
+        self._feed_keep = (indptr, indices, rows, keep, checked)
+        if check:
+            self.feed_status()
+        return losses
+
     # ------------------------------------------------------------------ evaluation half of the VAE pre-stage (csrc/eval_half.h)
     def vae_eval_holdout(self, w1, b1, w2, b2, w3, b3, w4, b4, train_csr_dev, held_csr_dev, k, metric, batch=500, out=None, logits=None,
                          check=False):
