@@ -606,7 +606,15 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
         if (i < nt) kstep(tag, fa0, fb0, fa1, fb1, 1, ra0, rb0, 0, i + 4);   // odd count (its pieces are harmless)
       };
       if (wave_active) run(std::true_type{});
-      else run(std::false_type{});   // a wave whose tile range lies outside the matrix only feeds the pipeline
+      else {
+        run(std::false_type{});   // a wave whose tile range lies outside the matrix only feeds the pipeline
+        // Its loads end here, in so many words.  To the compiler the two loops are one straight line (the wave-uniform branch between them
+        // is structurised away), and the prefetch registers of this loop are where the other keeps its fragments: without this wait the
+        // ACTIVE loop gets an s_waitcnt vmcnt(0) in front of its first fragment reads - against loads this path never brings there - and
+        // every pair of K-steps waits for the operand loads it has just issued, requested four K-steps ahead for nothing.  With it the
+        // loop's waits are the counted ones in front of the LDS stores (tests/test_sampler_kernel_resources.py).
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0); expcnt and lgkmcnt left alone
+      }
     }
   } else {
     // k-major operands (wgrad: both operands are row-major over the reduction index; also the 16-wide MFMA
