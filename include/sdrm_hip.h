@@ -775,6 +775,34 @@ int sdrm_mlp_train_steps(sdrm_engine* e, const sdrm_mlp_train* s, const int64_t*
                          int64_t n, int batch, int64_t step0, float lr, float beta1, float beta2, float eps, float p_drop, int mode,
                          const uint8_t* keep, uint64_t seed, uint32_t call_id, double* losses, float* const* grads_out, void* stream);
 
+/* The MLP evaluator's EVAL-MODE forward on the device (reference: mlp_benchmark.py:92 the `RootMeanSquaredError` metric, :109 the per-epoch
+ * validation pass of `model.fit`, :114 `model.predict`; restated in sdrm_amd/mlp_eval.py; csrc/mlp_eval.h).  In inference the dropouts are
+ * the identity; the input rows are 0 / 1, given as the PATTERN of a device CSR matrix [n_rows, n_items] with nnz entries:
+ *   a1 = relu(b1 + sum_j E[x_rj] W1[8j ..]);  a2 = relu(a1 W2 + b2);  a3 = relu(a2 W3 + b3);  y = a3 W4 + b4;  p = sigmoid(y)
+ * The struct holds DEVICE pointers to the nine LIVE tensors in sdrm_mlp_train's order and layout, every base on the 16-byte grid; they are
+ * READ, nothing is re-packed on the host, and they are free again once the call is ordered on `stream`.
+ * sdrm_mlp_eval evaluates the n rows rows[0 .. n) (DEVICE int64 row ids; any order, repeats allowed) or, with rows null, the rows row0 ..
+ *   row0 + n - 1, looping over batches of `batch` rows itself.  out: null, or DEVICE float32 [n, n_items] contiguous that receives p (kind 0) or
+ *   y (kind 1).  sse: null, or ONE DEVICE float64 that receives the sum over the n x n_items elements of (p - x)^2 - probabilities whatever
+ *   `kind` says - the numerator of the RMSE.  With out null nothing of size n x n_items exists: one [batch][n_items] scratch buffer is reused.
+ *   W1 is read ONCE per call: one pass folds it into a row per item, D[j] = sum_f (E[1][f] - E[0][f]) W1[8j + f] (float64 sums, rounded
+ *   once), and the sums B_f = sum_j W1[8j + f]; a row's first layer is then a sum of its entries' rows of D in fp32.  Layers 2, 3 and the
+ *   output layer are the fp32-MFMA GEMMs on weights staged once per call.  The SSE is SSE_r = sum_j p_rj^2 - sum_{j in row r} (2 p_rj - 1)
+ *   per row in float64, the rows added in a fixed order by the call's last launch.  No floating-point atomic: two runs of a call give the
+ *   same bits, and a row's output has the same bits wherever it stands in any call made with the same `batch` (the tile goes by `batch`).
+ *   Launches: 7 per call (8 with sse) and 5 per batch - more only where the output layer goes out in row bands, never for a batch of
+ *   at most 1792 rows; all enqueued on `stream`, nothing is read back and nothing synchronises.  Scratch is library-owned and grow-only,
+ *   as for sdrm_neumf_train_steps.
+ *   Range checks, into the status word sdrm_feed_status reports: a row id outside [0, n_rows), or an indptr pair that is negative, out of
+ *   order or reaches behind nnz, makes a DEAD row - its row of out is zero and it adds nothing to sse; a column outside [0, n_items) is
+ *   skipped by the first layer and by sse.  The columns of a row must be distinct.  No load or store uses an unchecked index.
+ *   SDRM_ERR_SHAPE: n_items outside 1 .. 36864, n_users < 2, batch outside 1 .. 4096, n < 1, n_rows < 1, a contiguous range that starts below
+ *   0 or ends behind n_rows, nnz < 0, n x n_items at or above 2^40, out and sse both null, a tensor off the 16-byte grid; SDRM_ERR_ARG: a
+ *   null pointer, kind outside {0, 1}.  Refused calls launch nothing. */
+typedef struct sdrm_mlp_eval_w { const float* p[9]; int n_users, n_items; } sdrm_mlp_eval_w;
+int sdrm_mlp_eval(sdrm_engine* e, const sdrm_mlp_eval_w* w, const int64_t* indptr, const int32_t* indices, int64_t nnz, int64_t n_rows,
+                  const int64_t* rows, int64_t row0, int64_t n, int batch, int kind, float* out, double* sse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

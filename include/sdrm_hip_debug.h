@@ -240,6 +240,13 @@ int sdrm_debug_neumf_train_args(int n_users, int n_items, int factor, int64_t n,
 int sdrm_debug_mlp_train_args(int n_users, int n_items, int64_t n, int batch, int64_t step0, float p_drop, int with_grads, const uint64_t* addr,
                               int n_addr);
 
+/* The host side of sdrm_mlp_eval that needs no device: SDRM_OK, or SDRM_ERR_SHAPE for a call outside its envelope (n_items outside 1 .. 36864,
+ * n_users < 2, batch outside 1 .. 4096, n < 1, n_rows < 1, nnz < 0, without a row list - rows_listed == 0 - a range row0 .. row0 + n - 1 that
+ * starts below 0 or ends behind n_rows, n x n_items at or above 2^40, neither with_out nor with_sse, and, when `addr` is given - the base
+ * addresses of the nine tensors, n_addr = 9 - one off the 16-byte grid); SDRM_ERR_ARG for a null address or another n_addr. */
+int sdrm_debug_mlp_eval_args(int n_users, int n_items, int64_t nnz, int64_t n_rows, int rows_listed, int64_t row0, int64_t n, int batch, int with_out,
+                             int with_sse, const uint64_t* addr, int n_addr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,10 @@ class MlpTrain(C.Structure):
     _fields_ = [("p", c_void_p * 9), ("m", c_void_p * 9), ("v", c_void_p * 9), ("n_users", c_int), ("n_items", c_int)]
 
 
+class MlpEvalW(C.Structure):
+    _fields_ = [("p", c_void_p * 9), ("n_users", c_int), ("n_items", c_int)]
+
+
 class Neumf(C.Structure):
     _fields_ = [(name, c_void_p) for name in ("embed_user_gmf", "embed_item_gmf", "embed_user_mlp", "embed_item_mlp", "w1", "b1", "w2", "b2",
                                               "w3", "b3", "wp", "bp")] + [("n_users", c_int), ("n_items", c_int), ("factor", c_int)]
@@ -154,6 +158,8 @@ SIGNATURES = {
                                        c_void_p, c_uint64, C.c_uint32, c_void_p, c_void_p, c_void_p]),
     "sdrm_mlp_train_steps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_float, c_float, c_float,
                                      c_float, c_float, c_int, c_void_p, c_uint64, C.c_uint32, c_void_p, c_void_p, c_void_p]),
+    "sdrm_mlp_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
+                              c_void_p]),
     "sdrm_source_hash": (C.c_char_p, []),
     # include/sdrm_hip_debug.h (test / tuning hooks; every setter acts on one handle)
     "sdrm_debug_philox_draws": (c_int, [c_void_p, c_uint64, C.c_uint32, C.c_uint32, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -171,6 +177,7 @@ SIGNATURES = {
     "sdrm_debug_neumf_args": (c_int, [c_int, c_int, c_int, c_int64, c_int64]),
     "sdrm_debug_neumf_train_args": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int64, c_float]),
     "sdrm_debug_mlp_train_args": (c_int, [c_int, c_int, c_int64, c_int, c_int64, c_float, c_int, C.POINTER(c_uint64), c_int]),
+    "sdrm_debug_mlp_eval_args": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int, C.POINTER(c_uint64), c_int]),
     "sdrm_debug_holdout_args": (c_int, [c_int, c_int64, c_int64, C.c_double, c_int64, C.POINTER(c_int64)]),
     "sdrm_debug_set_tile": (c_int, [c_void_p, c_int]),
     "sdrm_debug_set_nt32_rows": (c_int, [c_void_p, c_int, c_int]),

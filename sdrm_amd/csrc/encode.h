@@ -82,7 +82,10 @@ struct EncodeCsrArgs {
 // with a column outside [0, n_items) becomes (column 0, value 0): no stray load, and it adds +0.  sum(value^2) runs alongside in every thread.
 // CHECKED == false is k_encode_csr as it always was: the upper end of an indptr pair is the caller's (the feed entry points are given
 // no nnz).  CHECKED == true also holds it against a.nnz: a pair that reaches behind the index array is the empty row and raises FEED_BAD_PTR.
-template <int TPR, int NV, int U, bool CHECKED>
+// ACT is what follows the sum: ENC_ACT_NORM_TANH is the encoder's tanh(sum / max(|x|_2, 1e-12) + b1); ENC_ACT_RELU is relu(sum + b1) with no
+// scaling (the MLP evaluator's first layer from its folded rows, csrc/mlp_eval.h: sum(value^2) is then dead code).
+enum : int { ENC_ACT_NORM_TANH = 0, ENC_ACT_RELU = 1 };
+template <int TPR, int NV, int U, bool CHECKED, int ACT = ENC_ACT_NORM_TANH>
 __device__ __forceinline__ void encode_csr_rows(const EncodeCsrArgs& a) {
   constexpr int RPW = 256 / TPR;   // rows per work-group
   __shared__ int2 ent[RPW][TPR];
@@ -135,8 +138,11 @@ __device__ __forceinline__ void encode_csr_rows(const EncodeCsrArgs& a) {
     const int s = slot + v * TPR;
     if (s < q) {
       const float4 b = b4[s];
-      out[s] = make_float4(tanh_fast(fmaf(acc[v].x, inv, b.x)), tanh_fast(fmaf(acc[v].y, inv, b.y)), tanh_fast(fmaf(acc[v].z, inv, b.z)),
-                           tanh_fast(fmaf(acc[v].w, inv, b.w)));
+      if constexpr (ACT == ENC_ACT_RELU)
+        out[s] = make_float4(fmaxf(acc[v].x + b.x, 0.f), fmaxf(acc[v].y + b.y, 0.f), fmaxf(acc[v].z + b.z, 0.f), fmaxf(acc[v].w + b.w, 0.f));
+      else
+        out[s] = make_float4(tanh_fast(fmaf(acc[v].x, inv, b.x)), tanh_fast(fmaf(acc[v].y, inv, b.y)), tanh_fast(fmaf(acc[v].z, inv, b.z)),
+                             tanh_fast(fmaf(acc[v].w, inv, b.w)));
     }
   }
   for (int s = q + slot; s < (a.Hp >> 2); s += TPR) out[s] = make_float4(0.f, 0.f, 0.f, 0.f);   // the GEMM's K padding

@@ -58,8 +58,10 @@ enum : int {
   EPI_BIAS_PRELU = 10,   // C = prelu(acc + bias[n]; slopeE): the sampler's hidden layers store the ACTIVATION - nothing reads their
                          // pre-activations again (no backward), and the next layer then loads its operand without the PReLU-on-load
                          // transform, which costs the 5429-row launches ~1.5 us each (12.7 us plain against 16 us with it)
-  EPI_DTANH_G = 11       // C = acc * (1 - aux^2), bounds-checked into an unpadded caller buffer: the dgrad through a stored tanh
+  EPI_DTANH_G = 11,      // C = acc * (1 - aux^2), bounds-checked into an unpadded caller buffer: the dgrad through a stored tanh
                          // ACTIVATION aux (csrc/latent.h: d loss / d pre of the VAE encoder's hidden layer)
+  EPI_BIAS_SIGMOID_G = 12   // C = sigmoid(acc + bias[n]), bounds-checked into an unpadded caller buffer (the MLP evaluator's output layer,
+                         // csrc/mlp_eval.h)
 };
 
 constexpr int NTHREADS = 256;
@@ -131,6 +133,8 @@ struct GemmArgs {
 };
 
 __device__ __forceinline__ float prelu_f(float v, float a) { return v > 0.f ? v : a * v; }
+// 1 / (1 + e^-y) by libm's expf and a true division: the probabilities are compared at float32's own rounding
+__device__ __forceinline__ float sigmoid_f(float y) { return 1.f / (1.f + expf(-y)); }
 
 // tanh through the hardware exp2/rcp: 1 - 2/(e^{2x}+1).  Absolute error ~1e-7 (the eps-net output is
 // compared at 1e-4 of max|y| ~ 0.3); libm's tanhf costs ~30 instructions per element, which on a
@@ -723,7 +727,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
       const int rbase = tm0 + 4 * lhi;
       float bias = 0.f;
       if (EPI == EPI_BIAS || EPI == EPI_BIAS_TANH || EPI == EPI_BIAS_TANH_G || EPI == EPI_TANH_REV || EPI == EPI_BIAS_G ||
-          EPI == EPI_BIAS_PRELU)
+          EPI == EPI_BIAS_PRELU || EPI == EPI_BIAS_SIGMOID_G)
         bias = PF_BIAS ? pf_bias[a][b] : p.bias[col];
       if (EPI == EPI_BIAS || EPI == EPI_PLAIN) {
 #pragma unroll
@@ -785,6 +789,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
         for (int r = 0; r < NR; ++r) {
           const int row = rbase + rowoff(r);
           if (row < p.rows_valid && col < p.cols_valid) Cp[(size_t)row * p.ldc + col] = acc[a][b][r] + bias;
+        }
+      } else if (EPI == EPI_BIAS_SIGMOID_G) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          const int row = rbase + rowoff(r);
+          if (row < p.rows_valid && col < p.cols_valid) Cp[(size_t)row * p.ldc + col] = sigmoid_f(acc[a][b][r] + bias);
         }
       } else if (EPI == EPI_DTANH_G) {
         const float* __restrict__ auxp = p.aux;

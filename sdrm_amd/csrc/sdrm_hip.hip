@@ -31,6 +31,7 @@
 #include "latent.h"
 #include "neumf.h"
 #include "mlp_train.h"
+#include "mlp_eval.h"
 #include "neumf_train.h"
 #include "nll.h"
 #include "nmf.h"
@@ -194,6 +195,10 @@ enum Scratch {
   // sdrm_mlp_train_steps (csrc/mlp_train.h), 8-byte words: [B_f of the weights, two copies | the W1 pass's partial B_f and dE[1] | the gather's
   // partial sums | loss partials | a1, a2, a3, dz1, dz2, dz3, dy (float) | live words | item mask]
   SCR_MLP_TRAIN_WS,
+  // sdrm_mlp_eval (csrc/mlp_eval.h), 8-byte words, every piece written by the call that reads it: [B_f | the fold's partial B_f | the rows' SSE
+  // | D [items][512], base, the zero slope, W2^T, W3^T, W4^T [Ir][256], b4 [Ir], a1, a2, a3 [MP][.] (float) | the batch's [batch][items] output
+  // (when the caller gives none)]
+  SCR_MLP_EVAL_WS,
   SCR_CSR_WS,        // sdrm_equal_sparsity_csr_begin / _end (csrc/compact.h), 8-byte words: [mask words | row offsets int64 | row counts uint32]
   // sdrm_csr_transpose / sdrm_csr_vstack (csrc/csr_transpose.h), 8-byte words: [checked | total | bit table | colptr int64 | offsets uint32 |
   // column counts uint32] and [total | indptr int64 | row lengths uint32]
@@ -307,7 +312,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_MLP_FWD, PC_MLP_BWD, PC_MLP_W1, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_MLP_FWD, PC_MLP_BWD, PC_MLP_W1, PC_MLP_FOLD, PC_MLP_EVAL, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -351,7 +356,9 @@ static const char* kProfNames[PC_COUNT] = {
     "nmf evaluator: k_nmf_expand the rank-k expansion W H into dense float32 scores (float64 sums, rounded once)",
     "mlp train step: k_mlp_mask / k_mlp_gather / k_mlp_z1 / k_mlp_fwd train-mode forward from CSR rows with the three dropouts, the loss terms and dy",
     "mlp train step: k_mlp_dgrad / k_mlp_adam / k_mlp_embed / k_mlp_bsum input gradients, Keras's Adam on W2 .. b4 and on E's two rows with the gradient made inside the pass, the loss, B_f",
-    "mlp train step: k_mlp_w1 the one read-modify-write pass over W1 and its moments (gradient per element from S and T_j, Keras's Adam, partial B_f and dE[1])"};
+    "mlp train step: k_mlp_w1 the one read-modify-write pass over W1 and its moments (gradient per element from S and T_j, Keras's Adam, partial B_f and dE[1])",
+    "mlp evaluation: k_mlp_fold the one read-only pass over W1 that leaves D [items][512] and the partial B_f",
+    "mlp evaluation: k_mlp_bsum / k_mlp_base / k_pad2d / k_encode_w1t staging once per call, then per batch k_mlp_rows_relu / gemm_kernel<0,0,0,0,10> x2 / gemm_kernel<0,0,0,0,7> or <0,0,0,0,12> / k_mlp_sse, and k_mlp_sse_sum: the eval-mode forward from CSR rows, probabilities or logits, and the sum of squared errors"};
 
 namespace {
 
@@ -4556,6 +4563,132 @@ int sdrm_mlp_train_steps(sdrm_engine* e, const sdrm_mlp_train* s, const int64_t*
     if (int rc = launch_k(e, pcb, "k_mlp_embed", k_mlp_embed, dim3(1), dim3(256), 0, st, ea)) return rc;
     if (int rc = launch_k(e, pcb, "k_mlp_bsum", k_mlp_bsum, dim3((unsigned)(BF / 16)), dim3(256), 0, st, (const double*)bpart, w1_blocks, bnext)) return rc;
   }
+  return SDRM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The MLP evaluator's eval-mode forward, validation SSE and predict (mlp_benchmark.py:92, :109, :114), csrc/mlp_eval.h.
+namespace {
+
+constexpr int MLP_EVAL_MAX_BATCH = 4096;
+
+const char* const kMlpEvalEnvelope = ": n_items outside 1 .. 36864, n_users < 2, batch outside 1 .. 4096, n < 1, a row range that starts below 0 or ends behind "
+                                     "n_rows, n_rows < 1, a negative nnz, n x n_items at or above 2^40, neither out nor sse, or a tensor off the 16-byte grid "
+                                     "(SDRM_ERR_SHAPE); a null tensor or another count of addresses (SDRM_ERR_ARG)";
+
+}  // namespace
+
+// The host side that needs no device: the envelope of sdrm_mlp_eval and, with `addr`, the checks of its nine tensors' addresses.
+int sdrm_debug_mlp_eval_args(int n_users, int n_items, int64_t nnz, int64_t n_rows, int rows_listed, int64_t row0, int64_t n, int batch, int with_out,
+                             int with_sse, const uint64_t* addr, int n_addr) {
+  if (n_items < 1 || n_items > MLP_MAX_ITEMS || n_users < 2 || batch < 1 || batch > MLP_EVAL_MAX_BATCH || n < 1 || n_rows < 1 || nnz < 0)
+    return SDRM_ERR_SHAPE;
+  if (!rows_listed && (row0 < 0 || row0 > n_rows || n > n_rows - row0)) return SDRM_ERR_SHAPE;
+  if (n > (((int64_t)1 << 40) - 1) / n_items) return SDRM_ERR_SHAPE;   // n x n_items < 2^40
+  if (!with_out && !with_sse) return SDRM_ERR_SHAPE;
+  for (int cfg = 0; cfg < N_TILE_CFGS; ++cfg) {   // the three GEMM launches on any tile (K = 512, 256, 256; A's stride equal to K)
+    if (gemm_nt_band_rows(cfg, MLP_H2) < 1 || gemm_nt_band_rows(cfg, round_up(n_items, 32)) < 1) return SDRM_ERR_SHAPE;
+    if (!gemm_span_ok(cfg, true, MLP_H1, MLP_H1, MLP_H1) || !gemm_span_ok(cfg, true, MLP_H2, MLP_H2, MLP_H2)) return SDRM_ERR_SHAPE;
+  }
+  if (!addr) return SDRM_OK;
+  if (n_addr != MLP_TENSORS) return SDRM_ERR_ARG;
+  for (int i = 0; i < n_addr; ++i) {
+    if (!addr[i]) return SDRM_ERR_ARG;
+    if (addr[i] & 15u) return SDRM_ERR_SHAPE;
+  }
+  return SDRM_OK;
+}
+
+int sdrm_mlp_eval(sdrm_engine* e, const sdrm_mlp_eval_w* w, const int64_t* indptr, const int32_t* indices, int64_t nnz, int64_t n_rows,
+                  const int64_t* rows, int64_t row0, int64_t n, int batch, int kind, float* out, double* sse, void* stream) {
+  const char* who = "sdrm_mlp_eval";
+  if (!e) return SDRM_ERR_ARG;
+  if (!w || !indptr || !indices) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (kind != 0 && kind != 1) return fail(e, SDRM_ERR_ARG, std::string(who) + ": kind is neither 0 (probabilities) nor 1 (logits)");
+  uint64_t addr[MLP_TENSORS];
+  for (int i = 0; i < MLP_TENSORS; ++i) addr[i] = (uint64_t)(uintptr_t)w->p[i];
+  if (int rc = sdrm_debug_mlp_eval_args(w->n_users, w->n_items, nnz, n_rows, rows != nullptr, row0, n, batch, out != nullptr, sse != nullptr, addr,
+                                        MLP_TENSORS))
+    return fail(e, rc, std::string(who) + kMlpEvalEnvelope);
+  hipStream_t st = (hipStream_t)stream;
+  if (int jr = chains_join(e, st)) return jr;
+  const int I = w->n_items, Ip = round_up(I, 32), Ir = round_up(Ip, 128);
+  const int bmax = (int)std::min<int64_t>(batch, n), MP = round_up(bmax, 128);
+  const int fold_blocks = (I + MLP_W1_ITEMS - 1) / MLP_W1_ITEMS;
+  const size_t BF = (size_t)MLP_F * MLP_H1;
+  // the workspace: 8-byte words first, every piece on the 16-byte grid
+  size_t at = 0;
+  const auto take = [&](size_t words) { const size_t o = at; at += (words + 1) / 2 * 2; return o; };
+  const auto take_f = [&](size_t floats) { return take((floats + 1) / 2); };
+  const size_t o_bsum = take(BF), o_bpart = take((size_t)fold_blocks * BF), o_rowsse = take(sse ? (size_t)n : 0);
+  const size_t o_D = take_f((size_t)I * MLP_H1), o_base = take_f(MLP_H1), o_zero = take_f(4), o_w2 = take_f((size_t)MLP_H2 * MLP_H1),
+               o_w3 = take_f((size_t)MLP_H3 * MLP_H2), o_w4 = take_f((size_t)Ir * MLP_H3), o_b4 = take_f(Ir), o_a1 = take_f((size_t)MP * MLP_H1),
+               o_a2 = take_f((size_t)MP * MLP_H2), o_a3 = take_f((size_t)MP * MLP_H3), o_out = take_f(out ? 0 : (size_t)bmax * I);
+  double* ws;
+  if (int rc = scratch(e, SCR_MLP_EVAL_WS, at, &ws)) return rc;
+  double *bsum = ws + o_bsum, *bpart = ws + o_bpart, *rowsse = sse ? ws + o_rowsse : nullptr;
+  const auto fl = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
+  float *D = fl(o_D), *base = fl(o_base), *zero = fl(o_zero), *w2t = fl(o_w2), *w3t = fl(o_w3), *w4t = fl(o_w4), *b4p = fl(o_b4), *a1 = fl(o_a1),
+        *a2 = fl(o_a2), *a3 = fl(o_a3), *own_out = out ? nullptr : fl(o_out);
+  const float* const* P = w->p;
+  const LaunchClass pc(PC_MLP_EVAL);
+  int rc;
+  // once per call: the fold of W1, B_f, base; the zero slope; b4 padded, the three Keras kernels transposed
+  {
+    const MlpFoldArgs fa{P[1], P[0], D, bpart, I};
+    if ((rc = launch_k(e, LaunchClass(PC_MLP_FOLD), "k_mlp_fold", k_mlp_fold, dim3((unsigned)fold_blocks), dim3(128), 0, st, fa))) return rc;
+    if ((rc = launch_k(e, pc, "k_mlp_bsum", k_mlp_bsum, dim3((unsigned)(BF / 16)), dim3(256), 0, st, (const double*)bpart, fold_blocks, bsum))) return rc;
+    if ((rc = launch_k(e, pc, "k_mlp_base", k_mlp_base, dim3(1), dim3(MLP_H1), 0, st, P[0], P[2], (const double*)bsum, base))) return rc;
+    HIP_TRY(e, hipMemsetAsync(zero, 0, 4 * sizeof(float), st));
+    PadList pad;
+    pad.add(P[8], 1, I, b4p, 1, Ir);
+    if ((rc = pad.launch(e, pc, st)) || (rc = launch_w1t(e, pc, P[3], MLP_H1, MLP_H2, w2t, MLP_H1, st)) ||
+        (rc = launch_w1t(e, pc, P[5], MLP_H2, MLP_H3, w3t, MLP_H2, st)) || (rc = launch_w1t(e, pc, P[7], MLP_H3, I, w4t, MLP_H3, st)))
+      return rc;
+  }
+  // the tile goes by `batch` alone, so that a row has the same bits in every call made with the same batch
+  const int cfg = choose_cfg(e->tune, round_up(batch, BM), e->tune.nt32_max_rows);
+  for (int64_t j0 = 0; j0 < n; j0 += batch) {
+    const int b = (int)std::min<int64_t>(batch, n - j0);
+    const int rows64 = round_up(b, BM);
+    const CsrBatch cb{indptr, indices, nullptr, rows ? rows + j0 : nullptr, rows ? 0 : row0 + j0, n_rows, b, I, e->feed_flag};
+    // 1: a1 = relu(base + the row's rows of D) into the padded operand
+    {
+      EncodeCsrArgs a{};
+      a.csr = cb; a.w1t = D; a.b1 = base; a.Hq = MLP_H1; a.Hp = MLP_H1; a.hid = a1; a.nnz = nnz;
+      if ((rc = launch_gather_rows(e, pc, "k_mlp_rows_relu", MLP_H1 / 4, a, st,
+                                   [](auto tpr, auto nv, auto u) { return k_mlp_rows_relu<VAL(tpr), VAL(nv), VAL(u)>; })))
+        return rc;
+    }
+    // 2, 3: a2 = relu(a1 W2 + b2), a3 = relu(a2 W3 + b3): PReLU with a zero slope
+    {
+      GemmArgs a{};
+      a.B = w2t; a.ldb = MLP_H1; a.C = a2; a.ldc = MLP_H2; a.K = MLP_H1; a.bias = P[4]; a.slopeE = zero;
+      if ((rc = gemm_nt_banded<EPI_BIAS_PRELU>(e, a, a1, MLP_H1, rows64, MLP_H2, b, st, Prof{e, PC_MLP_EVAL, 2.0 * b * (double)MLP_H1 * MLP_H2}, cfg))) return rc;
+    }
+    {
+      GemmArgs a{};
+      a.B = w3t; a.ldb = MLP_H2; a.C = a3; a.ldc = MLP_H3; a.K = MLP_H2; a.bias = P[6]; a.slopeE = zero;
+      if ((rc = gemm_nt_banded<EPI_BIAS_PRELU>(e, a, a2, MLP_H2, rows64, MLP_H3, b, st, Prof{e, PC_MLP_EVAL, 2.0 * b * (double)MLP_H2 * MLP_H3}, cfg))) return rc;
+    }
+    // 4: the output layer, bounds-checked into the batch's [b][I]: the caller's rows j0 .., or the scratch (always probabilities)
+    float* s_out = out ? out + (size_t)j0 * I : own_out;
+    const bool logits = out && kind == 1;
+    {
+      GemmArgs a{};
+      a.B = w4t; a.ldb = MLP_H3; a.C = s_out; a.ldc = I; a.K = MLP_H3; a.bias = b4p; a.cols_valid = I;
+      const Prof pr{e, PC_MLP_EVAL, 2.0 * b * (double)I * MLP_H3};
+      if ((rc = logits ? gemm_nt_banded<EPI_BIAS_G>(e, a, a3, MLP_H3, rows64, Ip, b, st, pr, cfg)
+                       : gemm_nt_banded<EPI_BIAS_SIGMOID_G>(e, a, a3, MLP_H3, rows64, Ip, b, st, pr, cfg)))
+        return rc;
+    }
+    // 5: dead rows zeroed, the rows' SSE
+    {
+      const MlpSseArgs a{cb, nnz, s_out, rowsse ? rowsse + j0 : nullptr, logits ? 1 : 0};
+      if ((rc = launch_k(e, pc, "k_mlp_sse", k_mlp_sse, dim3((unsigned)b), dim3(256), 0, st, a))) return rc;
+    }
+  }
+  if (sse) return launch_k(e, pc, "k_mlp_sse_sum", k_mlp_sse_sum, dim3(1), dim3(256), 0, st, (const double*)rowsse, n, sse);
   return SDRM_OK;
 }
 

@@ -1472,6 +1472,65 @@ class Engine:
             self.feed_status()
         return losses
 
+    # ------------------------------------------------------------------ MLP evaluator's eval-mode forward (csrc/mlp_eval.h)
+    MLP_EVAL_MAX_BATCH = 4096
+
+    def mlp_eval(self, weights, csr_dev, rows=None, row0=0, n=None, batch=1024, logits=False, out=None, sse=False, check=True):
+        """`model.predict` (mlp_benchmark.py:114) and the numerator of the validation `RootMeanSquaredError` (:92, :109) on the device
+        (sdrm_mlp_eval): the model's inference-mode forward for the rows `rows` (int64, any order, repeats allowed) or row0 .. row0 + n - 1
+        (default: up to the last row) of the 0 / 1 matrix `csr_dev` (a `csr_to_device` tuple; only its pattern is read), in batches of
+        `batch` rows inside the one call, with no dense input and ONE pass over W1.  `weights`: the nine live float32 tensors as
+        `mlp_train_steps` takes them, read in place.  `out`: None - a new float32 [n, n_items] -, a tensor of that shape to fill, or False:
+        no output of that size exists anywhere.  It receives sigmoid(y), or the logits y with `logits=True`.  `sse=True`: also a float64
+        device tensor of ONE element, the sum over all n x n_items elements of (sigmoid(y) - x)^2, whatever `logits` says.  Returns `out`,
+        `(out, sse_tensor)`, or `sse_tensor` alone when `out is False`.  Nothing is read back; row ids, indptr pairs and column indices
+        are range-checked on the device (a bad row is zero in `out` and absent from the sum; `check` as in `csr_rows_to_dense`)."""
+        who = "mlp_eval"
+        lst = list(weights.values()) if isinstance(weights, dict) else list(weights)
+        if len(lst) != len(self.MLP_TENSORS):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: weights has {len(lst)} tensors; the model has nine ({', '.join(self.MLP_TENSORS)})")
+        e, w1 = lst[0], lst[1]
+        if not isinstance(e, torch.Tensor) or e.dim() != 2 or not isinstance(w1, torch.Tensor) or w1.dim() != 2 or w1.shape[0] % self.MLP_FACTORS:
+            raise SdrmError(f"{who}: {self.MLP_TENSORS[0]} must be a 2-D tensor [n_users, 8] and {self.MLP_TENSORS[1]} one [8 n_items, 512]")
+        n_users, n_items = int(e.shape[0]), int(w1.shape[0]) // self.MLP_FACTORS
+        checked = [self._f32(who, f"weights[{name}]", t.detach() if isinstance(t, torch.Tensor) else t, shape)
+                   for name, t, shape in zip(self.MLP_TENSORS, lst, self.mlp_shapes(n_users, n_items))]
+        indptr, indices, _, m_rows, m_cols, nnz = self._sparse_dev(who, "csr", csr_dev)
+        if m_cols != n_items:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: the matrix has {m_cols} columns, the model {n_items} items")
+        if rows is not None:
+            if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.device != self.device or not rows.is_contiguous() or rows.dim() != 1:
+                raise SdrmError(f"{who}: rows must be a contiguous 1-D int64 tensor on the engine's device")
+            n = int(rows.numel())
+        elif n is None:
+            n = m_rows - int(row0)
+        n, row0, batch = int(n), int(row0), int(batch)
+        if out is False and not sse:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: out=False without sse=True asks for nothing")
+        rc = self.lib.sdrm_debug_mlp_eval_args(n_users, n_items, nnz, m_rows, int(rows is not None), row0, n, batch, int(out is not False), int(bool(sse)),
+                                               None, 0)
+        if rc:
+            raise SdrmError(f"{who}: {_lib.STATUS.get(rc, rc)}: n_items = {n_items} outside 1 .. {self.MLP_MAX_ITEMS}, n_users = {n_users} < 2, batch = "
+                            f"{batch} outside 1 .. {self.MLP_EVAL_MAX_BATCH}, n = {n} < 1, rows {row0} .. {row0 + n - 1} outside the matrix's {m_rows}, or "
+                            f"n x n_items at or above 2^40")
+        if out is None:
+            out = torch.empty(n, n_items, dtype=torch.float32, device=self.device)
+        elif out is not False:
+            out = self._f32(who, "out", out, (n, n_items))
+        sse_t = torch.empty(1, dtype=torch.float64, device=self.device) if sse else None
+        rec = _lib.MlpEvalW()
+        for i, t in enumerate(checked):
+            rec.p[i] = t.data_ptr()
+        rec.n_users, rec.n_items = n_users, n_items
+        self._check(self.lib.sdrm_mlp_eval(self._h, C.byref(rec), _ptr(indptr), _ptr(indices), nnz, m_rows, _ptr(rows), row0, n, batch, int(bool(logits)),
+                                           _ptr(out) if out is not False else None, _ptr(sse_t), _stream()), "sdrm_mlp_eval")
+        self._feed_keep = (indptr, indices, rows, checked)
+        if check:
+            self.feed_status()
+        if out is False:
+            return sse_t
+        return (out, sse_t) if sse else out
+
     # ------------------------------------------------------------------ evaluation half of the VAE pre-stage (csrc/eval_half.h)
     def vae_eval_holdout(self, w1, b1, w2, b2, w3, b3, w4, b4, train_csr_dev, held_csr_dev, k, metric, batch=500, out=None, logits=None,
                          check=False):

@@ -2,7 +2,8 @@
 
 The reference is TensorFlow code and TensorFlow is not part of this project's environment, so this file RESTATES it from the Keras
 facts named below; parity with Keras itself has not been run.  The torch loop here is the checker; with `device_train=True` an epoch's
-batch loop is ONE `Engine.mlp_train_steps` call (csrc/mlp_train.h).
+batch loop is ONE `Engine.mlp_train_steps` call (csrc/mlp_train.h), and in `compute_mlp_results_device` the per-epoch validation RMSE
+and the final `predict` are `Engine.mlp_eval` calls on device CSR rows (csrc/mlp_eval.h): with both, the module's forward never runs.
 
 The model (`get_model`, :37-62, called with layers=[512, 512, 256, 256]: the Dense loop starts at index 1, so the widths are 512, 256,
 256).  The input x is a 0 / 1 row of n_items; `Embedding(num_users, 8)` is indexed BY THE INPUT VALUES, so only its rows 0 and 1 are
@@ -212,10 +213,28 @@ def compute_mlp_results(training_data, validation_data, combine_training=False, 
     `Engine.mlp_train_steps` call on the device CSR of the training rows, the epoch's row order uploaded as int64; Adam's moments are
     nine zero tensors made once, its step count runs on across the epochs, no autograd runs.  The DROPOUT draws are then the engine's
     Philox4x32-10 of (seed, epoch, the row's place in the epoch's order, column), so the trained weights differ from the torch loop's as
-    two seeds of it differ.  The per-epoch validation RMSE and the final `predict` stay torch on the engine's device; with an engine the
-    final ranking is `Engine.rank_metrics` and `feed_status()` is asked once per epoch.
+    two seeds of it differ.  The per-epoch validation RMSE and the final `predict` stay torch on the engine's device - their device form
+    is `compute_mlp_results_device`; with an engine the final ranking is `Engine.rank_metrics` and `feed_status()` is asked once per epoch.
     `history`: a dict that receives 'val_rmse' (per epoch), 'train_loss' (every step's loss), 'best_epoch', 'epochs_run', 'per_user'
     (the final per-user recall / ndcg [6, users]) and 'model' (the module that ranked)."""
+    return _mlp_results(training_data, validation_data, combine_training, engine, seed, epochs, device, history, device_train, False)
+
+
+def compute_mlp_results_device(training_data, validation_data, engine, combine_training=False, seed=0, epochs=EPOCHS, history=None, device_train=True):
+    """`compute_mlp_results` with the evaluation half on the device as well (named as `pipeline.compute_mf_results_device` is): the same
+    driver, results and `history`, on the engine's device.  The per-epoch RMSE comes from ONE `Engine.mlp_eval(..., row0=n_fit,
+    n=n - n_fit, out=False, sse=True)` on the training CSR resident on the device (the train loop's upload, else one upload of its own):
+    no dense rows, one scalar read back per epoch - which the early stop needs anyway.  The final scores are one `Engine.mlp_eval` on the
+    validation users' 80 % part, uploaded once, ranked by `Engine.rank_metrics` in its device-CSR form.  `device_train` chooses the train
+    loop as `compute_mlp_results` does: with True (the default here) `MLP.forward` is never called; with False the torch loop trains and
+    the trajectory is that of `compute_mlp_results` from the same seed."""
+    if engine is None:
+        raise ValueError("compute_mlp_results_device needs an engine (the forward runs on the device CSR; the torch path is compute_mlp_results)")
+    return _mlp_results(training_data, validation_data, combine_training, engine, seed, epochs, None, history, device_train, True)
+
+
+def _mlp_results(training_data, validation_data, combine_training, engine, seed, epochs, device, history, device_train, device_eval):
+    """The driver behind `compute_mlp_results` (device_eval False) and `compute_mlp_results_device` (True)."""
     train = _binary_csr(training_data, "training_data")
     valid = _binary_csr(validation_data, "validation_data")
     n_users, n_items = train.shape
@@ -240,9 +259,10 @@ def compute_mlp_results(training_data, validation_data, combine_training=False, 
     if device_train:
         live = [p.data for p in model.engine_weights()]            # the parameters' own storage: the engine updates it in place
         exp_avg, exp_avg_sq = [torch.zeros_like(t) for t in live], [torch.zeros_like(t) for t in live]
-        csr_dev = engine.csr_to_device(train)
     else:
         optimizer = KerasAdam(model.engine_weights(), lr=LR, betas=BETAS, eps=EPS)
+    if device_train or device_eval:
+        csr_dev = engine.csr_to_device(train)
     stopper = EarlyStop(PATIENCE, MIN_DELTA)
     best_weights, val_rmse, train_loss, steps_done, epochs_run = None, [], [], 0, 0
     for epoch in range(int(epochs)):
@@ -267,7 +287,12 @@ def compute_mlp_results(training_data, validation_data, combine_training=False, 
                 step_losses.append(loss.detach())
             train_loss.extend(torch.stack(step_losses).double().cpu().tolist())
         model.eval()
-        rmse = validation_rmse(model, held, device)
+        if device_eval:
+            sse = engine.mlp_eval([p.data for p in model.engine_weights()], csr_dev, row0=n_fit, n=n - n_fit, out=False, sse=True, check=False)
+            rmse = math.sqrt(float(sse.item()) / ((n - n_fit) * n_items))
+            engine.feed_status()
+        else:
+            rmse = validation_rmse(model, held, device)
         val_rmse.append(rmse)
         if stopper.update(rmse):
             best_weights = copy.deepcopy(model.state_dict())
@@ -279,15 +304,21 @@ def compute_mlp_results(training_data, validation_data, combine_training=False, 
     else:
         best_epoch = epochs_run - 1          # no epoch improved on +inf (a nan RMSE): the live weights rank
     model.eval()
-    scores = torch.cat([model.predict(_dense(valid_train[s:s + PREDICT_BATCH], device)) for s in range(0, valid_train.shape[0], PREDICT_BATCH)])
-    if engine is not None:
-        rec, ndcg = engine.rank_metrics(scores, valid_test, valid_train, ks=K_LIST)
+    if device_eval:
+        seen_dev = engine.csr_to_device(valid_train)
+        scores = engine.mlp_eval([p.data for p in model.engine_weights()], seen_dev)
+        rec, ndcg = engine.rank_metrics(scores, engine.csr_to_device(valid_test), seen_dev, ks=K_LIST)
         rec, ndcg = rec.cpu().numpy(), ndcg.cpu().numpy()
     else:
-        masked = metrics.mask_training_examples(sparse_training_set=valid_train, dense_matrix=scores.cpu().numpy().astype(np.float64))
-        with np.errstate(invalid="ignore", divide="ignore"):
-            rec = np.stack([metrics.recall_at_k_batch(masked, valid_test, k=k) for k in K_LIST])
-            ndcg = np.stack([metrics.NDCG_binary_at_k_batch(masked, valid_test, k=k) for k in K_LIST])
+        scores = torch.cat([model.predict(_dense(valid_train[s:s + PREDICT_BATCH], device)) for s in range(0, valid_train.shape[0], PREDICT_BATCH)])
+        if engine is not None:
+            rec, ndcg = engine.rank_metrics(scores, valid_test, valid_train, ks=K_LIST)
+            rec, ndcg = rec.cpu().numpy(), ndcg.cpu().numpy()
+        else:
+            masked = metrics.mask_training_examples(sparse_training_set=valid_train, dense_matrix=scores.cpu().numpy().astype(np.float64))
+            with np.errstate(invalid="ignore", divide="ignore"):
+                rec = np.stack([metrics.recall_at_k_batch(masked, valid_test, k=k) for k in K_LIST])
+                ndcg = np.stack([metrics.NDCG_binary_at_k_batch(masked, valid_test, k=k) for k in K_LIST])
     if history is not None:
         history.update(val_rmse=val_rmse, train_loss=train_loss, best_epoch=best_epoch, epochs_run=epochs_run, per_user=(rec, ndcg), model=model)
     with np.errstate(invalid="ignore"):

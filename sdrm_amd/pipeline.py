@@ -19,6 +19,7 @@ import torch
 from scipy.sparse import csr_matrix, issparse, vstack
 
 from . import metrics
+from .mlp_eval import compute_mlp_results_device
 
 K_LIST = (1, 3, 5, 10, 20, 50)
 
@@ -223,6 +224,25 @@ def compute_mf_results_resident(training_dataset, testing_dataset, synthetic_dat
             np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
 
 
+def evaluate_synthetic(train, valid, raw, sparsity, engine, hp, seed):
+    """The downstream evaluation of ONE synthetic matrix `raw` (dense scores on the engine's device, binarised here to the training
+    data's sparsity): the evaluator `hp` chooses, called as `run_experiment` always called it.  `hp["evaluator"] == "mlp"` is the
+    reference's `main.py --model mlp` route (main.py:197-214) without augmentation: `compute_mlp_results_device` on the binarised matrix with the
+    train epochs, the per-epoch validation RMSE and the final scores on the device (`hp["mlp_epochs"]`, 200 when absent).  Without the
+    key: `hp["resident_svd"]`, `hp["device_svd"]`, `hp["sparse_synthetic"]` and `hp["nmf"]` as `run_experiment` documents them."""
+    binarise = equal_sparsity_csr if hp.get("sparse_synthetic", False) else equal_sparsity   # opt-in: CSR made on the device
+    if hp.get("evaluator") == "mlp":
+        return compute_mlp_results_device(binarise(raw, sparsity, engine), valid, engine, device_train=True, seed=seed, epochs=hp.get("mlp_epochs", 200))
+    if hp.get("evaluator") is not None:
+        raise ValueError(f"evaluate_synthetic: hp['evaluator'] = {hp['evaluator']!r}; 'mlp' is the one evaluator the key selects")
+    nmf = {"nnmf": True} if hp.get("nmf", False) else {}   # opt-in, the two device routes only: the NMF evaluator in the SVD's place (csrc/nmf.h)
+    if hp.get("resident_svd", False):   # opt-in: the CSR made on the device stays there, stacked and transposed on the device (csrc/csr_transpose.h)
+        return compute_mf_results_resident(train, valid, engine.equal_sparsity_csr(raw, sparsity), engine, only_synthetic=True, seed=seed, **nmf)
+    if hp.get("device_svd", False):   # opt-in: the downstream evaluator on the device (csrc/svd_eval.h)
+        return compute_mf_results_device(train, valid, binarise(raw, sparsity, engine), engine, only_synthetic=True, seed=seed, **nmf)
+    return compute_mf_results(train, valid, binarise(raw, sparsity, engine), only_synthetic=True)
+
+
 # the pre-stage's opt-in flags that `hp` may carry, under `train_SDRM`'s keyword names
 VAE_FLAGS = ("vae_device_feed", "vae_device_holdout", "vae_sparse_input", "vae_device_latent", "vae_device_decoder", "vae_device_optimizer",
              "vae_device_eval")
@@ -234,7 +254,8 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
     under the same names, and an `hp` without them makes the call it always made.  `hp["device_svd"]` (False when absent) sends the
     three evaluations to `compute_mf_results_device` instead of `compute_mf_results`; nothing of it reaches `train_SDRM`.  `hp["resident_svd"]` (False when absent) binarises with
     `Engine.equal_sparsity_csr` and hands the device tuple to `compute_mf_results_resident`: no host copy of the synthetic matrix.
-    `hp["nmf"]` (False when absent) makes those two device routes evaluate with `nnmf=True`, the reference's NMF of 15 components."""
+    `hp["nmf"]` (False when absent) makes those two device routes evaluate with `nnmf=True`, the reference's NMF of 15 components.
+    `hp["evaluator"] == "mlp"` sends them to the MLP evaluator on the device instead (`evaluate_synthetic`, which makes the choice per tag)."""
     from . import train_SDRM as ts
     train, train_partial, valid = split
     n_users, n_items = train.shape
@@ -253,13 +274,6 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
     M = ts.sample_ddpm(n_users, net, vae, hp["latent"], hp["nd"], timesteps="random", n_timesteps=hp["T"]).detach()
     F = ts.sample_ddpm(n_users, net, vae, hp["latent"], hp["nd"], n_timesteps=hp["T"]).detach()
     V = vae.sample(n_users)
-    binarise = equal_sparsity_csr if hp.get("sparse_synthetic", False) else equal_sparsity   # opt-in: CSR made on the device
-    nmf = {"nnmf": True} if hp.get("nmf", False) else {}   # opt-in, the two device routes only: the NMF evaluator in the SVD's place (csrc/nmf.h)
     for tag, raw in (("M", M), ("F", F), ("V", V)):
-        if hp.get("resident_svd", False):   # opt-in: the CSR made on the device stays there, stacked and transposed on the device (csrc/csr_transpose.h)
-            out[tag] = compute_mf_results_resident(train, valid, net.engine().equal_sparsity_csr(raw, sparsity), net.engine(), only_synthetic=True, seed=seed, **nmf)
-        elif hp.get("device_svd", False):   # opt-in: the downstream evaluator on the device (csrc/svd_eval.h)
-            out[tag] = compute_mf_results_device(train, valid, binarise(raw, sparsity, net.engine()), net.engine(), only_synthetic=True, seed=seed, **nmf)
-        else:
-            out[tag] = compute_mf_results(train, valid, binarise(raw, sparsity, net.engine()), only_synthetic=True)
+        out[tag] = evaluate_synthetic(train, valid, raw, sparsity, net.engine(), hp, seed)
     return out
