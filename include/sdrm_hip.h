@@ -15,7 +15,11 @@
  *    contiguous ROCm torch tensor).  The library owns only handle-internal buffers and never
  *    allocates in a step call.
  *  - `stream` is a `hipStream_t` passed as `void*` (NULL = the default stream).  All work is
- *    enqueued on it and nothing synchronises unless stated.
+ *    enqueued on it and nothing synchronises unless stated.  It may be a non-blocking stream with work of the caller's still
+ *    pending, beside a busy default stream: inputs need only be ready in `stream` order, and outputs are final in `stream` order
+ *    (tests/test_stream_order.py holds every entry point to this).  One exception covers every entry point with library-owned,
+ *    grow-only scratch: a call whose scratch must GROW - the first one of its family on a handle, and each larger one - waits for
+ *    the device before it frees the old buffer and for the zeroing of the new one; a call that fits does not wait.
  *  - All arithmetic is fp32; `t` / `Tj` are int64 as in the reference (`torch.randint`, :327).
  *  - Return value: 0 on success, negative `sdrm_status` otherwise; never throws.  The message of the
  *    last failure on a handle is returned by sdrm_last_error().
@@ -80,6 +84,8 @@ const char* sdrm_last_error(const sdrm_engine* e);
 int64_t sdrm_param_count(const sdrm_engine* e);
 
 /* ---- schedule (train_SDRM.py:296-303; module globals b_t/a_t/ab_t, quirk Q10) ---------------- */
+/* sdrm_set_schedule takes no stream: it WAITS FOR THE DEVICE (every stream), then rewrites the tables with blocking copies.  Work queued
+ * before the call, on any stream, uses the old schedule; work queued after it the new one.  A once-per-run call. */
 int sdrm_set_schedule(sdrm_engine* e, float beta1, float beta2);
 /* Copies beta, alpha, alpha-bar ([T+1] each) to HOST arrays. */
 int sdrm_get_schedule(const sdrm_engine* e, float* beta_host, float* alpha_host, float* alphabar_host);
@@ -182,7 +188,8 @@ int sdrm_forward(sdrm_engine* e, const float* x, const int64_t* t, int n, int mo
  * injected at step i ALREADY multiplied by noise_divider (z[1] is ignored: no noise at i==1, Q9),
  * keep[T+1,n,L] dropout keep-masks per step.  PHILOX mode: all of those (and Tj when
  * `multires` != 0) are drawn on device; Tj_out (device int64 [n], may be NULL) receives the drawn
- * start steps. */
+ * start steps.  A caller's Tj (EXPLICIT mode, Tj != NULL) is read back to order the rows on the host: that one form synchronises
+ * `stream` once, in sdrm_sample / sdrm_sample_begin; no other form of the call waits. */
 int sdrm_sample(sdrm_engine* e, int n, float noise_divider, int multires, int mode, const float* xT,
                 const float* z, const uint8_t* keep, const int64_t* Tj, uint64_t seed, uint64_t call_id,
                 int64_t row0, float* out, int64_t* Tj_out, void* stream);

@@ -410,11 +410,16 @@ hipError_t allow_full_lds(const void* kernel, int bytes = LDS_MAX_BYTES) {
   return st;
 }
 
+// The zeroing goes to the default stream and hipMemset does not wait for it: behind a busy default stream it would land on a buffer that a
+// caller's non-blocking stream has long written (tests/test_stream_order.py met it in the mask of sdrm_equal_sparsity_csr_begin).  So
+// the allocation waits for it - a call whose scratch grows may synchronise (include/sdrm_hip.h, Conventions).
 template <typename Tp>
 hipError_t dalloc(Tp** p, size_t n) {
   hipError_t st = hipMalloc((void**)p, (n + SLACK) * sizeof(Tp));
   if (st != hipSuccess) return st;
-  return hipMemset(*p, 0, (n + SLACK) * sizeof(Tp));
+  st = hipMemset(*p, 0, (n + SLACK) * sizeof(Tp));
+  if (st != hipSuccess) return st;
+  return hipStreamSynchronize(nullptr);
 }
 
 // One buffer of the scratch pool (enum Scratch), as elements of Tp: *out holds n of them afterwards (and SLACK zeroed ones behind).
