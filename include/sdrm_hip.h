@@ -748,6 +748,39 @@ int sdrm_neumf_train_steps(sdrm_engine* e, const sdrm_neumf_train* s, const int3
                            float beta1, float beta2, float eps, float p_drop, int mode, const uint8_t* keep, uint64_t seed, uint32_t call_id,
                            double* losses, float* const* grads, void* stream);
 
+/* An epoch's data preparation of the NeuMF evaluator on the device (reference: neural_cf_benchmark_pt.py:180-184 - `train_test_split` of the
+ * training triples 80/20, the label-0 rows of the 80 % drawn again with replacement, one per label-1 row, the concatenation shuffled;
+ * csrc/neumf_draw.h).  The reference's draws are unseeded; this call's are a function of (seed, epoch) and the triples alone, so that
+ * tests/neumf_draw_ref.py restates it exactly in numpy.  triples [n][3] int32 (user, item, label) stay on the device across epochs.
+ * The keyed permutation perm(n, seed, epoch, draw) of 0 .. n-1, n >= 1:  b = max(1, bit_length(n - 1)), h = (b + 1) / 2, mask = 2^h - 1 (the
+ *   domain 4^h >= n).  For a value x: L = x >> h, R = x & mask; six rounds r = 0 .. 5 of (L, R) <- (R, L ^ (W & mask)), W = word 0 of
+ *   Philox4x32-10 with counter (R, r, 12 | draw << 8, epoch) and key seed; then x = L << h | R.  perm(i) starts at x = i and repeats that map
+ *   until x < n (cycle walking): a bijection of [0, n) - the construction of thrust::shuffle.  It is a good shuffle for batches and splits,
+ *   every element is equally likely at every place, but it is NOT uniform over the n! orders (at tiny n it reaches only part of them).
+ *   The device loop is bounded at 1024 applications; a lane that reaches the bound makes the call fail with SDRM_ERR_STATE, and nothing is
+ *   promised about the outputs then (the longest walk seen over n up to 1.3 M was 43).
+ * The draw, with n_part = n - n_hold:
+ *   hold[j] = T[perm(n; draw 0)(j)], j < n_hold;   part[q] = T[perm(n; draw 0)(n_hold + q)], q < n_part;
+ *   g_0 < g_1 < ... the places q where part[q] has label 0, n_neg of them; n_pos the number of places with label 1 (any other label counts
+ *   in neither and passes through);   n_extra = n_pos if n_neg > 0, else 0;
+ *   extra[k] = part[g_r], r = (w n_neg) >> 32, w = word k & 3 of Philox4x32-10 with counter (k >> 2, 0, 12 | 1 << 8, epoch) and key seed;
+ *   m = n_part + n_extra;   out[p] = (part ++ extra)[perm(m; draw 2)(p)], p < m.
+ * hold [n_hold][3] and out [capacity][3] (rows m .. capacity - 1 are left as they were) receive whole triples, verbatim.
+ * present: null, or uint8 [n_users]: the call zeroes it and sets byte u for every user id u in [0, n_users) that occurs in hold; a hold
+ *   triple with a user id outside that range raises the "row" bit of the feed status word (sdrm_feed_status), is not marked and is still
+ *   copied verbatim (sdrm_neumf_train_steps range-checks its own ids).  With present null, n_users is ignored.
+ * counts_host: HOST int64 [3] that receives n_pos, n_neg, m.
+ * The call takes NO stream and is DEVICE-SYNCHRONOUS, like sdrm_set_schedule: it waits for the device (every stream) before its first
+ *   launch, runs its four launches on a stream of the library's own and waits for them before it returns.  So inputs written by work queued
+ *   earlier on any stream are seen, and the outputs and counts are complete on return: the host sizes the train call from m.  It cannot
+ *   run under graph capture.  Scratch is library-owned and grow-only, as for sdrm_neumf_train_steps.  Integer work only: the same bytes on
+ *   every run.
+ * SDRM_ERR_SHAPE, before any launch: n outside 2 .. 2^30 (2 n_part stays an int32 index), n_hold outside 1 .. n - 1, capacity below
+ *   2 (n - n_hold), n_users < 1 with present.  SDRM_ERR_ARG: a null handle, triples, hold, out or counts_host.  Refused calls launch and
+ *   write nothing. */
+int sdrm_neumf_epoch_draw(sdrm_engine* e, const int32_t* triples, int64_t n, int64_t n_hold, uint64_t seed, uint32_t epoch, int32_t* hold,
+                          int32_t* out, int64_t capacity, uint8_t* present, int n_users, int64_t* counts_host);
+
 /* The MLP evaluator's TRAIN steps on the device (reference: mlp_benchmark.py:37-62 the model, :85-110 `model.fit` with Keras's Adam and
  * `binary_crossentropy`; restated, with the Keras facts it rests on, in sdrm_amd/mlp_eval.py; csrc/mlp_train.h).  The input rows are 0 / 1,
  * given as the PATTERN of a device CSR matrix [n_rows, n_items] (an entry means 1).  With s = 1 / (1 - p_drop) and k1, k2, k3 the keep

@@ -156,6 +156,8 @@ SIGNATURES = {
     "sdrm_neumf_pair_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sdrm_neumf_train_steps": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_float, c_float, c_float, c_float, c_float, c_int,
                                        c_void_p, c_uint64, C.c_uint32, c_void_p, c_void_p, c_void_p]),
+    "sdrm_neumf_epoch_draw": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_uint64, C.c_uint32, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                      C.POINTER(c_int64)]),
     "sdrm_mlp_train_steps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_float, c_float, c_float,
                                      c_float, c_float, c_int, c_void_p, c_uint64, C.c_uint32, c_void_p, c_void_p, c_void_p]),
     "sdrm_mlp_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
@@ -176,6 +178,7 @@ SIGNATURES = {
     "sdrm_debug_svd_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_debug_neumf_args": (c_int, [c_int, c_int, c_int, c_int64, c_int64]),
     "sdrm_debug_neumf_train_args": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int64, c_float]),
+    "sdrm_debug_neumf_draw_args": (c_int, [c_int64, c_int64, c_int64, c_int, c_int]),
     "sdrm_debug_mlp_train_args": (c_int, [c_int, c_int, c_int64, c_int, c_int64, c_float, c_int, C.POINTER(c_uint64), c_int]),
     "sdrm_debug_mlp_eval_args": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int, C.POINTER(c_uint64), c_int]),
     "sdrm_debug_holdout_args": (c_int, [c_int, c_int64, c_int64, C.c_double, c_int64, C.POINTER(c_int64)]),

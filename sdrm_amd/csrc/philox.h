@@ -19,7 +19,9 @@ enum : uint32_t {
   PURPOSE_HOLDOUT = 8,     // sort key of the per-user hold-out split (csrc/holdout.h): word p & 3 of (feed row, quad of the place p in the row)
   PURPOSE_VAE_EPS = 9,     // reparameterisation draw of the VAE encoder in train mode (csrc/latent.h): normal j & 3 of (feed row, column quad j >> 2)
   PURPOSE_NEUMF_DROP = 10, // the three dropouts of a NeuMF train step (csrc/neumf_train.h): word c & 3 of (pair's place in the call, quad of the column c of its 14F)
-  PURPOSE_MLP_DROP = 11     // the three dropouts of an MLP-evaluator train step (csrc/mlp_train.h): word c & 3 of (row's place in the call, quad of the column c of its 1024)
+  PURPOSE_MLP_DROP = 11,    // the three dropouts of an MLP-evaluator train step (csrc/mlp_train.h): word c & 3 of (row's place in the call, quad of the column c of its 1024)
+  PURPOSE_NEUMF_EPOCH = 12  // an epoch's split, negatives and shuffle of the NeuMF evaluator (csrc/neumf_draw.h; the draw in bits 8..): draws 0 and 2 word 0 of
+                            // (right half, Feistel round), draw 1 word k & 3 of (quad of the extra row k, 0); counter word 3 is the epoch
 };
 
 struct U4 { uint32_t x, y, z, w; };

@@ -32,6 +32,7 @@
 #include "neumf.h"
 #include "mlp_train.h"
 #include "mlp_eval.h"
+#include "neumf_draw.h"
 #include "neumf_train.h"
 #include "nll.h"
 #include "nmf.h"
@@ -155,7 +156,7 @@ struct ChainSched {
   bool hold_marked = false;    // ev_hold is recorded behind its weight gradients
 };
 
-constexpr int PROF_SLOTS = 48;   // room for the profile classes (ProfClass below holds PC_COUNT to it)
+constexpr int PROF_SLOTS = 56;   // room for the profile classes (ProfClass below holds PC_COUNT to it)
 
 // The library-owned device scratch of the utility entry points (sdrm_engine::scratch, reached through scratch<T>() only): one slot per
 // buffer, every slot grow-only and owned by ONE family of entry points, so nothing a family leaves behind is touched by another.  Two
@@ -192,6 +193,9 @@ enum Scratch {
   // eight tower tensors behind it | the dense gradients of the four embedding tables, ALL ZERO between two calls (a step writes the rows
   // its pairs name and zeroes them again): nothing else may ever be carved out of that slot
   SCR_NEUMF_TRAIN_WS, SCR_NEUMF_TRAIN_TAB,
+  // sdrm_neumf_epoch_draw (csrc/neumf_draw.h), 8-byte words, every piece written by the call that reads it: [counts int64 [3] | status word |
+  // label-0 mask words | part_src int32 [n_part] | neg_src int32 [n_part] | work-group counts uint32 [2][blocks] | their scan uint32 [blocks]]
+  SCR_NEUMF_DRAW_WS,
   // sdrm_mlp_train_steps (csrc/mlp_train.h), 8-byte words: [B_f of the weights, two copies | the W1 pass's partial B_f and dE[1] | the gather's
   // partial sums | loss partials | a1, a2, a3, dz1, dz2, dz3, dy (float) | live words | item mask]
   SCR_MLP_TRAIN_WS,
@@ -293,6 +297,7 @@ struct sdrm_engine {
   SampleCall call;
   // sampler row chains: row ranges of one sampling call on streams of their own (ChainSched)
   hipStream_t aux[3] = {nullptr, nullptr, nullptr};
+  hipStream_t draw_stream = nullptr;   // sdrm_neumf_epoch_draw's own stream (a device-synchronous call: made on its first call)
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_hold = nullptr;      // behind the weight gradients of a train step that runs between two sampling steps (chains_wgrads_queued)
   ChainSched chain_sched;
@@ -312,7 +317,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_MLP_FWD, PC_MLP_BWD, PC_MLP_W1, PC_MLP_FOLD, PC_MLP_EVAL, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_MLP_FWD, PC_MLP_BWD, PC_MLP_W1, PC_MLP_FOLD, PC_MLP_EVAL, PC_NEUMF_DRAW_SPLIT, PC_NEUMF_DRAW_SCAN, PC_NEUMF_DRAW_NEG, PC_NEUMF_DRAW_OUT, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -358,7 +363,11 @@ static const char* kProfNames[PC_COUNT] = {
     "mlp train step: k_mlp_dgrad / k_mlp_adam / k_mlp_embed / k_mlp_bsum input gradients, Keras's Adam on W2 .. b4 and on E's two rows with the gradient made inside the pass, the loss, B_f",
     "mlp train step: k_mlp_w1 the one read-modify-write pass over W1 and its moments (gradient per element from S and T_j, Keras's Adam, partial B_f and dE[1])",
     "mlp evaluation: k_mlp_fold the one read-only pass over W1 that leaves D [items][512] and the partial B_f",
-    "mlp evaluation: k_mlp_bsum / k_mlp_base / k_pad2d / k_encode_w1t staging once per call, then per batch k_mlp_rows_relu / gemm_kernel<0,0,0,0,10> x2 / gemm_kernel<0,0,0,0,7> or <0,0,0,0,12> / k_mlp_sse, and k_mlp_sse_sum: the eval-mode forward from CSR rows, probabilities or logits, and the sum of squared errors"};
+    "mlp evaluation: k_mlp_bsum / k_mlp_base / k_pad2d / k_encode_w1t staging once per call, then per batch k_mlp_rows_relu / gemm_kernel<0,0,0,0,10> x2 / gemm_kernel<0,0,0,0,7> or <0,0,0,0,12> / k_mlp_sse, and k_mlp_sse_sum: the eval-mode forward from CSR rows, probabilities or logits, and the sum of squared errors",
+    "neumf epoch draw: k_draw_split the hold-out rows gathered through the keyed Feistel permutation and `present` marked; the source places, label-0 mask words and work-group counts of the other rows",
+    "neumf epoch draw: k_draw_scan exclusive scan of the work-groups' label-0 counts with a carry, n_pos, n_neg and m (one work-group)",
+    "neumf epoch draw: k_draw_neg the source places of the label-0 rows in ascending order, from the mask words and the scanned offsets",
+    "neumf epoch draw: k_draw_out the shuffled rows gathered through the second permutation, the extra rows' Philox draws among the label-0 rows"};
 
 namespace {
 
@@ -1759,6 +1768,7 @@ int sdrm_destroy(sdrm_engine* e) {
     if (e->ev_join[c]) (void)hipEventDestroy(e->ev_join[c]);
     if (e->aux[c]) (void)hipStreamDestroy(e->aux[c]);
   }
+  if (e->draw_stream) (void)hipStreamDestroy(e->draw_stream);
   delete e;
   return SDRM_OK;
 }
@@ -4414,6 +4424,58 @@ int sdrm_neumf_train_steps(sdrm_engine* e, const sdrm_neumf_train* s, const int3
   hipStream_t st = (hipStream_t)stream;
   if (s->factor == 8) return neumf_train_steps<8>(e, s, triples, n, batch, step0, lr, beta1, beta2, eps, p_drop, k, seed, call_id, losses, grads, st);
   return neumf_train_steps<16>(e, s, triples, n, batch, step0, lr, beta1, beta2, eps, p_drop, k, seed, call_id, losses, grads, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// An epoch's split, negatives and shuffle of the NeuMF evaluator (neural_cf_benchmark_pt.py:180-184), csrc/neumf_draw.h.  A
+// device-synchronous call on a stream of the library's own: it hands three counts to the host, which sizes the train call from them.
+
+// The host side that needs no device: the envelope.
+int sdrm_debug_neumf_draw_args(int64_t n, int64_t n_hold, int64_t capacity, int with_present, int n_users) {
+  if (n < 2 || n > ((int64_t)1 << 30)) return SDRM_ERR_SHAPE;          // (2 n_part stays an int32 index)
+  if (n_hold < 1 || n_hold >= n) return SDRM_ERR_SHAPE;
+  if (capacity < 2 * (n - n_hold)) return SDRM_ERR_SHAPE;
+  if (with_present && n_users < 1) return SDRM_ERR_SHAPE;
+  return SDRM_OK;
+}
+
+int sdrm_neumf_epoch_draw(sdrm_engine* e, const int32_t* triples, int64_t n, int64_t n_hold, uint64_t seed, uint32_t epoch, int32_t* hold,
+                          int32_t* out, int64_t capacity, uint8_t* present, int n_users, int64_t* counts_host) {
+  const char* who = "sdrm_neumf_epoch_draw";
+  if (!e) return SDRM_ERR_ARG;
+  if (!triples || !hold || !out || !counts_host) return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (int rc = sdrm_debug_neumf_draw_args(n, n_hold, capacity, present != nullptr, n_users))
+    return fail(e, rc, std::string(who) + ": n outside 2 .. 2^30, n_hold outside 1 .. n - 1, capacity below 2 (n - n_hold), or present with n_users < 1");
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipDeviceSynchronize());     // every stream: whatever wrote the triples is done, whatever reads the outputs has not begun
+  if (!e->draw_stream) HIP_TRY(e, hipStreamCreateWithFlags(&e->draw_stream, hipStreamNonBlocking));
+  hipStream_t st = e->draw_stream;
+  DrawArgs a{};
+  a.T = (const DrawTriple*)triples; a.n = (uint32_t)n; a.n_hold = (uint32_t)n_hold; a.n_part = (uint32_t)(n - n_hold);
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.epoch = epoch;
+  a.hold = (DrawTriple*)hold; a.out = (DrawTriple*)out; a.present = present; a.n_users = present ? n_users : 0;
+  a.hold_blocks = (a.n_hold + 255u) / 256u; a.part_blocks = (a.n_part + 255u) / 256u;
+  const size_t w_head = 4, w_mask = ((size_t)a.n_part + 63) / 64, w_src = ((size_t)a.n_part + 1) / 2, w_blk = ((size_t)a.part_blocks + 1) / 2;
+  uint64_t* ws = nullptr;
+  if (int rc = scratch(e, SCR_NEUMF_DRAW_WS, w_head + w_mask + 2 * w_src + 3 * w_blk, &ws)) return rc;
+  a.counts = (int64_t*)ws; a.status = (unsigned*)(ws + 3);
+  a.mask0 = ws + w_head;
+  a.part_src = (int32_t*)(a.mask0 + w_mask); a.neg_src = (int32_t*)(a.mask0 + w_mask + w_src);
+  a.cnt = (uint32_t*)(a.mask0 + w_mask + 2 * w_src); a.off0 = (uint32_t*)(a.mask0 + w_mask + 2 * w_src + 2 * w_blk);
+  a.flag = e->feed_flag;
+  HIP_TRY(e, hipMemsetAsync(ws, 0, w_head * sizeof(uint64_t), st));
+  if (present) HIP_TRY(e, hipMemsetAsync(present, 0, (size_t)n_users, st));
+  if (int rc = launch_k(e, PC_NEUMF_DRAW_SPLIT, "k_draw_split", k_draw_split, dim3(a.hold_blocks + a.part_blocks), dim3(256), 0, st, a)) return rc;
+  if (int rc = launch_k(e, PC_NEUMF_DRAW_SCAN, "k_draw_scan", k_draw_scan, dim3(1), dim3(256), 0, st, a)) return rc;
+  if (int rc = launch_k(e, PC_NEUMF_DRAW_NEG, "k_draw_neg", k_draw_neg, dim3(a.part_blocks), dim3(256), 0, st, a)) return rc;
+  if (int rc = launch_k(e, PC_NEUMF_DRAW_OUT, "k_draw_out", k_draw_out, dim3((2u * a.n_part + 255u) / 256u), dim3(256), 0, st, a)) return rc;
+  int64_t head[4] = {0, 0, 0, 0};
+  HIP_TRY(e, hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipStreamSynchronize(st));
+  if ((unsigned)head[3] & DRAW_STATUS_WALK)
+    return fail(e, SDRM_ERR_STATE, std::string(who) + ": a lane walked its permutation's cycle " + std::to_string(DRAW_MAX_WALKS) + " times without coming back inside; the outputs are not the draw");
+  counts_host[0] = head[0]; counts_host[1] = head[1]; counts_host[2] = head[2];
+  return SDRM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

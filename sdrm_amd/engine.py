@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -1394,6 +1395,44 @@ class Engine:
         if check:
             self.feed_status()
         return losses
+
+    # ------------------------------------------------------------------ NeuMF evaluator's epoch draw (csrc/neumf_draw.h)
+    def neumf_epoch_draw(self, triples, n_hold=None, seed=0, epoch=0, n_users=None, out=None):
+        """neural_cf_benchmark_pt.py:180-184 on the device (sdrm_neumf_epoch_draw): an epoch's 80/20 split of `triples` (int32 device
+        tensor [n, 3]: user, item, label; left as it is), the label-0 rows of the 80 % drawn again with replacement, one per label-1 row,
+        and the shuffle of both - a function of (seed, epoch) and the triples alone, defined in include/sdrm_hip.h and restated in
+        tests/neumf_draw_ref.py; never numpy's or torch's generator.  `n_hold`: rows of the hold-out part, default ceil(0.2 n).
+        Returns (hold, part, counts, present): hold int32 [n_hold, 3]; part the view [:m] of an int32 [2 (n - n_hold), 3] buffer, what
+        `neumf_train_steps` takes; counts the Python tuple (n_pos, n_neg, m); present a uint8 device tensor [n_users], 1 for every user id
+        of hold inside [0, n_users) (an id outside raises the feed status word's row bit: ask `feed_status`), or None without `n_users`.
+        `out`: (hold buffer [n_hold, 3], part buffer [>= 2 (n - n_hold), 3]) to fill, so that a driver reuses both across epochs; rows of
+        the part buffer behind m keep what they held.  The call is DEVICE-SYNCHRONOUS and takes no stream: it waits for every stream before it starts and for its own work
+        before it returns, so it cannot run under graph capture."""
+        who = "neumf_epoch_draw"
+        if (not isinstance(triples, torch.Tensor) or triples.dtype != torch.int32 or triples.device != self.device or not triples.is_contiguous()
+                or triples.dim() != 2 or triples.shape[1] != 3):
+            raise SdrmError(f"{who}: triples must be a contiguous int32 tensor [n, 3] on the engine's device")
+        n = int(triples.shape[0])
+        n_hold = int(math.ceil(0.2 * n)) if n_hold is None else int(n_hold)
+        if n < 2 or n > 2 ** 30 or n_hold < 1 or n_hold >= n:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: n = {n} outside 2 .. 2^30 or n_hold = {n_hold} outside 1 .. n - 1")
+        if n_users is not None and int(n_users) < 1:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: n_users = {n_users} < 1")
+        cap = 2 * (n - n_hold)
+        if out is None:
+            out = (torch.empty(n_hold, 3, dtype=torch.int32, device=self.device), torch.empty(cap, 3, dtype=torch.int32, device=self.device))
+        hold, buf = out
+        for name, t, rows in (("out[0]", hold, n_hold), ("out[1]", buf, cap)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous()
+                    or t.dim() != 2 or t.shape[1] != 3 or (t.shape[0] != rows if name == "out[0]" else t.shape[0] < rows)):
+                raise SdrmError(f"{who}: {name} must be a contiguous int32 tensor [{'' if name == 'out[0]' else '>= '}{rows}, 3] on the engine's device")
+        present = None if n_users is None else torch.empty(int(n_users), dtype=torch.uint8, device=self.device)
+        counts = (C.c_int64 * 3)()
+        self._check(self.lib.sdrm_neumf_epoch_draw(self._h, _ptr(triples), n, n_hold, int(seed) & (2 ** 64 - 1), int(epoch) & 0xFFFFFFFF, _ptr(hold),
+                                                   _ptr(buf), int(buf.shape[0]), _ptr(present), 0 if n_users is None else int(n_users), counts),
+                    "sdrm_neumf_epoch_draw")
+        n_pos, n_neg, m = (int(c) for c in counts)
+        return hold, buf[:m], (n_pos, n_neg, m), present
 
     # ------------------------------------------------------------------ MLP evaluator's train steps (csrc/mlp_train.h)
     MLP_TENSORS = ("mf_embedding_user", "layer1/kernel", "layer1/bias", "layer2/kernel", "layer2/bias", "layer3/kernel", "layer3/bias",

@@ -5,7 +5,8 @@ of the validation users and the training items through the model in batches of 1
 CSR matrices through Python dicts, densifies them and ranks.  Here that evaluation half has a device form: `Engine.neumf_scores`
 (csrc/neumf.h) gives the dense logit matrix, `Engine.rank_metrics` masks and ranks it, `Engine.neumf_pair_logits` gives the per-epoch
 validation loss.  The train loop is PyTorch by default; with `device_train=True` an epoch's batch loop is ONE `Engine.neumf_train_steps`
-call (csrc/neumf_train.h: forward with dropout, loss, backward and Adam on the device).  With `engine=None` the same functions run torch and numpy on the host - the checker.
+call (csrc/neumf_train.h: forward with dropout, loss, backward and Adam on the device), and with `device_draw=True` on top the epoch's
+split, negatives and shuffle are ONE `Engine.neumf_epoch_draw` call on triples uploaded once (csrc/neumf_draw.h).  With `engine=None` the same functions run torch and numpy on the host - the checker.
 
 Triples are a numpy int array [n, 3] (user, item, label); a (user, item) pair occurs at most once per array.  Labels are taken as
 binary (> 0), which is what the reference feeds its evaluators.  No pandas, no sklearn."""
@@ -93,6 +94,43 @@ def ranking_problem(training, heldout, users):
     return users, cols, compact(heldout[heldout[:, 2] > 0]), compact(training)
 
 
+class RankingProblem:
+    """`ranking_problem(training, heldout, users)` for any `users`, with the work that does not depend on them done ONCE: the columns,
+    and both CSR matrices over every user id that occurs (rows by ascending id, columns sorted and unique).  `select(users)` is then a row
+    selection - no `np.isin` over the triples, no CSR build - and returns what `ranking_problem` returns, array for array."""
+
+    def __init__(self, training, heldout):
+        training, heldout = _as_triples(training, "training"), _as_triples(heldout, "heldout")
+        self.cols = np.unique(training[:, 1])
+        self._relevant = self._rows(heldout[heldout[:, 2] > 0])
+        self._seen = self._rows(training)
+
+    def _rows(self, t):
+        """(ids ascending and unique, indptr, indices) of the triples whose item is a column: per user id its distinct columns, ascending."""
+        t = t[np.isin(t[:, 1], self.cols)]
+        ids, r = np.unique(t[:, 0], return_inverse=True)
+        m = csr_matrix((np.ones(t.shape[0], dtype=np.float32), (r.reshape(-1), np.searchsorted(self.cols, t[:, 1]))),
+                       shape=(ids.shape[0], self.cols.shape[0]))
+        m.sum_duplicates()
+        m.sort_indices()
+        return ids, m.indptr.astype(np.int64), m.indices
+
+    def _select(self, rows, users):
+        ids, indptr, indices = rows
+        start = length = np.zeros(users.shape[0], dtype=np.int64)
+        if ids.shape[0]:
+            at = np.minimum(np.searchsorted(ids, users), ids.shape[0] - 1)
+            known = ids[at] == users                         # (an id that occurs nowhere: an empty row)
+            start, length = np.where(known, indptr[at], 0), np.where(known, indptr[at + 1] - indptr[at], 0)
+        out_ptr = np.concatenate([[0], np.cumsum(length)]).astype(np.int64)
+        take = np.repeat(start - out_ptr[:-1], length) + np.arange(out_ptr[-1])
+        return csr_matrix((np.ones(take.shape[0], dtype=np.float32), indices[take], out_ptr), shape=(users.shape[0], self.cols.shape[0]))
+
+    def select(self, users):
+        users = np.unique(np.asarray(users, dtype=np.int64))
+        return users, self.cols, self._select(self._relevant, users), self._select(self._seen, users)
+
+
 def _idcg_table():
     tp = 1.0 / np.log2(np.arange(2, max(K_LIST) + 2))
     return tp, np.asarray([tp[:m].sum() for m in range(max(K_LIST) + 1)])
@@ -133,7 +171,7 @@ def host_scores(model, users, items):
     return torch.cat(out).reshape(len(users), len(items)).cpu().numpy()
 
 
-def rank_all_items(model, training, heldout, users, engine=None):
+def rank_all_items(model, training, heldout, users, engine=None, problem=None):
     """The reference's testing block (:294-332; the per-epoch one :215-246 is the same) for `model`: per-user (recall [6, U], ndcg [6, U])
     float64 numpy arrays for `K_LIST`, row q of either for the q-th smallest id in `users`.  As the reference behaves:
       * the columns are the item ids that occur in `training`; a held-out item that never occurs there is dropped;
@@ -142,8 +180,10 @@ def rank_all_items(model, training, heldout, users, engine=None):
       * the ideal DCG counts min(columns, k) items for every user (see `host_metrics`); a user without a relevant item: recall nan, NDCG 0.
     With an engine the two CSR matrices are compacted here with numpy and uploaded, the logits are ONE `neumf_scores` call, masking and
     ranking are the existing `rank_metrics`; its NDCG (ideal DCG of min(relevant, k) items, nan without one) is put on the reference's
-    footing from the per-user counts on the host.  `feed_status()` is asked once.  Without one, torch and numpy do all of it."""
-    users, cols, relevant, seen = ranking_problem(training, heldout, users)
+    footing from the per-user counts on the host.  `feed_status()` is asked once.  Without one, torch and numpy do all of it.
+    `problem`: a `RankingProblem(training, heldout)` of the same two arrays, built once by a caller that ranks more than once; the index
+    arrays are then a row selection from it, the same as `ranking_problem`'s."""
+    users, cols, relevant, seen = ranking_problem(training, heldout, users) if problem is None else problem.select(users)
     if cols.shape[0] <= max(K_LIST):
         raise ValueError(f"ranking needs more than {max(K_LIST)} training items, got {cols.shape[0]}")
     if engine is None:
@@ -169,7 +209,17 @@ def _bce_with_logits(logits, labels):
 
 def validation_loss(model, triples, engine=None):
     """`BCEWithLogitsLoss` of the model in eval mode on (user, item, label) triples (:203-211) as a Python float: `neumf_pair_logits`'s
-    loss sum over n with an engine, torch's own on the model's device without."""
+    loss sum over n with an engine, torch's own on the model's device without.  With an engine `triples` may also be an int32 tensor
+    [n, 3] on the engine's device (the hold-out part `Engine.neumf_epoch_draw` leaves): its columns become contiguous device arrays with
+    torch ops, nothing is uploaded, and the divisor is n."""
+    if isinstance(triples, torch.Tensor):
+        if engine is None:
+            raise ValueError("validation_loss: device triples need an engine (the host form takes the numpy array)")
+        if triples.dtype != torch.int32 or triples.dim() != 2 or triples.shape[1] != 3 or triples.device != engine.device:
+            raise ValueError(f"validation_loss: device triples must be an int32 tensor [n, 3] on {engine.device}, got {triples.dtype} {tuple(triples.shape)} on {triples.device}")
+        _, loss_sum = engine.neumf_pair_logits(model.engine_weights(engine.device), triples[:, 0].contiguous(), triples[:, 1].contiguous(),
+                                               triples[:, 2].to(torch.float32).contiguous(), check=False)
+        return float(loss_sum.item()) / triples.shape[0]
     triples = _as_triples(triples, "triples")
     if engine is not None:
         dev = engine.device
@@ -188,7 +238,7 @@ def validation_loss(model, triples, engine=None):
 
 
 def compute_neuralcf_results(training, validation, n_users, n_items, engine=None, seed=0, epochs=20, eval_recall=True, device=None,
-                             history=None, device_train=False):
+                             history=None, device_train=False, device_draw=False):
     """The reference's driver (:154-334) over int triples [n, 3]: (recall [6], ndcg [6]) for `K_LIST`, nanmean over the validation users
     rounded to 4 places.  As the reference: NCF(factor 8, three layers, dropout 0.5), Adam(1e-3), BCEWithLogitsLoss, batches of 256; per
     epoch a fresh 80/20 split of `training`, as many label-0 rows of the 80 % drawn again WITH replacement as it has label-1 rows
@@ -212,10 +262,24 @@ def compute_neuralcf_results(training, validation, n_users, n_items, engine=None
     shuffle, the early stop and which weights rank are untouched - but the DROPOUT draws are then the engine's Philox4x32-10 of
     (seed, epoch, the triple's place in the epoch's array, column), not torch's generator, so the trained weights differ from the torch
     loop's as two seeds of it differ.  `history` then also receives 'train_loss': every step's loss, read back once per epoch.
+    `device_draw=True` (needs `device_train=True` and an engine) moves the epoch's data preparation to the device as well: `training` is
+    cast to int32 and uploaded ONCE per call, and per epoch ONE `Engine.neumf_epoch_draw(seed=seed, epoch=epoch)` fills device buffers
+    with the split, the negatives and the shuffle - the draw defined in include/sdrm_hip.h at sdrm_neumf_epoch_draw (keyed Feistel
+    permutations of Philox4x32-10, restated in tests/neumf_draw_ref.py).  `neumf_train_steps` reads the shuffled part in place, the
+    validation loss reads the device-resident hold-out part, and the epoch's users come from n_users bytes read back.  Sizes, the
+    condition for the negatives (label-1 and label-0 rows both present) and everything behind the draw are untouched - but the draws are
+    then a function of (seed, epoch) alone and `numpy.random.default_rng(seed)` is not consumed, so the trained weights differ from the
+    host-draw path's as two seeds of it differ.  Torch's global generator is seeded and used for the initialisation as in every mode.
+    `history` then also receives 'draw_counts': one (n_pos, n_neg, m) per epoch.
+    In every mode the ranking problem (columns and both CSR matrices) is built once per call (`RankingProblem`) and the per-epoch and
+    final rankings select their users' rows from it: the same index arrays as before, without the per-epoch rebuild.
     `history`: a dict that receives 'valid_loss' (per epoch), 'recall10' (per epoch, with eval_recall), 'best_epoch' (the epoch whose
     weights ranked), 'reference_has_no_checkpoint', 'best_recall_epoch', 'epochs_run', 'per_user' (the final per-user recall / ndcg)
     and 'model' (the module that ranked)."""
     training, validation = _as_triples(training, "training"), _as_triples(validation, "validation")
+    if device_draw and (engine is None or not device_train):
+        raise ValueError("compute_neuralcf_results: device_draw=True needs device_train=True and an engine (the draw fills device buffers that the "
+                         "device train step reads in place; there is no host form)")
     device = torch.device(device) if device is not None else (engine.device if engine is not None else torch.device("cpu"))
     if device_train:
         if engine is None:
@@ -235,18 +299,30 @@ def compute_neuralcf_results(training, validation, n_users, n_items, engine=None
     kept = {0: None}
     valid_losses, recalls, epochs_run = [], [], 0
     n_hold = int(math.ceil(0.2 * training.shape[0]))          # sklearn's train_test_split(test_size=0.2): ceil for the test part
+    problem = RankingProblem(training, validation)
+    draw_counts = []
+    if device_draw:
+        training_dev = torch.from_numpy(np.ascontiguousarray(training, dtype=np.int32)).to(device)
+        draw_bufs = (torch.empty(n_hold, 3, dtype=torch.int32, device=device),
+                     torch.empty(2 * (training.shape[0] - n_hold), 3, dtype=torch.int32, device=device))
     for epoch in range(epochs):
         epochs_run += 1
         model.train()
-        perm = rng.permutation(training.shape[0])
-        hold, part = training[perm[:n_hold]], training[perm[n_hold:]]
-        negatives = part[part[:, 2] == 0]
-        n_pos = int((part[:, 2] == 1).sum())
-        if n_pos and negatives.shape[0]:
-            part = np.concatenate([part, negatives[rng.integers(0, negatives.shape[0], size=n_pos * NUM_NEG)]])
-        part = part[rng.permutation(part.shape[0])]
+        if device_draw:
+            hold, triples_dev, counts, present = engine.neumf_epoch_draw(training_dev, n_hold, seed=seed, epoch=epoch, out=draw_bufs,
+                                                                         n_users=n_users if eval_recall else None)   # (`present` only where a ranking reads it)
+            draw_counts.append(counts)
+        else:
+            perm = rng.permutation(training.shape[0])
+            hold, part = training[perm[:n_hold]], training[perm[n_hold:]]
+            negatives = part[part[:, 2] == 0]
+            n_pos = int((part[:, 2] == 1).sum())
+            if n_pos and negatives.shape[0]:
+                part = np.concatenate([part, negatives[rng.integers(0, negatives.shape[0], size=n_pos * NUM_NEG)]])
+            part = part[rng.permutation(part.shape[0])]
         if device_train:
-            triples_dev = torch.from_numpy(np.ascontiguousarray(part, dtype=np.int32)).to(device)
+            if not device_draw:
+                triples_dev = torch.from_numpy(np.ascontiguousarray(part, dtype=np.int32)).to(device)
             losses = engine.neumf_train_steps(live, exp_avg, exp_avg_sq, triples_dev, BATCH, steps_done, lr=LR, p_drop=0.5, seed=seed, call_id=epoch,
                                               check=False)     # (the evaluation below asks feed_status)
             steps_done += int(losses.numel())
@@ -261,7 +337,8 @@ def compute_neuralcf_results(training, validation, n_users, n_items, engine=None
         valid_loss = validation_loss(model, hold, engine)
         valid_losses.append(valid_loss)
         if eval_recall:
-            rec, _ = rank_all_items(model, training, validation, hold[:, 0], engine)
+            epoch_users = np.flatnonzero(present.cpu().numpy()) if device_draw else hold[:, 0]
+            rec, _ = rank_all_items(model, training, validation, epoch_users, engine, problem=problem)
             with np.errstate(invalid="ignore"):
                 recall10 = float(np.nanmean(rec[K_LIST.index(10)])) if rec.shape[1] else float("nan")
             recalls.append(recall10)
@@ -289,11 +366,13 @@ def compute_neuralcf_results(training, validation, n_users, n_items, engine=None
     else:
         model.load_state_dict(kept[best_epoch])
     model.eval()
-    rec, ndcg = rank_all_items(model, training, validation, validation[:, 0], engine)
+    rec, ndcg = rank_all_items(model, training, validation, validation[:, 0], engine, problem=problem)
     if history is not None:
         history.update(valid_loss=valid_losses, recall10=recalls, best_epoch=best_epoch, reference_has_no_checkpoint=no_checkpoint, best_recall_epoch=best_recall_epoch, epochs_run=epochs_run, per_user=(rec, ndcg), model=model)
         if device_train:
             history["train_loss"] = train_losses
+        if device_draw:
+            history["draw_counts"] = draw_counts
     with np.errstate(invalid="ignore"):
         return (np.array([np.round(np.nanmean(rec[q]), 4) for q in range(len(K_LIST))]),
                 np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
