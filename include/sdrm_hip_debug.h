@@ -172,6 +172,12 @@ enum { SDRM_SAMPLE_PATH_SKINNY = 0,      /* the narrow nets' one launch for the 
        SDRM_SAMPLE_PATH_PERSIST = 1,     /* reverse steps without kernel boundaries (csrc/sample_persist.h) */
        SDRM_SAMPLE_PATH_PER_LAYER = 2 }; /* one launch per layer */
 int sdrm_debug_last_plan(const sdrm_engine* e, int* train_path, int* parts, int* dgrad, int* sample_path);
+/* What the last train forward staged, read only (every kernel path leaves both: the staging of a step is one definition, csrc/train_math.h):
+ * staged [3][B][L] float32 - the layer-0 inputs of the P, S and Q pass (q_sample and the three dropout masks applied), in user order
+ * whatever the stacked row order of the path - and t [B] int32, the users' timesteps; DEVICE pointers, either may be NULL.  Enqueued
+ * on `stream`; SDRM_ERR_STATE before the first forward.  Valid until the next train forward on the handle (the backward reads, never
+ * writes, what this returns). */
+int sdrm_debug_get_staged(const sdrm_engine* e, float* staged, int* t, void* stream);
 
 /* Gradient all-reduces of sdrm_train_step_sharded: 1 (default) = one all-reduce of the whole flat gradient after the one-call
  * backward; 2 = the two buckets of sdrm_grad_buckets, the first overlapped with the upper layers' weight gradients on the

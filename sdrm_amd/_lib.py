@@ -197,6 +197,7 @@ SIGNATURES = {
     "sdrm_debug_set_sample_persist": (c_int, [c_void_p, c_int]),
     "sdrm_debug_set_rows48_share": (c_int, [c_void_p, c_int]),
     "sdrm_debug_rowchain_available": (c_int, [c_void_p]),
+    "sdrm_debug_get_staged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_debug_set_wgrad_strips": (c_int, [c_void_p, c_int]),
     "sdrm_debug_set_dgrad_rows": (c_int, [c_void_p, c_int]),
     "sdrm_debug_comm_handle": (c_void_p, [c_void_p]),

@@ -195,10 +195,14 @@ __device__ __forceinline__ void rc_acc_settle(f32x4 (&acc)[3][CT]) {
 // only the first MFMA of every tile is issued (its four lane groups hold the four real k), and nothing is fetched behind it.
 enum { RC_PLAIN = 0, RC_NEXT_LIGHT = 1, RC_LIGHT = 2 };
 // RTS: rows between two of the wave's row tiles in the LDS tile (the users of a group: 32 here, 16 in rows48.h)
-template <int CT, int LDA, int NS, bool STREAM, bool NT, int MODE = RC_PLAIN, int RTS = RC_USERS>
+// AIMM >= 0 (the 96-row forward's loops): the next step's A fragments are read at `arun` + AIMM bytes, where arun[0] is this lane's
+// running byte offset of row tiles 0 and 1 and arun[1] that of row tile 2 (two tiles further the offset no longer fits the 16-bit
+// field of a ds_read) - the caller advances both ONCE per loop trip, and a K-step holds no address arithmetic for them at all: the
+// opaque statement that pins a read to its slot works on the running register itself, where a by-value offset costs a copy per read
+template <int CT, int LDA, int NS, bool STREAM, bool NT, int MODE = RC_PLAIN, int RTS = RC_USERS, int AIMM = -1>
 __device__ __forceinline__ void rc_kstep(f32x4 (&acc)[3][CT], const f32x4 (&ac)[3], const f32x4 (&bc)[CT], f32x4 (&an)[3],
                                          f32x4 (&bn)[CT], brsrc wres, uint32_t wnext, uint32_t lane16, uint32_t anext,
-                                         const float* __restrict__ Act, brsrc sres, RcStream& sw) {
+                                         const float* __restrict__ Act, brsrc sres, RcStream& sw, uint32_t* arun = nullptr) {
   constexpr int NE = MODE == RC_LIGHT ? 1 : 4;
   constexpr int NSLOT = 3 * NE * CT;
   constexpr int P_A = MODE == RC_LIGHT ? 0 : CT, P_S = MODE == RC_LIGHT ? 0 : CT + 3, NPIECE = P_S + (STREAM ? 2 * NS : 0);
@@ -228,10 +232,17 @@ __device__ __forceinline__ void rc_kstep(f32x4 (&acc)[3][CT], const f32x4 (&ac)[
         }
       } else if (p < P_S) {
         if (!(RC_DIAG & 4)) {
-          uint32_t ao = anext;
-          asm volatile("" : "+v"(ao));
-          if (MODE == RC_NEXT_LIGHT) an[p - P_A][0] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(Act) + ao + (p - P_A) * RTS * LDA * 4);
-          else an[p - P_A] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(Act) + ao + (p - P_A) * RTS * LDA * 4);
+          if constexpr (AIMM >= 0) {
+            static_assert(MODE == RC_PLAIN, "running offsets are those of the plain fragment layout");
+            uint32_t& ar = arun[p - P_A == 2 ? 1 : 0];
+            asm volatile("" : "+v"(ar));
+            an[p - P_A] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(Act) + ar + AIMM + (p - P_A == 1 ? RTS * LDA * 4 : 0));
+          } else {
+            uint32_t ao = anext;
+            asm volatile("" : "+v"(ao));
+            if (MODE == RC_NEXT_LIGHT) an[p - P_A][0] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(Act) + ao + (p - P_A) * RTS * LDA * 4);
+            else an[p - P_A] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(Act) + ao + (p - P_A) * RTS * LDA * 4);
+          }
         }
       } else {
         // tile stream, chunk q: LDS read, then (NS pieces later) the HBM store
@@ -274,9 +285,42 @@ __device__ __forceinline__ void block_sum4(double (&v)[4], double* sh /* [16] */
   for (int j = 0; j < 4; ++j) v[j] = (sh[j] + sh[4 + j]) + (sh[8 + j] + sh[12 + j]);
 }
 
+// ---- staging of the 96-row forward, four columns wide (train_math.h has the contract; k_prep_train, rows48.h and the narrow nets
+// keep the per-element helpers)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// bit p of a keep word as a mask over a float's bits (one v_bfe_i32): `keep ? v : 0.f` is then one v_and, without a compare
+__device__ __forceinline__ uint32_t rc_keep_mask(uint32_t w, int p) { return (uint32_t)((int32_t)(w << (31 - p)) >> 31); }
+
+// The three staged inputs of a column quad from its x0 (X), its scaled normals (E) and its four keep words (bits 0 .. 2: P, S, Q;
+// a word of a column beyond L or of a user beyond the batch is zero, and so are its three inputs).  Written on f32x4 so that the
+// compiler pairs it into v_pk_mul / v_pk_add / v_pk_fma, and with contraction OFF and every fma spelled out: the results are, bit
+// for bit, those of the per-element text this replaces (stage_element under the compiler's default contraction), which came out as
+//   P = 2 (sa x + om e) with BOTH products rounded, except - at eleven column tiles only (FMA0) - in column 0 of a quad, where
+//       sa x went into the add unrounded: fma(sa, x, om e);   S = 2 x;   Q = 2 fma(e, mu, x).
+template <bool FMA0>
+__device__ __forceinline__ void rc_stage_quad(f32x4 X, f32x4 E, float sa, float om, const uint32_t (&kw)[4], f32x4& P, f32x4& S, f32x4& Q) {
+#pragma clang fp contract(off)
+  const f32x4 oe = om * E;
+  f32x4 p = sa * X + oe;
+  if (FMA0) p[0] = __builtin_fmaf(sa, X[0], oe[0]);
+  p = 2.f * p;
+  const f32x4 s = 2.f * X;
+  const f32x4 q = 2.f * __builtin_elementwise_fma(E, f32x4{MU, MU, MU, MU}, X);
+  u32x4 mP, mS, mQ;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { mP[k] = rc_keep_mask(kw[k], 0); mS[k] = rc_keep_mask(kw[k], 1); mQ[k] = rc_keep_mask(kw[k], 2); }
+  P = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, p) & mP);
+  S = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, s) & mS);
+  Q = __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, q) & mQ);
+}
+
+// The kernel is two: k_row_fwd<CT, LIGHT> draws its randoms itself (PHILOX), k_row_fwd_explicit<CT, LIGHT> reads them from the
+// step's noise / t / keep arrays; the host picks by the step's mode (sdrm_hip.hip: launch_row_forward).  The PHILOX text has no
+// mode branch, no 64-bit element index and no load in its per-element code.
 // LIGHT: the weight copies' last K-step is compact (a.light; the host picks the instantiation)
-template <int CT, bool LIGHT = false>
-__global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd(const RowChainArgs a) {
+template <int CT, bool LIGHT, bool PHILOX>
+__device__ __forceinline__ void row_fwd_body(const RowChainArgs& a) {
   typedef RowChainCfg<CT> C;
   constexpr int NP = C::NP, NCT = C::NCT, KS = C::KS, QP = C::QP, LDA = C::LDA, RT = 3;
   static_assert(KS % 2 == 0, "K-steps are taken in pairs");
@@ -295,94 +339,124 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd(const RowChainArgs a) {
   RC_STAMP(0);
 
   // ---------------------------------------------------------------- staging
-  if (tid < RC_USERS) {
-    const int usr = u0 + tid;
-    int t0 = 0;
-    if (usr < a.B) {
-      t0 = train_timestep(a.mode, a.t, a.row0, usr, a.step, a.seed_lo, a.seed_hi, a.T);
-      a.tdev[usr] = t0;
-    }
-    trow[tid] = t0;
-  }
-  // thread -> (user tid >> 3, column quads (tid & 7) + 8 j): every x0 quad of the thread is requested before the first is used
+  // thread -> (user tid >> 3, column quads (tid & 7) + 8 j): every x0 quad of the thread is requested before anything else
   constexpr int NQ = QP / 8;   // = CT
   const int su = tid >> 3, sq = tid & 7;
   const int susr = u0 + su;
-  float4 xs[NQ];
-#pragma unroll
-  for (int j = 0; j < NQ; ++j) {
-    const int c = 4 * (sq + 8 * j);
-    xs[j] = (susr < a.B && c < a.L) ? load4_unpadded(a.x0, susr, c, a.L) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __syncthreads();
+  const bool live = susr < a.B;
+  // By raw buffer loads over the group's rows of x0 (at most 32 L floats): a user beyond the batch lies beyond the resource and
+  // a column beyond L is sent there, both read zero - no branch around a load.  (Through load4_unpadded every quad sat in control
+  // flow of its own and the compiler put an s_waitcnt vmcnt(0) behind each: NQ round trips to memory, one after the other.)
+  f32x4 xs[NQ];
   {
-    // the time-embedding columns of U, temb[t] of the row's timestep (read by the layer-0 weight gradient only: they deliver
-    // M = dpre0^T * temb, tail.h; rows of users beyond the batch stay all-zero): the P, S and Q row of this thread's user, column
-    // quads sq + 8 j - issued first, they drain while the randoms are drawn
-    const int TPc = a.K0 - a.LPs;          // a multiple of 32 columns
-    const int TQ8 = TPc >> 5;              // groups of eight quads
-    const bool uin = susr < a.B;
-    const float* trow_p = a.tembP + (size_t)(uin ? trow[su] : 0) * TPc + 4 * sq;
+    const brsrc xres = make_brsrc(a.x0 + (size_t)u0 * a.L, (uint32_t)(min(max(a.B - u0, 0), RC_USERS) * a.L * 4));
+    constexpr uint32_t BEYOND = 0x7ffffff0u;
+    const uint32_t xrow = (uint32_t)(su * a.L * 4);
+    if ((a.L & 3) == 0) {
+#pragma unroll
+      for (int j = 0; j < NQ; ++j) {
+        const int c = 4 * (sq + 8 * j);
+        xs[j] = bload4(xres, c < a.L ? xrow + 4u * c : BEYOND, 0u);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < NQ; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int c = 4 * (sq + 8 * j) + k;
+          xs[j][k] = bload1(xres, c < a.L ? xrow + 4u * c : BEYOND, 0u);
+        }
+    }
+  }
+  // the user's timestep: each of the user's eight threads draws it itself (one more call beside the thread's NQ), so nothing waits
+  // for a hand-over through LDS; trow[] is for the layers (the row's line of B0tab), read behind the barrier that ends the staging
+  int tt = 0;
+  if constexpr (PHILOX) {
+    const int td = train_timestep(1, nullptr, a.row0, susr, a.step, a.seed_lo, a.seed_hi, a.T);
+    tt = live ? td : 0;
+  } else {
+    if (live) tt = train_timestep(0, a.t, a.row0, susr, a.step, a.seed_lo, a.seed_hi, a.T);
+  }
+  if (sq == 0) {
+    trow[su] = tt;
+    if (live) a.tdev[susr] = tt;
+  }
+  const float sa = a.sqrt_ab[tt], om = a.one_minus_ab[tt];
+  // the time-embedding columns of U, temb[t] of the row's timestep (read by the layer-0 weight gradient only: they deliver
+  // M = dpre0^T * temb, tail.h; rows of users beyond the batch stay all-zero): the P, S and Q row of this thread's user, column
+  // quads sq + 8 jq.  The first TE_AHEAD groups of eight quads are requested here, before the draws, and stored behind them; again
+  // by buffer accesses, a group that is not there (or the row of no user) lies beyond the resource: it reads zero, its store is dropped
+  const int TPc = a.K0 - a.LPs;          // a multiple of 32 columns
+  const int TQ8 = TPc >> 5;              // groups of eight quads
+  constexpr int TE_AHEAD = 4;
+  constexpr uint32_t TE_BEYOND = 0x7ffffff0u;
+  const brsrc tres = make_brsrc(a.tembP, (uint32_t)((a.T + 1) * TPc * 4));
+  const uint32_t tvo = live ? (uint32_t)((tt * TPc + 4 * sq) * 4) : TE_BEYOND;
+  f32x4 te[TE_AHEAD];
+#pragma unroll
+  for (int jq = 0; jq < TE_AHEAD; ++jq) te[jq] = bload4(tres, jq < TQ8 ? tvo + 128u * jq : TE_BEYOND, 0u);
+  // PHILOX: the thread's NQ calls (one per column quad: two normal pairs and, in the low bits of word j, the three keep bits of
+  // column j) in ONE straight-line block - a call is a serial chain of 10 rounds, and with one wave per SIMD nothing but the other
+  // calls of the same thread can fill its latencies
+  U4 rw[NQ];
+  if constexpr (PHILOX) {
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) rw[j] = train_quad_draw(a.row0, susr, sq + 8 * j, a.step, a.seed_lo, a.seed_hi);
+    // (the stores below stay behind the draws: the words are operands of a statement that keeps its place among the stores)
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) asm volatile("" : : "v"(rw[j].x));
+  }
+  {
     const brsrc ures = make_brsrc(a.U + grow0 * a.K0, (uint32_t)(RC_ROWS * a.K0 * 4));
     const uint32_t uvo = (uint32_t)((su * a.K0 + a.LPs + 4 * sq) * 4);
-    for (int jq = 0; jq < TQ8; ++jq) {
-      const float4 te = uin ? *reinterpret_cast<const float4*>(trow_p + 32 * jq) : make_float4(0.f, 0.f, 0.f, 0.f);
-      const f32x4 oh = {te.x, te.y, te.z, te.w};
+#pragma unroll
+    for (int jq = 0; jq < TE_AHEAD; ++jq)
+#pragma unroll
+      for (int pass = 0; pass < 3; ++pass)
+        bstore4<true>(ures, jq < TQ8 ? uvo + 128u * jq : TE_BEYOND, (uint32_t)(pass * RC_USERS * a.K0 * 4), te[jq]);
+    for (int jq = TE_AHEAD; jq < TQ8; ++jq) {   // (more than 128 time-embedding columns)
+      const f32x4 oh = bload4(tres, tvo, 128u * jq);
 #pragma unroll
       for (int pass = 0; pass < 3; ++pass) bstore4<true>(ures, uvo, (uint32_t)((pass * RC_USERS * a.K0 + 32 * jq) * 4), oh);
     }
   }
-  {
-    const int tt = trow[su];
-    const float sa = a.sqrt_ab[tt], om = a.one_minus_ab[tt];
-    // PHILOX mode: the thread's NQ calls (one per column quad: two normal pairs and, in the low bits of word j, the three keep
-    // bits of column j) in ONE straight-line block - a call is a serial chain of 10 rounds, and with one wave per SIMD nothing
-    // but the other calls of the same thread can fill its latencies
-    U4 rw[NQ];
-    if (a.mode != 0) {
 #pragma unroll
-      for (int j = 0; j < NQ; ++j)
-        rw[j] = train_quad_draw(a.row0, susr, sq + 8 * j, a.step, a.seed_lo, a.seed_hi);
-    }
+  for (int j = 0; j < NQ; ++j) {
+    const int c = 4 * (sq + 8 * j);
+    const int nvalid = live ? min(max(a.L - c, 0), 4) : 0;   // real columns of this quad: 4 but for the ragged one and those beyond L
+    const f32x4 X = xs[j];
+    f32x4 E;
+    uint32_t kw[4];
+    if constexpr (PHILOX) {
+      float e[4];
+      train_quad_decode(rw[j], a.nd, e, kw);
+      E = f32x4{e[0], e[1], e[2], e[3]};
+    } else {
+      const size_t idx = (size_t)susr * a.L + c, BL = (size_t)a.B * a.L;
 #pragma unroll
-    for (int j = 0; j < NQ; ++j) {
-      const int c = 4 * (sq + 8 * j);
-      float vP[4] = {0.f, 0.f, 0.f, 0.f}, vS[4] = {0.f, 0.f, 0.f, 0.f}, vQ[4] = {0.f, 0.f, 0.f, 0.f};
-      if (susr < a.B && c < a.L) {
-        const float x_[4] = {xs[j].x, xs[j].y, xs[j].z, xs[j].w};
-        float e[4] = {0.f, 0.f, 0.f, 0.f};
-        uint32_t bits[4] = {0u, 0u, 0u, 0u};
-        if (a.mode != 0) {
-          train_quad_decode(rw[j], a.nd, e, bits);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (c + k < a.L) {
-            const size_t idx = (size_t)susr * a.L + c + k;
-            const float x = x_[k];
-            bool k1, k2, k3;
-            float ee;
-            if (a.mode == 0) {
-              ee = a.noise[idx];
-              const size_t BL = (size_t)a.B * a.L;
-              k1 = a.keep[idx] != 0; k2 = a.keep[BL + idx] != 0; k3 = a.keep[2 * BL + idx] != 0;
-            } else {
-              ee = e[k];
-              k1 = bits[k] & 1u; k2 = (bits[k] >> 1) & 1u; k3 = (bits[k] >> 2) & 1u;
-            }
-            stage_element(x, ee, sa, om, k1, k2, k3, vP[k], vS[k], vQ[k]);
-          }
+      for (int k = 0; k < 4; ++k) {
+        E[k] = 0.f; kw[k] = 0u;
+        if (k < nvalid) {
+          E[k] = a.noise[idx + k];
+          kw[k] = (a.keep[idx + k] != 0 ? 1u : 0u) | (a.keep[BL + idx + k] != 0 ? 2u : 0u) | (a.keep[2 * BL + idx + k] != 0 ? 4u : 0u);
         }
       }
-      if (c == (a.ones_col & ~3)) {   // the ones column (a pad column: layer 0's weights are zero there)
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (k == (a.ones_col & 3)) vP[k] = vS[k] = vQ[k] = 1.f;
-      }
-      *reinterpret_cast<float4*>(Act + su * LDA + c) = make_float4(vP[0], vP[1], vP[2], vP[3]);
-      *reinterpret_cast<float4*>(Act + (RC_USERS + su) * LDA + c) = make_float4(vS[0], vS[1], vS[2], vS[3]);
-      *reinterpret_cast<float4*>(Act + (2 * RC_USERS + su) * LDA + c) = make_float4(vQ[0], vQ[1], vQ[2], vQ[3]);
     }
+    if (PHILOX && nvalid < 4) {   // the edge: no keep bit, hence a zero, in a column that does not exist
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k >= nvalid) kw[k] = 0u;
+    }
+    f32x4 vP, vS, vQ;
+    rc_stage_quad<CT == 11>(X, E, sa, om, kw, vP, vS, vQ);
+    if (c == (a.ones_col & ~3)) {   // the ones column (a pad column: layer 0's weights are zero there)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k == (a.ones_col & 3)) vP[k] = vS[k] = vQ[k] = 1.f;
+    }
+    *reinterpret_cast<f32x4*>(Act + su * LDA + c) = vP;
+    *reinterpret_cast<f32x4*>(Act + (RC_USERS + su) * LDA + c) = vS;
+    *reinterpret_cast<f32x4*>(Act + (2 * RC_USERS + su) * LDA + c) = vQ;
   }
   __syncthreads();
   RC_STAMP(1);
@@ -443,17 +517,20 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd(const RowChainArgs a) {
     auto kloop = [&](auto stream_tag, auto nt_tag) {
       constexpr bool STREAM = decltype(stream_tag)::value, NT = decltype(nt_tag)::value;
       constexpr uint32_t WS = NCT * 1024;
+      // the A fragment reads of K-step ks + 1 / ks + 2 sit 64 / 128 bytes behind the running offsets of K-step ks
+      uint32_t arun[2] = {aoff, aoff + (uint32_t)(2 * RC_USERS * LDA * 4)};
       for (uint32_t ks = 0; ks < (uint32_t)KS - 2; ks += 2) {
-        rc_kstep<CT, LDA, 2, STREAM, NT>(acc, a0, b0, a1, b1, Wf, (ks + 1) * WS, lane16, aoff + 64u * (ks + 1), Act, sres, sw);
-        rc_kstep<CT, LDA, 1, STREAM, NT>(acc, a1, b1, a0, b0, Wf, (ks + 2) * WS, lane16, aoff + 64u * (ks + 2), Act, sres, sw);
+        rc_kstep<CT, LDA, 2, STREAM, NT, RC_PLAIN, RC_USERS, 64>(acc, a0, b0, a1, b1, Wf, (ks + 1) * WS, lane16, 0u, Act, sres, sw, arun);
+        rc_kstep<CT, LDA, 1, STREAM, NT, RC_PLAIN, RC_USERS, 128>(acc, a1, b1, a0, b0, Wf, (ks + 2) * WS, lane16, 0u, Act, sres, sw, arun);
+        arun[0] += 128u; arun[1] += 128u;
       }
       // the last pair: K-step KS - 1 may be the compact one (a.light: four real k in its sixteen)
       if constexpr (LIGHT) {
         rc_kstep<CT, LDA, 2, STREAM, NT, RC_NEXT_LIGHT>(acc, a0, b0, a1, b1, Wf, (KS - 1) * WS, lane16, aoffl + 64u * (KS - 1), Act, sres, sw);
         rc_kstep<CT, LDA, 1, STREAM, NT, RC_LIGHT>(acc, a1, b1, a0, b0, Wf, 0u, lane16, aoff, Act, sres, sw);
       } else {
-        rc_kstep<CT, LDA, 2, STREAM, NT>(acc, a0, b0, a1, b1, Wf, (KS - 1) * WS, lane16, aoff + 64u * (KS - 1), Act, sres, sw);
-        rc_kstep<CT, LDA, 1, STREAM, NT>(acc, a1, b1, a0, b0, Wf, (KS - 2) * WS, lane16, aoff + 64u * (KS - 2), Act, sres, sw);   // past the end: a harmless re-read
+        rc_kstep<CT, LDA, 2, STREAM, NT, RC_PLAIN, RC_USERS, 64>(acc, a0, b0, a1, b1, Wf, (KS - 1) * WS, lane16, 0u, Act, sres, sw, arun);
+        rc_kstep<CT, LDA, 1, STREAM, NT, RC_PLAIN, RC_USERS, 0>(acc, a1, b1, a0, b0, Wf, (KS - 2) * WS, lane16, 0u, Act, sres, sw, arun);   // past the end: a harmless re-read
       }
     };
     rc_acc_begin<CT>(acc);
@@ -530,5 +607,10 @@ __global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd(const RowChainArgs a) {
   }
 #endif
 }
+
+template <int CT, bool LIGHT = false>
+__global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd(const RowChainArgs a) { row_fwd_body<CT, LIGHT, true>(a); }
+template <int CT, bool LIGHT = false>
+__global__ __launch_bounds__(NTHREADS, 1) void k_row_fwd_explicit(const RowChainArgs a) { row_fwd_body<CT, LIGHT, false>(a); }
 
 }  // namespace sdrm

@@ -1264,7 +1264,9 @@ int launch_row_forward(sdrm_engine* e, const StepPlan& p, const float* x0, int64
   }
   return with_row_form(e, [&](auto ct, auto light) {
     return hip_rc(e, "k_row_fwd", profiled(e, PC_ROW_FWD, flops, st, [&] {
-      SDRM_LAUNCH(e, (k_row_fwd<VAL(ct), VAL(light)>), dim3((unsigned)G), dim3(NTHREADS), 0, st, a);
+      // two kernels: the one that draws its randoms itself, and the one that reads the step's noise / t / keep arrays (csrc/rowchain.h)
+      if (mode == SDRM_RNG_EXPLICIT) SDRM_LAUNCH(e, (k_row_fwd_explicit<VAL(ct), VAL(light)>), dim3((unsigned)G), dim3(NTHREADS), 0, st, a);
+      else SDRM_LAUNCH(e, (k_row_fwd<VAL(ct), VAL(light)>), dim3((unsigned)G), dim3(NTHREADS), 0, st, a);
       return hipGetLastError();
     }));
   });
@@ -1878,9 +1880,12 @@ static int train_forward_impl(sdrm_engine* e, const float* x0, int B, int64_t ro
     }
     p.loss_parts = ka.NP;
   } else if (p.path == StepPlan::ROW96 || p.path == StepPlan::ROW48) {
-    // row-owned forward (rowchain.h; rows48.h: the same on 48-row work-groups, p.parts of them per row group): the step's tables
-    // (the launch also pulls the batch into L2), then staging + every layer + the loss partial sums in ONE launch
-    int rc = emb_tables(e, st, x0, (size_t)B * e->L);
+    // row-owned forward (rowchain.h; rows48.h: the same on 48-row work-groups, p.parts of them per row group): the step's tables,
+    // then staging + every layer + the loss partial sums in ONE launch.  In front of the 48-row kernels the tables launch also
+    // pulls the batch into L2 (their staging asks for a thread's x0 quads one after the other); the 96-row forward requests every
+    // quad of a thread at once and is no faster behind the warm-up, so its tables launch goes without
+    const bool warm = p.path == StepPlan::ROW48;
+    int rc = emb_tables(e, st, warm ? x0 : nullptr, warm ? (size_t)B * e->L : 0);
     if (rc) return rc;
     rc = launch_row_forward(e, p, x0, row0, mode, rnd, seed, step, nd, st);
     if (rc) return rc;
@@ -2413,6 +2418,19 @@ int sdrm_get_train_outputs(const sdrm_engine* e, float* psq, void* stream) {
   SDRM_LAUNCH(e, k_unpad_psq, dim3(256), dim3(256), 0, (hipStream_t)stream, (const float*)e->Y, e->plan.B, e->L,
                      e->LP, e->plan.order, psq);
   HIP_TRY(me, hipGetLastError());
+  return SDRM_OK;
+}
+
+// test hook: the staged layer-0 inputs (the latent columns of U, in user order) and the timesteps of the last train forward
+int sdrm_debug_get_staged(const sdrm_engine* e, float* staged, int* t, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  sdrm_engine* me = const_cast<sdrm_engine*>(e);
+  if (!e->fwd_done) return fail(me, SDRM_ERR_STATE, "sdrm_debug_get_staged: no forward yet");
+  if (staged) {
+    SDRM_LAUNCH(e, k_unpad_psq, dim3(256), dim3(256), 0, (hipStream_t)stream, (const float*)e->U, e->plan.B, e->L, e->K0, e->plan.order, staged);
+    HIP_TRY(me, hipGetLastError());
+  }
+  if (t) HIP_TRY(me, hipMemcpyAsync(t, e->tdev, (size_t)e->plan.B * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return SDRM_OK;
 }
 

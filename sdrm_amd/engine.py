@@ -376,6 +376,14 @@ class Engine:
         self._check(self.lib.sdrm_get_train_outputs(self._h, _ptr(out), _stream()), "sdrm_get_train_outputs")
         return out
 
+    def staged(self, B):
+        """Test hook (sdrm_debug_get_staged): what the last train forward staged - the layer-0 inputs [3,B,L] of the P, S and Q
+        pass in user order, and the users' timesteps [B] int32."""
+        out = torch.empty(3, B, self.L, dtype=torch.float32, device=self.device)
+        t = torch.empty(B, dtype=torch.int32, device=self.device)
+        self._check(self.lib.sdrm_debug_get_staged(self._h, _ptr(out), _ptr(t), _stream()), "sdrm_debug_get_staged")
+        return out, t
+
     def preacts(self, layer, B):
         """Pre-activations [3,B,W] of layer `layer` from the last train forward (parity tests)."""
         out = torch.empty(3, B, self.W, dtype=torch.float32, device=self.device)

@@ -90,6 +90,10 @@ int main(int argc, char** argv) {
   float* dom = dalloc<float>(T + 1); CHECK(hipMemcpy(dom, hom.data(), (T + 1) * 4, hipMemcpyHostToDevice));
   float* dsl = dalloc<float>(2);
   { const float s2[2] = {slope0, slopeh}; CHECK(hipMemcpy(dsl, s2, 8, hipMemcpyHostToDevice)); }
+  // the time-embedding table the staging copies into U's upper columns: one-hot rows, as the parity check below expects
+  std::vector<float> htemb((size_t)(T + 1) * TP, 0.f);
+  for (int t = 0; t <= T; ++t) htemb[(size_t)t * TP + t] = 1.f;
+  float* dtemb = dalloc<float>(htemb.size()); CHECK(hipMemcpy(dtemb, htemb.data(), htemb.size() * 4, hipMemcpyHostToDevice));
   float* dU = dalloc<float>((size_t)MP * K0);
   float* dpre = dalloc<float>((size_t)(H + 1) * MP * NP);
   float* dY = dalloc<float>((size_t)MP * NP);
@@ -98,7 +102,7 @@ int main(int argc, char** argv) {
   double* dpart = dalloc<double>((size_t)4 * G);
 
   RowChainArgs a{};
-  a.x0 = dx0; a.noise = dnoise; a.t = dt; a.keep = dkeep; a.sqrt_ab = dsq; a.one_minus_ab = dom;
+  a.x0 = dx0; a.noise = dnoise; a.t = dt; a.keep = dkeep; a.sqrt_ab = dsq; a.one_minus_ab = dom; a.tembP = dtemb;
   a.B = B; a.L = L; a.T = T; a.H = H; a.mode = 0; a.seed_lo = 123u; a.seed_hi = 0u; a.step = 5u; a.row0 = 0; a.nd = 1.f;
   a.W0f = dWf[0]; a.Whf = dWf[1]; a.Wof = dWf[2]; a.bh = dbh; a.bo = dbo; a.B0tab = dB0tab; a.ldtab = NP;
   a.slope0 = dsl; a.slopeh = dsl + 1;
@@ -109,7 +113,8 @@ int main(int argc, char** argv) {
     RowChainArgs b = a;
     b.mode = mode;
     if (mode) { b.noise = nullptr; b.t = nullptr; b.keep = nullptr; }
-    hipLaunchKernelGGL((k_row_fwd<CT, true>), dim3(G), dim3(NTHREADS), 0, 0, b);
+    if (mode) hipLaunchKernelGGL((k_row_fwd<CT, true>), dim3(G), dim3(NTHREADS), 0, 0, b);
+    else hipLaunchKernelGGL((k_row_fwd_explicit<CT, true>), dim3(G), dim3(NTHREADS), 0, 0, b);
   };
   // the per-layer path's three NT launches on the same shapes (inputs: whatever the row kernel left in U / pre)
   auto launch_layers = [&]() {
