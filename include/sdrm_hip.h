@@ -330,6 +330,41 @@ typedef struct sdrm_csr_part {
 int sdrm_csr_vstack(sdrm_engine* e, const sdrm_csr_part* parts, int n_parts, int n_cols, int64_t* indptr_out, int32_t* indices_out,
                     float* data_out, int64_t capacity_out, void* stream);
 
+/* The NeuMF evaluator's (user, item, label) triples from up to 8 device-resident CSR parts (reference: main.py:218-283, the frames of
+ * the two tails of the synthetic matrix and of the validation users' training half, concatenated; csrc/neumf_triples.h; restated in
+ * tests/neumf_triples_ref.py).  Only a part's PATTERN is read: indptr [n_rows + 1] holds absolute offsets and need not start at 0 (a row
+ * range of a larger matrix is a pointer offset), `capacity` is the number of elements of indices, as in sdrm_csr_part.  Row r of a part
+ * is user user0 + r, and every triple of a part carries the part's label, 0 or 1.
+ * The order, which is the definition: the parts in the order given; within a part the rows ascending; within a row the entries in
+ *   their stored order.  Entry j of row r of part p becomes the record (parts[p].user0 + r, indices[j], parts[p].label), three int32.
+ *   triples_out [capacity_out][3] is dense - a row without entries, or an emptied one, leaves no hole - and rows m .. capacity_out - 1
+ *   are left as they were.  It is the buffer sdrm_neumf_epoch_draw reads.
+ * Row checks, exactly sdrm_csr_vstack's: a row whose indptr pair is negative, out of order, reaches behind its part's capacity or spans
+ *   more than n_items entries is EMPTY in the output and raises the status word sdrm_feed_status reports under sdrm_csr_vstack's indptr
+ *   bit; a row that holds a column outside [0, n_items) is EMPTY too and raises the column bit.  Should the checked lengths add up
+ *   to more than capacity_out (parts whose rows share entries), the triples behind capacity_out are dropped, m is capacity_out and the
+ *   indptr bit is raised.  No load or store uses an unchecked index; no store lands outside [0, capacity_out) of triples_out,
+ *   [0, n_items) of item_present or [0, 4) of counts_dev, for any input.
+ * counts_dev: DEVICE int64 [4], written by the call: m; the number of label-1 triples; max user + 1 and max item + 1 over the emitted
+ *   triples (both 0 when m is 0) - what main.py:283 takes for n_users and n_items.
+ * item_present: null, or DEVICE uint8 [n_items]: the call zeroes it and sets byte i for every emitted item i - the ranking's column list
+ *   without the triples crossing to the host.
+ * Three launches behind three memsets, all enqueued on `hip_stream` - the caller's stream, under the contract of every `stream` argument
+ *   of this header (Conventions); nothing is read back and nothing synchronises (except the device
+ *   synchronise when the grow-only scratch of 20 bytes per row must grow).  Integer atomics only, for the three counts behind m; the
+ *   scratch is cleared on the stream by every call: the same bytes on every run, whatever earlier calls left behind.
+ * Refused before any launch, nothing written: SDRM_ERR_ARG for a null handle, null parts, triples_out or counts_dev, a part with a null
+ *   indptr, or with null indices and capacity > 0; SDRM_ERR_SHAPE for n_parts outside 1 .. 8, n_items outside 1 .. 2^22, total rows
+ *   outside 1 .. 2^22 (a part may have none), a label outside {0, 1}, user0 < 0 or user0 + n_rows above 2^31 - 1, a negative capacity,
+ *   capacity_out below the sum of the parts' capacities (the host cannot know less) or above 2^30 (sdrm_neumf_epoch_draw's bound on n). */
+typedef struct sdrm_triple_part {
+  const int64_t* indptr; const int32_t* indices;
+  int64_t n_rows; int64_t capacity;
+  int32_t user0; int32_t label;
+} sdrm_triple_part;
+int sdrm_neumf_triples(sdrm_engine* e, const sdrm_triple_part* parts, int n_parts, int n_items, int32_t* triples_out, int64_t capacity_out,
+                       uint8_t* item_present, int64_t* counts_dev, void* hip_stream);
+
 /* The VAE decode hook on the device (reference: train_SDRM.py:212-214 `decoder = Linear(latent, hidden) -> Tanh ->
  * Linear(hidden, N_ITEMS)`, :252-254 `VAE.decode`, called by sample_ddpm at :49 / :61 on the sampled latents): two launches of
  * the engine's fp32 MFMA GEMM with the bias + tanh / bias epilogues.  The struct holds DEVICE pointers to the four nn.Linear

@@ -36,6 +36,10 @@ class CsrPart(C.Structure):
     _fields_ = [("indptr", c_void_p), ("indices", c_void_p), ("data", c_void_p), ("n_rows", c_int64), ("capacity", c_int64)]
 
 
+class TriplePart(C.Structure):
+    _fields_ = [("indptr", c_void_p), ("indices", c_void_p), ("n_rows", c_int64), ("capacity", c_int64), ("user0", C.c_int32), ("label", C.c_int32)]
+
+
 class NeumfTrain(C.Structure):
     _fields_ = [("p", c_void_p * 12), ("m", c_void_p * 12), ("v", c_void_p * 12), ("n_users", c_int), ("n_items", c_int), ("factor", c_int)]
 
@@ -142,6 +146,7 @@ SIGNATURES = {
     "sdrm_equal_sparsity_csr_end": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "sdrm_csr_transpose": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_csr_vstack": (c_int, [c_void_p, C.POINTER(CsrPart), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sdrm_neumf_triples": (c_int, [c_void_p, C.POINTER(TriplePart), c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sdrm_rank_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_svd_fit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_uint64,
@@ -179,6 +184,7 @@ SIGNATURES = {
     "sdrm_debug_neumf_args": (c_int, [c_int, c_int, c_int, c_int64, c_int64]),
     "sdrm_debug_neumf_train_args": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int64, c_float]),
     "sdrm_debug_neumf_draw_args": (c_int, [c_int64, c_int64, c_int64, c_int, c_int]),
+    "sdrm_debug_neumf_triples_args": (c_int, [C.POINTER(TriplePart), c_int, c_int, c_int64]),
     "sdrm_debug_mlp_train_args": (c_int, [c_int, c_int, c_int64, c_int, c_int64, c_float, c_int, C.POINTER(c_uint64), c_int]),
     "sdrm_debug_mlp_eval_args": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int, C.POINTER(c_uint64), c_int]),
     "sdrm_debug_holdout_args": (c_int, [c_int, c_int64, c_int64, C.c_double, c_int64, C.POINTER(c_int64)]),

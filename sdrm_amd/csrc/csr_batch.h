@@ -23,18 +23,20 @@ struct FeedStatusText { unsigned bit; const char* text; };
 constexpr FeedStatusText FEED_STATUS_TEXT[] = {
     {FEED_BAD_ROW, " a row id outside [0, n_rows) (its output row is zero);"},
     {FEED_BAD_PTR, " an indptr pair that is negative or not ordered (its output row is zero);"},
-    {FEED_BAD_COL, " a column index outside [0, n_items) (that entry was skipped);"},
+    {FEED_BAD_COL, " a column index outside [0, n_items) (that entry was skipped; sdrm_neumf_triples: the row is empty in the output);"},
     {FEED_HOLD_PTR, " sdrm_holdout_split: an indptr pair that is out of order, reaches outside [0, nnz] or spans more than n_items entries (the row is empty in both outputs);"},
     {FEED_HOLD_COL, " sdrm_holdout_split: a column index outside [0, n_items) (the row is empty in both outputs);"},
     {FEED_T_DUP, " sdrm_csr_transpose: a row that holds a column more than once (the output is not the transpose);"},
-    {FEED_STACK_PTR, " sdrm_csr_vstack: an indptr pair that is out of order, reaches outside its part's arrays or spans more than n_cols entries (the row is empty in the output);"},
+    {FEED_STACK_PTR, " sdrm_csr_vstack: an indptr pair that is out of order, reaches outside its part's arrays or spans more than n_cols entries (the row is empty in the output; sdrm_neumf_triples reports its rows here too, and triples dropped behind capacity_out);"},
     {FEED_STACK_COL, " sdrm_csr_vstack: a column index outside [0, n_cols) (the row is empty in the output);"},
 };
 
 // Feed row `src` and CSR stretch [p0, p1) of batch row r, range-checked: a row id outside the matrix or an indptr pair out of order
 // leaves the empty stretch, and the thread with `owner` == 0 among those that own the row raises the status word.  (The index, not
 // the compare: a flag worked out by the caller is evaluated ahead of the loads and moves the register counts of k_nll_*.)
+// PTR_BIT: the bit a bad indptr pair raises (sdrm_neumf_triples reports its rows under sdrm_csr_vstack's bit).
 struct CsrSpan { int64_t src, p0, p1; };
+template <unsigned PTR_BIT = FEED_BAD_PTR>
 __device__ __forceinline__ CsrSpan csr_row_span(const CsrBatch& c, int r, int owner) {
   CsrSpan s{c.rows ? c.rows[r] : c.row0 + r, 0, 0};
   if (s.src < 0 || s.src >= c.n_rows) {
@@ -43,7 +45,7 @@ __device__ __forceinline__ CsrSpan csr_row_span(const CsrBatch& c, int r, int ow
   }
   const int64_t q0 = c.indptr[s.src], q1 = c.indptr[s.src + 1];
   if (q0 < 0 || q1 < q0) {
-    if (owner == 0) atomicOr(c.flag, (unsigned)FEED_BAD_PTR);
+    if (owner == 0) atomicOr(c.flag, PTR_BIT);
     return s;
   }
   s.p0 = q0; s.p1 = q1;

@@ -183,8 +183,9 @@ struct CsrStackArgs {
   unsigned* flag;            // the handle's feed status word
 };
 
-// The part of output row R (wave-uniform) and the row's number inside it.
-__device__ __forceinline__ int stack_part_of(const CsrStackArgs& a, int64_t R, int64_t& r) {
+// The part of output row R (wave-uniform) and the row's number inside it; A holds n_parts and first[] (csrc/neumf_triples.h's too).
+template <class A>
+__device__ __forceinline__ int stack_part_of(const A& a, int64_t R, int64_t& r) {
   int k = 0;
   while (k + 1 < a.n_parts && R >= a.first[k + 1]) ++k;
   r = R - a.first[k];

@@ -34,6 +34,7 @@
 #include "mlp_eval.h"
 #include "neumf_draw.h"
 #include "neumf_train.h"
+#include "neumf_triples.h"
 #include "nll.h"
 #include "nmf.h"
 #include "rank.h"
@@ -207,6 +208,9 @@ enum Scratch {
   // sdrm_csr_transpose / sdrm_csr_vstack (csrc/csr_transpose.h), 8-byte words: [checked | total | bit table | colptr int64 | offsets uint32 |
   // column counts uint32] and [total | indptr int64 | row lengths uint32]
   SCR_CSRT_WS, SCR_STACK_WS,
+  // sdrm_neumf_triples (csrc/neumf_triples.h), 8-byte words, cleared on the stream by every call: [total | row bases int64 [rows + 1], twice
+  // (k_csr_scan writes two copies) | row lengths uint32]
+  SCR_TRIPLE_WS,
   // sdrm_nmf_fit (csrc/nmf.h), float64: [the fit's state (2) | Gram partials [NMF_PARTS][16][16] | the product [max(m, n)][16] | violation
   // partials of the W half, of the H half]; sdrm_nmf_init, float64: [mean, sigma [16] (32) | norm partials of U, of V [NMF_PARTS][2][16] each
   // | V^T [n][16] | X V^T [m][16]]
@@ -317,7 +321,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_MLP_FWD, PC_MLP_BWD, PC_MLP_W1, PC_MLP_FOLD, PC_MLP_EVAL, PC_NEUMF_DRAW_SPLIT, PC_NEUMF_DRAW_SCAN, PC_NEUMF_DRAW_NEG, PC_NEUMF_DRAW_OUT, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_MLP_FWD, PC_MLP_BWD, PC_MLP_W1, PC_MLP_FOLD, PC_MLP_EVAL, PC_NEUMF_DRAW_SPLIT, PC_NEUMF_DRAW_SCAN, PC_NEUMF_DRAW_NEG, PC_NEUMF_DRAW_OUT, PC_NEUMF_TRIPLES, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -367,7 +371,8 @@ static const char* kProfNames[PC_COUNT] = {
     "neumf epoch draw: k_draw_split the hold-out rows gathered through the keyed Feistel permutation and `present` marked; the source places, label-0 mask words and work-group counts of the other rows",
     "neumf epoch draw: k_draw_scan exclusive scan of the work-groups' label-0 counts with a carry, n_pos, n_neg and m (one work-group)",
     "neumf epoch draw: k_draw_neg the source places of the label-0 rows in ascending order, from the mask words and the scanned offsets",
-    "neumf epoch draw: k_draw_out the shuffled rows gathered through the second permutation, the extra rows' Philox draws among the label-0 rows"};
+    "neumf epoch draw: k_draw_out the shuffled rows gathered through the second permutation, the extra rows' Philox draws among the label-0 rows",
+    "neumf triples: k_triple_counts / k_csr_scan / k_triple_fill checked row lengths, the rows' bases, and the (user, item, label) records of up to 8 CSR parts with item_present and the four counts"};
 
 namespace {
 
@@ -3824,6 +3829,74 @@ int sdrm_csr_vstack(sdrm_engine* e, const sdrm_csr_part* parts, int n_parts, int
     SDRM_LAUNCH(e, k_stack_counts, dim3(waves), dim3(256), 0, st, a);
     SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)a.cnt, rows, own, indptr_out, reinterpret_cast<int64_t*>(ws));
     SDRM_LAUNCH(e, k_stack_copy, dim3(waves), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }));
+}
+
+// ---------------------------------------------------------------------------------------------
+// The NeuMF evaluator's triples from device CSR parts (main.py:218-283), csrc/neumf_triples.h.
+
+// The host side that needs no device: everything sdrm_neumf_triples refuses but the handle and the two output pointers.
+int sdrm_debug_neumf_triples_args(const sdrm_triple_part* parts, int n_parts, int n_items, int64_t capacity_out) {
+  if (!parts) return SDRM_ERR_ARG;
+  if (n_parts < 1 || n_parts > CSR_STACK_MAX) return SDRM_ERR_SHAPE;
+  if (n_items < 1 || n_items > CSRT_MAX_DIM) return SDRM_ERR_SHAPE;
+  int64_t rows = 0, cap = 0;
+  for (int k = 0; k < n_parts; ++k) {
+    const sdrm_triple_part& p = parts[k];
+    if (p.n_rows < 0 || p.n_rows > CSRT_MAX_DIM || p.capacity < 0 || p.capacity > TRIPLE_MAX_OUT) return SDRM_ERR_SHAPE;
+    if (!p.indptr || (!p.indices && p.capacity > 0)) return SDRM_ERR_ARG;
+    if (p.label != 0 && p.label != 1) return SDRM_ERR_SHAPE;
+    if (p.user0 < 0 || (int64_t)p.user0 + p.n_rows > (int64_t)0x7fffffff) return SDRM_ERR_SHAPE;
+    rows += p.n_rows; cap += p.capacity;
+  }
+  if (rows < 1 || rows > CSRT_MAX_DIM) return SDRM_ERR_SHAPE;
+  if (capacity_out < cap || capacity_out > TRIPLE_MAX_OUT) return SDRM_ERR_SHAPE;
+  return SDRM_OK;
+}
+
+int sdrm_neumf_triples(sdrm_engine* e, const sdrm_triple_part* parts, int n_parts, int n_items, int32_t* triples_out, int64_t capacity_out,
+                       uint8_t* item_present, int64_t* counts_dev, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!parts || !triples_out || !counts_dev) return fail(e, SDRM_ERR_ARG, "sdrm_neumf_triples: null pointer");
+  if (int rc = sdrm_debug_neumf_triples_args(parts, n_parts, n_items, capacity_out))
+    return fail(e, rc, rc == SDRM_ERR_ARG ? "sdrm_neumf_triples: a part without indptr, or without indices and capacity > 0"
+                                          : "sdrm_neumf_triples: n_parts outside 1 .. 8, n_items or total rows outside 1 .. 2^22, a label outside {0, 1}, user0 < 0 or "
+                                            "user0 + n_rows above 2^31 - 1, a part's n_rows or capacity out of range, or capacity_out below the sum of the "
+                                            "parts' capacities or above 2^30");
+  TripleArgs a{};
+  int64_t rows = 0;
+  for (int k = 0; k < n_parts; ++k) {
+    const sdrm_triple_part& p = parts[k];
+    a.part[k] = TriplePart{p.indptr, p.indices, p.n_rows, p.capacity, p.user0, p.label};
+    a.first[k] = rows;
+    rows += p.n_rows;
+  }
+  for (int k = n_parts; k <= CSR_STACK_MAX; ++k) a.first[k] = rows;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t off_base = 1, off_copy = off_base + (size_t)rows + 1, off_cnt = off_copy + (size_t)rows + 1, words = off_cnt + ((size_t)rows + 1) / 2;
+  uint64_t* ws;
+  if (int rc = scratch(e, SCR_TRIPLE_WS, words, &ws)) return rc;
+  int64_t* base = reinterpret_cast<int64_t*>(ws + off_base);
+  a.n_parts = n_parts; a.n_items = n_items;
+  a.cnt = reinterpret_cast<uint32_t*>(ws + off_cnt);
+  a.base = base;
+  a.out = triples_out; a.capacity_out = capacity_out;
+  a.present = item_present;
+  a.counts = reinterpret_cast<unsigned long long*>(counts_dev);
+  a.flag = e->feed_flag;
+  const unsigned waves = (unsigned)std::min<int64_t>((rows + 3) / 4, 1 << 16);
+  const unsigned groups = (unsigned)((rows + TRIPLE_ROWS - 1) / TRIPLE_ROWS);   // (at most 2^18)
+  return hip_rc(e, "k_triple_fill", profiled(e, PC_NEUMF_TRIPLES, 0.0, st, [&] {
+    // the scratch, the counts and the item bytes are this call's own, made anew on the stream every time
+    hipError_t rc = hipMemsetAsync(ws, 0, words * sizeof(uint64_t), st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(counts_dev, 0, 4 * sizeof(int64_t), st);
+    if (rc == hipSuccess && item_present) rc = hipMemsetAsync(item_present, 0, (size_t)n_items, st);
+    if (rc != hipSuccess) return rc;
+    SDRM_LAUNCH(e, k_triple_counts, dim3(waves), dim3(256), 0, st, a);
+    SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)a.cnt, rows, base, reinterpret_cast<int64_t*>(ws + off_copy),
+                reinterpret_cast<int64_t*>(ws));
+    SDRM_LAUNCH(e, k_triple_fill, dim3(groups), dim3(256), 0, st, a);
     return hipGetLastError();
   }));
 }

@@ -1442,6 +1442,58 @@ class Engine:
         n_pos, n_neg, m = (int(c) for c in counts)
         return hold, buf[:m], (n_pos, n_neg, m), present
 
+    # ------------------------------------------------------------------ NeuMF evaluator's triples from CSR parts (csrc/neumf_triples.h)
+    NEUMF_TRIPLES_MAX = 2 ** 30   # rows of the triple buffer: neumf_epoch_draw's bound on n
+
+    def neumf_triples(self, parts, n_items, out=None, present=True, check=True):
+        """main.py:218-283's frames and `concat` on the device (sdrm_neumf_triples): the (user, item, label) triples of up to 8 device CSR
+        parts, in the order include/sdrm_hip.h defines - parts as given, rows ascending, entries in their stored order, dense.  `parts`: a
+        list of (device CSR tuple as `equal_sparsity_csr` / `csr_to_device` / `holdout_split` return, user0, label): row r of the part is
+        user user0 + r, label is 0 or 1; only the pattern is read, values are ignored.  `n_items`: the width every part is held to.
+        Returns (triples, counts, item_present): triples the int32 view [m, 3] of `out` or of a fresh buffer with the summed capacities
+        as rows - what `neumf_epoch_draw` takes; counts the Python tuple (m, label-1 triples, max user + 1, max item + 1), the ONE
+        readback, 32 bytes, which also sizes the view; item_present a uint8 device tensor [n_items], 1 for every item that occurs (None
+        with `present=False`).  `out`: a contiguous int32 device tensor [>= summed capacities, 3] to fill; rows behind m keep what they
+        held.  A row with a bad indptr pair or a column outside [0, n_items) is EMPTY in the output and raises the feed status word
+        (`check` as in `csr_rows_to_dense`)."""
+        who = "neumf_triples"
+        parts = list(parts)
+        if not 1 <= len(parts) <= self.CSR_STACK_MAX:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {len(parts)} parts, outside 1 .. {self.CSR_STACK_MAX}")
+        n_items = int(n_items)
+        arrays = []
+        for i, p in enumerate(parts):
+            if not isinstance(p, (tuple, list)) or len(p) != 3:
+                raise SdrmError(f"{who}: part {i} must be (device CSR tuple, user0, label)")
+            indptr, indices, _, n_rows, n_cols, cap = self._csr_arrays(who, f"part {i}", p[0])
+            user0, label = int(p[1]), int(p[2])
+            if n_cols > n_items:
+                raise SdrmError(f"{who}: SDRM_ERR_SHAPE: part {i} has {n_cols} columns, n_items is {n_items}")
+            if label not in (0, 1) or user0 < 0 or user0 + n_rows > 2 ** 31 - 1:
+                raise SdrmError(f"{who}: SDRM_ERR_SHAPE: part {i}: label {label} outside {{0, 1}}, or users {user0} .. {user0 + n_rows - 1} outside int32")
+            arrays.append((indptr, indices, n_rows, cap, user0, label))
+        rows, capacity = sum(a[2] for a in arrays), sum(a[3] for a in arrays)
+        if not (1 <= rows <= 2 ** 22 and 1 <= n_items <= 2 ** 22) or capacity > self.NEUMF_TRIPLES_MAX:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {rows} rows or {n_items} items outside 1 .. 2^22, or {capacity} entries above 2^30")
+        if out is None:
+            out = torch.empty(max(capacity, 1), 3, dtype=torch.int32, device=self.device)
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.device != self.device or not out.is_contiguous() or out.dim() != 2
+                or out.shape[1] != 3 or not max(capacity, 1) <= out.shape[0] <= self.NEUMF_TRIPLES_MAX):
+            raise SdrmError(f"{who}: out must be a contiguous int32 tensor [{max(capacity, 1)} .. 2^30, 3] on the engine's device")
+        item_present = torch.empty(n_items, dtype=torch.uint8, device=self.device) if present else None
+        counts_dev = torch.empty(4, dtype=torch.int64, device=self.device)
+        desc = (_lib.TriplePart * len(arrays))()
+        for d, (ip, ix, n_rows, cap, user0, label) in zip(desc, arrays):
+            d.indptr, d.indices = ip.data_ptr(), ix.data_ptr() if cap else None   # (an empty tensor has no address; the ABI takes null with capacity 0)
+            d.n_rows, d.capacity, d.user0, d.label = n_rows, cap, user0, label
+        self._check(self.lib.sdrm_neumf_triples(self._h, desc, len(arrays), n_items, _ptr(out), int(out.shape[0]), _ptr(item_present), _ptr(counts_dev),
+                                                _stream()), "sdrm_neumf_triples")
+        self._feed_keep = arrays
+        counts = tuple(int(c) for c in counts_dev.cpu().tolist())
+        if check:
+            self.feed_status()
+        return out[:counts[0]], counts, item_present
+
     # ------------------------------------------------------------------ MLP evaluator's train steps (csrc/mlp_train.h)
     MLP_TENSORS = ("mf_embedding_user", "layer1/kernel", "layer1/bias", "layer2/kernel", "layer2/bias", "layer3/kernel", "layer3/bias",
                    "prediction/kernel", "prediction/bias")

@@ -7,6 +7,9 @@ CSR matrices through Python dicts, densifies them and ranks.  Here that evaluati
 validation loss.  The train loop is PyTorch by default; with `device_train=True` an epoch's batch loop is ONE `Engine.neumf_train_steps`
 call (csrc/neumf_train.h: forward with dropout, loss, backward and Adam on the device), and with `device_draw=True` on top the epoch's
 split, negatives and shuffle are ONE `Engine.neumf_epoch_draw` call on triples uploaded once (csrc/neumf_draw.h).  With `engine=None` the same functions run torch and numpy on the host - the checker.
+The triples themselves - main.py:218-283's frames of a synthetic matrix's two tails and the split validation users - are stated once in
+`synthetic_parts_host` / `assemble_triples`; `compute_neuralcf_results_synthetic` assembles them on the device instead, from CSR parts that
+never leave it (`Engine.neumf_triples`, csrc/neumf_triples.h), and is what `pipeline.evaluate_synthetic` calls for hp["evaluator"] == "neumf".
 
 Triples are a numpy int array [n, 3] (user, item, label); a (user, item) pair occurs at most once per array.  Labels are taken as
 binary (> 0), which is what the reference feeds its evaluators.  No pandas, no sklearn."""
@@ -115,6 +118,33 @@ class RankingProblem:
         m.sort_indices()
         return ids, m.indptr.astype(np.int64), m.indices
 
+    @classmethod
+    def from_parts(cls, parts, cols, heldout):
+        """The object `RankingProblem(assemble_triples(parts)[0], heldout)` builds, array for array, from the parts' CSR patterns and
+        `cols` - the ascending list of the item ids that occur in them (`flatnonzero` of `Engine.neumf_triples`' item_present) - without
+        a triple array: a part's rows land at its user ids, a (user, item) pair that several parts hold is merged as `sum_duplicates`
+        merges it.  `parts`: (scipy CSR pattern, user0, label) as `synthetic_parts_host` returns them."""
+        self = cls.__new__(cls)
+        self.cols = np.asarray(cols, dtype=np.int64)
+        heldout = _as_triples(heldout, "heldout")
+        self._relevant = self._rows(heldout[heldout[:, 2] > 0])
+        top = max([int(user0) + m.shape[0] for m, user0, _ in parts] + [1])
+        seen = csr_matrix((top, self.cols.shape[0]), dtype=np.float32)
+        for m, user0, _ in parts:
+            m = csr_matrix(m)
+            m.sort_indices()
+            counts = np.diff(m.indptr)
+            keep = np.isin(m.indices, self.cols)
+            r = np.repeat(np.arange(m.shape[0], dtype=np.int64) + int(user0), counts)[keep]
+            c = np.searchsorted(self.cols, m.indices[keep])
+            seen = seen + csr_matrix((np.ones(r.shape[0], dtype=np.float32), (r, c)), shape=seen.shape)
+        seen.sum_duplicates()
+        seen.sort_indices()
+        ids = np.flatnonzero(np.diff(seen.indptr)).astype(np.int64)
+        indptr = np.concatenate([[0], np.cumsum(np.diff(seen.indptr)[ids])]).astype(np.int64)
+        self._seen = (ids, indptr, seen.indices)
+        return self
+
     def _select(self, rows, users):
         ids, indptr, indices = rows
         start = length = np.zeros(users.shape[0], dtype=np.int64)
@@ -129,6 +159,56 @@ class RankingProblem:
     def select(self, users):
         users = np.unique(np.asarray(users, dtype=np.int64))
         return users, self.cols, self._select(self._relevant, users), self._select(self._seen, users)
+
+
+def synthetic_parts_host(train_shape, valid, ones, zeros):
+    """What main.py:218-283 hands to `compute_neuralcf_results` for ONE synthetic matrix in its non-augmented branch
+    (`args.augment_training_data` false, `data = equal_sparsity_valid_train`, :279-280 - the branch the `mlp` route takes too), as
+    (parts, validation): `parts` a list of (scipy CSR pattern, user0, label) whose triples - `assemble_triples(parts)` - are the training
+    frame, `validation` the int64 [n, 3] validation triples.
+      * `zeros`, the lower tail `raw <= quantile(raw, 1 - sparsity)` (:259-262, :270): label 0, user = row with NO offset - :275 builds the
+        training frame before :277 adds TRAIN_DATA.shape[0] + VALID_DATA.shape[0] to the users, and that is kept;
+      * `ones`, the upper tail `raw >= quantile(raw, sparsity)` (:258-261, :267): label 1, user = row;
+      * valid_train, valid_test = `metrics.split_train_test_proportion_from_csr_matrix(valid.copy(), batch_size=10, random_seed=123,
+        ignore_zeros=True)` (:226-228; it renumbers the users it keeps, those with two entries or more): valid_train's entries get label 1
+        and user = row + train_shape[0] (:230-233); the validation triples are valid_test's entries, row-major, the same offset, label 1
+        (:235-237).
+    The parts come in the order zeros, ones, valid_train (:273-275).  NOT reproduced, on purpose:
+      * the reference shuffles the frames with a fixed pandas seed (`sample(frac=1, random_state=123)`, :240, :246, :273, :275): every
+        consumer here shuffles per epoch, so the order is `assemble_triples`' and no pandas draw is made;
+      * the halves of the "stored zeros of VALID_DATA" (:240-249) are empty for every dataset the project loads (binarised CSR matrices
+        store no zero); a `valid` with a stored value other than 1 is refused rather than guessed at;
+      * the augmented branch (:251-254 `train_data[~train_data.isin(valid_data)]`, :278) is not built;
+      * the reference's M arm thresholds F_SDRM once more (:287-291), so its "M" figure is F's: here each tag evaluates its own matrix."""
+    from . import metrics
+    valid = csr_matrix(valid)
+    if valid.nnz and np.any(valid.data != 1):
+        raise ValueError("synthetic_parts_host: `valid` stores a value other than 1; main.py:242 would send its stored zeros, shuffled by pandas, "
+                         "into both frames, which is not reproduced")
+    valid_train, valid_test = metrics.split_train_test_proportion_from_csr_matrix(valid.copy(), batch_size=10, random_seed=123, ignore_zeros=True)
+    offset = int(train_shape[0])
+
+    def pattern(m):
+        m = csr_matrix(m)
+        m.sort_indices()
+        return m
+    valid_test = pattern(valid_test)
+    users = np.repeat(np.arange(valid_test.shape[0], dtype=np.int64), np.diff(valid_test.indptr)) + offset
+    validation = np.stack([users, valid_test.indices.astype(np.int64), np.ones(users.shape[0], dtype=np.int64)], axis=1)
+    return [(pattern(zeros), 0, 0), (pattern(ones), 0, 1), (pattern(valid_train), offset, 1)], validation
+
+
+def assemble_triples(parts):
+    """The host form of sdrm_neumf_triples' order (include/sdrm_hip.h): (triples int64 [m, 3], (n_users, n_items)) of (scipy CSR pattern,
+    user0, label) parts - the parts in the order given, rows ascending, a row's entries in their stored order; n_users = max user + 1 and
+    n_items = max item + 1 over the triples, as main.py:283 takes them (0, 0 without a triple)."""
+    out = []
+    for m, user0, label in parts:
+        users = np.repeat(np.arange(m.shape[0], dtype=np.int64), np.diff(m.indptr)) + int(user0)
+        out.append(np.stack([users, m.indices[m.indptr[0]:m.indptr[-1]].astype(np.int64), np.full(users.shape[0], int(label), dtype=np.int64)], axis=1))
+    triples = np.concatenate(out) if out else np.zeros((0, 3), dtype=np.int64)
+    dims = (int(triples[:, 0].max()) + 1, int(triples[:, 1].max()) + 1) if triples.shape[0] else (0, 0)
+    return triples, dims
 
 
 def _idcg_table():
@@ -276,7 +356,30 @@ def compute_neuralcf_results(training, validation, n_users, n_items, engine=None
     `history`: a dict that receives 'valid_loss' (per epoch), 'recall10' (per epoch, with eval_recall), 'best_epoch' (the epoch whose
     weights ranked), 'reference_has_no_checkpoint', 'best_recall_epoch', 'epochs_run', 'per_user' (the final per-user recall / ndcg)
     and 'model' (the module that ranked)."""
-    training, validation = _as_triples(training, "training"), _as_triples(validation, "validation")
+    return compute_neuralcf_results_resident(training, validation, n_users, n_items, engine=engine, seed=seed, epochs=epochs, eval_recall=eval_recall,
+                                             device=device, history=history, device_train=device_train, device_draw=device_draw)
+
+
+def compute_neuralcf_results_resident(training, validation, n_users, n_items, engine=None, seed=0, epochs=20, eval_recall=True, device=None,
+                                      history=None, device_train=False, device_draw=False, training_dev=None, problem=None):
+    """`compute_neuralcf_results` - its body: that function is this one with the last two arguments left out, and everything its docstring
+    says holds here - with two more keyword arguments for a caller whose training triples are on the device already.
+    `training_dev` and `problem` (both None by default; either one needs `device_draw=True` and raises ValueError without it, and they come together): the training triples
+    as an int32 tensor [n, 3] already on the engine's device - `Engine.neumf_triples`' view - used in place of the cast and upload, and a
+    `RankingProblem` of the same triples (`RankingProblem.from_parts`) used in place of `RankingProblem(training, validation)`.
+    `training` may then be None: nothing else reads it, and the hold-out size comes from `training_dev.shape[0]`.
+    They are their own function because `compute_neuralcf_results`' parameter list is pinned by tests/test_neumf_epoch_draw_host.py."""
+    if (training_dev is not None or problem is not None) and not device_draw:
+        raise ValueError("compute_neuralcf_results_resident: training_dev and problem stand in for the upload and the ranking problem of device_draw=True; "
+                         "without it the host draws from `training`")
+    resident = training_dev is not None and problem is not None
+    if (training_dev is None) != (problem is None):
+        raise ValueError("compute_neuralcf_results_resident: training_dev and problem come together (the ranking problem of the device triples)")
+    if training is None and not resident:
+        raise ValueError("compute_neuralcf_results: training is None; only training_dev with problem (device_draw=True) can stand in for it")
+    validation = _as_triples(validation, "validation")
+    if training is not None:
+        training = _as_triples(training, "training")
     if device_draw and (engine is None or not device_train):
         raise ValueError("compute_neuralcf_results: device_draw=True needs device_train=True and an engine (the draw fills device buffers that the "
                          "device train step reads in place; there is no host form)")
@@ -298,13 +401,16 @@ def compute_neuralcf_results(training, validation, n_users, n_items, engine=None
     best_loss, best_epoch, best_recall, best_recall_epoch, early_stop = math.inf, 0, 0.0, None, 0
     kept = {0: None}
     valid_losses, recalls, epochs_run = [], [], 0
-    n_hold = int(math.ceil(0.2 * training.shape[0]))          # sklearn's train_test_split(test_size=0.2): ceil for the test part
-    problem = RankingProblem(training, validation)
+    n_train = int(training_dev.shape[0]) if resident else training.shape[0]
+    n_hold = int(math.ceil(0.2 * n_train))                    # sklearn's train_test_split(test_size=0.2): ceil for the test part
+    if not resident:
+        problem = RankingProblem(training, validation)
     draw_counts = []
     if device_draw:
-        training_dev = torch.from_numpy(np.ascontiguousarray(training, dtype=np.int32)).to(device)
+        if not resident:
+            training_dev = torch.from_numpy(np.ascontiguousarray(training, dtype=np.int32)).to(device)
         draw_bufs = (torch.empty(n_hold, 3, dtype=torch.int32, device=device),
-                     torch.empty(2 * (training.shape[0] - n_hold), 3, dtype=torch.int32, device=device))
+                     torch.empty(2 * (n_train - n_hold), 3, dtype=torch.int32, device=device))
     for epoch in range(epochs):
         epochs_run += 1
         model.train()
@@ -376,3 +482,37 @@ def compute_neuralcf_results(training, validation, n_users, n_items, engine=None
     with np.errstate(invalid="ignore"):
         return (np.array([np.round(np.nanmean(rec[q]), 4) for q in range(len(K_LIST))]),
                 np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
+
+
+def compute_neuralcf_results_synthetic(train_shape, valid, raw, sparsity, engine, seed=0, epochs=20, eval_recall=True, history=None):
+    """main.py's NeuMF arm for ONE synthetic matrix `raw` (dense scores, on the engine's device or the host; main.py:256-283, the
+    non-augmented branch - see `synthetic_parts_host` for what is kept and what is not) with the training triples ASSEMBLED ON THE
+    DEVICE: both tails come from `Engine.equal_sparsity_csr` and stay resident, the validation users' training half
+    (`synthetic_parts_host`'s split, a few hundred users) is uploaded with `csr_to_device`, ONE `Engine.neumf_triples` call writes the
+    triples into the buffer `neumf_epoch_draw` reads, and `compute_neuralcf_results_resident(None, validation, n_users, n_items, engine,
+    device_train=True, device_draw=True, training_dev=..., problem=...)` trains and ranks; n_users and n_items are the call's counts
+    (max user + 1, max item + 1: main.py:283).  Neither the dense 0/1 matrix nor the triples cross to the host.  What does cross: 32 bytes
+    of counts, n_items bytes of `item_present` (the ranking's columns) and, once, the two tails' indptr / indices, from which
+    `RankingProblem.from_parts` builds the host-side ranking problem - a device-resident ranking problem is not built."""
+    if engine is None:
+        raise ValueError("compute_neuralcf_results_synthetic: needs an engine (the host form is compute_neuralcf_results on "
+                         "assemble_triples(synthetic_parts_host(...)))")
+    n_items = int(raw.shape[1])
+    ones_dev = engine.equal_sparsity_csr(raw, float(sparsity), side=">=")
+    zeros_dev = engine.equal_sparsity_csr(raw, 1.0 - float(sparsity), side="<=")
+    empty = csr_matrix((int(raw.shape[0]), n_items), dtype=np.float32)
+    parts, validation = synthetic_parts_host(train_shape, valid, empty, empty)   # (the split and the validation triples; the tails stay on the device)
+    valid_train, offset, _ = parts[2]
+    device_parts = [(zeros_dev, 0, 0), (ones_dev, 0, 1)]
+    if valid_train.shape[0]:
+        device_parts.append((engine.csr_to_device(valid_train), offset, 1))
+    training_dev, counts, item_present = engine.neumf_triples(device_parts, n_items)
+
+    def host_pattern(dev):
+        indptr, indices, shape = dev
+        indptr, indices = indptr.cpu().numpy(), indices.cpu().numpy()
+        return csr_matrix((np.ones(indices.shape[0], dtype=np.float32), indices, indptr), shape=shape)
+    host_parts = [(host_pattern(zeros_dev), 0, 0), (host_pattern(ones_dev), 0, 1), (valid_train, offset, 1)]
+    problem = RankingProblem.from_parts(host_parts, np.flatnonzero(item_present.cpu().numpy()), validation)
+    return compute_neuralcf_results_resident(None, validation, counts[2], counts[3], engine=engine, seed=seed, epochs=epochs, eval_recall=eval_recall,
+                                             history=history, device_train=True, device_draw=True, training_dev=training_dev, problem=problem)

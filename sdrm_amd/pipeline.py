@@ -20,6 +20,7 @@ from scipy.sparse import csr_matrix, issparse, vstack
 
 from . import metrics
 from .mlp_eval import compute_mlp_results_device
+from .neumf import compute_neuralcf_results_synthetic
 
 K_LIST = (1, 3, 5, 10, 20, 50)
 
@@ -228,13 +229,19 @@ def evaluate_synthetic(train, valid, raw, sparsity, engine, hp, seed):
     """The downstream evaluation of ONE synthetic matrix `raw` (dense scores on the engine's device, binarised here to the training
     data's sparsity): the evaluator `hp` chooses, called as `run_experiment` always called it.  `hp["evaluator"] == "mlp"` is the
     reference's `main.py --model mlp` route (main.py:197-214) without augmentation: `compute_mlp_results_device` on the binarised matrix with the
-    train epochs, the per-epoch validation RMSE and the final scores on the device (`hp["mlp_epochs"]`, 200 when absent).  Without the
+    train epochs, the per-epoch validation RMSE and the final scores on the device (`hp["mlp_epochs"]`, 200 when absent).
+    `hp["evaluator"] == "neumf"` is the `--model neumf` route (main.py:218-283, non-augmented): `neumf.compute_neuralcf_results_synthetic`,
+    which takes both tails of `raw` on the device, assembles the training triples there (`Engine.neumf_triples`) and trains and ranks NeuMF
+    on the device (`hp["neumf_epochs"]`, 20 when absent; `hp["neumf_eval_recall"]`, True when absent, as main.py:283 calls it).  Without the
     key: `hp["resident_svd"]`, `hp["device_svd"]`, `hp["sparse_synthetic"]` and `hp["nmf"]` as `run_experiment` documents them."""
     binarise = equal_sparsity_csr if hp.get("sparse_synthetic", False) else equal_sparsity   # opt-in: CSR made on the device
     if hp.get("evaluator") == "mlp":
         return compute_mlp_results_device(binarise(raw, sparsity, engine), valid, engine, device_train=True, seed=seed, epochs=hp.get("mlp_epochs", 200))
+    if hp.get("evaluator") == "neumf":
+        return compute_neuralcf_results_synthetic(train.shape, valid, raw, sparsity, engine, seed=seed, epochs=hp.get("neumf_epochs", 20),
+                                                  eval_recall=hp.get("neumf_eval_recall", True))
     if hp.get("evaluator") is not None:
-        raise ValueError(f"evaluate_synthetic: hp['evaluator'] = {hp['evaluator']!r}; 'mlp' is the one evaluator the key selects")
+        raise ValueError(f"evaluate_synthetic: hp['evaluator'] = {hp['evaluator']!r}; 'mlp' and 'neumf' are the evaluators the key selects")
     nmf = {"nnmf": True} if hp.get("nmf", False) else {}   # opt-in, the two device routes only: the NMF evaluator in the SVD's place (csrc/nmf.h)
     if hp.get("resident_svd", False):   # opt-in: the CSR made on the device stays there, stacked and transposed on the device (csrc/csr_transpose.h)
         return compute_mf_results_resident(train, valid, engine.equal_sparsity_csr(raw, sparsity), engine, only_synthetic=True, seed=seed, **nmf)
@@ -255,7 +262,8 @@ def run_experiment(split, hp, seed, vae_dir, verbose=False):
     three evaluations to `compute_mf_results_device` instead of `compute_mf_results`; nothing of it reaches `train_SDRM`.  `hp["resident_svd"]` (False when absent) binarises with
     `Engine.equal_sparsity_csr` and hands the device tuple to `compute_mf_results_resident`: no host copy of the synthetic matrix.
     `hp["nmf"]` (False when absent) makes those two device routes evaluate with `nnmf=True`, the reference's NMF of 15 components.
-    `hp["evaluator"] == "mlp"` sends them to the MLP evaluator on the device instead (`evaluate_synthetic`, which makes the choice per tag)."""
+    `hp["evaluator"] == "mlp"` sends them to the MLP evaluator on the device instead, `hp["evaluator"] == "neumf"` to NeuMF with its training
+    triples assembled on the device (`evaluate_synthetic`, which makes the choice per tag and documents their keys)."""
     from . import train_SDRM as ts
     train, train_partial, valid = split
     n_users, n_items = train.shape
