@@ -365,6 +365,49 @@ typedef struct sdrm_triple_part {
 int sdrm_neumf_triples(sdrm_engine* e, const sdrm_triple_part* parts, int n_parts, int n_items, int32_t* triples_out, int64_t capacity_out,
                        uint8_t* item_present, int64_t* counts_dev, void* hip_stream);
 
+/* The NeuMF evaluator's ranking problem, built on the device from the parts sdrm_neumf_triples read (reference:
+ * neural_cf_benchmark_pt.py:294-326, the testing block: the two merges in pandas and the two CSR matrices rebuilt through Python dicts;
+ * here what sdrm_amd/neumf.py's RankingProblem.from_parts builds on the host with scipy - one csr + csr per part, np.isin, searchsorted,
+ * sum_duplicates, sort_indices; csrc/neumf_rank.h; restated in tests/neumf_rank_ref.py).  parts / n_parts / n_items: as sdrm_neumf_triples
+ * takes them, only the PATTERN is read.  item_present: DEVICE uint8 [n_items], the bytes that call wrote (any non-zero byte counts).
+ * heldout: DEVICE int32 [n_heldout][3] (user, item, label), null only with n_heldout 0.  n_rows: the number of user ids.
+ * The outputs, which are the definition:
+ *   cols_out [capacity_cols >= n_items]: the item ids i with item_present[i] != 0, ascending, C of them; col_of[i] is the place of i in
+ *     it, -1 for an absent item.  Elements C .. are left as they were.
+ *   seen: a canonical CSR [n_rows, C], int64 indptr [n_rows + 1] from 0, int32 indices, no data; ROWS ARE DENSE BY USER ID, row u is user u:
+ *     the ascending, duplicate-free union, over every part p with user0_p <= u < user0_p + n_rows_p, of col_of[] of the present items of
+ *     that part's row u - user0_p, whatever the part's label.  A user no part covers has an empty row.  capacity_seen is at least the sum
+ *     of the parts' capacities; elements behind indptr[n_rows] are left as they were.
+ *   relevant: the same form from the held-out triples with label > 0 whose item is present, duplicates merged; capacity_relevant is at
+ *     least n_heldout.  A triple, whatever its label, whose user is outside [0, n_rows) is dropped and raises the row bit of the status
+ *     word sdrm_feed_status reports, one whose item is outside [0, n_items) is dropped and raises the column bit; a triple whose item is
+ *     in range but absent is dropped silently, as the reference drops a held-out item that never occurs in training.
+ * Part rows are checked exactly as sdrm_neumf_triples checks them - an indptr pair that is negative, out of order, reaches behind its
+ *   part's capacity or spans more than n_items entries (sdrm_csr_vstack's indptr bit), a column outside [0, n_items) (the column bit) -
+ *   and an offending row contributes nothing.  A part row with entries whose user is n_rows or above contributes nothing and raises the
+ *   row bit.  Should part rows that share entries make seen longer than capacity_seen, the columns behind it are dropped, the count says
+ *   capacity_seen and the indptr bit is raised.  No load or store uses an unchecked index.
+ * counts_dev: DEVICE int64 [4], written by the call: C; seen's entries; relevant's entries; the held-out triples dropped for a range defect.
+ * Order: two memsets (the scratch - two bit tables of n_rows x ceil(n_items / 64) 64-bit words over raw item ids and 20 bytes per user
+ *   and 4 per item - and counts_dev) lead seven launches (six with n_heldout 0), all enqueued on `hip_stream` - the caller's stream, under the
+ *   contract of every `stream` argument of this header (Conventions); nothing is read back and nothing synchronises (except the device
+ *   synchronise when the grow-only scratch must grow).  64-bit integer atomic ORs into the cleared tables - one per run of a part row's
+ *   entries that fall into one word, one per held-out triple - and one integer add: the same bytes on every run.
+ * Refused before any launch, nothing written: SDRM_ERR_ARG for a null handle or pointer, a part with a null indptr, or with null indices
+ *   and capacity > 0; SDRM_ERR_SHAPE for n_parts outside 1 .. 8, n_items, n_rows or the parts' total rows outside 1 .. 2^22, one bit table
+ *   above 2^31 bytes, n_heldout outside 0 .. 2^30, a part as sdrm_neumf_triples refuses it (label, user0, n_rows, capacity), capacity_cols
+ *   below n_items, capacity_seen below the sum of the parts' capacities, capacity_relevant below n_heldout. */
+int sdrm_neumf_rank_problem(sdrm_engine* e, const sdrm_triple_part* parts, int n_parts, int n_items, const uint8_t* item_present,
+                            const int32_t* heldout, int64_t n_heldout, int64_t n_rows, int32_t* cols_out, int64_t capacity_cols,
+                            int64_t* seen_indptr, int32_t* seen_indices, int64_t capacity_seen, int64_t* relevant_indptr,
+                            int32_t* relevant_indices, int64_t capacity_relevant, int64_t* counts_dev, void* hip_stream);
+
+/* A ranking's users from a mask (reference: neural_cf_benchmark_pt.py:215-217, the users of the epoch's 20 %; here np.flatnonzero of the
+ * bytes sdrm_neumf_epoch_draw leaves in `present`, on the device): users_out [n_rows] receives the ids u with mask[u] != 0, ascending,
+ * U of them (elements U .. are left as they were), and count_dev, DEVICE int64 [1], receives U.  One launch of one work-group on
+ * `hip_stream` (the caller's stream, as above); nothing is read back.  SDRM_ERR_ARG: a null pointer; SDRM_ERR_SHAPE: n_rows outside 1 .. 2^22. */
+int sdrm_neumf_rank_users(sdrm_engine* e, const uint8_t* mask, int64_t n_rows, int32_t* users_out, int64_t* count_dev, void* hip_stream);
+
 /* The VAE decode hook on the device (reference: train_SDRM.py:212-214 `decoder = Linear(latent, hidden) -> Tanh ->
  * Linear(hidden, N_ITEMS)`, :252-254 `VAE.decode`, called by sample_ddpm at :49 / :61 on the sampled latents): two launches of
  * the engine's fp32 MFMA GEMM with the bias + tanh / bias epilogues.  The struct holds DEVICE pointers to the four nn.Linear
@@ -605,6 +648,26 @@ int sdrm_rank_metrics(sdrm_engine* e, const float* scores, int U, int I, const i
                       const int32_t* held_indices, const int64_t* train_indptr, const int32_t* train_indices,
                       const int32_t* ks_host, int nk, const double* tp, const double* idcg, double* recall, double* ndcg,
                       void* stream);
+/* sdrm_rank_metrics with a row map, for any caller whose score rows are a selection of the rows of two resident matrices (reference:
+ * the same utilities.py:116-171; for the NeuMF evaluator neural_cf_benchmark_pt.py:294-332, where sdrm_amd/neumf.py's rank_all_items
+ * selected the rows on the host, uploaded both selections and re-footed the NDCG there).  scores [U, I]; held_* / train_* are CSR index
+ * arrays over n_rows rows (int64 indptr [n_rows + 1], int32 columns, held_nnz / train_nnz the capacities of the index arrays) and score
+ * row q ranks against CSR row rows[q] of both (rows: DEVICE int32 [U], any order, repeats allowed).  Nothing is trusted: rows[q] outside
+ * [0, n_rows) is an empty row and raises the row bit of the status word sdrm_feed_status reports; an indptr pair that is out of order or
+ * reaches outside [0, nnz] is an empty row (the indptr bit), an entry with a column outside [0, I) is skipped, a held one does not count
+ * as held (the column bit).  ks_host, tp, idcg, recall, ndcg, the bound I <= 36864, the k rules and the ties: sdrm_rank_metrics'.
+ * full_idcg == 0: sdrm_rank_metrics' NDCG, dcg / idcg[min(n_true, k)], nan without a held-out item.  full_idcg != 0: the NeuMF footing -
+ *   the reference's held-out matrix stores every pair of the cartesian product, so its ideal DCG counts min(I, k) items for every user
+ *   and a user without a relevant item has NDCG 0.  The device makes the three float64 operations rank_all_items made on the host, in
+ *   its order, so the bits are its bits: t = dcg / idcg[min(n_true, k)]; ndcg = n_true > 0 ? t * idcg[min(n_true, k)] / idcg[min(I, k)]
+ *   : 0.0 - not the shortcut dcg / idcg[min(I, k)].  Recall is the same either way: nan without a relevant item.
+ * One launch on `hip_stream` (the caller's stream, under the contract of every `stream` argument of this header); nothing is read back.
+ * SDRM_ERR_ARG: a null pointer (train_* may both be null), nk outside 1 .. 8, a k outside [1, min(128, I)]; SDRM_ERR_SHAPE: U < 1, I
+ * outside 1 .. 36864, n_rows < 1, a negative capacity. */
+int sdrm_rank_metrics_rows(sdrm_engine* e, const float* scores, int U, int I, const int32_t* rows, int64_t n_rows, const int64_t* held_indptr,
+                           const int32_t* held_indices, int64_t held_nnz, const int64_t* train_indptr, const int32_t* train_indices,
+                           int64_t train_nnz, const int32_t* ks_host, int nk, const double* tp, const double* idcg, double* recall, double* ndcg,
+                           int full_idcg, void* hip_stream);
 /* The evaluation half of a VAE pre-stage epoch on the device (reference: train_SDRM.py:160-177 with is_training == 0 and dropout
  * off), one call for all users of a hold-out split.  enc / dec are the eight LIVE nn.Linear tensors as nn.Linear stores them (their
  * n_items, hidden and latent must agree); train_* / held_* are the two CSR index pairs sdrm_holdout_split leaves (int64 indptr

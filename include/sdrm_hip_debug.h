@@ -247,6 +247,12 @@ int sdrm_debug_neumf_draw_args(int64_t n, int64_t n_hold, int64_t capacity, int 
  * compared with null only, never followed. */
 int sdrm_debug_neumf_triples_args(const sdrm_triple_part* parts, int n_parts, int n_items, int64_t capacity_out);
 
+/* The host side of sdrm_neumf_rank_problem that needs no device: SDRM_OK, SDRM_ERR_ARG (null parts, a part with a null indptr, or with
+ * null indices and capacity > 0) or SDRM_ERR_SHAPE for a call outside its envelope, as listed at sdrm_neumf_rank_problem.  The part's
+ * pointers are compared with null only, never followed. */
+int sdrm_debug_neumf_rank_args(const sdrm_triple_part* parts, int n_parts, int n_items, int64_t n_heldout, int64_t n_rows, int64_t capacity_cols,
+                               int64_t capacity_seen, int64_t capacity_relevant);
+
 /* The host side of sdrm_mlp_train_steps that needs no device: SDRM_OK, SDRM_ERR_SHAPE for a call outside its envelope (n_items outside
  * 1 .. 36864, n_users < 2, batch outside 1 .. 16, n outside 1 .. 2^31 - 1, step0 < 0, p_drop outside [0, 1) or not a number), or
  * SDRM_ERR_ARG: with_grads for more than one step (n > batch) and, when `addr` is given - the base addresses of p[9], m[9], v[9] and, with

@@ -149,6 +149,11 @@ SIGNATURES = {
     "sdrm_neumf_triples": (c_int, [c_void_p, C.POINTER(TriplePart), c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sdrm_rank_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sdrm_neumf_rank_problem": (c_int, [c_void_p, C.POINTER(TriplePart), c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+                                        c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sdrm_neumf_rank_users": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sdrm_rank_metrics_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                       c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "sdrm_svd_fit": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_uint64,
                              C.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sdrm_svd_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p,
@@ -185,6 +190,7 @@ SIGNATURES = {
     "sdrm_debug_neumf_train_args": (c_int, [c_int, c_int, c_int, c_int64, c_int, c_int64, c_float]),
     "sdrm_debug_neumf_draw_args": (c_int, [c_int64, c_int64, c_int64, c_int, c_int]),
     "sdrm_debug_neumf_triples_args": (c_int, [C.POINTER(TriplePart), c_int, c_int, c_int64]),
+    "sdrm_debug_neumf_rank_args": (c_int, [C.POINTER(TriplePart), c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_int64]),
     "sdrm_debug_mlp_train_args": (c_int, [c_int, c_int, c_int64, c_int, c_int64, c_float, c_int, C.POINTER(c_uint64), c_int]),
     "sdrm_debug_mlp_eval_args": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_int, C.POINTER(c_uint64), c_int]),
     "sdrm_debug_holdout_args": (c_int, [c_int, c_int64, c_int64, C.c_double, c_int64, C.POINTER(c_int64)]),

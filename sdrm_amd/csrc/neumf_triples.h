@@ -41,13 +41,15 @@ struct TripleArgs {
   unsigned* flag;                     // the handle's feed status word
 };
 
-__device__ __forceinline__ CsrBatch triple_batch(const TripleArgs& a, const TriplePart& pt) {
+template <class A>   // TripleArgs, or csrc/neumf_rank.h's RankProblemArgs: n_items and flag
+__device__ __forceinline__ CsrBatch triple_batch(const A& a, const TriplePart& pt) {
   return CsrBatch{pt.indptr, pt.indices, nullptr, nullptr, 0, pt.n_rows, 0, a.n_items, a.flag};
 }
 
 // Row r of a part, checked as sdrm_csr_vstack checks its rows: csr_row_span's pair, held to the part's capacity and to n_items entries.
 // `owner` as in csr_row_span (0: this thread reports).
-__device__ __forceinline__ CsrSpan triple_row_span(const TripleArgs& a, const TriplePart& pt, int64_t r, int owner) {
+template <class A>
+__device__ __forceinline__ CsrSpan triple_row_span(const A& a, const TriplePart& pt, int64_t r, int owner) {
   CsrSpan s = csr_row_span<FEED_STACK_PTR>(triple_batch(a, pt), (int)r, owner);
   if (s.p1 > pt.capacity || s.p1 - s.p0 > (int64_t)a.n_items) {
     if (owner == 0) atomicOr(a.flag, (unsigned)FEED_STACK_PTR);

@@ -57,9 +57,17 @@ __device__ inline double np_pairwise_sum(const double* a, int n) {
 // FEED_BAD_PTR / FEED_BAD_COL.  It writes the metrics whose pointer is not null.
 struct RankCheck { int64_t held_nnz, train_nnz; unsigned* flag; };
 
+// What the row-mapped form (k_rank_metrics_rows, csrc/neumf_rank.h) knows beside both: score row q ranks against CSR row rows[q] of both
+// matrices [n_rows, I] (an id outside [0, n_rows) is an empty row and raises FEED_BAD_ROW), and whether the NDCG goes on the NeuMF footing.
+struct RankRows { const int32_t* rows; int64_t n_rows; int full_idcg; };
+
 // One work-group, one user.  CHECKED == false is k_rank_metrics as it always was: `ck` is not looked at.
-template <bool CHECKED>
-__device__ __forceinline__ void rank_metrics_user(const RankArgs& a, const RankCheck& ck) {
+// ROWMAP: the CSR row of score row q is rm.rows[q], not q.  FOOTING: with rm.full_idcg the NDCG is put on the footing of
+// neural_cf_benchmark_pt.py's testing block (sdrm_amd/neumf.py: host_metrics), whose held-out matrix stores every pair of the cartesian
+// product - the ideal DCG counts min(I, k) items for every user, and a user without a relevant item has NDCG 0 - by the three float64
+// operations `rank_all_items` makes on the host, in its order: t = dcg / idcg[m]; t * idcg[m] / idcg[min(I, k)].  Recall is untouched.
+template <bool CHECKED, bool ROWMAP = false, bool FOOTING = false>
+__device__ __forceinline__ void rank_metrics_user(const RankArgs& a, const RankCheck& ck, const RankRows& rm = RankRows{}) {
   extern __shared__ float row[];            // [I] scores of this user, then the reduction scratch
   __shared__ int red[4];
   __shared__ double vec[RANK_MAX_K];        // hit * discount by rank
@@ -70,8 +78,14 @@ __device__ __forceinline__ void rank_metrics_user(const RankArgs& a, const RankC
   for (int r = tid; r < RANK_MAX_K; r += 256) hit[r] = 0;
   __syncthreads();
   unsigned bad = 0;
+  int64_t cr = u;                           // the CSR row of both matrices; -1: none (an empty row)
+  if (ROWMAP) {
+    cr = rm.rows[u];
+    if (cr < 0 || cr >= rm.n_rows) { bad |= (unsigned)FEED_BAD_ROW; cr = -1; }
+  }
   if (a.train_indptr) {
-    int64_t t0 = a.train_indptr[u], t1 = a.train_indptr[u + 1];
+    int64_t t0 = 0, t1 = 0;
+    if (!ROWMAP || cr >= 0) { t0 = a.train_indptr[cr]; t1 = a.train_indptr[cr + 1]; }
     if (CHECKED && (t0 < 0 || t1 < t0 || t1 > ck.train_nnz)) { bad |= (unsigned)FEED_BAD_PTR; t0 = t1 = 0; }
     for (int64_t t = t0 + tid; t < t1; t += 256) {
       const int c = a.train_indices[t];
@@ -80,7 +94,8 @@ __device__ __forceinline__ void rank_metrics_user(const RankArgs& a, const RankC
     }
     __syncthreads();
   }
-  int64_t h0 = a.held_indptr[u], h1 = a.held_indptr[u + 1];
+  int64_t h0 = 0, h1 = 0;
+  if (!ROWMAP || cr >= 0) { h0 = a.held_indptr[cr]; h1 = a.held_indptr[cr + 1]; }
   if (CHECKED && (h0 < 0 || h1 < h0 || h1 > ck.held_nnz)) { bad |= (unsigned)FEED_BAD_PTR; h0 = h1 = 0; }
   int n_true = (int)(h1 - h0);
   for (int64_t h = h0; h < h1; ++h) {
@@ -113,7 +128,9 @@ __device__ __forceinline__ void rank_metrics_user(const RankArgs& a, const RankC
       const double dcg = np_pairwise_sum(vec, k);
       const int m = n_true < k ? n_true : k;
       if (!CHECKED || a.recall) a.recall[(size_t)q * a.U + u] = (double)hits / (double)m;          // 0/0 -> nan, like the reference
-      if (!CHECKED || a.ndcg) a.ndcg[(size_t)q * a.U + u] = dcg / a.idcg[m];                      // idcg[0] = 0 -> nan
+      double nd = dcg / a.idcg[m];                                                                 // idcg[0] = 0 -> nan
+      if (FOOTING && rm.full_idcg) nd = n_true > 0 ? nd * a.idcg[m] / a.idcg[a.I < k ? a.I : k] : 0.0;
+      if (!CHECKED || a.ndcg) a.ndcg[(size_t)q * a.U + u] = nd;
     }
   }
   if (CHECKED && bad) atomicOr(ck.flag, bad);

@@ -34,6 +34,7 @@
 #include "mlp_eval.h"
 #include "neumf_draw.h"
 #include "neumf_train.h"
+#include "neumf_rank.h"
 #include "neumf_triples.h"
 #include "nll.h"
 #include "nmf.h"
@@ -211,6 +212,10 @@ enum Scratch {
   // sdrm_neumf_triples (csrc/neumf_triples.h), 8-byte words, cleared on the stream by every call: [total | row bases int64 [rows + 1], twice
   // (k_csr_scan writes two copies) | row lengths uint32]
   SCR_TRIPLE_WS,
+  // sdrm_neumf_rank_problem (csrc/neumf_rank.h), 8-byte words, cleared on the stream by every call: [totals int64 [2] | bit table of seen,
+  // of relevant [n_rows][wpr] | row offsets int64 [n_rows + 1] of seen, of relevant (the scan's own copies) | row lengths uint32 [n_rows] of
+  // seen, of relevant | col_of int32 [n_items]]
+  SCR_RANK_WS,
   // sdrm_nmf_fit (csrc/nmf.h), float64: [the fit's state (2) | Gram partials [NMF_PARTS][16][16] | the product [max(m, n)][16] | violation
   // partials of the W half, of the H half]; sdrm_nmf_init, float64: [mean, sigma [16] (32) | norm partials of U, of V [NMF_PARTS][2][16] each
   // | V^T [n][16] | X V^T [m][16]]
@@ -321,7 +326,7 @@ struct sdrm_engine {
 constexpr int NLL_PARTS = 2048;   // most work-groups of k_nll_rows (8 per CU): the float64 partials k_nll_sum adds (csrc/nll.h)
 
 enum ProfClass { PC_FWD_L0 = 0, PC_FWD_HIDDEN, PC_FWD_OUT, PC_DGRAD, PC_WGRAD, PC_WGRAD_L0, PC_SMP_L0, PC_SMP_HIDDEN,
-                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_MLP_FWD, PC_MLP_BWD, PC_MLP_W1, PC_MLP_FOLD, PC_MLP_EVAL, PC_NEUMF_DRAW_SPLIT, PC_NEUMF_DRAW_SCAN, PC_NEUMF_DRAW_NEG, PC_NEUMF_DRAW_OUT, PC_NEUMF_TRIPLES, PC_COUNT };
+                 PC_SMP_OUT, PC_ROW_FWD, PC_WGRAD_STRIPS, PC_DGRAD_ROWS, PC_SMP_PERSIST, PC_NLL, PC_INPUT_LAYER, PC_HOLDOUT, PC_LATENT, PC_DECODER, PC_VAE_ADAM, PC_EVAL_HALF, PC_SVD_SPMM, PC_SVD_GRAM, PC_SVD_CHOL, PC_SVD_APPLY, PC_SVD_EXPAND, PC_NEUMF_STAGE, PC_NEUMF_SCORES, PC_NEUMF_PAIRS, PC_NEUMF_TRAIN_PAIRS, PC_NEUMF_TRAIN_GRADS, PC_NEUMF_TRAIN_ADAM, PC_NEUMF_TRAIN_CLEAR, PC_CSRT_MARK, PC_CSRT_COLSCAN, PC_CSRT_SCAN, PC_CSRT_FILL, PC_CSR_VSTACK, PC_NMF_STEP, PC_NMF_INIT, PC_NMF_EXPAND, PC_MLP_FWD, PC_MLP_BWD, PC_MLP_W1, PC_MLP_FOLD, PC_MLP_EVAL, PC_NEUMF_DRAW_SPLIT, PC_NEUMF_DRAW_SCAN, PC_NEUMF_DRAW_NEG, PC_NEUMF_DRAW_OUT, PC_NEUMF_TRIPLES, PC_NEUMF_RANK_PROBLEM, PC_NEUMF_RANK_USERS, PC_RANK_ROWS, PC_COUNT };
 static_assert(PC_COUNT <= PROF_SLOTS, "sdrm_engine::prof_ms / prof_fl / prof_n hold one slot per class");
 // the template arguments are <LOADA,LOADB,XFA,XFB,EPI> of gemm_kernel (what rocprofv3 prints after the tile type)
 static const char* kProfNames[PC_COUNT] = {
@@ -372,7 +377,10 @@ static const char* kProfNames[PC_COUNT] = {
     "neumf epoch draw: k_draw_scan exclusive scan of the work-groups' label-0 counts with a carry, n_pos, n_neg and m (one work-group)",
     "neumf epoch draw: k_draw_neg the source places of the label-0 rows in ascending order, from the mask words and the scanned offsets",
     "neumf epoch draw: k_draw_out the shuffled rows gathered through the second permutation, the extra rows' Philox draws among the label-0 rows",
-    "neumf triples: k_triple_counts / k_csr_scan / k_triple_fill checked row lengths, the rows' bases, and the (user, item, label) records of up to 8 CSR parts with item_present and the four counts"};
+    "neumf triples: k_triple_counts / k_csr_scan / k_triple_fill checked row lengths, the rows' bases, and the (user, item, label) records of up to 8 CSR parts with item_present and the four counts",
+    "neumf ranking problem: k_rank_cols / k_rank_mark_parts / k_rank_mark_held / k_rank_counts / k_csr_scan x2 / k_rank_fill the columns, the seen and the relevant CSR matrix by user id from up to 8 CSR parts and the held-out triples (one bit table each, 64-bit integer atomics)",
+    "neumf ranking users: k_rank_users a uint8 mask compacted into the ascending user list and its length (one work-group)",
+    "rank metrics by rows: k_rank_metrics_rows the checked ranking body with a row map into both CSR matrices and the NeuMF footing of the NDCG"};
 
 namespace {
 
@@ -3902,6 +3910,105 @@ int sdrm_neumf_triples(sdrm_engine* e, const sdrm_triple_part* parts, int n_part
 }
 
 // ---------------------------------------------------------------------------------------------
+// The NeuMF evaluator's ranking problem from device CSR parts and held-out triples (neural_cf_benchmark_pt.py:294-326), csrc/neumf_rank.h.
+
+// The host side that needs no device: everything sdrm_neumf_rank_problem refuses but the handle and the data pointers beside the parts'.
+int sdrm_debug_neumf_rank_args(const sdrm_triple_part* parts, int n_parts, int n_items, int64_t n_heldout, int64_t n_rows, int64_t capacity_cols,
+                               int64_t capacity_seen, int64_t capacity_relevant) {
+  if (!parts) return SDRM_ERR_ARG;
+  if (n_parts < 1 || n_parts > CSR_STACK_MAX) return SDRM_ERR_SHAPE;
+  if (n_items < 1 || n_items > RANKP_MAX_DIM) return SDRM_ERR_SHAPE;
+  if (n_rows < 1 || n_rows > RANKP_MAX_DIM) return SDRM_ERR_SHAPE;
+  if (n_heldout < 0 || n_heldout > RANKP_MAX_HELD) return SDRM_ERR_SHAPE;
+  if (n_rows * (((int64_t)n_items + 63) / 64) * 8 > RANKP_MAX_TABLE) return SDRM_ERR_SHAPE;
+  int64_t rows = 0, cap = 0;
+  for (int k = 0; k < n_parts; ++k) {
+    const sdrm_triple_part& p = parts[k];
+    if (p.n_rows < 0 || p.n_rows > RANKP_MAX_DIM || p.capacity < 0 || p.capacity > TRIPLE_MAX_OUT) return SDRM_ERR_SHAPE;
+    if (!p.indptr || (!p.indices && p.capacity > 0)) return SDRM_ERR_ARG;
+    if (p.label != 0 && p.label != 1) return SDRM_ERR_SHAPE;
+    if (p.user0 < 0 || (int64_t)p.user0 + p.n_rows > (int64_t)0x7fffffff) return SDRM_ERR_SHAPE;
+    rows += p.n_rows; cap += p.capacity;
+  }
+  if (rows < 1 || rows > RANKP_MAX_DIM) return SDRM_ERR_SHAPE;
+  if (capacity_cols < n_items || capacity_seen < cap || capacity_relevant < n_heldout) return SDRM_ERR_SHAPE;
+  return SDRM_OK;
+}
+
+int sdrm_neumf_rank_problem(sdrm_engine* e, const sdrm_triple_part* parts, int n_parts, int n_items, const uint8_t* item_present,
+                            const int32_t* heldout, int64_t n_heldout, int64_t n_rows, int32_t* cols_out, int64_t capacity_cols,
+                            int64_t* seen_indptr, int32_t* seen_indices, int64_t capacity_seen, int64_t* relevant_indptr,
+                            int32_t* relevant_indices, int64_t capacity_relevant, int64_t* counts_dev, void* stream) {
+  const char* who = "sdrm_neumf_rank_problem";
+  if (!e) return SDRM_ERR_ARG;
+  if (!parts || !item_present || !cols_out || !seen_indptr || !seen_indices || !relevant_indptr || !relevant_indices || !counts_dev ||
+      (!heldout && n_heldout > 0))
+    return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if (int rc = sdrm_debug_neumf_rank_args(parts, n_parts, n_items, n_heldout, n_rows, capacity_cols, capacity_seen, capacity_relevant))
+    return fail(e, rc, std::string(who) + (rc == SDRM_ERR_ARG ? ": a part without indptr, or without indices and capacity > 0"
+                                                                : ": n_parts outside 1 .. 8, n_items, n_rows or the parts' total rows outside 1 .. 2^22, a bit table "
+                                                                  "n_rows x ceil(n_items / 64) x 8 above 2^31 bytes, n_heldout outside 0 .. 2^30, a part as "
+                                                                  "sdrm_neumf_triples refuses it, or a capacity below n_items (cols), the sum of the parts' capacities "
+                                                                  "(seen) or n_heldout (relevant)"));
+  RankProblemArgs a{};
+  int64_t rows = 0;
+  for (int k = 0; k < n_parts; ++k) {
+    const sdrm_triple_part& p = parts[k];
+    a.part[k] = TriplePart{p.indptr, p.indices, p.n_rows, p.capacity, p.user0, p.label};
+    a.first[k] = rows;
+    rows += p.n_rows;
+  }
+  for (int k = n_parts; k <= CSR_STACK_MAX; ++k) a.first[k] = rows;
+  hipStream_t st = (hipStream_t)stream;
+  const int wpr = (n_items + 63) / 64;
+  const size_t table = (size_t)n_rows * (size_t)wpr, ptr = (size_t)n_rows + 1, cnt = ((size_t)n_rows + 1) / 2;
+  const size_t off_tab = 2, off_ptr = off_tab + 2 * table, off_cnt = off_ptr + 2 * ptr, off_col = off_cnt + 2 * cnt;
+  const size_t words = off_col + ((size_t)n_items + 1) / 2;
+  uint64_t* ws;
+  if (int rc = scratch(e, SCR_RANK_WS, words, &ws)) return rc;
+  a.n_parts = n_parts; a.n_items = n_items; a.flag = e->feed_flag;
+  a.n_rows = n_rows; a.wpr = wpr;
+  a.present = item_present; a.held = heldout; a.n_held = n_heldout;
+  int64_t* own[2];
+  for (int t = 0; t < 2; ++t) {
+    a.table[t] = ws + off_tab + (size_t)t * table;
+    own[t] = reinterpret_cast<int64_t*>(ws + off_ptr + (size_t)t * ptr);
+    a.own[t] = own[t];
+    a.cnt[t] = reinterpret_cast<uint32_t*>(ws + off_cnt + (size_t)t * cnt);
+  }
+  a.col_of = reinterpret_cast<int32_t*>(ws + off_col);
+  a.cols = cols_out;
+  a.indices[0] = seen_indices; a.capacity[0] = capacity_seen;
+  a.indices[1] = relevant_indices; a.capacity[1] = capacity_relevant;
+  a.counts = reinterpret_cast<unsigned long long*>(counts_dev);
+  const unsigned part_waves = (unsigned)std::min<int64_t>((rows + 3) / 4, 1 << 16);
+  const unsigned row_waves = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 1 << 16);
+  const unsigned count_waves = (unsigned)std::min<int64_t>((2 * n_rows + 3) / 4, 1 << 16);
+  return hip_rc(e, "k_rank_fill", profiled(e, PC_NEUMF_RANK_PROBLEM, 0.0, st, [&] {
+    // the scratch (the two bit tables first of all) and the counts are this call's own, made anew on the stream every time
+    hipError_t rc = hipMemsetAsync(ws, 0, words * sizeof(uint64_t), st);
+    if (rc == hipSuccess) rc = hipMemsetAsync(counts_dev, 0, 4 * sizeof(int64_t), st);
+    if (rc != hipSuccess) return rc;
+    SDRM_LAUNCH(e, k_rank_cols, dim3(1), dim3(256), 0, st, a);
+    SDRM_LAUNCH(e, k_rank_mark_parts, dim3(part_waves), dim3(256), 0, st, a);
+    if (n_heldout > 0) SDRM_LAUNCH(e, k_rank_mark_held, dim3((unsigned)((n_heldout + 255) / 256)), dim3(256), 0, st, a);
+    SDRM_LAUNCH(e, k_rank_counts, dim3(count_waves), dim3(256), 0, st, a);
+    SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)a.cnt[0], n_rows, own[0], seen_indptr, reinterpret_cast<int64_t*>(ws));
+    SDRM_LAUNCH(e, k_csr_scan, dim3(1), dim3(256), 0, st, (const uint32_t*)a.cnt[1], n_rows, own[1], relevant_indptr, reinterpret_cast<int64_t*>(ws + 1));
+    SDRM_LAUNCH(e, k_rank_fill, dim3(row_waves, 2), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }));
+}
+
+int sdrm_neumf_rank_users(sdrm_engine* e, const uint8_t* mask, int64_t n_rows, int32_t* users_out, int64_t* count_dev, void* stream) {
+  if (!e) return SDRM_ERR_ARG;
+  if (!mask || !users_out || !count_dev) return fail(e, SDRM_ERR_ARG, "sdrm_neumf_rank_users: null pointer");
+  if (n_rows < 1 || n_rows > RANKP_MAX_DIM) return fail(e, SDRM_ERR_SHAPE, "sdrm_neumf_rank_users: n_rows outside 1 .. 2^22");
+  return launch_k(e, PC_NEUMF_RANK_USERS, "k_rank_users", k_rank_users, dim3(1), dim3(256), 0, (hipStream_t)stream, mask, n_rows, users_out,
+                  reinterpret_cast<unsigned long long*>(count_dev));
+}
+
+// ---------------------------------------------------------------------------------------------
 // Recall@k / NDCG@k against held-out interactions (utilities.py:116-171), csrc/rank.h.
 int sdrm_rank_metrics(sdrm_engine* e, const float* scores, int U, int I, const int64_t* held_indptr,
                       const int32_t* held_indices, const int64_t* train_indptr, const int32_t* train_indices,
@@ -3929,6 +4036,40 @@ int sdrm_rank_metrics(sdrm_engine* e, const float* scores, int U, int I, const i
   if (lds > 48 * 1024)
     HIP_TRY(e, hipFuncSetAttribute((const void*)k_rank_metrics, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   return launch_k(e, PC_NONE, "k_rank_metrics", k_rank_metrics, dim3(U), dim3(256), lds, (hipStream_t)stream, a);
+}
+
+// The same ranking with a row map into both matrices, every offset and column checked, and the NeuMF footing of the NDCG on request
+// (k_rank_metrics_rows, csrc/neumf_rank.h).
+int sdrm_rank_metrics_rows(sdrm_engine* e, const float* scores, int U, int I, const int32_t* rows, int64_t n_rows, const int64_t* held_indptr,
+                           const int32_t* held_indices, int64_t held_nnz, const int64_t* train_indptr, const int32_t* train_indices,
+                           int64_t train_nnz, const int32_t* ks_host, int nk, const double* tp, const double* idcg, double* recall, double* ndcg,
+                           int full_idcg, void* stream) {
+  const char* who = "sdrm_rank_metrics_rows";
+  if (!e) return SDRM_ERR_ARG;
+  if (!scores || !rows || !held_indptr || !held_indices || !ks_host || !tp || !idcg || !recall || !ndcg)
+    return fail(e, SDRM_ERR_ARG, std::string(who) + ": null pointer");
+  if ((train_indptr == nullptr) != (train_indices == nullptr))
+    return fail(e, SDRM_ERR_ARG, std::string(who) + ": train_indptr and train_indices go together");
+  if (U < 1 || I < 1 || I > 36864) return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": U < 1 or I outside [1, 36864]");
+  if (n_rows < 1 || held_nnz < 0 || train_nnz < 0) return fail(e, SDRM_ERR_SHAPE, std::string(who) + ": n_rows < 1 or a negative index capacity");
+  if (nk < 1 || nk > RANK_MAX_NK) return fail(e, SDRM_ERR_ARG, std::string(who) + ": nk outside [1, 8]");
+  RankArgs a{};
+  a.scores = scores; a.U = U; a.I = I;
+  a.held_indptr = held_indptr; a.held_indices = held_indices;
+  a.train_indptr = train_indptr; a.train_indices = train_indices;
+  a.nk = nk; a.kmax = 0;
+  for (int q = 0; q < nk; ++q) {
+    if (ks_host[q] < 1 || ks_host[q] > RANK_MAX_K || ks_host[q] > I)
+      return fail(e, SDRM_ERR_ARG, std::string(who) + ": k outside [1, min(128, I)]");
+    a.ks[q] = ks_host[q];
+    if (ks_host[q] > a.kmax) a.kmax = ks_host[q];
+  }
+  a.tp = tp; a.idcg = idcg; a.recall = recall; a.ndcg = ndcg;
+  const RankCheck ck{held_nnz, train_nnz, e->feed_flag};
+  const RankRows rm{rows, n_rows, full_idcg != 0};
+  const size_t lds = (size_t)I * sizeof(float);
+  if (lds > 48 * 1024) HIP_TRY(e, allow_full_lds((const void*)k_rank_metrics_rows, 36864 * (int)sizeof(float)));
+  return launch_k(e, PC_RANK_ROWS, "k_rank_metrics_rows", k_rank_metrics_rows, dim3(U), dim3(256), lds, (hipStream_t)stream, a, ck, rm);
 }
 
 // ---------------------------------------------------------------------------------------------

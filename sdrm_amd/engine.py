@@ -33,6 +33,10 @@ TRAIN_PATHS = ("per_layer", "skinny", "row96", "row48")
 DGRAD_FORMS = ("tiles", "rows_per_layer", "chain", "skinny_own")
 SAMPLE_PATHS = ("skinny", "persist", "per_layer")
 LastPlan = collections.namedtuple("LastPlan", "train_path parts dgrad sample_path")
+# Engine.neumf_rank_problem's record: cols the int32 device view [C]; seen and relevant device CSR tuples (indptr int64 [n_rows + 1], int32
+# index view cut to the count, None, (n_rows, C)), rows dense by user id; counts the Python tuple (C, seen's entries, relevant's entries,
+# held-out triples dropped for a range defect)
+NeumfRankProblem = collections.namedtuple("NeumfRankProblem", "cols seen relevant counts")
 
 
 class _ParamSpan:
@@ -1493,6 +1497,116 @@ class Engine:
         if check:
             self.feed_status()
         return out[:counts[0]], counts, item_present
+
+    # ------------------------------------------------------------------ NeuMF evaluator's ranking problem on the device (csrc/neumf_rank.h)
+    def neumf_rank_problem(self, parts, n_items, item_present, heldout, n_rows, check=True):
+        """neural_cf_benchmark_pt.py:294-326's ranking problem on the device (sdrm_neumf_rank_problem; include/sdrm_hip.h defines it,
+        tests/neumf_rank_ref.py restates it): what `neumf.RankingProblem.from_parts` builds on the host, with the rows of both matrices
+        dense by user id.  `parts`, `n_items`: as `neumf_triples` takes them; `item_present`: the uint8 device tensor [n_items] that call
+        returned; `heldout`: int32 device tensor [n, 3] of (user, item, label) triples, n may be 0; `n_rows`: the number of user ids.
+        Returns a `NeumfRankProblem`; its counts are the call's ONE readback, 32 bytes, which also sizes the views.  A part row that
+        fails `neumf_triples`' checks contributes nothing, a held-out triple with a user outside [0, n_rows) or an item outside
+        [0, n_items) is dropped, and either raises the feed status word (`check` as in `csr_rows_to_dense`)."""
+        who = "neumf_rank_problem"
+        parts = list(parts)
+        if not 1 <= len(parts) <= self.CSR_STACK_MAX:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {len(parts)} parts, outside 1 .. {self.CSR_STACK_MAX}")
+        n_items, n_rows = int(n_items), int(n_rows)
+        arrays = []
+        for i, p in enumerate(parts):
+            if not isinstance(p, (tuple, list)) or len(p) != 3:
+                raise SdrmError(f"{who}: part {i} must be (device CSR tuple, user0, label)")
+            indptr, indices, _, rows_p, n_cols, cap = self._csr_arrays(who, f"part {i}", p[0])
+            user0, label = int(p[1]), int(p[2])
+            if n_cols > n_items:
+                raise SdrmError(f"{who}: SDRM_ERR_SHAPE: part {i} has {n_cols} columns, n_items is {n_items}")
+            if label not in (0, 1) or user0 < 0 or user0 + rows_p > 2 ** 31 - 1:
+                raise SdrmError(f"{who}: SDRM_ERR_SHAPE: part {i}: label {label} outside {{0, 1}}, or users {user0} .. {user0 + rows_p - 1} outside int32")
+            arrays.append((indptr, indices, rows_p, cap, user0, label))
+        rows, capacity = sum(a[2] for a in arrays), sum(a[3] for a in arrays)
+        if (not (1 <= rows <= 2 ** 22 and 1 <= n_items <= 2 ** 22 and 1 <= n_rows <= 2 ** 22) or capacity > self.NEUMF_TRIPLES_MAX
+                or n_rows * -(-n_items // 64) * 8 > 2 ** 31):
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {rows} part rows, {n_items} items or {n_rows} users outside 1 .. 2^22, {capacity} entries above "
+                            f"2^30, or a bit table above 2^31 bytes")
+        if (not isinstance(item_present, torch.Tensor) or item_present.dtype != torch.uint8 or item_present.device != self.device
+                or not item_present.is_contiguous() or tuple(item_present.shape) != (n_items,)):
+            raise SdrmError(f"{who}: item_present must be a contiguous uint8 tensor [{n_items}] on the engine's device")
+        if (not isinstance(heldout, torch.Tensor) or heldout.dtype != torch.int32 or heldout.device != self.device or not heldout.is_contiguous()
+                or heldout.dim() != 2 or heldout.shape[1] != 3 or heldout.shape[0] > 2 ** 30):
+            raise SdrmError(f"{who}: heldout must be a contiguous int32 tensor [0 .. 2^30, 3] on the engine's device")
+        n_held = int(heldout.shape[0])
+        cols = torch.empty(n_items, dtype=torch.int32, device=self.device)
+        seen_ptr = torch.empty(n_rows + 1, dtype=torch.int64, device=self.device)
+        seen_idx = torch.empty(max(capacity, 1), dtype=torch.int32, device=self.device)
+        rel_ptr = torch.empty(n_rows + 1, dtype=torch.int64, device=self.device)
+        rel_idx = torch.empty(max(n_held, 1), dtype=torch.int32, device=self.device)
+        counts_dev = torch.empty(4, dtype=torch.int64, device=self.device)
+        desc = (_lib.TriplePart * len(arrays))()
+        for d, (ip, ix, rows_p, cap, user0, label) in zip(desc, arrays):
+            d.indptr, d.indices = ip.data_ptr(), ix.data_ptr() if cap else None   # (an empty tensor has no address; the ABI takes null with capacity 0)
+            d.n_rows, d.capacity, d.user0, d.label = rows_p, cap, user0, label
+        self._check(self.lib.sdrm_neumf_rank_problem(self._h, desc, len(arrays), n_items, _ptr(item_present), _ptr(heldout) if n_held else None, n_held,
+                                                     n_rows, _ptr(cols), n_items, _ptr(seen_ptr), _ptr(seen_idx), int(seen_idx.numel()), _ptr(rel_ptr),
+                                                     _ptr(rel_idx), int(rel_idx.numel()), _ptr(counts_dev), _stream()), "sdrm_neumf_rank_problem")
+        self._feed_keep = (arrays, item_present, heldout)
+        counts = tuple(int(c) for c in counts_dev.cpu().tolist())
+        if check:
+            self.feed_status()
+        C_, shape = counts[0], (n_rows, counts[0])
+        return NeumfRankProblem(cols[:C_], (seen_ptr, seen_idx[:counts[1]], None, shape), (rel_ptr, rel_idx[:counts[2]], None, shape), counts)
+
+    def neumf_rank_users(self, mask):
+        """The ascending int32 user list of a uint8 device mask [n_rows] (sdrm_neumf_rank_users): `np.flatnonzero` of the bytes
+        `neumf_epoch_draw` leaves in `present`, on the device.  Returns the view [U]; U is the call's one readback, 8 bytes (it sizes the
+        score matrix of the ranking that follows)."""
+        who = "neumf_rank_users"
+        if (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.dim() != 1 or mask.device != self.device
+                or not mask.is_contiguous()):
+            raise SdrmError(f"{who}: mask must be a contiguous 1-D uint8 tensor on the engine's device")
+        n_rows = int(mask.numel())
+        if not 1 <= n_rows <= 2 ** 22:
+            raise SdrmError(f"{who}: SDRM_ERR_SHAPE: {n_rows} users, outside 1 .. 2^22")
+        users = torch.empty(n_rows, dtype=torch.int32, device=self.device)
+        count_dev = torch.empty(1, dtype=torch.int64, device=self.device)
+        self._check(self.lib.sdrm_neumf_rank_users(self._h, _ptr(mask), n_rows, _ptr(users), _ptr(count_dev), _stream()), "sdrm_neumf_rank_users")
+        return users[:int(count_dev.cpu().item())]
+
+    def rank_metrics_rows(self, scores, rows, heldout, train=None, ks=(1, 3, 5, 10, 20, 50), full_idcg=False):
+        """`rank_metrics` for score rows that are a SELECTION of the rows of two resident matrices (sdrm_rank_metrics_rows): score row q of
+        the float32 device matrix [U, I] ranks against CSR row rows[q] (int32 device tensor [U], any order, repeats allowed) of the device
+        CSR tuples `heldout` and `train` [n_rows, I] - no gather of either.  Every row id, offset and column is range-checked on the
+        device into the feed status word (ask `feed_status()`).  `full_idcg=True`: the NDCG on the NeuMF evaluator's footing, ideal DCG
+        of min(I, k) items for every user and 0 without a relevant item - the bits `neumf.rank_all_items` makes on the host.  The discount
+        tables come from the per-`ks` cache `rank_metrics` uses.  Returns (recall [nk, U], ndcg [nk, U]) float64 device tensors."""
+        who = "rank_metrics_rows"
+        if not isinstance(scores, torch.Tensor) or scores.dim() != 2:
+            raise SdrmError(f"{who}: scores must be a float32 device matrix [U, I]")
+        scores = self._f32(who, "scores", scores, tuple(scores.shape))
+        U, I = (int(v) for v in scores.shape)
+        if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 1 or rows.device != self.device or not rows.is_contiguous()
+                or rows.numel() != U):
+            raise SdrmError(f"{who}: rows must be a contiguous int32 tensor [{U}] on the engine's device")
+        if train is not None and not isinstance(train, tuple):
+            raise SdrmError(f"{who}: heldout and train are device CSR tuples")
+        n_rows = int(heldout[3][0])
+
+        def matrix(name, csr_dev):
+            indptr, indices, _, rows_m, width, cap = self._csr_arrays(who, name, csr_dev)
+            if width != I or rows_m != n_rows:
+                raise SdrmError(f"{who}: SDRM_ERR_SHAPE: the {name} matrix is {rows_m} x {width}, the scores have {I} columns and the held-out matrix {n_rows} rows")
+            return indptr, indices if cap else indices.new_zeros(1), cap
+        hp, hi, hn = matrix("held-out", heldout)
+        tp_, ti, tn = matrix("train", train) if train is not None else (None, None, 0)
+        ks_h, tp_d, idcg_d = self._rank_tables(ks)
+        recall = torch.empty(len(ks_h), U, dtype=torch.float64, device=self.device)
+        ndcg = torch.empty(len(ks_h), U, dtype=torch.float64, device=self.device)
+        if U == 0:
+            return recall, ndcg
+        self._check(self.lib.sdrm_rank_metrics_rows(self._h, _ptr(scores), U, I, _ptr(rows), n_rows, _ptr(hp), _ptr(hi), hn, _ptr(tp_), _ptr(ti), tn,
+                                                    ks_h.ctypes.data_as(C.c_void_p), len(ks_h), _ptr(tp_d), _ptr(idcg_d), _ptr(recall), _ptr(ndcg),
+                                                    int(bool(full_idcg)), _stream()), "sdrm_rank_metrics_rows")
+        self._keepalive = (scores, rows, hp, hi, tp_, ti)
+        return recall, ndcg
 
     # ------------------------------------------------------------------ MLP evaluator's train steps (csrc/mlp_train.h)
     MLP_TENSORS = ("mf_embedding_user", "layer1/kernel", "layer1/bias", "layer2/kernel", "layer2/bias", "layer3/kernel", "layer3/bias",

@@ -9,7 +9,9 @@ call (csrc/neumf_train.h: forward with dropout, loss, backward and Adam on the d
 split, negatives and shuffle are ONE `Engine.neumf_epoch_draw` call on triples uploaded once (csrc/neumf_draw.h).  With `engine=None` the same functions run torch and numpy on the host - the checker.
 The triples themselves - main.py:218-283's frames of a synthetic matrix's two tails and the split validation users - are stated once in
 `synthetic_parts_host` / `assemble_triples`; `compute_neuralcf_results_synthetic` assembles them on the device instead, from CSR parts that
-never leave it (`Engine.neumf_triples`, csrc/neumf_triples.h), and is what `pipeline.evaluate_synthetic` calls for hp["evaluator"] == "neumf".
+never leave it (`Engine.neumf_triples`, csrc/neumf_triples.h), and is what `pipeline.evaluate_synthetic` calls for hp["evaluator"] == "neumf";
+with `device_ranking=True` the ranking problem is built from the same parts and its users selected on the device too
+(`DeviceRankingProblem`, csrc/neumf_rank.h).
 
 Triples are a numpy int array [n, 3] (user, item, label); a (user, item) pair occurs at most once per array.  Labels are taken as
 binary (> 0), which is what the reference feeds its evaluators.  No pandas, no sklearn."""
@@ -161,6 +163,61 @@ class RankingProblem:
         return users, self.cols, self._select(self._relevant, users), self._select(self._seen, users)
 
 
+class DeviceRankingProblem:
+    """The ranking problem resident on the engine's device (`Engine.neumf_rank_problem`, csrc/neumf_rank.h): the columns and both CSR
+    matrices with their rows DENSE BY USER ID - row u is user u - so that a ranking's users need no row selection: `rank` hands their ids
+    to `Engine.rank_metrics_rows` as a row map.  `rank_all_items(..., problem=<this>)` dispatches here."""
+
+    def __init__(self, engine, record, n_items):
+        self.engine, self.n_items = engine, int(n_items)
+        self.cols, self.seen, self.relevant, self.counts = record.cols, record.seen, record.relevant, record.counts
+        self.n_rows = int(self.seen[3][0])
+
+    @classmethod
+    def build(cls, engine, device_parts, n_items, item_present, validation, n_rows):
+        """From what `compute_neuralcf_results_synthetic` holds behind `Engine.neumf_triples`: the same `device_parts` ((device CSR tuple,
+        user0, label), ...), that call's `item_present`, the validation triples (an int array [n, 3], uploaded here once, or an int32
+        device tensor) and the number of user ids (that call's counts[2]).  ONE `neumf_rank_problem` call; its 32 bytes of counts are all
+        that comes back."""
+        if not isinstance(validation, torch.Tensor):
+            validation = torch.from_numpy(np.ascontiguousarray(_as_triples(validation, "validation"), dtype=np.int32)).to(engine.device)
+        return cls(engine, engine.neumf_rank_problem(device_parts, n_items, item_present, validation, n_rows), n_items)
+
+    def to_host(self):
+        """The `RankingProblem` that `RankingProblem.from_parts` builds from the same parts, array for array (tests and debugging only: it
+        reads everything back)."""
+        host = RankingProblem.__new__(RankingProblem)
+        host.cols = self.cols.cpu().numpy().astype(np.int64)
+
+        def rows(csr_dev):
+            indptr, indices = csr_dev[0].cpu().numpy(), csr_dev[1].cpu().numpy()
+            lengths = np.diff(indptr)
+            ids = np.flatnonzero(lengths).astype(np.int64)
+            return ids, np.concatenate([[0], np.cumsum(lengths[ids])]).astype(np.int64), indices[:indptr[-1]].astype(np.int32)
+        host._relevant, host._seen = rows(self.relevant), rows(self.seen)
+        return host
+
+    def rank(self, model, users):
+        """`rank_all_items`' result for `users`: the uint8 device mask [n_rows] that `Engine.neumf_epoch_draw` leaves in `present`
+        (compacted on the device, `Engine.neumf_rank_users`), or an array of ids (made unique on the host and uploaded: the final
+        ranking's few hundred validation users)."""
+        engine = self.engine
+        if int(self.cols.numel()) <= max(K_LIST):
+            raise ValueError(f"ranking needs more than {max(K_LIST)} training items, got {int(self.cols.numel())}")
+        if isinstance(users, torch.Tensor) and users.dtype == torch.uint8:
+            users_dev = engine.neumf_rank_users(users)
+        else:
+            users = users.cpu().numpy() if isinstance(users, torch.Tensor) else users
+            users_dev = torch.from_numpy(np.unique(np.asarray(users, dtype=np.int64)).astype(np.int32)).to(engine.device)
+        if users_dev.numel() == 0:
+            return np.empty((len(K_LIST), 0)), np.empty((len(K_LIST), 0))
+        scores = engine.neumf_scores(model.engine_weights(engine.device), users_dev, self.cols, check=False)
+        rec, ndcg = engine.rank_metrics_rows(scores, users_dev, self.relevant, self.seen, ks=K_LIST, full_idcg=True)
+        rec, ndcg = rec.cpu().numpy(), ndcg.cpu().numpy()
+        engine.feed_status()
+        return rec, ndcg
+
+
 def synthetic_parts_host(train_shape, valid, ones, zeros):
     """What main.py:218-283 hands to `compute_neuralcf_results` for ONE synthetic matrix in its non-augmented branch
     (`args.augment_training_data` false, `data = equal_sparsity_valid_train`, :279-280 - the branch the `mlp` route takes too), as
@@ -262,7 +319,14 @@ def rank_all_items(model, training, heldout, users, engine=None, problem=None):
     ranking are the existing `rank_metrics`; its NDCG (ideal DCG of min(relevant, k) items, nan without one) is put on the reference's
     footing from the per-user counts on the host.  `feed_status()` is asked once.  Without one, torch and numpy do all of it.
     `problem`: a `RankingProblem(training, heldout)` of the same two arrays, built once by a caller that ranks more than once; the index
-    arrays are then a row selection from it, the same as `ranking_problem`'s."""
+    arrays are then a row selection from it, the same as `ranking_problem`'s.  A `DeviceRankingProblem` (needs its engine) ranks without
+    one: `users` is then the uint8 device mask of the users or an id array, both matrices stay on the device and are read through a row
+    map (`DeviceRankingProblem.rank`: ONE `neumf_scores` call, `Engine.rank_metrics_rows(..., full_idcg=True)` - the footing made on the
+    device in the host's three operations - and `feed_status()` once), and the result is the same pair of arrays."""
+    if isinstance(problem, DeviceRankingProblem):
+        if engine is None or engine is not problem.engine:
+            raise ValueError("rank_all_items: a DeviceRankingProblem ranks on the engine that built it")
+        return problem.rank(model, users)
     users, cols, relevant, seen = ranking_problem(training, heldout, users) if problem is None else problem.select(users)
     if cols.shape[0] <= max(K_LIST):
         raise ValueError(f"ranking needs more than {max(K_LIST)} training items, got {cols.shape[0]}")
@@ -366,7 +430,8 @@ def compute_neuralcf_results_resident(training, validation, n_users, n_items, en
     says holds here - with two more keyword arguments for a caller whose training triples are on the device already.
     `training_dev` and `problem` (both None by default; either one needs `device_draw=True` and raises ValueError without it, and they come together): the training triples
     as an int32 tensor [n, 3] already on the engine's device - `Engine.neumf_triples`' view - used in place of the cast and upload, and a
-    `RankingProblem` of the same triples (`RankingProblem.from_parts`) used in place of `RankingProblem(training, validation)`.
+    `RankingProblem` of the same triples (`RankingProblem.from_parts`) used in place of `RankingProblem(training, validation)` - or a
+    `DeviceRankingProblem` of them (`DeviceRankingProblem.build`), with which an epoch's users are `present` itself, never read back.
     `training` may then be None: nothing else reads it, and the hold-out size comes from `training_dev.shape[0]`.
     They are their own function because `compute_neuralcf_results`' parameter list is pinned by tests/test_neumf_epoch_draw_host.py."""
     if (training_dev is not None or problem is not None) and not device_draw:
@@ -443,7 +508,10 @@ def compute_neuralcf_results_resident(training, validation, n_users, n_items, en
         valid_loss = validation_loss(model, hold, engine)
         valid_losses.append(valid_loss)
         if eval_recall:
-            epoch_users = np.flatnonzero(present.cpu().numpy()) if device_draw else hold[:, 0]
+            if isinstance(problem, DeviceRankingProblem):
+                epoch_users = present                          # the mask itself: compacted, scored and ranked on the device
+            else:
+                epoch_users = np.flatnonzero(present.cpu().numpy()) if device_draw else hold[:, 0]
             rec, _ = rank_all_items(model, training, validation, epoch_users, engine, problem=problem)
             with np.errstate(invalid="ignore"):
                 recall10 = float(np.nanmean(rec[K_LIST.index(10)])) if rec.shape[1] else float("nan")
@@ -484,7 +552,8 @@ def compute_neuralcf_results_resident(training, validation, n_users, n_items, en
                 np.array([np.round(np.nanmean(ndcg[q]), 4) for q in range(len(K_LIST))]))
 
 
-def compute_neuralcf_results_synthetic(train_shape, valid, raw, sparsity, engine, seed=0, epochs=20, eval_recall=True, history=None):
+def compute_neuralcf_results_synthetic(train_shape, valid, raw, sparsity, engine, seed=0, epochs=20, eval_recall=True, history=None,
+                                       device_ranking=False):
     """main.py's NeuMF arm for ONE synthetic matrix `raw` (dense scores, on the engine's device or the host; main.py:256-283, the
     non-augmented branch - see `synthetic_parts_host` for what is kept and what is not) with the training triples ASSEMBLED ON THE
     DEVICE: both tails come from `Engine.equal_sparsity_csr` and stay resident, the validation users' training half
@@ -493,7 +562,11 @@ def compute_neuralcf_results_synthetic(train_shape, valid, raw, sparsity, engine
     device_train=True, device_draw=True, training_dev=..., problem=...)` trains and ranks; n_users and n_items are the call's counts
     (max user + 1, max item + 1: main.py:283).  Neither the dense 0/1 matrix nor the triples cross to the host.  What does cross: 32 bytes
     of counts, n_items bytes of `item_present` (the ranking's columns) and, once, the two tails' indptr / indices, from which
-    `RankingProblem.from_parts` builds the host-side ranking problem - a device-resident ranking problem is not built."""
+    `RankingProblem.from_parts` builds the host-side ranking problem.
+    `device_ranking=True` builds the ranking problem on the device instead (`DeviceRankingProblem.build`: ONE `Engine.neumf_rank_problem`
+    call from the same parts, `item_present`, the call's user count and the validation triples, uploaded once): the tails are not read
+    back, `from_parts` is not called, and per ranking the epoch's `present` mask is compacted, scored and ranked on the device.  What
+    crosses then: the counts (32 bytes twice), 8 bytes per ranking (the number of its users) and the per-user metrics, 2 x 6 x U doubles."""
     if engine is None:
         raise ValueError("compute_neuralcf_results_synthetic: needs an engine (the host form is compute_neuralcf_results on "
                          "assemble_triples(synthetic_parts_host(...)))")
@@ -507,6 +580,10 @@ def compute_neuralcf_results_synthetic(train_shape, valid, raw, sparsity, engine
     if valid_train.shape[0]:
         device_parts.append((engine.csr_to_device(valid_train), offset, 1))
     training_dev, counts, item_present = engine.neumf_triples(device_parts, n_items)
+    if device_ranking:
+        problem = DeviceRankingProblem.build(engine, device_parts, n_items, item_present, validation, counts[2])
+        return compute_neuralcf_results_resident(None, validation, counts[2], counts[3], engine=engine, seed=seed, epochs=epochs, eval_recall=eval_recall,
+                                                 history=history, device_train=True, device_draw=True, training_dev=training_dev, problem=problem)
 
     def host_pattern(dev):
         indptr, indices, shape = dev

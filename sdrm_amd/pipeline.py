@@ -232,14 +232,17 @@ def evaluate_synthetic(train, valid, raw, sparsity, engine, hp, seed):
     train epochs, the per-epoch validation RMSE and the final scores on the device (`hp["mlp_epochs"]`, 200 when absent).
     `hp["evaluator"] == "neumf"` is the `--model neumf` route (main.py:218-283, non-augmented): `neumf.compute_neuralcf_results_synthetic`,
     which takes both tails of `raw` on the device, assembles the training triples there (`Engine.neumf_triples`) and trains and ranks NeuMF
-    on the device (`hp["neumf_epochs"]`, 20 when absent; `hp["neumf_eval_recall"]`, True when absent, as main.py:283 calls it).  Without the
+    on the device (`hp["neumf_epochs"]`, 20 when absent; `hp["neumf_eval_recall"]`, True when absent, as main.py:283 calls it;
+    `hp["neumf_device_ranking"]`, passed on as `device_ranking` only when the key is present: the ranking problem built and its users selected on
+    the device).  Without the
     key: `hp["resident_svd"]`, `hp["device_svd"]`, `hp["sparse_synthetic"]` and `hp["nmf"]` as `run_experiment` documents them."""
     binarise = equal_sparsity_csr if hp.get("sparse_synthetic", False) else equal_sparsity   # opt-in: CSR made on the device
     if hp.get("evaluator") == "mlp":
         return compute_mlp_results_device(binarise(raw, sparsity, engine), valid, engine, device_train=True, seed=seed, epochs=hp.get("mlp_epochs", 200))
     if hp.get("evaluator") == "neumf":
+        ranking = {"device_ranking": bool(hp["neumf_device_ranking"])} if "neumf_device_ranking" in hp else {}   # opt-in: csrc/neumf_rank.h
         return compute_neuralcf_results_synthetic(train.shape, valid, raw, sparsity, engine, seed=seed, epochs=hp.get("neumf_epochs", 20),
-                                                  eval_recall=hp.get("neumf_eval_recall", True))
+                                                  eval_recall=hp.get("neumf_eval_recall", True), **ranking)
     if hp.get("evaluator") is not None:
         raise ValueError(f"evaluate_synthetic: hp['evaluator'] = {hp['evaluator']!r}; 'mlp' and 'neumf' are the evaluators the key selects")
     nmf = {"nnmf": True} if hp.get("nmf", False) else {}   # opt-in, the two device routes only: the NMF evaluator in the SVD's place (csrc/nmf.h)
